@@ -398,6 +398,39 @@ def emit(result, workload, write_file=True):
     print(text, flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs DIR: what the last timed step handed its caller, one ``DIR/<name>.npy`` (float32) per array, in
+    DUMP_LIMIT_BYTES at most.  Past that limit every array of more than one row keeps the same share of its rows, a fixed
+    sample drawn from a seed of the array's name, so two builds write the same rows."""
+    import re
+    import zlib
+
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float32) for name, a in arrays.items()}  # the path computes in fp32
+    # every array gets at most `level` bytes: small arrays stay whole, the large ones share what is left equally
+    level, left = float("inf"), DUMP_LIMIT_BYTES
+    sizes = sorted(a.nbytes for a in arrays.values())
+    for i, size in enumerate(sizes):
+        if size > left / (len(sizes) - i):
+            level = left / (len(sizes) - i)
+            break
+        left -= size
+    for name, a in arrays.items():
+        if a.nbytes > level and a.ndim > 0 and a.shape[0] > 1:
+            k = max(1, int(a.shape[0] * level / a.nbytes))
+            rows = np.random.default_rng(zlib.crc32(name.encode())).choice(a.shape[0], size=k, replace=False)
+            a = a[np.sort(rows)]
+        np.save(os.path.join(dirname, re.sub(r"[^A-Za-z0-9_.-]+", "_", name) + ".npy"), a)
+
+
+def grads_of(variables):
+    """name -> gradient of every variable that has one (the order of ``variables`` numbers them)"""
+    return {f"grad_{i:03d}_{v.name}": v.grad.detach().cpu() for i, v in enumerate(variables) if v.grad is not None}
+
+
 # --------------------------------------------------------------------------------------------------------------------
 # workload construction / launch
 # --------------------------------------------------------------------------------------------------------------------
@@ -490,6 +523,7 @@ def run_ppi(args, wl):
     ops.set_gemm_mode(args.gemm_mode)
     E = [0]
     calls = [0]
+    last_step = {}  # --dump-outputs: what the last step handed its caller
 
     # Input pipeline: like the headline workload (and the reference's background batching thread + tf.data prefetch,
     # data/graph_dataset.py:292-295), the finalisation + bucketing of batch i+1 is enqueued on a second stream at the start of
@@ -530,6 +564,8 @@ def run_ppi(args, wl):
         model.backward()
         if g_ is not None:
             g_.close()
+        if args.dump_outputs:
+            last_step["output"], last_step["loss"] = out[0], metrics["loss"]
         return metrics
 
     for _ in range(max(args.warmup, 3)):
@@ -543,6 +579,9 @@ def run_ppi(args, wl):
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
     products = products_from_counts(c0, ops.launch_counts(), args.steps)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"per_node_logits": last_step["output"].cpu(), "loss": last_step["loss"].cpu().reshape(1),
+                                         **grads_of(model.trainable_variables)})
     # host time: how long the enqueue of a step takes (each step timed on an idle queue, then waited for)
     host = []
     for _ in range(min(args.steps, 10)):
@@ -705,7 +744,15 @@ def main():
                     help="skip the short timings of the other BASELINE workloads that the default run reports under `other_configs`")
     ap.add_argument("--plumbing-only", action="store_true",
                     help="no device work: spawn / rendezvous (gloo) / sharding / collectives only - the CPU test of the N > 1 launch path")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them handed its caller (rank 0: output representations, "
+                         "weight gradients) as DIR/<name>.npy in float32, at most 64 MB in all (a fixed row sample past that); "
+                         "the inputs are seeded, so runs with the same arguments can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.plumbing_only:
+        ap.error("--dump-outputs needs the device path (not --plumbing-only)")
 
     if os.environ.get("TFGNN_BENCH_WATCHDOG"):  # debugging aid: every process dumps its Python stacks if it still runs after N seconds
         import faulthandler
@@ -832,6 +879,7 @@ def main():
             return ops.Graph(adj, V, wait=False, parts=gnn.graph_parts(V, ept)), x  # only the tables this stack reads
 
     allreduce_events = []
+    last_step = {}  # --dump-outputs: what the last step handed its caller
 
     def step():
         # a training step ends with an in-place weight update, which invalidates the split forms of the weights the f16x2
@@ -851,11 +899,14 @@ def main():
             g.wait()
             pending.append(prepare_batch())  # next batch, overlapped with this step
         out = gnn(GNNInput(x, g, n2g, G), training=True)
+        pooled = None
         if pool is not None:
-            pool(NodesToGraphRepresentationInput(out, n2g, G), training=True)
+            pooled = pool(NodesToGraphRepresentationInput(out, n2g, G), training=True)
             gnn.backward(pool.backward(dOut))
         else:
             gnn.backward(dOut)
+        if args.dump_outputs:
+            last_step["node_representations"], last_step["graph_representations"] = out, pooled
         if args.allreduce_grads:
             # timed on the device (events on the launch stream; read after the run): the exchange's share of every rank's step
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -882,6 +933,8 @@ def main():
         trace = os.environ.get("TFGNN_BENCH_TRACE") == "1"
         for i in range(max_batches):
             nb = int(min(10, max(2, round(30.0 / max(ms_guess[0], 0.3)))))
+            if args.dump_outputs:  # whole turns of the distinct batches: the last timed step trains on the same one every run
+                nb = K_batches * -(-nb // K_batches)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for _ in range(nb):
@@ -906,6 +959,13 @@ def main():
             step()
         if not args.no_settle:
             settle()
+        if args.dump_outputs:
+            # the dropout seeds are drawn from per-process call counters: restart them, so that the masks of the timed steps
+            # do not depend on how many steps settle() took
+            from tf2_gnn_amd.layers.nodes_to_graph_representation import MLP
+
+            gnn._dropout_calls = 0
+            MLP._seed_counter[0] = 0
         barrier()
         c0 = ops.launch_counts()
         t0 = time.perf_counter()
@@ -926,6 +986,9 @@ def main():
 
     ops.set_gemm_mode(args.gemm_mode)
     elapsed = timed(args.warmup, args.steps)
+    if args.dump_outputs and rank == 0:
+        variables = list(gnn.trainable_variables) + (list(pool.trainable_variables) if pool is not None else [])
+        dump_outputs(args.dump_outputs, {**{k: v.cpu() for k, v in last_step.items() if v is not None}, **grads_of(variables)})
     ms_per_step_per_rank = [1000.0 * t / args.steps for t in per_rank_seconds]
     # the spread guard of the f16x2 products (tfgnn_sp_spread_flag) demotes the mode to bf16x3 when it trips: the timed steps
     # must have run in the mode the line reports

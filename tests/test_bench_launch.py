@@ -101,3 +101,30 @@ def test_plumbing_run_prints_detail_before_the_final_line():
     assert any(l.startswith("BENCH_DETAIL {") for l in lines[:-1])
     last = json.loads(lines[-1])
     assert last["n_gpus"] == 2 and last["config"]["rccl"]["backend"] == "gloo" and last["config"]["rccl"]["world_size_reported"] == 2
+
+
+def test_dump_outputs_keeps_small_arrays_whole_and_samples_the_rest_the_same_way(tmp_path):
+    """bench.dump_outputs: float32 .npy files of at most 64 MB in all; past that the large arrays keep a row sample drawn
+    from a seed of their name (the same rows in every run), the small ones stay whole."""
+    import numpy as np
+
+    import bench
+
+    rng = np.random.default_rng(0)
+    arrays = {"node_representations": rng.standard_normal((60000, 320)), "grad_000_gnn/kernel:0": rng.standard_normal((320, 320)),
+              "loss": np.array([0.5])}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["grad_000_gnn_kernel_0.npy", "loss.npy", "node_representations.npy"]
+    out = {n: np.load(tmp_path / "a" / n) for n in names}
+    assert all(a.dtype == np.float32 for a in out.values())
+    assert sum(a.nbytes for a in out.values()) <= bench.DUMP_LIMIT_BYTES
+    assert out["grad_000_gnn_kernel_0.npy"].shape == (320, 320) and out["loss.npy"].shape == (1,)
+    sample = out["node_representations.npy"]
+    assert 40000 < sample.shape[0] < 60000 and sample.shape[1] == 320
+    assert all(np.array_equal(a, np.load(tmp_path / "b" / n)) for n, a in out.items())
+    # every sampled row is a row of the array, in order
+    full = arrays["node_representations"].astype(np.float32)
+    idx = [int(np.flatnonzero((full[:, 0] == r[0]) & (full[:, 1] == r[1]))[0]) for r in sample[:50]]
+    assert idx == sorted(idx) and all(np.array_equal(full[i], r) for i, r in zip(idx, sample[:50]))

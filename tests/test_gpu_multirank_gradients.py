@@ -62,12 +62,14 @@ def test_sharded_step_with_the_k_split_products_of_small_shards(tmp_path):
 
 
 @pytest.mark.timeout(600)
-def test_eight_ranks_on_one_device_rendezvous_and_run():
-    """bench.py --gpus 8 with all ranks on cuda:0: the self-spawn / rendezvous / port path of the 8-GPU driver run."""
+def test_four_ranks_on_one_device_rendezvous_and_run():
+    """bench.py --gpus 4 with all ranks on cuda:0: the self-spawn / rendezvous / port path of the multi-GPU driver run through
+    the HIP step.  Four ranks: with this process they are five on the device, and a shared device takes at most six processes
+    at once (the spawn and rendezvous do not depend on the rank count)."""
     env = dict(os.environ, TFGNN_BENCH_SINGLE_DEVICE="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--workload", "qm9-tiny", "--steps", "2",
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--workload", "qm9-tiny", "--steps", "2",
                           "--warmup", "1", "--no-settle", "--no-cpu-baseline", "--no-alt-mode", "--no-roofline", "--no-other-configs",
                           "--allreduce-grads"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=500)
@@ -75,5 +77,5 @@ def test_eight_ranks_on_one_device_rendezvous_and_run():
     line = [l for l in res.stdout.splitlines() if l.startswith("{")]
     assert len(line) == 1
     r = json.loads(line[0])
-    assert r["n_gpus"] == 8 and len(r["config"]["edges_per_rank"]) == 8 and r["value"] > 0
-    assert len(r["config"]["ms_per_step_per_rank"]) == 8
+    assert r["n_gpus"] == 4 and len(r["config"]["edges_per_rank"]) == 4 and r["value"] > 0
+    assert len(r["config"]["ms_per_step_per_rank"]) == 4

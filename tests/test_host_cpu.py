@@ -247,13 +247,24 @@ def test_round5_host_side_queries_and_validation_without_gpu():
     two = lib.tfgnn_sp_gemm_tn_wide_workspace_bytes(1280, 320, 30000, 1280, 320)
     assert one > 1280 * 320 * 4 and two > 1280 * 320 * 4
     assert ops.TN_WIDE_MAX_ROWS == 512 * ops.TN_GROUPED_MAX_CHUNK == 512 * 2016
-    # the in-launch K split is a host-side switch with counters (no device needed to flip and read it)
-    import ctypes
+    # the in-launch K split is a host-side switch with counters (no device needed to flip and read it).  Its state belongs to
+    # the process, and GPU tests earlier in the same run set a workspace and split products: read it in a fresh interpreter
+    import subprocess
+    import sys
 
-    timed_out, launches = ctypes.c_int(-1), ctypes.c_int64(-1)
-    assert lib.tfgnn_sp_gemm_nt_splitk_status(-1, ctypes.byref(timed_out), ctypes.byref(launches)) == 0  # no workspace set: no splits
-    assert timed_out.value == 0 and launches.value == 0
-    assert lib.tfgnn_sp_gemm_nt_splitk_status(0, None, None) == 0 and lib.tfgnn_sp_gemm_nt_splitk_status(1, None, None) == 0
+    code = ("import ctypes\n"
+            "from tf2_gnn_amd import _lib\n"
+            "lib = _lib.load()\n"
+            "timed_out, launches = ctypes.c_int(-1), ctypes.c_int64(-1)\n"
+            "status = lib.tfgnn_sp_gemm_nt_splitk_status(-1, ctypes.byref(timed_out), ctypes.byref(launches))\n"
+            "print(status, timed_out.value, launches.value, lib.tfgnn_sp_gemm_nt_splitk_status(0, None, None),\n"
+            "      lib.tfgnn_sp_gemm_nt_splitk_status(1, None, None))\n")
+    res = subprocess.run([sys.executable, "-c", code], cwd=str(ROOT), capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stderr[-2000:]
+    status, timed_out, launches, off, on = map(int, res.stdout.split())
+    assert status == 0  # no workspace set: no splits
+    assert timed_out == 0 and launches == 0
+    assert off == 0 and on == 0
     assert not hasattr(lib, "tfgnn_sp_gemm_nt_balance")  # round 6: the rejected heavy-tile helpers left the ABI (version 4)
     # grouped TN: null operands, then an unsupported width (N must tile: 128 / 256 / 320 columns)
     args = [512, 512, None, 2048, None, 512, 512, None, 2048, None, 2, None, 4, None, None, 512 * 512, 512, 1, None, 0, None]
