@@ -1,6 +1,7 @@
 """The parity tests of the benchmarked configuration with the hot products in the f16x2 mode (pre-split SP16 operands,
 csrc/gemm_sp.hip; everything else as in bf16x3).  Same oracles, same 1e-5 tolerance: the mode changes how the fp32 product
 is evaluated, not the contract."""
+import numpy as np
 import pytest
 import torch
 
@@ -405,6 +406,46 @@ def test_edge_mlp_first_layer_gradients_run_on_split_operands(dev, monkeypatch):
     with KernelsUsed() as k:
         check_layer_backward(dev, "edge_mlp_first_layer_exact", "GNN_Edge_MLP", {}, V=384, E=4200, L=5, H=128)
     assert k.delta["gather_sp"] == 0 and k.delta["sp_tn"] == 0, k.delta
+
+
+@pytest.mark.parametrize("V,E,local", [(384, 1200, False), (4100, 1200, True)], ids=["type_empty", "type_empty_below_2016"])
+def test_edge_mlp_first_layer_gradients_with_an_empty_type_and_gradient_rows_far_apart(dev, V, E, local):
+    """The first-layer route above with H0 = 320 and two edge types - one 128-column tile of the two-factor product holds the
+    end of type 0's block and the start of type 1's - where type 1 has no edges (or, over V = 4100 nodes, none among the first
+    2016: its block of the typed gradient is zero over whole K ranges), and dOut's rows of half the nodes (of the first 2016) are
+    2^-32 .. 2^-34 of the rest: the typed gradient rows of many nodes sit >= 2^32 below their block's largest, pair deficits
+    within the 2^44 the guard allows.  (Sources outside the first 2016 nodes send their type-0 edges there as well: no node has
+    one type's row at full size and the other's 2^32 below it, which the guard rightly reports.)  Every kernel gradient finite,
+    type 1's first-layer kernel gradient exactly 0 where the oracle's is, fp64 parity for the rest, on the split-operand
+    kernels, mode kept, guard quiet."""
+    from tests.helpers import KernelsUsed, random_graph
+    from tf2_gnn_amd import ops
+
+    L, H = 2, 320
+    rng = np.random.default_rng(12)
+    if local:
+        src = rng.integers(0, V, size=E // 2)
+        dst = np.where(src >= 2016, rng.integers(2016, V, size=E // 2), rng.integers(0, V, size=E // 2))
+        adjs = [np.stack([src, dst], axis=1).astype(np.int32), rng.integers(2016, V, size=(E // 2, 2)).astype(np.int32)]
+    else:
+        adjs = random_graph(V, E, L, seed=12, empty_types=(1,))
+    g = torch.Generator().manual_seed(V)
+    low = (torch.rand(V, generator=g) < 0.5) & (torch.arange(V) < 2016)
+    row_scale = torch.where(low, torch.exp2(-torch.randint(32, 35, (V,), generator=g).double()), torch.ones(V, dtype=torch.float64))
+    with KernelsUsed() as k:
+        # (gelu after the aggregation: nodes without incoming edges do not put a relu kink at 0; E x H0 relu units of the MLP
+        # leave kink-free inputs to find)
+        layer = check_layer_backward(dev, f"edge_mlp_first_layer_empty_type_v{V}", "GNN_Edge_MLP", {"message_activation_function": "gelu"},
+                                     V=V, E=E, L=L, H=H, adjs=adjs, dout_row_scale=row_scale.float())
+    assert k.delta["gather_sp"] >= 2 and k.delta["sp_tn"] >= 2, k.delta
+    for v in layer.trainable_variables:
+        assert bool(torch.isfinite(v.grad).all()), v.name
+    first_empty = layer._edge_type_mlps.vars[1][0].grad
+    if local:
+        assert bool(first_empty.any())
+    else:
+        assert not bool(first_empty.any())
+    assert ops.get_gemm_mode() == ops.GEMM_F16X2 and not ops.f16x2_guard_tripped_sync()
 
 
 @pytest.mark.parametrize("dout_scale", [1e-9, 1e4])

@@ -204,10 +204,11 @@ def test_layer_backward_parity(dev, name, cls_name, over):
     check_layer_backward(dev, name, cls_name, over, V=120, E=1500, L=3, H=32)
 
 
-def check_layer_backward(dev, name, cls_name, over, V, E, L, H, dout_scale=1.0, adjs=None):
+def check_layer_backward(dev, name, cls_name, over, V, E, L, H, dout_scale=1.0, adjs=None, dout_row_scale=None):
     """dout_scale: the HIP backward pass gets dOut * dout_scale (a real loss gradient is 1e-9, not N(0,1))
     and its gradients are scaled back before the comparison - the reference gradients are linear in dOut, so every bound
-    stays relative to the gradient's OWN magnitude."""
+    stays relative to the gradient's OWN magnitude.  dout_row_scale [V]: dOut's rows multiplied by it, for both the HIP pass and
+    the references (nodes whose gradients are orders of magnitude apart).  Returns the layer."""
     from tf2_gnn_amd.layers import MessagePassingInput
 
     if adjs is None:
@@ -216,6 +217,8 @@ def check_layer_backward(dev, name, cls_name, over, V, E, L, H, dout_scale=1.0, 
     layer, p = _build(cls_name, dict(over, hidden_dim=H), H, L)
     w32 = mp_weights_from_layer(layer)
     X, dOut = draw_inputs_clear_of_kinks(lambda x: orc.message_passing_call(cls_name, p, _to64(w32), x.double(), adj_t), V, H, 11)
+    if dout_row_scale is not None:
+        dOut = dOut * dout_row_scale.unsqueeze(-1)
     out = layer(MessagePassingInput(X.to(dev), to_dev(adjs, dev)), training=True)
     dX = layer.backward((dOut * dout_scale).to(dev)) / dout_scale
 
@@ -291,6 +294,7 @@ def check_layer_backward(dev, name, cls_name, over, V, E, L, H, dout_scale=1.0, 
         # evaluation itself is further from fp64 than that - at most `slack` times its error
         err32 = scaled_error(ref32_by_id[id(t)] / scale, rv / scale)
         assert_close(v.grad.cpu() / (scale * dout_scale), (rv / scale).float(), tol=max(1e-5, slack * err32), what=f"{name} d{v.name}")
+    return layer
 
 
 def _gnn_oracle_weights(gnn):

@@ -350,7 +350,7 @@ __device__ __forceinline__ void sp_tn_factors_body(const AuxTnFactors& a, unsign
   bool wide = false;
   for (int64_t k = chunk * per + threadIdx.x; k < kend; k += 256) {
     const float ia = k < a.K ? a.inv_a[k * a.ld_a + b] : 0.f, ib = (k < a.K && a.inv_b) ? a.inv_b[k * a.ld_b] : 1.f;
-    const float f = ia * ib * r;
+    const float f = sp_row_holds(ia, ib) ? ia * ib * r : 0.f;
     a.F[(int64_t)b * a.f_ld + k] = (_Float16)f;
     wide |= sp_row_too_small(f, ia, ib);  // the spread guard of sp_tn_factors_kernel (gemm_sp.hip)
   }

@@ -980,7 +980,7 @@ __global__ void __launch_bounds__(1024) sp_tn_factors_kernel(const float* __rest
   bool wide = false;
   for (int64_t k = chunk * per + threadIdx.x; k < kend; k += 1024) {
     const float ia = k < K ? inv_a[k * ld_a + b] : 0.f, ib = (k < K && inv_b) ? inv_b[k * ld_b] : 1.f;
-    const float f = ia * ib * r;
+    const float f = sp_row_holds(ia, ib) ? ia * ib * r : 0.f;
     F[(int64_t)b * f_ld + k] = (_Float16)f;
     // a NON-ZERO row more than 2^20 below the block's largest scale product (all-zero rows carry the smallest normal
     // scale, 2^-126: their factor is 0 and they contribute nothing).  Below 2^-13 a row's elements start to keep fewer
@@ -1294,7 +1294,7 @@ __global__ void __launch_bounds__(SP_NT, 1) gemm_sp_tn_kernel(SpTnArgs g) {
   if constexpr (FIK) {
     // ---- the factors of this workgroup's K range (while the first stages are in flight) --------------------------------
     // p[k][j] = inv_a[k0 + k, blk_first + j] * inv_b[k0 + k]; ref[j] = max_k p (1 if all zero); table[step][j][k % 16] =
-    // fp16(p / ref[j]) - powers of two, exact down to 2^-24, 0 below and past the range's end
+    // fp16(p / ref[j]) - powers of two, exact down to 2^-24, 0 below, past the range's end and for marker rows (sp_row_holds)
     _Float16* ftab = reinterpret_cast<_Float16*>(lds + G::FTAB);
     float (*fmx)[4] = reinterpret_cast<float (*)[4]>(lds + G::FTAB + SP_TN_FTAB_BYTES - 128);  // [4 waves][4 blocks]
     float* fref = reinterpret_cast<float*>(lds + G::FTAB + SP_TN_FTAB_BYTES - 64);            // 1 / reference of block j
@@ -1349,6 +1349,9 @@ __global__ void __launch_bounds__(SP_NT, 1) gemm_sp_tn_kernel(SpTnArgs g) {
         // every bit of its high pieces (2^-13 each), the absolute error of a row's term shrinks with the row (<= 2^-25 - e/2
         // of the largest term: a scaled low piece's rounding times the OTHER, scaled, operand) instead of staying 2^-25, and
         // the guard's 2^-22 per factor is reached at 2^-44 for the pair.
+        // Blocks that hold nothing at k (all zero, or below the 2^-112 floor: the marker scale 2^-126) get the factor 0: a block
+        // that is all zero over the whole K range has the reference 2^-126, so fa = 1 in every row, and fa * up reaches 2^16
+        // (fp16 inf; times the zero fragments: NaN) wherever the other blocks' rows at k sit 2^32 below their maxima.
         float fa[4], famax = 0.f;
         bool anz[4];
 #pragma unroll
@@ -1378,7 +1381,7 @@ __global__ void __launch_bounds__(SP_NT, 1) gemm_sp_tn_kernel(SpTnArgs g) {
         wide |= bnz && famax > 0.f && fb2 < 2.384185791015625e-07f;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float f = fa[j] * up;
+          const float f = anz[j] ? fa[j] * up : 0.f;
           ftab[(k >> 4) * FH + j * 16 + (k & 15)] = (_Float16)f;
           wide |= anz[j] && bnz && f < 2.384185791015625e-07f;
         }
@@ -1388,7 +1391,7 @@ __global__ void __launch_bounds__(SP_NT, 1) gemm_sp_tn_kernel(SpTnArgs g) {
           float f = 0.f, ia = 0.f;
           if (j < nb && k < krows) {
             ia = g.inv_a[(k0 + k) * g.a_nblk + blk_first + j];
-            f = ia * ib * fref[j];  // powers of two: exact
+            f = sp_row_holds(ia, ib) ? ia * ib * fref[j] : 0.f;  // powers of two: exact
           }
           ftab[(k >> 4) * FH + j * 16 + (k & 15)] = (_Float16)f;
           // the spread guard (see sp_tn_factors_kernel), relative to the largest scale (product) of THIS K range

@@ -35,6 +35,12 @@ __device__ __forceinline__ bool sp_row_too_small(float f, float inv_a, float inv
   return f < 9.5367431640625e-07f && inv_a > 1.2e-38f && inv_b > 1.2e-38f;
 }
 
+// does the pair of rows hold anything (neither carries the marker 2^-126)?  Only then does the one-factor product give it the
+// factor inv_a inv_b / ref; otherwise 0.  A block that is all zero over the whole K range has the reference 2^-126 * max inv_b,
+// whose inverse overflows to inf for any inv_b <= 2^-2 (row maxima below 2^13): its factors would be inf, and inf times its zero
+// fragments NaN.  Marker rows contribute nothing by design (zero fragments, or entries below the 2^-112 floor).
+__device__ __forceinline__ bool sp_row_holds(float inv_a, float inv_b) { return inv_a > 1.2e-38f && inv_b > 1.2e-38f; }
+
 __device__ __forceinline__ void sp_split(float xs, _Float16& h, _Float16& l) {
   h = (_Float16)xs;  // v_cvt_f16_f32: round to nearest even
   const float r = xs - (float)h;
