@@ -1039,6 +1039,64 @@ int tfgnn_mp_forward(const tfgnn_mp_forward_args* args, void* stream);
 /* = tfgnn_graph_gather_reduce_sp_deferred + tfgnn_sp_split_rows_job + tfgnn_aux_launch + tfgnn_sp_gemm_nt_rows + tfgnn_sp_gemm_tn */
 int tfgnn_mp_backward(const tfgnn_mp_backward_args* args, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Optimizer step (csrc/optim.hip): GraphTaskModel._apply_gradients (models/graph_task_model.py:279-324) with the optimizers
+ * of _make_optimizer (:224-277) - [ext] TF 2.x optimizer_v2 arithmetic, fp32:
+ *   SGD      momentum > 0: accum = accum * mu - lr * g;  w += accum          momentum 0: w -= lr * g
+ *   RMSprop  momentum > 0: ms += (g^2 - ms)(1 - rho);  mom = mom * mu + lr * g * rsqrt(ms + eps);  w -= mom
+ *            momentum 0:   ms = rho * ms + (1 - rho) g^2;  w -= lr * g / (sqrt(ms) + eps)          (non-centered)
+ *   Adam     t = iterations + 1, alpha = lr * sqrt(1 - b2^t) / (1 - b1^t);
+ *            m += (g - m)(1 - b1);  v += (g^2 - v)(1 - b2);  w -= m * alpha / (sqrt(v) + eps)
+ * after clipping the gradients (:296-322): by value (clip_by_value), per-tensor norm (g * c / max(|g|, c)) or global norm
+ * (g * c * min(1 / N, 1 / c), N the root of the sum of squares over every tensor of the call; N inf or NaN gives NaN).
+ * The learning rate is computed ON THE DEVICE from the step counter `iterations` (state[0]): constant, or the polynomial
+ * warm-up / decay schedule (utils/polynomial_warmup_and_decay_schedule.py:90-111) at step = (float)iterations, in fp32.
+ * Every call advances the counter once, so a call captured into a hipGraph follows the schedule on every replay.
+ *
+ * One call updates every tensor given to it: one launch per chunk of 32 tensors, and with a norm mode first one more launch
+ * per chunk that writes per-workgroup partial sums of squares to the workspace (reduced in a fixed order by the update:
+ * bit-reproducible, no float atomics).  The counter is advanced by the last workgroup to finish the last update launch
+ * (an integer ticket in state[1]), after every workgroup of the call has read it.
+ * ------------------------------------------------------------------------------------------ */
+typedef enum { TFGNN_OPT_SGD = 0, TFGNN_OPT_RMSPROP = 1, TFGNN_OPT_ADAM = 2 } tfgnn_opt_kind;
+typedef enum { TFGNN_CLIP_NONE = 0, TFGNN_CLIP_VALUE = 1, TFGNN_CLIP_NORM = 2, TFGNN_CLIP_GLOBAL_NORM = 3 } tfgnn_clip_mode;
+/* one variable and its gradient as 2-D row-major views (a 1-D tensor is one row): element (r, c) at value[r * ld_value + c] and
+ * grad[r * ld_grad + c], so column slices of a fused buffer are described in place.  The slots are contiguous [rows * cols]
+ * fp32 arrays owned by the optimizer, zero before the first call: SGD slot0 = accumulator (momentum > 0 only); RMSprop
+ * slot0 = mean square, slot1 = momentum (momentum > 0 only); Adam slot0 = m, slot1 = v.  Unused slots may be NULL. */
+typedef struct tfgnn_opt_tensor {
+  float* value;
+  int64_t ld_value;
+  const float* grad;
+  int64_t ld_grad;
+  int64_t rows;
+  int64_t cols;
+  float* slot0;
+  float* slot1;
+} tfgnn_opt_tensor;
+typedef struct tfgnn_opt_config {
+  size_t struct_size; /* sizeof(tfgnn_opt_config) */
+  int kind;           /* tfgnn_opt_kind */
+  int clip;           /* tfgnn_clip_mode */
+  float clip_value;   /* > 0 when clip != TFGNN_CLIP_NONE */
+  float momentum;     /* SGD, RMSprop: in [0, 1] */
+  float rho;          /* RMSprop */
+  float beta_1, beta_2, epsilon; /* Adam (beta_*), RMSprop and Adam (epsilon) */
+  int schedule;       /* 0: constant learning_rate; 1: polynomial warm-up and decay */
+  float learning_rate, initial_learning_rate, final_learning_rate, power;
+  int64_t warmup_steps, decay_steps;
+  int64_t* state;     /* device, 16 bytes, zero-initialised: [0] iterations, [1] ticket of the last update launch */
+  void* workspace;    /* tfgnn_optimizer_workspace_bytes(...) bytes (norm modes), 16-byte aligned */
+  size_t workspace_bytes;
+} tfgnn_opt_config;
+size_t tfgnn_optimizer_workspace_bytes(const tfgnn_opt_tensor* tensors, int n, int clip);
+int tfgnn_optimizer_apply(const tfgnn_opt_tensor* tensors, int n, const tfgnn_opt_config* config, void* stream);
+/* state[0] -> *out (device or host-mapped memory) / state[0] = value, state[1] = 0: one-thread kernels, capturable */
+int tfgnn_optimizer_iterations_get(const int64_t* state, int64_t* out, void* stream);
+int tfgnn_optimizer_iterations_set(int64_t* state, int64_t value, void* stream);
+/* host-side count of the kernel launches tfgnn_optimizer_apply has enqueued in this process (tests) */
+int64_t tfgnn_optimizer_launch_count(void);
+
 #ifdef __cplusplus
 }
 #endif

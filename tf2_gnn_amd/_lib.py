@@ -332,6 +332,15 @@ _SIGNATURES += [
     ("tfgnn_mp_backward", c_int, [c_void_p, c_void_p]),
 ]
 
+# optimizer step (include/tfgnn.h "Optimizer step", csrc/optim.hip): descriptors and config travel by pointer
+_SIGNATURES += [
+    ("tfgnn_optimizer_workspace_bytes", c_size_t, [c_void_p, c_int, c_int]),
+    ("tfgnn_optimizer_apply", c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    ("tfgnn_optimizer_iterations_get", c_int, [c_void_p, c_void_p, c_void_p]),
+    ("tfgnn_optimizer_iterations_set", c_int, [c_void_p, c_int64, c_void_p]),
+    ("tfgnn_optimizer_launch_count", c_int64, []),
+]
+
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
 ABI_VERSION = 4  # include/tfgnn.h TFGNN_ABI_VERSION
 
@@ -369,6 +378,19 @@ class MpBackwardArgs(ctypes.Structure):
         ("row_map", c_void_p), ("dw", c_void_p), ("x_sp", c_void_p), ("ld_x_sp_bytes", c_int64), ("x_inv_scale", c_void_p),
         ("tn_workspace", c_void_p), ("tn_workspace_bytes", ctypes.c_size_t), ("extra_jobs", c_void_p), ("num_extra_jobs", c_int),
         ("workspace", c_void_p), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
+class OptConfig(ctypes.Structure):
+    """tfgnn_opt_config (include/tfgnn.h), field for field.  The tensors go in as an int64 array [n, 8] laid out like
+    tfgnn_opt_tensor (value, ld_value, grad, ld_grad, rows, cols, slot0, slot1)."""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t), ("kind", c_int), ("clip", c_int), ("clip_value", c_float), ("momentum", c_float),
+        ("rho", c_float), ("beta_1", c_float), ("beta_2", c_float), ("epsilon", c_float), ("schedule", c_int),
+        ("learning_rate", c_float), ("initial_learning_rate", c_float), ("final_learning_rate", c_float), ("power", c_float),
+        ("warmup_steps", c_int64), ("decay_steps", c_int64), ("state", c_void_p), ("workspace", c_void_p),
+        ("workspace_bytes", ctypes.c_size_t),
     ]
 
 

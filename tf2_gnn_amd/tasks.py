@@ -6,8 +6,9 @@ Mirrors ``tf2_gnn.models`` for that computation only: ``compute_final_node_repre
 of ``GraphDataset._finalise_batch``: "node_features", "adjacency_list_<i>", "node_to_graph_map",
 "num_graphs_in_batch"; labels "node_labels" / "target_value") and result keys.  ``backward()`` stands in for the
 ``tf.GradientTape`` of ``GraphTaskModel._run_step`` (tf2_gnn/models/graph_task_model.py:327-357): it fills ``.grad``
-of every trainable variable with d loss / d variable.  The optimizer, the epoch loop, datasets and checkpoint I/O are
-the reference's control plane and stay out (out of scope).
+of every trainable variable with d loss / d variable.  The parameter update of that step (``_make_optimizer``,
+``_apply_gradients``: clipping + a Keras optimizer, optim.py) and the step / epoch methods around it (``_run_step``,
+``run_one_epoch``) are here too; the training CLI, datasets and checkpoint I/O stay out (out of scope).
 
 MLP-input dropout of the heads (``regression_mlp_dropout``, ``graph_aggregation_dropout_rate``; QM9 hands
 ``out_layer_dropout_keep_prob`` over as a rate) is applied in training mode as in the pooling layers (layers/nodes_to_graph_representation.py MLP).
@@ -16,9 +17,12 @@ from __future__ import annotations
 
 from typing import Any, Dict, List, Optional, Tuple
 
+import time
+
 import torch
 
 from . import _lib, ops
+from .optim import Optimizer, make_optimizer
 from .layers.gnn import GNN, GNNInput
 from .layers.message_passing.message_passing import Variable, default_device, glorot_uniform
 from .layers.nodes_to_graph_representation import (
@@ -31,7 +35,7 @@ from .layers.nodes_to_graph_representation import (
 
 
 class GraphTaskModel:
-    """tf2_gnn/models/graph_task_model.py:14-222 without the Keras / optimizer / epoch-loop plumbing."""
+    """tf2_gnn/models/graph_task_model.py:14-399 without the Keras plumbing."""
 
     @classmethod
     def get_default_hyperparameters(cls, mp_style: Optional[str] = None) -> Dict[str, Any]:
@@ -67,6 +71,10 @@ class GraphTaskModel:
         self._gnn: Optional[GNN] = None
         self.built = False
         self._step = None  # what backward() needs from the last forward / metrics call
+        self._optimizer: Optional[Optimizer] = None
+        # graph_task_model.py:50: training steps taken by _run_step (host-side; not saved, the reference saves weights only).
+        # A replayed CapturedStep does not advance it - the optimizer's device counter ``iterations`` does.
+        self._train_step_counter = 0
 
     # ---- structure (graph_task_model.py:93-131) --------------------------------------------------------------
     def build(self, input_shapes: Dict[str, Any]):
@@ -146,6 +154,75 @@ class GraphTaskModel:
 
     def _task_backward(self):
         raise NotImplementedError
+
+    # ---- the update (graph_task_model.py:224-324) -------------------------------------------------------------------
+    def _make_optimizer(self, learning_rate=None) -> Optimizer:
+        """A fresh optimizer from the hyper-parameters (optimizer name, learning rate and its warm-up / decay steps, momentum,
+        rmsprop_rho), or with the given learning rate (a float or a PolynomialWarmupAndDecaySchedule)."""
+        return make_optimizer(self._params, learning_rate)
+
+    def _apply_gradients(self, gradient_variable_pairs) -> None:
+        """Clip and apply gradients - ``(variable, grad)`` pairs as ``backward()`` returns them, or the reference's
+        ``(grad, variable)`` - with the model's optimizer (made at the first call).  One library call; no synchronisation."""
+        if getattr(self, "_optimizer", None) is None:
+            self._optimizer = self._make_optimizer()
+        clip_val = self._params.get("gradient_clip_value")
+        clip_norm_val = self._params.get("gradient_clip_norm")
+        clip_global_norm_val = self._params.get("gradient_clip_global_norm")
+        clip = None
+        if clip_val is not None:
+            if clip_norm_val is not None:
+                raise ValueError("Both 'gradient_clip_value' and 'gradient_clip_norm' are set, but can only use one at a time.")
+            if clip_global_norm_val is not None:
+                raise ValueError("Both 'gradient_clip_value' and 'gradient_clip_global_norm' are set, but can only use one at a time.")
+            clip = ("value", clip_val)
+        elif clip_norm_val is not None:
+            if clip_global_norm_val is not None:
+                raise ValueError("Both 'gradient_clip_norm' and 'gradient_clip_global_norm' are set, but can only use one at a time.")
+            clip = ("norm", clip_norm_val)
+        elif clip_global_norm_val is not None:
+            clip = ("global_norm", clip_global_norm_val)
+        self._optimizer.apply_gradients(gradient_variable_pairs, clip=clip)
+
+    # ---- training loop (graph_task_model.py:327-399) ------------------------------------------------------------------
+    def _run_step(self, batch_features, batch_labels, training: bool) -> Dict[str, Any]:
+        """Forward pass and metrics; when ``training``, the gradients and the update too."""
+        task_output = self(batch_features, training=training)
+        task_metrics = self.compute_task_metrics(batch_features=batch_features, task_output=task_output, batch_labels=batch_labels)
+        if training:
+            self._apply_gradients(self.backward())
+            self._train_step_counter += 1
+        return task_metrics
+
+    def run_one_epoch(self, dataset, quiet: bool = False, training: bool = True) -> Tuple[float, float, List[Any]]:
+        """One pass over ``dataset`` (an iterable of ``(batch_features, batch_labels)``) -> (average loss per graph, graphs per
+        second, the metrics of every step)."""
+        epoch_time_start = time.time()
+        total_num_graphs = 0
+        task_results = []
+        total_loss = 0.0
+        for step, (batch_features, batch_labels) in enumerate(dataset):
+            task_metrics = self._run_step(batch_features, batch_labels, training)
+            # task_metrics["loss"] is the batch average loss over graphs
+            num_graphs = int(batch_features["num_graphs_in_batch"])
+            total_loss = total_loss + task_metrics["loss"] * float(num_graphs)
+            total_num_graphs += num_graphs
+            task_results.append(task_metrics)
+            if not quiet:
+                epoch_graph_average_loss = float(total_loss) / float(total_num_graphs)
+                batch_graph_average_loss = float(task_metrics["loss"])
+                steps_per_second = step / (time.time() - epoch_time_start)
+                print(
+                    f"   Step: {step:4d}"
+                    f"  |  Epoch graph avg. loss = {epoch_graph_average_loss:.5f}"
+                    f"  |  Batch graph avg. loss = {batch_graph_average_loss:.5f}"
+                    f"  |  Steps per sec = {steps_per_second:.5f}",
+                    end="\r",
+                )
+        if not quiet:
+            print("\r\x1b[K", end="")
+        total_time = time.time() - epoch_time_start
+        return float(total_loss) / float(total_num_graphs), float(total_num_graphs) / total_time, task_results
 
 
 class NodeMulticlassTask(GraphTaskModel):
