@@ -59,8 +59,10 @@ const char* tfgnn_last_error(void);
 const char* tfgnn_version(void);
 /* Bumped whenever an existing entry point changes its signature or meaning (round 4: 2 - tfgnn_gemm_grad_epilogue gained
  * `accumulate` in round 3, tfgnn_gemm_get_mode can return TFGNN_GEMM_F16X2, the bucketing keeps list order inside a bucket).
+ * 5: tfgnn_sp_gemm_tn_wide lost its job argument, the layer-level argument structs lost their pending-job fields, and four
+ * entry points of rejected variants (staged weight-gradient products, a batched weight split) were removed.
  * A binding compares tfgnn_abi_version() with the TFGNN_ABI_VERSION it was written against (tf2_gnn_amd/_lib.py does). */
-#define TFGNN_ABI_VERSION 4
+#define TFGNN_ABI_VERSION 5
 int tfgnn_abi_version(void);
 
 /* Diagnostics (no reference counterpart): number of launches of each product-kernel family this process has enqueued
@@ -658,13 +660,6 @@ int tfgnn_sp_split_rows(const float* d_src, int64_t ld, int64_t seg_len, int64_t
                         const float* d_fixed_inv_scale, void* stream);
 int tfgnn_sp_split_cols(const float* d_src, int64_t ld, int64_t K, int64_t N, void* d_sp, int64_t ld_sp_bytes,
                         float* d_inv_scale, void* stream);
-/* Both operand forms of `count` (<= 16) stacked kernels [L, D, H] of one shape in a single launch - the per-step weight
- * preparation of a layer stack (after an optimizer update every kernel has to be split again; 2 x layers latency-bound
- * launches otherwise): h_cols_sp[i] receives tfgnn_sp_split_cols of the [L D, H] view (rows = H, cols = L D),
- * h_rows_sp[i] tfgnn_sp_split_rows of [W_0 | ... | W_{L-1}] (rows = D, cols = L H), each with one scale per row.  The
- * pointer arrays are HOST arrays of device pointers. */
-int tfgnn_sp_split_weights(int count, const float* const* h_src, int64_t L, int64_t D, int64_t H, void* const* h_cols_sp,
-                           float* const* h_cols_inv_scale, void* const* h_rows_sp, float* const* h_rows_inv_scale, void* stream);
 int tfgnn_sp_gemm_nt(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, const float* d_a_inv_scale,
                      int a_scale_block, const void* d_B_sp, int64_t ldb_bytes, const float* d_b_inv_scale, float* d_C,
                      int64_t ldc, const float* d_bias, int act, int accumulate, const float* d_mul, int64_t ld_mul,
@@ -726,14 +721,14 @@ int tfgnn_sp_gather_rows(const void* d_src_sp, int64_t ld_src_bytes, const float
  * the spread flag is set beyond that (for pairs of non-zero rows).  For products whose rows are un-normalised sums on both sides (the
  * per-relation weight gradients of RGIN at arxiv scale: row scales over 2^19 and 2^21, their products over 2^25 - the combined
  * factor of tfgnn_sp_gemm_tn trips its 2^20 guard there).  Costs 2 (N / 32) packed multiplies more per k16 step (~+25 %) and
- * more K ranges (workspace: tfgnn_sp_gemm_tn_wide_workspace_bytes).  reduce_job non-NULL: the split reduction as a job of
- * tfgnn_aux_launch, as tfgnn_sp_gemm_tn_deferred.  d_b_inv_scale is required.  Same result layout arguments. */
+ * more K ranges (workspace: tfgnn_sp_gemm_tn_wide_workspace_bytes).  d_b_inv_scale is required.  Same result layout
+ * arguments. */
 size_t tfgnn_sp_gemm_tn_wide_workspace_bytes(int64_t M, int64_t N, int64_t K, int64_t a_total_cols, int a_scale_block);
 int tfgnn_sp_gemm_tn_wide(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, int64_t a_first_col,
                           const float* d_a_inv_scale, int64_t a_total_cols, int a_scale_block, const void* d_B_sp,
                           int64_t ldb_bytes, int64_t b_first_col, const float* d_b_inv_scale, float* d_C, int64_t group_rows,
                           int64_t stride_group, int64_t stride_row, int64_t stride_col, int accumulate, void* d_workspace,
-                          size_t workspace_bytes, struct tfgnn_aux_job* reduce_job, void* stream);
+                          size_t workspace_bytes, void* stream);
 
 /* The wide-range product over ROW GROUPS of the same two operands in one launch (round 5; the kernel gradients dW_g = A_g^T B_g
  * of the per-relation MLPs): d_split_table int32 [num_splits][2] = (first row, rows <= 2016) of every K range, ranges of a group
@@ -805,10 +800,9 @@ int tfgnn_sp_gemm_nt_dropout(int64_t M, int64_t N, int64_t K, const void* d_A_sp
  * tfgnn_sp_gemm_tn_workspace_bytes bytes. */
 /* ---- small passes that share a launch ------------------------------------------------------------------------------
  * Around the big kernels of a layer sit passes of 5-15 us each that are bound by launch and dependent-load latency, not by
- * work: weight matrices into SP16 form, the combine pass of the gather's long buckets, the split-K reduction of a weight
- * gradient.  A `tfgnn_aux_job` describes one of them; tfgnn_aux_launch runs up to 8 per launch (more: several launches),
- * every job on its own workgroups - the launch takes as long as its longest job.  Jobs of one call must be independent
- * of each other.  The *_job / *_deferred functions FILL a job (host memory, nothing is launched for it) with exactly the
+ * work: weight matrices into SP16 form, the combine pass of the gather's long buckets.  A `tfgnn_aux_job` describes one of
+ * them; tfgnn_aux_launch runs up to 8 per launch (more: several launches), every job on its own workgroups - the launch
+ * takes as long as its longest job.  Jobs of one call must be independent of each other.  The *_job / *_deferred functions FILL a job (host memory, nothing is launched for it) with exactly the
  * work the function of the same name without the suffix would have launched; a job holds device pointers - keep the
  * buffers alive until the launch has run.  (No reference counterpart: TensorFlow schedules these ops one kernel each.) */
 typedef struct tfgnn_aux_job {
@@ -837,22 +831,6 @@ int tfgnn_graph_gather_reduce_sp_deferred(const tfgnn_graph* graph, int view, co
                                           int64_t ld_in, int width, void* d_out_sp, int64_t ld_out_sp_bytes,
                                           float* d_inv_scale, const float* d_fixed_inv_scale, void* d_workspace,
                                           size_t workspace_bytes, tfgnn_aux_job* combine_job, void* stream);
-/* tfgnn_sp_gemm_tn with BOTH of its small passes as jobs (K <= 131072 rows; TFGNN_ERR_UNSUPPORTED above): nothing is
- * launched; run *factors_job in a merged launch, then tfgnn_sp_gemm_tn_phase(2, same arguments), then *reduce_job.  A weight
- * gradient is off the critical path of the backward pass, so the whole product can wait for the next merged launch. */
-int tfgnn_sp_gemm_tn_jobs(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, int64_t a_first_col,
-                          const float* d_a_inv_scale, int64_t a_total_cols, int a_scale_block, const void* d_B_sp,
-                          int64_t ldb_bytes, int64_t b_first_col, const float* d_b_inv_scale, float* d_C, int64_t group_rows,
-                          int64_t stride_group, int64_t stride_row, int64_t stride_col, int accumulate, void* d_workspace,
-                          size_t workspace_bytes, tfgnn_aux_job* factors_job, tfgnn_aux_job* reduce_job);
-/* tfgnn_sp_gemm_tn: factor pass (with_factors != 0) and product are launched, the split reduction (+ scatter into d_C) comes
- * back in *reduce_job - a weight gradient is not read before the end of the backward pass, so the reductions of all layers
- * can share one launch.  The workspace must stay untouched until that launch. */
-int tfgnn_sp_gemm_tn_deferred(int with_factors, int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes,
-                              int64_t a_first_col, const float* d_a_inv_scale, int64_t a_total_cols, int a_scale_block,
-                              const void* d_B_sp, int64_t ldb_bytes, int64_t b_first_col, const float* d_b_inv_scale, float* d_C,
-                              int64_t group_rows, int64_t stride_group, int64_t stride_row, int64_t stride_col, int accumulate,
-                              void* d_workspace, size_t workspace_bytes, tfgnn_aux_job* reduce_job, void* stream);
 
 size_t tfgnn_sp_gemm_tn_workspace_bytes(int64_t M, int64_t N, int64_t K, int64_t a_total_cols, int a_scale_block);
 /* Guard of the limit above: the factor pass of every tfgnn_sp_gemm_tn sets a library-wide flag (host-visible without a
@@ -869,15 +847,6 @@ int tfgnn_sp_gemm_tn(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_
                      int64_t ldb_bytes, int64_t b_first_col, const float* d_b_inv_scale, float* d_C, int64_t group_rows,
                      int64_t stride_group, int64_t stride_row, int64_t stride_col, int accumulate, void* d_workspace,
                      size_t workspace_bytes, void* stream);
-/* The three passes of tfgnn_sp_gemm_tn separately - phases is a mask of 1 (per-k factors from the two scale arrays), 2 (the
- * product into the workspace), 4 (split reduction + scaling + scatter into d_C) - with the SAME arguments and workspace in
- * every call: the factor pass only needs the scales and can run on another stream beside the product before it, the
- * reduction beside whatever follows (the caller orders the streams; the workspace must live until the last phase). */
-int tfgnn_sp_gemm_tn_phase(int phases, int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, int64_t a_first_col,
-                           const float* d_a_inv_scale, int64_t a_total_cols, int a_scale_block, const void* d_B_sp,
-                           int64_t ldb_bytes, int64_t b_first_col, const float* d_b_inv_scale, float* d_C, int64_t group_rows,
-                           int64_t stride_group, int64_t stride_row, int64_t stride_col, int accumulate, void* d_workspace,
-                           size_t workspace_bytes, void* stream);
 
 /* Tensor-wide scales (d_fixed_inv_scale of the SP16 producers; tfgnn_sp_gemm_nt takes such an operand with a_scale_block < 0):
  * tfgnn_absmax gives *d_out = max(*d_out, scale * max |x|)
@@ -948,8 +917,7 @@ int tfgnn_regression_metrics(const float* d_pred, const float* d_target, int64_t
  *
  * All pointers are device pointers unless named h_*; buffers are the caller's (sizes in comments, V = nodes, L = edge types
  * of the graph handle, D = in_dim, H = hidden_dim).  `struct_size` = sizeof of the struct (a binding built against another
- * header is rejected).  `extra_jobs`: small passes the caller has pending (tfgnn_*_job / *_deferred), launched with this
- * call's own in ONE tfgnn_aux_launch.
+ * header is rejected).
  * ------------------------------------------------------------------------------------------ */
 typedef enum {
   TFGNN_MP_AGGREGATE_FIRST = 0 /* linear message per edge type, aggregated before the per-relation product */
@@ -981,8 +949,6 @@ typedef struct tfgnn_mp_forward_args {
   void* out_sp;             /* optional: the result as a split operand [V, H] + out_inv_scale [V * (H / tile width)] */
   int64_t ld_out_sp_bytes;
   float* out_inv_scale;
-  const struct tfgnn_aux_job* extra_jobs;
-  int num_extra_jobs;
   void* workspace;          /* tfgnn_graph_gather_workspace_bytes(graph, view, D) bytes */
   size_t workspace_bytes;
 } tfgnn_mp_forward_args;
@@ -1028,8 +994,6 @@ typedef struct tfgnn_mp_backward_args {
   const float* x_inv_scale;
   void* tn_workspace;       /* tfgnn_sp_gemm_tn_workspace_bytes(L * H, D, V, L * H, H) bytes, 256-byte aligned */
   size_t tn_workspace_bytes;
-  const struct tfgnn_aux_job* extra_jobs;
-  int num_extra_jobs;
   void* workspace;          /* tfgnn_graph_gather_workspace_bytes(graph, TFGNN_VIEW_BY_SRC_TYPED, H) bytes */
   size_t workspace_bytes;
 } tfgnn_mp_backward_args;

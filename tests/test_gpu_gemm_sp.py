@@ -557,55 +557,6 @@ def test_gemm_tn_row_count_not_a_multiple_of_the_tile(dev, K, M, N):
     assert torch.equal(dW.cpu().t(), out)
 
 
-def test_batched_weight_split_equals_the_two_single_splits(dev):
-    """tfgnn_sp_split_weights: both operand forms of several [L, D, H] kernel stacks in one launch, bit-equal to
-    tfgnn_sp_split_cols / tfgnn_sp_split_rows, and found by sp_weight_operand without another split."""
-    from tf2_gnn_amd import ops
-
-    L, D, H = 4, 320, 320
-    g = torch.Generator().manual_seed(3)
-    stacks = [(torch.randn((L, D, H), generator=g) * (0.05 * (i + 1))).to(dev) for i in range(5)]
-    stacks[2][1, 7] = 0.0
-    ops.clear_weight_operand_cache()
-    ops.sp_split_weights(stacks)
-
-    def fail():
-        raise AssertionError("the batched split should have filled the cache")
-
-    for W in stacks:
-        c = ops.sp_weight_operand(W, "cols", fail)
-        r = ops.sp_weight_operand(W, "rows", fail)
-        c_ref = ops.sp_split_cols(W.view(L * D, H))
-        r_ref = ops.sp_split_rows(W[0], segments=(H, D * H, L * H))
-        assert torch.equal(c.data, c_ref.data) and torch.equal(c.inv_scale.view(-1), c_ref.inv_scale.view(-1))
-        assert torch.equal(r.data, r_ref.data) and torch.equal(r.inv_scale.view(-1), r_ref.inv_scale.view(-1))
-    stacks[0].mul_(2.0)  # an optimizer update: the cached forms of this stack are stale
-    fresh = ops.sp_weight_operand(stacks[0], "cols", lambda: ops.sp_split_cols(stacks[0].view(L * D, H)))
-    assert torch.equal(fresh.data, ops.sp_split_cols(stacks[0].view(L * D, H)).data)
-
-
-def test_gemm_tn_in_three_phases_on_two_streams_equals_the_single_call(dev):
-    """tfgnn_sp_gemm_tn_phase through ops.SpGemmTnOverlapped (factor pass and reduction on the library's second stream):
-    bit-identical to tfgnn_sp_gemm_tn."""
-    from tf2_gnn_amd import ops
-
-    g = torch.Generator().manual_seed(11)
-    K, M, N = 5000, 1280, 320
-    G = (torch.randn((K, M), generator=g) * 1e-3).to(dev)
-    X = torch.randn((K, N), generator=g).to(dev)
-    gs, xs = ops.sp_split_rows(G, scale_block=320), ops.sp_split_rows(X)
-    ref = torch.empty((4, 320, 320), device=dev)
-    ops.sp_gemm_tn(gs, xs, out=ref, scatter=(320, 320 * 320, 1, 320))
-    out = torch.zeros_like(ref)
-    h = ops.SpGemmTnOverlapped(gs, xs, out=out, scatter=(320, 320 * 320, 1, 320))
-    filler = ops.sp_gemm_nt(gs, ops.sp_split_rows(torch.randn((320, M), device=dev)))  # something for the factor pass to run beside
-    h.product()
-    h.finish()
-    ops.join_aux_stream()
-    torch.cuda.synchronize()
-    assert torch.equal(out, ref) and bool(torch.isfinite(filler).all())
-
-
 @pytest.mark.parametrize("C", [64, 128, 256])
 def test_narrow_row_split_equals_the_general_kernel(dev, C):
     """rows of 64 / 128 / 256 columns take a one-pass kernel from 4096 rows on: same bytes and scales as the general kernel
@@ -627,9 +578,8 @@ def test_narrow_row_split_equals_the_general_kernel(dev, C):
 
 
 def test_small_passes_sharing_one_launch_equal_their_stand_alone_kernels(dev, monkeypatch):
-    """tfgnn_aux_launch (round 4): weight splits, the combine pass of the gather's long buckets and the split-K reduction of a
-    weight-gradient product, deferred and run as jobs of ONE launch, give bit-identical results to the kernels of their own;
-    urgent jobs run before the next library call, non-urgent ones (the reduction) at the explicit flush."""
+    """tfgnn_aux_launch (round 4): weight splits and the combine pass of the gather's long buckets, deferred and run as jobs of
+    ONE launch before the next library call, give bit-identical results to the kernels of their own."""
     from tf2_gnn_amd import _lib, ops
     from tf2_gnn_amd.data import make_synthetic_batch
 
@@ -648,7 +598,7 @@ def test_small_passes_sharing_one_launch_equal_their_stand_alone_kernels(dev, mo
         Y = ops.sp_gemm_nt(A, cols, act="relu")                                                 # flushes the three jobs first
         G = ops.graph_gather_sp(graph, ops.VIEW_BY_SRC_TYPED, dY, rows_per_operand_row=L, defer_combine=True)
         dW = torch.empty_like(W)
-        ops.sp_gemm_tn(G, ops.sp_split_rows(X), out=dW, scatter=(H, 320 * H, 1, H), defer_reduce=True)
+        ops.sp_gemm_tn(G, ops.sp_split_rows(X), out=dW, scatter=(H, 320 * H, 1, H))
         dX = ops.sp_gemm_nt(G, rows)
         ops.aux_flush()
         return [cols.data, cols.inv_scale, rows.data, rows.inv_scale, A.data, A.inv_scale, Y, G.data, G.inv_scale, dW, dX]
@@ -664,16 +614,65 @@ def test_small_passes_sharing_one_launch_equal_their_stand_alone_kernels(dev, mo
     names = ["W^T sp", "W^T inv", "W rows sp", "W rows inv", "A sp", "A inv", "Y", "G sp", "G inv", "dW", "dX"]
     for n, a, b in zip(names, got, ref):
         assert torch.equal(a, b), n
-    # a deferred reduction is NOT run by the next library call (non-urgent), only by a flush
-    dW2 = torch.full_like(W, 7.0)
-    G = ops.graph_gather_sp(graph, ops.VIEW_BY_SRC_TYPED, dY, rows_per_operand_row=L)
-    ops.aux_flush()
-    ops.sp_gemm_tn(G, ops.sp_split_rows(X), out=dW2, scatter=(H, 320 * H, 1, H), defer_reduce=True)
-    ops.add_scale(X, X, 0.5)
+    graph.close()
+
+
+def test_two_pass_weight_split_launches_on_the_stream_it_was_deferred_for(dev, monkeypatch):
+    """A long-K weight split deferred on one stream (the column maxima in one merged launch, the split in the next) and flushed
+    by a library call on ANOTHER stream: both launches go to the stream it was deferred for, and the operand is the one-pass
+    split's, bit for bit."""
+    from tf2_gnn_amd import _lib, ops
+
+    lib = _lib.load()
+    K, N = 40 * 64, 256
+    assert lib.tfgnn_sp_split_cols_two_pass_bytes(K, N) > 0
+    g = torch.Generator().manual_seed(17)
+    w = (torch.randn((K, N), generator=g) * torch.exp(torch.randn((1, N), generator=g) * 3)).to(dev)
+    ref = ops.sp_split_cols(w)
     torch.cuda.synchronize()
-    assert float(dW2.min()) == 7.0 and len(ops._AUX_PENDING) == 1  # (the factor pass, with the product chained to it)
-    ops.aux_flush()
-    assert torch.equal(dW2, ref[9])
+    monkeypatch.setenv("TFGNN_AUX_MERGE", "1")
+    streams = []
+    real = lib.tfgnn_aux_launch
+
+    def spy(jobs, n, stream):
+        streams.append(stream)
+        return real(jobs, n, stream)
+
+    monkeypatch.setattr(lib, "tfgnn_aux_launch", spy)
+    main, side = torch.cuda.current_stream(), torch.cuda.Stream()
+    op = ops.sp_split_cols(w, defer=True)
+    assert not streams
+    side.wait_stream(main)
+    with torch.cuda.stream(side):
+        ops.absmax(w)  # a library call: launches what is deferred first
+    torch.cuda.synchronize()
+    assert streams == [main.cuda_stream, main.cuda_stream], (streams, main.cuda_stream, side.cuda_stream)
+    assert torch.equal(op.data, ref.data) and torch.equal(op.inv_scale, ref.inv_scale)
+
+
+def test_layer_backward_after_a_rejected_call_builds_the_weight_operand(dev):
+    """ops.mp_backward that raises on its argument checks (no split form of the layer input) must not leave an unbuilt weight
+    operand in the cache: the next call with the same (never split) kernels builds it and gives dX and dW bit-equal to a
+    run with an empty cache."""
+    from tests.helpers import random_graph, to_dev
+    from tf2_gnn_amd import ops
+
+    V, E, L, D, H = 1200, 15000, 3, 128, 128
+    g = torch.Generator().manual_seed(29)
+    W = (torch.randn((L, D, H), generator=g) * 0.07).to(dev)
+    X = torch.randn((V, D), generator=g).to(dev)
+    d_pre = torch.randn((V, H), generator=g).to(dev)
+    graph = ops.Graph(to_dev(random_graph(V, E, L, seed=29), dev), V)
+    x_sp = ops.sp_split_rows(X)
+    ops.clear_weight_operand_cache()
+    with pytest.raises(ValueError):
+        ops.mp_backward(graph, d_pre, W, None)
+    dX, _, dW = ops.mp_backward(graph, d_pre, W, x_sp)
+    got = (dX.clone(), dW.clone())
+    ops.clear_weight_operand_cache()
+    dX, _, dW = ops.mp_backward(graph, d_pre, W, x_sp)
+    torch.cuda.synchronize()
+    assert torch.equal(got[0], dX) and torch.equal(got[1], dW)
     graph.close()
 
 

@@ -125,8 +125,8 @@ def test_two_factor_product_with_a_zero_block_and_large_deficits(dev, K, sb, M, 
 @pytest.mark.parametrize("sb,M,N", SHAPES, ids=[f"sb{s[0]}" for s in SHAPES])
 def test_two_factor_product_with_a_block_zero_over_some_k_ranges(dev, sb, M, N):
     """The same block zero only over rows [0, 4100) of 6053: every K range (<= 2016 rows) that lies wholly inside the interval
-    sees an all-zero block, the ranges after it do not.  Immediate call; deferred reduction (bit-equal); the row-range loop of
-    operands longer than one launch covers (TN_WIDE_MAX_ROWS patched to 2016, as for 10^6-row operands)."""
+    sees an all-zero block, the ranges after it do not.  Immediate call; the row-range loop of operands longer than one launch
+    covers (TN_WIDE_MAX_ROWS patched to 2016, as for 10^6-row operands)."""
     from tf2_gnn_amd import ops
 
     ops.set_gemm_mode("f16x2")
@@ -137,15 +137,9 @@ def test_two_factor_product_with_a_block_zero_over_some_k_ranges(dev, sb, M, N):
     now = ops.sp_gemm_tn(a_sp, b_sp, wide=True)
     check(now, r, m, 2e-6, f"wide, block zero over [0, 4100), sb={sb}")
     assert_quiet()
-    later = ops.sp_gemm_tn(a_sp, b_sp, wide=True, defer_reduce=True)
-    ops.aux_flush()
-    assert torch.equal(later, now)
     a2, b2 = zero_block_case(K, M, N, sb, 91 + sb, WIDE_DEFICITS)  # ... and zero over all of K
     a2_sp, b2_sp = ops.sp_split_rows(a2.to(dev), scale_block=sb), ops.sp_split_rows(b2.to(dev))
-    now2 = ops.sp_gemm_tn(a2_sp, b2_sp, wide=True)
-    later2 = ops.sp_gemm_tn(a2_sp, b2_sp, wide=True, defer_reduce=True)
-    ops.aux_flush()
-    assert torch.equal(later2, now2)
+    check(ops.sp_gemm_tn(a2_sp, b2_sp, wide=True), ref(a2, b2), mag(a2, b2), 2e-6, f"wide, block zero over all of K, sb={sb}")
     keep = ops.TN_WIDE_MAX_ROWS
     try:
         ops.TN_WIDE_MAX_ROWS = 2016
@@ -240,7 +234,7 @@ ONE_FACTOR_SHAPES = [(64, 256, 128, 2016), (128, 256, 128, 17), (320, 640, 128, 
 def test_one_factor_product_with_a_zero_block(dev, sb, M, N, K):
     """tfgnn_sp_gemm_tn (one combined factor on A's fragments): the same zero-block operands at spreads of the scale products up
     to 2^13 (A's rows over 2^9, B's over 2^4) - finite, exact zeros, the fp32 error class of the existing bound.  Also over
-    K ranges that hold the zero block only in part, and through the deferred reduction (bit-equal)."""
+    K ranges that hold the zero block only in part."""
     from tf2_gnn_amd import ops
 
     ops.set_gemm_mode("f16x2")
@@ -249,15 +243,12 @@ def test_one_factor_product_with_a_zero_block(dev, sb, M, N, K):
         a_sp, b_sp = ops.sp_split_rows(a.to(dev), scale_block=sb), ops.sp_split_rows(b.to(dev))
         got = ops.sp_gemm_tn(a_sp, b_sp)
         check(got, ref(a, b), mag(a, b), 6e-7, f"one-factor K={K} sb={sb} zero until {zero_until}")
-        later = ops.sp_gemm_tn(a_sp, b_sp, defer_reduce=True)
-        ops.aux_flush()
-        assert torch.equal(later, got)
     assert_quiet()
 
 
 def test_one_factor_product_with_a_zero_block_through_the_separate_factor_pass(dev):
     """The same with the factors computed by their own pass (sp_tn_factors_kernel; TFGNN_TN_FIK=0, read once per process: a
-    child process) and as a job of a merged small-pass launch (TFGNN_TN_CHAINED=1 with the deferred reduction)."""
+    child process)."""
     code = (
         "import torch\n"
         "from tf2_gnn_amd import ops\n"
@@ -269,16 +260,13 @@ def test_one_factor_product_with_a_zero_block_through_the_separate_factor_pass(d
         "    a_sp, b_sp = ops.sp_split_rows(a.to(dev), scale_block=sb), ops.sp_split_rows(b.to(dev))\n"
         "    r, m = ref(a, b), mag(a, b)\n"
         "    check(ops.sp_gemm_tn(a_sp, b_sp), r, m, 6e-7, 'factor pass')\n"
-        "    chained = ops.sp_gemm_tn(a_sp, b_sp, defer_reduce=True)\n"
-        "    ops.aux_flush()\n"
-        "    check(chained, r, m, 6e-7, 'factor job')\n"
         "torch.cuda.synchronize()\n"
         "from tf2_gnn_amd import _lib\n"
         "assert _lib.load().tfgnn_sp_spread_flag(0) == 0\n"
         "print('CHILD OK')\n"
     )
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, TFGNN_TN_FIK="0", TFGNN_TN_CHAINED="1",
+    env = dict(os.environ, TFGNN_TN_FIK="0",
                PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
     res = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300, cwd=root)
     assert res.returncode == 0 and "CHILD OK" in res.stdout, res.stdout[-2000:] + res.stderr[-3000:]

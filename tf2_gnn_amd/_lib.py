@@ -237,18 +237,12 @@ _SIGNATURES = [
         "tfgnn_sp_gemm_tn_wide",
         c_int,
         [c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p,
-         c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_size_t, c_void_p, c_void_p],
+         c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_size_t, c_void_p],
     ),
     (
         "tfgnn_sp_gemm_tn",
         c_int,
         [c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p,
-         c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_size_t, c_void_p],
-    ),
-    (
-        "tfgnn_sp_gemm_tn_phase",
-        c_int,
-        [c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p,
          c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_size_t, c_void_p],
     ),
     ("tfgnn_absmax", c_int, [c_void_p, c_int64, c_float, c_void_p, c_void_p]),
@@ -266,7 +260,6 @@ _SIGNATURES = [
         [c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
          c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p],
     ),
-    ("tfgnn_sp_split_weights", c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     (
         "tfgnn_sp_gemm_nt_sp",
         c_int,
@@ -288,18 +281,6 @@ _SIGNATURES = [
         c_int,
         [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
          c_size_t, c_void_p, c_void_p],
-    ),
-    (
-        "tfgnn_sp_gemm_tn_jobs",
-        c_int,
-        [c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p,
-         c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_size_t, c_void_p, c_void_p],
-    ),
-    (
-        "tfgnn_sp_gemm_tn_deferred",
-        c_int,
-        [c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p,
-         c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_size_t, c_void_p, c_void_p],
     ),
     (
         "tfgnn_sp_gemm_nt_dropout",
@@ -342,7 +323,7 @@ _SIGNATURES += [
 ]
 
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
-ABI_VERSION = 4  # include/tfgnn.h TFGNN_ABI_VERSION
+ABI_VERSION = 5  # include/tfgnn.h TFGNN_ABI_VERSION
 
 
 class AuxJob(ctypes.Structure):
@@ -360,8 +341,7 @@ class MpForwardArgs(ctypes.Structure):
         ("ld_wt_sp_bytes", c_int64), ("wt_inv_scale", c_void_p), ("agg_sp", c_void_p), ("agg_inv_scale", c_void_p), ("bias", c_void_p),
         ("act", c_int), ("dropout_rate", ctypes.c_float), ("dropout_seed", ctypes.c_uint64), ("tile_kmask", c_void_p),
         ("row_map", c_void_p), ("out", c_void_p), ("ld_out", c_int64), ("out_sp", c_void_p), ("ld_out_sp_bytes", c_int64),
-        ("out_inv_scale", c_void_p), ("extra_jobs", c_void_p), ("num_extra_jobs", c_int), ("workspace", c_void_p),
-        ("workspace_bytes", ctypes.c_size_t),
+        ("out_inv_scale", c_void_p), ("workspace", c_void_p), ("workspace_bytes", ctypes.c_size_t),
     ]
 
 
@@ -376,8 +356,8 @@ class MpBackwardArgs(ctypes.Structure):
         ("ld_saved", c_int64), ("saved_scale", ctypes.c_float), ("dropout_rate", ctypes.c_float), ("dropout_seed", ctypes.c_uint64),
         ("dx_sp", c_void_p), ("ld_dx_sp_bytes", c_int64), ("dx_inv_scale", c_void_p), ("tile_kmask", c_void_p), ("a_rows", c_void_p),
         ("row_map", c_void_p), ("dw", c_void_p), ("x_sp", c_void_p), ("ld_x_sp_bytes", c_int64), ("x_inv_scale", c_void_p),
-        ("tn_workspace", c_void_p), ("tn_workspace_bytes", ctypes.c_size_t), ("extra_jobs", c_void_p), ("num_extra_jobs", c_int),
-        ("workspace", c_void_p), ("workspace_bytes", ctypes.c_size_t),
+        ("tn_workspace", c_void_p), ("tn_workspace_bytes", ctypes.c_size_t), ("workspace", c_void_p),
+        ("workspace_bytes", ctypes.c_size_t),
     ]
 
 

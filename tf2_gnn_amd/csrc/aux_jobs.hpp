@@ -1,6 +1,6 @@
 // Small passes that ride together in ONE launch (tfgnn_aux_launch): the per-step preparation and finishing work around the
 // big kernels of a layer - splitting a weight matrix into SP16 operand form, combining the partial sums of the gather's
-// multi-item buckets, summing the split-K partials of a weight gradient - is a handful of kernels of 5-15 us each, every one
+// multi-item buckets - is a handful of kernels of 5-15 us each, every one
 // of them bound by launch + dependent-load latency, not by work.  Merged, the launch costs what its longest job costs.
 // A job = (kind, number of 256-thread workgroups, payload); the kernel finds a workgroup's job from blockIdx.x by walking the
 // table in the kernel-argument segment (scalar loads; no table in device memory, no copy command).
@@ -15,7 +15,8 @@
 
 namespace tfgnn {
 
-enum AuxKind { AUX_NONE = 0, AUX_SPLIT_ROWS = 1, AUX_SPLIT_COLS = 2, AUX_TN_REDUCE = 3, AUX_COMBINE_SP = 4, AUX_TN_FACTORS = 5, AUX_COL_ABSMAX = 6, AUX_KIND_END = 7 };
+// (3 and 5 were the reduction and factor pass of a weight-gradient product; they stay unused)
+enum AuxKind { AUX_NONE = 0, AUX_SPLIT_ROWS = 1, AUX_SPLIT_COLS = 2, AUX_COMBINE_SP = 4, AUX_COL_ABSMAX = 6 };
 
 struct AuxSplitRows {
   const float* src;
@@ -74,21 +75,8 @@ struct AuxCombineSp {
   float* inv_out;
   const float* fixed_inv;
 };
-struct AuxTnFactors {
-  const float* inv_a;
-  int64_t ld_a;
-  const float* inv_b;
-  int64_t ld_b;
-  int64_t K;
-  _Float16* F;
-  int64_t f_ld;
-  float* ref;
-  int* spread_flag;
-  int nchunks;
-};
-static_assert(sizeof(AuxTnFactors) <= sizeof(((tfgnn_aux_job*)0)->payload), "tfgnn_aux_job payload too small");
 static_assert(sizeof(AuxSplitRows) <= sizeof(((tfgnn_aux_job*)0)->payload) && sizeof(AuxSplitCols) <= sizeof(((tfgnn_aux_job*)0)->payload) &&
-                  sizeof(AuxTnReduce) <= sizeof(((tfgnn_aux_job*)0)->payload) && sizeof(AuxCombineSp) <= sizeof(((tfgnn_aux_job*)0)->payload),
+                  sizeof(AuxCombineSp) <= sizeof(((tfgnn_aux_job*)0)->payload),
               "tfgnn_aux_job payload too small");
 
 template <class P>
@@ -318,43 +306,6 @@ __device__ __forceinline__ void sp_tn_reduce_body(const AuxTnReduce& a, unsigned
     float* dst = a.C + gi * a.stride_group + mi * a.stride_row + n * a.stride_col;
     *dst = a.accumulate ? *dst + s : s;
   }
-}
-
-// ---- per-k factors of a weight-gradient product (gemm_sp.hip sp_tn_factors_kernel, as a 256-thread job): workgroup
-// (block b, chunk c) takes the maximum of inv_a[k, b] * inv_b[k] over ALL k itself, then writes its slice of F[b][.] ----------
-__device__ __forceinline__ void sp_tn_factors_body(const AuxTnFactors& a, unsigned block) {
-  __shared__ float red[4];
-  const int b = (int)block / a.nchunks, chunk = (int)block % a.nchunks;
-  float mx = 0.f;
-  for (int64_t k0 = threadIdx.x; k0 < a.K; k0 += 32 * 256) {
-    float va[32], vb[32];
-#pragma unroll
-    for (int u = 0; u < 32; ++u) {
-      const int64_t k = k0 + u * 256;
-      va[u] = k < a.K ? a.inv_a[k * a.ld_a + b] : 0.f;
-      vb[u] = (k < a.K && a.inv_b) ? a.inv_b[k * a.ld_b] : 1.f;
-    }
-#pragma unroll
-    for (int u = 0; u < 32; ++u) mx = fmaxf(mx, va[u] * vb[u]);
-  }
-#pragma unroll
-  for (int o = 32; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  if (mx == 0.f) mx = 1.f;
-  if (threadIdx.x == 0 && chunk == 0) a.ref[b] = mx;
-  const float r = 1.f / mx;  // powers of two: exact
-  const int64_t per = ((a.f_ld + a.nchunks - 1) / a.nchunks + 7) & ~7ll;
-  const int64_t kend = (chunk + 1) * per < a.f_ld ? (chunk + 1) * per : a.f_ld;
-  bool wide = false;
-  for (int64_t k = chunk * per + threadIdx.x; k < kend; k += 256) {
-    const float ia = k < a.K ? a.inv_a[k * a.ld_a + b] : 0.f, ib = (k < a.K && a.inv_b) ? a.inv_b[k * a.ld_b] : 1.f;
-    const float f = sp_row_holds(ia, ib) ? ia * ib * r : 0.f;
-    a.F[(int64_t)b * a.f_ld + k] = (_Float16)f;
-    wide |= sp_row_too_small(f, ia, ib);  // the spread guard of sp_tn_factors_kernel (gemm_sp.hip)
-  }
-  if (a.spread_flag && __any(wide) && (threadIdx.x & 63) == 0) *a.spread_flag = 1;
 }
 
 // ---- partial sums of the gather's multi-item buckets -> SP16 rows: one wave per bucket (width <= 2048 floats) ------------

@@ -182,29 +182,6 @@ __global__ void __launch_bounds__(256) sp_split_cols_kernel(const float* __restr
   sp_split_cols_body(src, ld, K, N, dst, ld_dst, inv, blockIdx.x, blockIdx.y, gridDim.y);
 }
 
-// Both operand forms of up to 16 stacked kernels [L, D, H] of the same shape in ONE launch (the per-step weight
-// preparation of a layer stack: 2 x layers small launches otherwise, each latency-bound): blockIdx.y = kernel stack;
-// workgroups [0, nc) do slice (x % ncx, x / ncx) of the transposed form [H, L D], the rest the stacked-rows form
-// [D, L H] (row d = [W_0[d, :] | W_1[d, :] | ...]).
-struct SpWeightJobs {
-  const float* src[16];
-  uint8_t* cols_sp[16];
-  float* cols_inv[16];
-  uint8_t* rows_sp[16];
-  float* rows_inv[16];
-  int64_t L, D, H;
-  unsigned ncx, ncy;
-};
-__global__ void __launch_bounds__(256) sp_split_weights_kernel(SpWeightJobs j) {
-  const unsigned w = blockIdx.y, nc = j.ncx * j.ncy;
-  if (blockIdx.x < nc) {
-    sp_split_cols_body(j.src[w], j.H, j.L * j.D, j.H, j.cols_sp[w], j.L * j.D * 4, j.cols_inv[w], blockIdx.x % j.ncx, blockIdx.x / j.ncx, j.ncy);
-  } else {
-    sp_split_rows_body(j.src[w], j.H, j.H, j.D * j.H, j.D, j.L * j.H, (int)(j.L * j.H), j.rows_sp[w], j.L * j.H * 4, j.rows_inv[w], nullptr,
-                       blockIdx.x - nc);
-  }
-}
-
 // ------------------------------------------------------------------------------------------------------
 // NT kernel
 // ------------------------------------------------------------------------------------------------------
@@ -1658,29 +1635,6 @@ int tfgnn_sp_split_cols(const float* d_src, int64_t ld, int64_t K, int64_t N, vo
   return TFGNN_OK;
 }
 
-int tfgnn_sp_split_weights(int count, const float* const* h_src, int64_t L, int64_t D, int64_t H, void* const* h_cols_sp,
-                           float* const* h_cols_inv_scale, void* const* h_rows_sp, float* const* h_rows_inv_scale, void* stream) {
-  TFGNN_REQUIRE(count >= 1 && count <= 16 && h_src && h_cols_sp && h_cols_inv_scale && h_rows_sp && h_rows_inv_scale,
-                "tfgnn_sp_split_weights: 1 .. 16 kernel stacks");
-  TFGNN_REQUIRE(L > 0 && D > 0 && H > 0 && (L * D) % 16 == 0 && (L * H) % 16 == 0 && H % 4 == 0,
-                "tfgnn_sp_split_weights: L D and L H must be multiples of 16, H a multiple of 4");
-  SpWeightJobs j{};
-  for (int i = 0; i < count; ++i) {
-    TFGNN_REQUIRE(h_src[i] && h_cols_sp[i] && h_cols_inv_scale[i] && h_rows_sp[i] && h_rows_inv_scale[i] &&
-                      (uintptr_t)h_src[i] % 16 == 0 && (uintptr_t)h_cols_sp[i] % 64 == 0 && (uintptr_t)h_rows_sp[i] % 64 == 0,
-                  "tfgnn_sp_split_weights: null or unaligned pointer");
-    j.src[i] = h_src[i]; j.cols_sp[i] = (uint8_t*)h_cols_sp[i]; j.cols_inv[i] = h_cols_inv_scale[i];
-    j.rows_sp[i] = (uint8_t*)h_rows_sp[i]; j.rows_inv[i] = h_rows_inv_scale[i];
-  }
-  j.L = L; j.D = D; j.H = H;
-  j.ncx = (unsigned)ceil_div(H, 16);
-  j.ncy = (unsigned)std::max<int64_t>(1, std::min<int64_t>(8, L * D / 128));
-  const unsigned nr = (unsigned)ceil_div(D, 4);  // one wave per row of the stacked-rows form
-  hipLaunchKernelGGL(sp_split_weights_kernel, dim3(j.ncx * j.ncy + nr, (unsigned)count), dim3(256), 0, (hipStream_t)stream, j);
-  TFGNN_LAUNCH_CHECK();
-  return TFGNN_OK;
-}
-
 static int sp_gemm_nt_impl(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, const float* d_a_inv_scale,
                            int a_scale_block, const void* d_B_sp, int64_t ldb_bytes, const float* d_b_inv_scale, float* d_C,
                            int64_t ldc, const float* d_bias, int act, int accumulate, const float* d_mul, int64_t ld_mul,
@@ -1893,12 +1847,11 @@ size_t tfgnn_sp_gemm_tn_wide_workspace_bytes(int64_t M, int64_t N, int64_t K, in
   return sp_gemm_tn_ws_bytes(M, N, K, a_total_cols, a_scale_block, true);
 }
 
-static int sp_gemm_tn_impl(int phases, int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, int64_t a_first_col,
+static int sp_gemm_tn_impl(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, int64_t a_first_col,
                            const float* d_a_inv_scale, int64_t a_total_cols, int a_scale_block, const void* d_B_sp,
                            int64_t ldb_bytes, int64_t b_first_col, const float* d_b_inv_scale, float* d_C, int64_t group_rows,
                            int64_t stride_group, int64_t stride_row, int64_t stride_col, int accumulate, void* d_workspace,
-                           size_t workspace_bytes, void* stream, tfgnn_aux_job* reduce_job = nullptr,
-                           tfgnn_aux_job* factors_job = nullptr, bool wide = false) {
+                           size_t workspace_bytes, void* stream, bool wide = false) {
   TFGNN_REQUIRE(d_A_sp && d_B_sp && d_C && d_a_inv_scale, "tfgnn_sp_gemm_tn: null pointer");
   TFGNN_REQUIRE(M > 0 && N > 0 && K > 0, "tfgnn_sp_gemm_tn: empty product");
   const int bn = sp_tile_width(N);
@@ -1921,7 +1874,7 @@ static int sp_gemm_tn_impl(int phases, int64_t M, int64_t N, int64_t K, const vo
   int splits = sp_tn_splits(Mp, N, K, bn);
   if (wide) {  // two-factor form: factors in the kernel, K ranges of at most SP_TN_BSC_MAX_CHUNK rows
     splits = (int)std::max<int64_t>(splits, ceil_div(K, SP_TN_BSC_MAX_CHUNK));
-    TFGNN_REQUIRE(splits <= 512 && (phases == (1 | 2 | 4) || phases == (1 | 2 | 8)) && d_b_inv_scale,
+    TFGNN_REQUIRE(splits <= 512 && d_b_inv_scale,
                   "tfgnn_sp_gemm_tn_wide: K too large (more than 512 ranges of 2016 rows), or no scales of B");
   }
   const int64_t nblk = a_total_cols / a_scale_block, kpad = (K + 15) & ~15ll;
@@ -1939,14 +1892,7 @@ static int sp_gemm_tn_impl(int phases, int64_t M, int64_t N, int64_t K, const vo
   const bool fik = wide || (fik_env && k_chunk_all <= SP_TN_FIK_MAX_CHUNK && splits <= 512);
   TFGNN_REQUIRE(!wide || k_chunk_all <= SP_TN_BSC_MAX_CHUNK, "tfgnn_sp_gemm_tn_wide: K range too long");
   float* ref_split = ref + nblk * (1 + SP_TN_MAXCHUNKS);  // [splits][nblk]
-  if (fik) phases &= ~(1 | 16);
-  if ((phases & 16) && factors_job) factors_job->kind = 0, factors_job->num_blocks = 0;
-  if (phases & 16) {  // the factor pass as a job of a merged launch (operands of up to 128k rows: one-stage factor pass)
-    TFGNN_REQUIRE(factors_job != nullptr && sp_tn_fchunks(K) == SP_TN_FCHUNKS, "tfgnn_sp_gemm_tn: factors job needs K <= 131072");
-    AuxTnFactors fa{d_a_inv_scale, nblk, d_b_inv_scale, 1, K, F, kpad, ref, sp_spread_flag_device(), SP_TN_FCHUNKS};
-    aux_job_set(factors_job, AUX_TN_FACTORS, (unsigned)(nblk * SP_TN_FCHUNKS), fa);
-  }
-  if (phases & 1) {
+  if (!fik) {
     const int fch = sp_tn_fchunks(K);
     float* slice_max = nullptr;
     if (fch > SP_TN_FCHUNKS) {  // two stages; the slice maxima live behind the reference scales (r_bytes reserves nblk * SP_TN_MAXCHUNKS floats for them)
@@ -1986,25 +1932,22 @@ static int sp_gemm_tn_impl(int phases, int64_t M, int64_t N, int64_t K, const vo
     }                                                                                                              \
     hipLaunchKernelGGL((gemm_sp_tn_kernel<T, FK, ##__VA_ARGS__>), grid, dim3(SP_NT), tn_lds, s, g);                \
   } while (0)
-  if (phases & 2) {
-    count_launch(TFGNN_KFAM_SP_TN);
-    if (wide) {
-      if (bn == 320) SP_LAUNCH_TN(5, true, true);
-      else if (bn == 256) SP_LAUNCH_TN(4, true, true);
-      else SP_LAUNCH_TN(2, true, true);
-    } else if (fik) {
-      if (bn == 320) SP_LAUNCH_TN(5, true);
-      else if (bn == 256) SP_LAUNCH_TN(4, true);
-      else SP_LAUNCH_TN(2, true);
-    } else {
-      if (bn == 320) SP_LAUNCH_TN(5, false);
-      else if (bn == 256) SP_LAUNCH_TN(4, false);
-      else SP_LAUNCH_TN(2, false);
-    }
-    TFGNN_LAUNCH_CHECK();
+  count_launch(TFGNN_KFAM_SP_TN);
+  if (wide) {
+    if (bn == 320) SP_LAUNCH_TN(5, true, true);
+    else if (bn == 256) SP_LAUNCH_TN(4, true, true);
+    else SP_LAUNCH_TN(2, true, true);
+  } else if (fik) {
+    if (bn == 320) SP_LAUNCH_TN(5, true);
+    else if (bn == 256) SP_LAUNCH_TN(4, true);
+    else SP_LAUNCH_TN(2, true);
+  } else {
+    if (bn == 320) SP_LAUNCH_TN(5, false);
+    else if (bn == 256) SP_LAUNCH_TN(4, false);
+    else SP_LAUNCH_TN(2, false);
   }
+  TFGNN_LAUNCH_CHECK();
 #undef SP_LAUNCH_TN
-  if (!(phases & 12)) return TFGNN_OK;
   const int64_t total = M * N;
   AuxTnReduce ra{};
   ra.partial = g.partial; ra.splits = splits_used; ra.M = M; ra.N = N; ra.ref = fik ? ref_split : ref; ra.a_col0 = a_first_col; ra.a_sb = a_scale_block;
@@ -2012,11 +1955,6 @@ static int sp_gemm_tn_impl(int phases, int64_t M, int64_t N, int64_t K, const vo
   ra.C = d_C; ra.group_rows = group_rows; ra.stride_group = stride_group; ra.stride_row = stride_row; ra.stride_col = stride_col;
   ra.accumulate = accumulate; ra.slab = Mp * N;
   const unsigned rblocks = (unsigned)std::min<int64_t>(ceil_div(total, 256), 2048);
-  if (phases & 8) {  // the reduction as a job of a later merged launch (tfgnn_aux_launch) instead of a launch of its own
-    TFGNN_REQUIRE(reduce_job != nullptr, "tfgnn_sp_gemm_tn: reduce_job is NULL");
-    aux_job_set(reduce_job, AUX_TN_REDUCE, rblocks, ra);
-    return TFGNN_OK;
-  }
   hipLaunchKernelGGL(sp_tn_reduce_kernel, dim3(rblocks), dim3(256), 0, s, ra);
   TFGNN_LAUNCH_CHECK();
   return TFGNN_OK;
@@ -2027,7 +1965,7 @@ int tfgnn_sp_gemm_tn(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_
                      int64_t ldb_bytes, int64_t b_first_col, const float* d_b_inv_scale, float* d_C, int64_t group_rows,
                      int64_t stride_group, int64_t stride_row, int64_t stride_col, int accumulate, void* d_workspace,
                      size_t workspace_bytes, void* stream) {
-  return sp_gemm_tn_impl(7, M, N, K, d_A_sp, lda_bytes, a_first_col, d_a_inv_scale, a_total_cols, a_scale_block, d_B_sp, ldb_bytes,
+  return sp_gemm_tn_impl(M, N, K, d_A_sp, lda_bytes, a_first_col, d_a_inv_scale, a_total_cols, a_scale_block, d_B_sp, ldb_bytes,
                          b_first_col, d_b_inv_scale, d_C, group_rows, stride_group, stride_row, stride_col, accumulate, d_workspace,
                          workspace_bytes, stream);
 }
@@ -2036,10 +1974,10 @@ int tfgnn_sp_gemm_tn_wide(int64_t M, int64_t N, int64_t K, const void* d_A_sp, i
                           const float* d_a_inv_scale, int64_t a_total_cols, int a_scale_block, const void* d_B_sp,
                           int64_t ldb_bytes, int64_t b_first_col, const float* d_b_inv_scale, float* d_C, int64_t group_rows,
                           int64_t stride_group, int64_t stride_row, int64_t stride_col, int accumulate, void* d_workspace,
-                          size_t workspace_bytes, tfgnn_aux_job* reduce_job, void* stream) {
-  return sp_gemm_tn_impl(reduce_job ? (1 | 2 | 8) : 7, M, N, K, d_A_sp, lda_bytes, a_first_col, d_a_inv_scale, a_total_cols, a_scale_block,
-                         d_B_sp, ldb_bytes, b_first_col, d_b_inv_scale, d_C, group_rows, stride_group, stride_row, stride_col, accumulate,
-                         d_workspace, workspace_bytes, stream, reduce_job, nullptr, true);
+                          size_t workspace_bytes, void* stream) {
+  return sp_gemm_tn_impl(M, N, K, d_A_sp, lda_bytes, a_first_col, d_a_inv_scale, a_total_cols, a_scale_block, d_B_sp, ldb_bytes,
+                         b_first_col, d_b_inv_scale, d_C, group_rows, stride_group, stride_row, stride_col, accumulate, d_workspace,
+                         workspace_bytes, stream, true);
 }
 
 int tfgnn_sp_gemm_tn_grouped(int64_t M, int64_t N, const void* d_A_sp, int64_t lda_bytes, const float* d_a_inv_scale,
@@ -2110,46 +2048,6 @@ int tfgnn_sp_gemm_tn_grouped(int64_t M, int64_t N, const void* d_A_sp, int64_t l
                      c_group_stride);
   TFGNN_LAUNCH_CHECK();
   return TFGNN_OK;
-}
-
-int tfgnn_sp_gemm_tn_phase(int phases, int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, int64_t a_first_col,
-                           const float* d_a_inv_scale, int64_t a_total_cols, int a_scale_block, const void* d_B_sp,
-                           int64_t ldb_bytes, int64_t b_first_col, const float* d_b_inv_scale, float* d_C, int64_t group_rows,
-                           int64_t stride_group, int64_t stride_row, int64_t stride_col, int accumulate, void* d_workspace,
-                           size_t workspace_bytes, void* stream) {
-  TFGNN_REQUIRE(phases >= 1 && phases <= 7, "tfgnn_sp_gemm_tn_phase: phases is a mask of 1 (factors), 2 (product), 4 (reduce)");
-  return sp_gemm_tn_impl(phases, M, N, K, d_A_sp, lda_bytes, a_first_col, d_a_inv_scale, a_total_cols, a_scale_block, d_B_sp, ldb_bytes,
-                         b_first_col, d_b_inv_scale, d_C, group_rows, stride_group, stride_row, stride_col, accumulate, d_workspace,
-                         workspace_bytes, stream);
-}
-
-/* factors (if asked for) + product now, the split reduction as a job for tfgnn_aux_launch */
-int tfgnn_sp_gemm_tn_deferred(int with_factors, int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, int64_t a_first_col,
-                              const float* d_a_inv_scale, int64_t a_total_cols, int a_scale_block, const void* d_B_sp,
-                              int64_t ldb_bytes, int64_t b_first_col, const float* d_b_inv_scale, float* d_C, int64_t group_rows,
-                              int64_t stride_group, int64_t stride_row, int64_t stride_col, int accumulate, void* d_workspace,
-                              size_t workspace_bytes, tfgnn_aux_job* reduce_job, void* stream) {
-  TFGNN_REQUIRE(reduce_job != nullptr, "tfgnn_sp_gemm_tn_deferred: reduce_job is NULL");
-  return sp_gemm_tn_impl((with_factors ? 1 : 0) | 2 | 8, M, N, K, d_A_sp, lda_bytes, a_first_col, d_a_inv_scale, a_total_cols,
-                         a_scale_block, d_B_sp, ldb_bytes, b_first_col, d_b_inv_scale, d_C, group_rows, stride_group, stride_row,
-                         stride_col, accumulate, d_workspace, workspace_bytes, stream, reduce_job);
-}
-
-/* nothing is launched: the factor pass and the split reduction of tfgnn_sp_gemm_tn as jobs; the product itself is
- * tfgnn_sp_gemm_tn_phase(2, ...) with the same arguments, after the factors job and before the reduce job have run */
-int tfgnn_sp_gemm_tn_jobs(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, int64_t a_first_col,
-                          const float* d_a_inv_scale, int64_t a_total_cols, int a_scale_block, const void* d_B_sp,
-                          int64_t ldb_bytes, int64_t b_first_col, const float* d_b_inv_scale, float* d_C, int64_t group_rows,
-                          int64_t stride_group, int64_t stride_row, int64_t stride_col, int accumulate, void* d_workspace,
-                          size_t workspace_bytes, tfgnn_aux_job* factors_job, tfgnn_aux_job* reduce_job) {
-  TFGNN_REQUIRE(reduce_job != nullptr && factors_job != nullptr, "tfgnn_sp_gemm_tn_jobs: NULL job");
-  if (K > 131072) {
-    set_error("tfgnn_sp_gemm_tn_jobs: operands of more than 131072 rows take the two-stage factor pass (tfgnn_sp_gemm_tn_deferred)");
-    return TFGNN_ERR_UNSUPPORTED;
-  }
-  return sp_gemm_tn_impl(16 | 8, M, N, K, d_A_sp, lda_bytes, a_first_col, d_a_inv_scale, a_total_cols, a_scale_block, d_B_sp,
-                         ldb_bytes, b_first_col, d_b_inv_scale, d_C, group_rows, stride_group, stride_row, stride_col, accumulate,
-                         d_workspace, workspace_bytes, nullptr, reduce_job, factors_job);
 }
 
 int tfgnn_sp_split_rows_job(const float* d_src, int64_t ld, int64_t seg_len, int64_t seg_stride, int64_t rows, int64_t cols,

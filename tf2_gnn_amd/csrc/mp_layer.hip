@@ -16,27 +16,11 @@
 // (tests/test_gpu_mp_entry.py) - without Python in between.  A binding from another framework needs
 // these two calls per layer, the graph handle, and the loss.
 #include <cstring>
-#include <vector>
 
 #include "common.hpp"
 #include "tfgnn.h"
 
 using namespace tfgnn;
-
-namespace {
-
-int launch_small_passes(const tfgnn_aux_job* own, int num_own, const tfgnn_aux_job* extra, int num_extra, void* stream) {
-  std::vector<tfgnn_aux_job> jobs;
-  jobs.reserve((size_t)num_own + (size_t)(num_extra > 0 ? num_extra : 0));
-  for (int i = 0; i < num_extra; ++i)
-    if (extra[i].kind != 0 && extra[i].num_blocks != 0) jobs.push_back(extra[i]);
-  for (int i = 0; i < num_own; ++i)
-    if (own[i].kind != 0 && own[i].num_blocks != 0) jobs.push_back(own[i]);
-  if (jobs.empty()) return TFGNN_OK;
-  return tfgnn_aux_launch(jobs.data(), (int)jobs.size(), stream);
-}
-
-}  // namespace
 
 extern "C" int tfgnn_mp_forward(const tfgnn_mp_forward_args* a, void* stream) {
   TFGNN_REQUIRE(a != nullptr && a->struct_size == sizeof(tfgnn_mp_forward_args),
@@ -46,7 +30,6 @@ extern "C" int tfgnn_mp_forward(const tfgnn_mp_forward_args* a, void* stream) {
                 "tfgnn_mp_forward: NULL pointer");
   TFGNN_REQUIRE(a->view == TFGNN_VIEW_BY_DST_TYPED || a->view == TFGNN_VIEW_BY_DST_TYPED_PATTERN,
                 "tfgnn_mp_forward: the forward pass gathers over the by-target typed buckets (view %d)", a->view);
-  TFGNN_REQUIRE(a->num_extra_jobs >= 0 && (a->num_extra_jobs == 0 || a->extra_jobs), "tfgnn_mp_forward: extra jobs");
   int64_t V = 0, E = 0;
   int L = 0;
   int rc = tfgnn_graph_dims(a->graph, &V, &L, &E);
@@ -64,8 +47,8 @@ extern "C" int tfgnn_mp_forward(const tfgnn_mp_forward_args* a, void* stream) {
     rc = tfgnn_sp_split_cols_job(a->w, H, K, H, a->wt_sp, a->ld_wt_sp_bytes, a->wt_inv_scale, &own[1]);
     if (rc) return rc;
   }
-  // 3. the small passes in one launch: the combine pass of the long buckets, the weight split, whatever the caller queued
-  rc = launch_small_passes(own, 2, a->extra_jobs, a->num_extra_jobs, stream);
+  // 3. the small passes in one launch: the combine pass of the long buckets, the weight split
+  rc = tfgnn_aux_launch(own, 2, stream);  // (skips empty jobs: nothing is launched when both are)
   if (rc) return rc;
   // 4. the product with its epilogue
   return tfgnn_sp_gemm_nt_rows(V, H, K, a->agg_sp, K * 4, a->agg_inv_scale, (int)D, nullptr, a->wt_sp, a->ld_wt_sp_bytes, a->wt_inv_scale,
@@ -80,7 +63,6 @@ extern "C" int tfgnn_mp_backward(const tfgnn_mp_backward_args* a, void* stream) 
   TFGNN_REQUIRE(a->graph && a->d_pre && a->wh_sp && a->wh_inv_scale && a->g_sp && a->g_inv_scale && (a->dx || a->dx_sp),
                 "tfgnn_mp_backward: NULL pointer");
   TFGNN_REQUIRE(!a->dw || (a->x_sp && a->x_inv_scale), "tfgnn_mp_backward: the kernel gradients need the layer input as a split operand");
-  TFGNN_REQUIRE(a->num_extra_jobs >= 0 && (a->num_extra_jobs == 0 || a->extra_jobs), "tfgnn_mp_backward: extra jobs");
   int64_t V = 0, E = 0;
   int L = 0;
   int rc = tfgnn_graph_dims(a->graph, &V, &L, &E);
@@ -99,7 +81,7 @@ extern "C" int tfgnn_mp_backward(const tfgnn_mp_backward_args* a, void* stream) 
     rc = tfgnn_sp_split_rows_job(a->w, H, H, D * H, D, K, (int)K, a->wh_sp, a->ld_wh_sp_bytes, a->wh_inv_scale, nullptr, &own[1]);
     if (rc) return rc;
   }
-  rc = launch_small_passes(own, 2, a->extra_jobs, a->num_extra_jobs, stream);
+  rc = tfgnn_aux_launch(own, 2, stream);
   if (rc) return rc;
   // 3. dX = G W^T with the gradient factors of the op below in the epilogue; rows in by-source pattern order when asked
   rc = tfgnn_sp_gemm_nt_rows(V, D, K, a->g_sp, K * 4, a->g_inv_scale, (int)H, a->a_rows, a->wh_sp, a->ld_wh_sp_bytes, a->wh_inv_scale, a->dx,

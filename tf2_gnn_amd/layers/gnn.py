@@ -323,17 +323,6 @@ class GNN:
         steps = []
         NL = self._num_layers
 
-        if training and ops.get_gemm_mode() == ops.GEMM_F16X2 and ops.env("TFGNN_BATCHED_WEIGHT_SPLIT", "0") == "1":
-            # Opt-in: both split forms of every layer's kernel stack in ONE launch at the start of the step instead of two
-            # small launches per layer.  Measured a LOSS (2.67 vs 2.62 ms per step): the batched launch is 59 us less
-            # split-kernel time, but every layer product then starts on a weight operand that is no longer in L2 and takes
-            # 15-17 us longer (80 -> 97 us forward, 95 -> 111 us dX) - splitting a kernel right before the product that
-            # re-reads it 235 times doubles as its prefetch.
-            stacks = [mp._edge_type_mlps.kernels[0] for mp in self._mp_layers
-                      if getattr(mp, "_edge_type_mlps", None) is not None and hasattr(mp, "_f16x2_eligible")
-                      and mp._path() == "A" and mp._f16x2_eligible(V, self._hidden_dim, graph.num_edge_types, self._hidden_dim)]
-            if len(stacks) > 1 and len({tuple(w.shape) for w in stacks}) == 1:
-                ops.sp_split_weights(stacks)
         # the dropout seeds, in the order the stack draws them (one per layer input, one per global exchange)
         drop_seed, ex_seed = [None] * NL, {}
         for i in range(NL):
@@ -517,11 +506,7 @@ class GNN:
                     result = self._backward_walk(ctx, g, False, None, extras, need_input_grad)
             return result
         finally:
-            # stand-alone layer.backward() calls after this pass join the second stream themselves again
-            for mp in self._mp_layers:
-                mp._defer_aux_join = False
-            ops.aux_flush()        # the deferred split reductions of the weight gradients: one launch for all layers
-            ops.join_aux_stream()  # weight gradients whose last pass ran on the second stream
+            ops.aux_flush()  # nothing the pass deferred is left for a later call
 
     def guard_state(self) -> Dict[str, Any]:
         """What the spread-guard policy has done to this stack so far: ``tripped`` (the last backward pass, see
@@ -587,7 +572,6 @@ class GNN:
         for layer_idx in range(self._num_layers - 1, -1, -1):
             st = ctx["steps"][layer_idx]
             mp = self._mp_layers[layer_idx]
-            mp._defer_aux_join = True  # joined once, at the end of this backward pass
             has_ln = self._use_inter_layer_layernorm
             has_ex = str(layer_idx) in self._global_exchange_layers
             if layer_idx % self._dense_every_num_layers == 0:

@@ -490,10 +490,7 @@ class GNN_Edge_MLP(MessagePassing):
         L, H = g.num_edge_types, self._hidden_dim
         mlps = self._edge_type_mlps
         W = mlps.kernels[0]  # [L, D, H]
-        import os
-
-        overlap = ops.env("TFGNN_TN_OVERLAP", "0") == "1"
-        if ops.mp_entry_enabled() and not overlap:
+        if ops.mp_entry_enabled():
             # round 6: the whole pass in ONE library call (tfgnn_mp_backward): gather over the by-source buckets, the rows form of
             # the kernels when stale, the merged small passes, dX = G W^T with its epilogue, dW = X^T G - the op-level sequence below
             skip = {}
@@ -516,12 +513,6 @@ class GNN_Edge_MLP(MessagePassing):
             return dX
         G_sp = ops.graph_gather_sp(g, ops.VIEW_BY_SRC_TYPED, d_agg.contiguous(), edge_weight=ew_s, rows_per_operand_row=L,
                                    defer_combine=True)
-        # the weight gradient dW = X^T G is off the critical path of the backward pass: its two small passes (per-k factors,
-        # split reduction) run on the library's second stream beside the big kernels around them
-        tn = None
-        if overlap:
-            dW = torch.empty_like(W)
-            tn = ops.SpGemmTnOverlapped(G_sp, ops.sp_rows_of(X), out=dW, scatter=(H, D * H, 1, H))  # factors: second stream
         Wh_sp = ops.sp_weight_operand(W, "rows", lambda: ops.sp_split_rows(W[0], segments=(H, D * H, L * H), defer=True))
         epi = getattr(self, "_out_epilogue", None)
         acc = getattr(self, "_dx_accumulate", None)
@@ -545,18 +536,10 @@ class GNN_Edge_MLP(MessagePassing):
             self._out_epilogue = None  # consumed
         else:
             dX = ops.sp_gemm_nt(G_sp, Wh_sp, **skip)
-        if tn is not None:
-            tn.product()
-            tn.finish()  # the reduction runs beside the next layer's gather; GNN.backward joins the second stream at its end
-            if not getattr(self, "_defer_aux_join", False):
-                ops.join_aux_stream()  # stand-alone layer call: the gradients are complete when backward() returns
-        else:
-            X_sp = ops.sp_rows_of(X)  # written by the dropout kernel when X came out of one
-            dW = torch.empty_like(W)
-            # element ((l, h), d) -> dW[l, d, h].  (The split reduction stays right behind the product: deferred into a later
-            # merged launch - ops.sp_gemm_tn(defer_reduce=True) - it finds its 41 MB of partials evicted and takes 45 us
-            # instead of 14.)
-            ops.sp_gemm_tn(G_sp, X_sp, out=dW, scatter=(H, D * H, 1, H))
+        X_sp = ops.sp_rows_of(X)  # written by the dropout kernel when X came out of one
+        dW = torch.empty_like(W)
+        # element ((l, h), d) -> dW[l, d, h]  (the split reduction stays right behind the product: NOTEBOOK.md 4.4)
+        ops.sp_gemm_tn(G_sp, X_sp, out=dW, scatter=(H, D * H, 1, H))
         mlps.grads = [dW]
         mlps.publish_grads()
         return dX

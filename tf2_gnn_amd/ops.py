@@ -93,24 +93,22 @@ def _raw_stream() -> int:
 def _stream() -> int:
     """The launch stream of a library call.  Every wrapper evaluates this right before its C call, which makes it the one
     place where deferred small passes (``aux_defer``) that the coming kernel may depend on are launched first."""
-    while _AUX_PENDING and _AUX_URGENT[0]:  # (a launched job may chain an urgent one behind it: the two-pass weight split)
-        aux_flush(everything=False)
+    if _AUX_PENDING:
+        aux_flush()
     return _raw_stream()
 
 
 # ---- small passes that share a launch (include/tfgnn.h tfgnn_aux_launch) ---------------------------------------------------------
-# A deferred job runs at the next library launch on the stream (urgent jobs: something may read their result) or at the next
-# flush that has an urgent job / an explicit aux_flush() (non-urgent: results nobody reads before the end of the pass, e.g. the
-# split-K reductions of weight gradients).  Deferring only ever moves a pass LATER, and nothing is launched between a deferral
-# and the flush that runs it, so every input of a job is complete and none is overwritten in between; non-urgent jobs own
-# their inputs (the workspace of a weight-gradient product is kept by the job).  Jobs pending on one stream are flushed before
-# work is enqueued for another stream.
+# A deferred job runs in the next library launch: ``_stream()`` flushes the queue before every library call.  A flush launches
+# the stage-0 jobs, then the stage-1 jobs (which read what a stage-0 job wrote: the split behind the column maxima of a
+# two-pass weight split), both on the stream the jobs were deferred for.  Deferring only ever moves a pass LATER, and nothing
+# is launched between a deferral and the flush that runs it, so every input of a job is complete and none is overwritten in
+# between.  Jobs pending for one stream are flushed before a job for another stream is queued.
 # INTERNAL: ``defer=`` / ``defer_combine=`` arguments of the wrappers are for the layer code of this package, which always issues
 # the consumer of a deferred result as a library call right behind it.  A caller outside the library that reads a deferred
 # result with torch (or synchronises and expects it to exist) must call ``aux_flush()`` first; ``SplitOperand.synced()`` does.
 # The queue is guarded by a lock: autograd runs ``GNN.backward`` on its own thread (ADVICE r4).
-_AUX_PENDING = []     # [(AuxJob, keep-alive tuple)]
-_AUX_URGENT = [False]
+_AUX_PENDING = []  # [(stage, AuxJob, keep-alive tuple)]
 _AUX_STREAM = [None]
 _AUX_LOCK = threading.RLock()
 
@@ -121,41 +119,30 @@ def aux_enabled() -> bool:
     return env("TFGNN_AUX_MERGE", "1") != "0"
 
 
-def aux_defer(job, keep=(), urgent: bool = True, then=None) -> None:
-    """Queue a tfgnn_aux_job (``_lib.AuxJob``; kind 0 = nothing) for the next merged launch.  ``then()`` runs right after the
-    launch that carries the job (work that needs the job's result but is itself off the critical path: a weight-gradient
-    product behind its factor pass)."""
-    if (job.kind == 0 or job.num_blocks == 0) and then is None:
+def aux_defer(job, keep=(), stage: int = 0) -> None:
+    """Queue a tfgnn_aux_job (``_lib.AuxJob``; kind 0 = nothing) for the next flush, in its stage-0 launch or (stage 1) in
+    the launch after it.  ``keep``: tensors the job reads or writes, held until it has been launched."""
+    if job.kind == 0 or job.num_blocks == 0:
         return
     st = _raw_stream()
     with _AUX_LOCK:
         if _AUX_PENDING and _AUX_STREAM[0] != st:
             aux_flush()
         _AUX_STREAM[0] = st
-        _AUX_PENDING.append((job, keep, then))
-        if urgent:
-            _AUX_URGENT[0] = True
+        _AUX_PENDING.append((stage, job, keep))
 
 
-def aux_flush(everything: bool = True) -> None:
-    """Launch what has been deferred so far (one launch per 8 jobs) on the stream it was deferred for, then the work chained
-    to those jobs.  ``everything``: repeat until nothing is pending (chained work may defer further non-urgent jobs - the
-    reduction behind a deferred product); otherwise one round (what ``_stream()`` does before a library call)."""
-    while _AUX_PENDING:
-        with _AUX_LOCK:
-            batch = list(_AUX_PENDING)
-            del _AUX_PENDING[:]
-            _AUX_URGENT[0] = False
-            st = _AUX_STREAM[0]
-        live = [j for j, _, _ in batch if j.kind != 0 and j.num_blocks != 0]
-        if live:
-            jobs = (_lib.AuxJob * len(live))(*live)
-            _lib.check(_lib.load().tfgnn_aux_launch(jobs, len(jobs), st))
-        for _, _, then in batch:
-            if then is not None:
-                then()
-        if not everything:
-            break
+def aux_flush() -> None:
+    """Launch what has been deferred (one launch per 8 jobs): the stage-0 jobs, then the stage-1 jobs, on the stream they
+    were deferred for."""
+    with _AUX_LOCK:
+        batch = list(_AUX_PENDING)
+        del _AUX_PENDING[:]
+        for stage in (0, 1):
+            live = [j for s, j, _ in batch if s == stage]
+            if live:
+                jobs = (_lib.AuxJob * len(live))(*live)
+                _lib.check(_lib.load().tfgnn_aux_launch(jobs, len(jobs), _AUX_STREAM[0]))
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -1425,13 +1412,14 @@ def sp_split_cols(w: torch.Tensor, defer: bool = False, out: Optional[SplitOpera
         two_pass = lib.tfgnn_sp_split_cols_two_pass_bytes(K, N)
         if two_pass:
             # long K (the stacked kernels of many relations): the column maxima as a pass of their own in THIS merged launch, the
-            # conversion - which then reads every byte once instead of once per K slice - in the next one (the chained job is
-            # deferred as urgent: ``_stream()`` launches it before the consumer's kernel)
+            # conversion - which then reads every byte once instead of once per K slice - in the next one (stage 1 of the
+            # same flush: before the consumer's kernel)
             cm = torch.empty(two_pass, dtype=torch.uint8, device=w.device)
             mjob, sjob = _lib.AuxJob(), _lib.AuxJob()
             _lib.check(lib.tfgnn_sp_split_cols_jobs(_ptr(w), ld, K, N, _ptr(data), data.stride(0), _ptr(inv), _ptr(cm), two_pass,
                                                     ctypes.byref(mjob), ctypes.byref(sjob)))
-            aux_defer(mjob, keep=(w, cm), then=lambda: aux_defer(sjob, keep=(w, data, inv, cm)))
+            aux_defer(mjob, keep=(w, cm))
+            aux_defer(sjob, keep=(w, data, inv, cm), stage=1)
             return SplitOperand(data, inv, N, K, K)
         job = _lib.AuxJob()
         _lib.check(lib.tfgnn_sp_split_cols_job(_ptr(w), ld, K, N, _ptr(data), data.stride(0), _ptr(inv), ctypes.byref(job)))
@@ -1764,29 +1752,15 @@ def mp_entry_enabled() -> bool:
     return env("TFGNN_MP_ENTRY", "1") != "0"
 
 
-def _take_pending_jobs():
-    """What ``aux_defer`` holds for the current stream, handed to a layer-level call that launches it with its own small passes.
-    -> (ctypes array | None, count, callbacks to run after the call, keep-alive)"""
-    with _AUX_LOCK:
-        batch = list(_AUX_PENDING)
-        del _AUX_PENDING[:]
-        _AUX_URGENT[0] = False
-    live = [j for j, _, _ in batch if j.kind != 0 and j.num_blocks != 0]
-    arr = (_lib.AuxJob * len(live))(*live) if live else None
-    return arr, len(live), [t for _, _, t in batch if t is not None], batch
-
-
-def _fresh_weight_operand(w: torch.Tensor, kind: str, rows: int, cols: int):
-    """-> (operand, stale): the cached split form of weight ``w`` or a new, still EMPTY one registered in the cache - the
-    layer-level call that receives ``stale`` = True builds it in its merged small-pass launch."""
-    made = []
-
-    def build():
-        made.append(True)
-        return SplitOperand(torch.empty((rows, cols * 4), dtype=torch.uint8, device=w.device),
-                            torch.empty((rows, 1), dtype=torch.float32, device=w.device), rows, cols, cols)
-
-    return sp_weight_operand(w, kind, build), bool(made)
+def _weight_operand_for_call(w: torch.Tensor, kind: str, rows: int, cols: int):
+    """-> (operand, stale): the cached split form of weight ``w``, or (stale = True) a new, still EMPTY one that the
+    layer-level call builds in its merged small-pass launch; the caller caches it (``_cache_weight_operand``) once that call
+    has succeeded."""
+    op = _cached_weight_operand(w, kind)
+    if op is not None:
+        return op, False
+    return SplitOperand(torch.empty((rows, cols * 4), dtype=torch.uint8, device=w.device),
+                        torch.empty((rows, 1), dtype=torch.float32, device=w.device), rows, cols, cols), True
 
 
 def mp_forward(graph: "Graph", view: int, x: torch.Tensor, W: torch.Tensor, *, row_scale=None, act=ACT_NONE, dropout=None,
@@ -1803,7 +1777,7 @@ def mp_forward(graph: "Graph", view: int, x: torch.Tensor, W: torch.Tensor, *, r
     x, ldx = _rowmajor(x, "x")
     dev = x.device
     graph.ensure(_VIEW_PARTS[view])
-    wt, stale = _fresh_weight_operand(W, "cols", H, L * D)
+    wt, stale = _weight_operand_for_call(W, "cols", H, L * D)
     agg = torch.empty((V, L * D * 4), dtype=torch.uint8, device=dev)
     agg_inv = torch.empty((V, L), dtype=torch.float32, device=dev)
     out = torch.empty((V, H), dtype=torch.float32, device=dev) if want_fp32 else None
@@ -1816,8 +1790,7 @@ def mp_forward(graph: "Graph", view: int, x: torch.Tensor, W: torch.Tensor, *, r
     ws = _workspace(dev, ws_bytes) if ws_bytes else None
     rate, seed = dropout if dropout is not None else (0.0, 0)
     _ensure_splitk_workspace(dev, V)
-    stream = _stream()  # (launches what was deferred as urgent before this layer: its inputs may depend on it)
-    jobs, njobs, after, keep = _take_pending_jobs()
+    stream = _stream()  # (launches what was deferred before this layer: its inputs may depend on it)
     a = _lib.MpForwardArgs()
     a.struct_size = ctypes.sizeof(_lib.MpForwardArgs)
     a.kind = 0
@@ -1836,18 +1809,10 @@ def mp_forward(graph: "Graph", view: int, x: torch.Tensor, W: torch.Tensor, *, r
     a.out, a.ld_out = (out.data_ptr(), H) if out is not None else (None, 0)
     if op is not None:
         a.out_sp, a.ld_out_sp_bytes, a.out_inv_scale = op.data.data_ptr(), op.data.stride(0), op.inv_scale.data_ptr()
-    a.extra_jobs = ctypes.cast(jobs, ctypes.c_void_p) if jobs is not None else None
-    a.num_extra_jobs = njobs
     a.workspace, a.workspace_bytes = (ws.data_ptr(), ws.numel()) if ws is not None else (None, 0)
-    try:
-        _lib.check(lib.tfgnn_mp_forward(ctypes.byref(a), stream))
-    except Exception:
-        if stale:  # the cache holds an operand this call was to fill: forget it
-            notify_weights_changed(W)
-        raise
-    del keep
-    for then in after:
-        then()
+    _lib.check(lib.tfgnn_mp_forward(ctypes.byref(a), stream))
+    if stale:
+        _cache_weight_operand(W, "cols", wt)
     if out is not None and op is not None:
         _remember_split_rows(out, op)
     return out, op
@@ -1870,7 +1835,7 @@ def mp_backward(graph: "Graph", d_pre: torch.Tensor, W: torch.Tensor, x_sp: Opti
     d_pre, ldg = _rowmajor(d_pre, "d_pre")
     dev = d_pre.device
     graph.ensure(_VIEW_PARTS[VIEW_BY_SRC_TYPED])
-    wh, stale = _fresh_weight_operand(W, "rows", D, L * H)
+    wh, stale = _weight_operand_for_call(W, "rows", D, L * H)
     g_sp = torch.empty((V, L * H * 4), dtype=torch.uint8, device=dev)
     g_inv = torch.empty((V, L), dtype=torch.float32, device=dev)
     if out is None:
@@ -1905,7 +1870,6 @@ def mp_backward(graph: "Graph", d_pre: torch.Tensor, W: torch.Tensor, x_sp: Opti
             tn_ptr, tn_len = tn_ws.data_ptr() + off, tn_ws.numel() - off
     _ensure_splitk_workspace(dev, V)
     stream = _stream()
-    jobs, njobs, after, keep = _take_pending_jobs()
     skip = skip or {}
     a = _lib.MpBackwardArgs()
     a.struct_size = ctypes.sizeof(_lib.MpBackwardArgs)
@@ -1934,18 +1898,11 @@ def mp_backward(graph: "Graph", d_pre: torch.Tensor, W: torch.Tensor, x_sp: Opti
         a.dw = dW.data_ptr()
         a.x_sp, a.ld_x_sp_bytes, a.x_inv_scale = x_sp.data.data_ptr(), x_sp.data.stride(0), x_sp.inv_scale.data_ptr()
         a.tn_workspace, a.tn_workspace_bytes = tn_ptr, tn_len
-    a.extra_jobs = ctypes.cast(jobs, ctypes.c_void_p) if jobs is not None else None
-    a.num_extra_jobs = njobs
     a.workspace, a.workspace_bytes = (ws.data_ptr(), ws.numel()) if ws is not None else (None, 0)
-    try:
-        _lib.check(lib.tfgnn_mp_backward(ctypes.byref(a), stream))
-    except Exception:
-        if stale:
-            notify_weights_changed(W)
-        raise
-    del keep, tn_ws
-    for then in after:
-        then()
+    _lib.check(lib.tfgnn_mp_backward(ctypes.byref(a), stream))
+    if stale:
+        _cache_weight_operand(W, "rows", wh)
+    del tn_ws
     torch.autograd.graph.increment_version(out)
     if op is not None:
         _remember_split_rows(out, op)
@@ -1954,7 +1911,7 @@ def mp_backward(graph: "Graph", d_pre: torch.Tensor, W: torch.Tensor, x_sp: Opti
 
 @_writes_out
 def sp_gemm_tn(a: SplitOperand, b: SplitOperand, *, a_cols=None, b_cols=None, out: Optional[torch.Tensor] = None,
-               scatter=None, accumulate: bool = False, defer_reduce: bool = False, wide: bool = False) -> torch.Tensor:
+               scatter=None, accumulate: bool = False, wide: bool = False) -> torch.Tensor:
     """C[m, n] = sum_k a[k, a0 + m] * b[k, b0 + n] (tfgnn_sp_gemm_tn).  ``a`` carries one scale per (row, block),
     ``b`` one per row - what sp_split_rows / graph_gather_sp write.  ``a_cols`` / ``b_cols`` = (first column, count)
     select column ranges.  ``scatter`` = (group_rows, stride_group, stride_row, stride_col) writes element (m, n) at
@@ -1969,8 +1926,8 @@ def sp_gemm_tn(a: SplitOperand, b: SplitOperand, *, a_cols=None, b_cols=None, ou
     if wide and a.rows > TN_WIDE_MAX_ROWS:
         # the two-factor product takes at most 512 K ranges of 2016 rows per launch: longer operands (10^6 node rows) run as
         # consecutive row ranges, each adding into ``out``
-        if out is None or defer_reduce:
-            raise ValueError("sp_gemm_tn(wide=True) over more than %d rows needs out and no deferred reduction" % TN_WIDE_MAX_ROWS)
+        if out is None:
+            raise ValueError("sp_gemm_tn(wide=True) over more than %d rows needs out" % TN_WIDE_MAX_ROWS)
         for r0 in range(0, a.rows, TN_WIDE_MAX_ROWS):
             r1 = min(a.rows, r0 + TN_WIDE_MAX_ROWS)
             sp_gemm_tn(SplitOperand(a.data[r0:r1], a.inv_scale[r0:r1], r1 - r0, a.cols, a.scale_block),
@@ -1988,126 +1945,18 @@ def sp_gemm_tn(a: SplitOperand, b: SplitOperand, *, a_cols=None, b_cols=None, ou
         raise ValueError(f"out must be contiguous with {M * N} elements")
     gr, sg, sr, sc = scatter if scatter is not None else (M, 0, N, 1)
     ws_bytes = (lib.tfgnn_sp_gemm_tn_wide_workspace_bytes if wide else lib.tfgnn_sp_gemm_tn_workspace_bytes)(M, N, K, a.cols, a.scale_block)
-    defer_reduce = bool(defer_reduce) and aux_enabled() and ws_bytes > 0
-    if defer_reduce:
-        # ``out`` is complete only after the next aux_flush(): a weight gradient is not read before the end of the backward pass,
-        # so the split reductions of all layers share a launch.  The job owns its workspace until then.
-        ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=a.data.device)
-    else:
-        ws = _workspace(a.data.device, ws_bytes + 256) if ws_bytes else None
+    ws = _workspace(a.data.device, ws_bytes + 256) if ws_bytes else None
     ws_ptr, ws_len = None, 0
     if ws is not None:
         off = (-ws.data_ptr()) % 256
         ws_ptr, ws_len = ctypes.c_void_p(ws.data_ptr() + off), ws.numel() - off
-    if wide:
-        args = (M, N, K, _ptr(a.data), a.data.stride(0), a0, _ptr(a.inv_scale), a.cols, a.scale_block, _ptr(b.data),
-                b.data.stride(0), b0, _ptr(b.inv_scale), _ptr(out), gr, sg, sr, sc, int(accumulate), ws_ptr, ws_len)
-        if defer_reduce:
-            rjob = _lib.AuxJob()
-            _lib.check(lib.tfgnn_sp_gemm_tn_wide(*args, ctypes.byref(rjob), _stream()))
-            aux_defer(rjob, keep=(ws, out, a.data, a.inv_scale, b.data, b.inv_scale), urgent=False)
-        else:
-            _lib.check(lib.tfgnn_sp_gemm_tn_wide(*args, None, _stream()))
-        return out
-    if defer_reduce:
-        args = (M, N, K, _ptr(a.data), a.data.stride(0), a0, _ptr(a.inv_scale), a.cols, a.scale_block, _ptr(b.data),
-                b.data.stride(0), b0, _ptr(b.inv_scale), _ptr(out), gr, sg, sr, sc, int(accumulate), ws_ptr, ws_len)
-        keep = (ws, out, a.data, a.inv_scale, b.data, b.inv_scale)
-        rjob = _lib.AuxJob()
-        if K <= 131072 and env("TFGNN_TN_CHAINED", "0") == "1":  # opt-in: measured slower (NOTEBOOK.md 4.7)
-            # the whole product waits for the next merged launch: its factor pass rides there, the product follows it, the
-            # reduction rides in a later one (a weight gradient is off the critical path of the backward pass)
-            fjob = _lib.AuxJob()
-            _lib.check(lib.tfgnn_sp_gemm_tn_jobs(*args, ctypes.byref(fjob), ctypes.byref(rjob)))
-
-            def product():
-                _lib.check(lib.tfgnn_sp_gemm_tn_phase(2, *args, _stream()))
-                aux_defer(rjob, keep=keep, urgent=False)
-
-            aux_defer(fjob, keep=keep, urgent=False, then=product)
-            return out
-        _lib.check(lib.tfgnn_sp_gemm_tn_deferred(1, *args, ctypes.byref(rjob), _stream()))
-        aux_defer(rjob, keep=keep, urgent=False)
-        return out
     _lib.check(
-        lib.tfgnn_sp_gemm_tn(
+        (lib.tfgnn_sp_gemm_tn_wide if wide else lib.tfgnn_sp_gemm_tn)(
             M, N, K, _ptr(a.data), a.data.stride(0), a0, _ptr(a.inv_scale), a.cols, a.scale_block, _ptr(b.data),
             b.data.stride(0), b0, _ptr(b.inv_scale), _ptr(out), gr, sg, sr, sc, int(accumulate), ws_ptr, ws_len, _stream(),
         )
     )
     return out
-
-
-_aux_streams = {}
-_aux_pending = []
-def aux_stream(device) -> "torch.cuda.Stream":
-    """The library's second stream of a device: small passes that are off the critical path (the factor and reduction
-    passes of a weight-gradient product) run there beside the big kernels of the main stream."""
-    key = (device.type, device.index)
-    st = _aux_streams.get(key)
-    if st is None:
-        st = torch.cuda.Stream(device=device)
-        _aux_streams[key] = st
-    return st
-
-
-def join_aux_stream() -> None:
-    """Make the current stream wait for everything handed to the second stream (call before the results - weight
-    gradients - are read)."""
-    cur = torch.cuda.current_stream()
-    while _aux_pending:
-        cur.wait_event(_aux_pending.pop())
-
-
-class SpGemmTnOverlapped:
-    """sp_gemm_tn in three calls, the small passes on the second stream:
-         h = SpGemmTnOverlapped(a, b, out=..., scatter=...)   # factor pass: second stream, beside what the caller enqueues next
-         ...                                                   # e.g. the input-gradient product that precedes it
-         h.product()                                           # the product: current stream, after the factors
-         h.finish()                                            # reduction + scatter: second stream, beside what follows
-       ``join_aux_stream()`` before the result is read."""
-
-    def __init__(self, a: "SplitOperand", b: "SplitOperand", *, out: torch.Tensor, scatter=None, accumulate: bool = False):
-        if a.scale_block <= 0 or b.scale_block != b.cols or a.rows != b.rows:
-            raise ValueError("SpGemmTnOverlapped: operands as for sp_gemm_tn")
-        lib = _lib.load()
-        self.M, self.N, self.K = a.cols, b.cols, a.rows
-        if not out.is_contiguous() or out.numel() != self.M * self.N:
-            raise ValueError(f"out must be contiguous with {self.M * self.N} elements")
-        self.a, self.b, self.out, self.accumulate = a, b, out, accumulate
-        self.scatter = scatter if scatter is not None else (self.M, 0, self.N, 1)
-        ws_bytes = lib.tfgnn_sp_gemm_tn_workspace_bytes(self.M, self.N, self.K, a.cols, a.scale_block)
-        self.ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=a.data.device)
-        self.main = torch.cuda.current_stream()
-        self.side = aux_stream(a.data.device)
-        for t in (self.ws, out, a.inv_scale, b.inv_scale):
-            t.record_stream(self.side)
-        self.side.wait_stream(self.main)  # the scales are written
-        with torch.cuda.stream(self.side):
-            self._phase(1)
-            self.ev_factors = self.side.record_event()
-
-    def _phase(self, phases: int):
-        a, b = self.a, self.b
-        off = (-self.ws.data_ptr()) % 256
-        gr, sg, sr, sc = self.scatter
-        _lib.check(_lib.load().tfgnn_sp_gemm_tn_phase(
-            phases, self.M, self.N, self.K, _ptr(a.data), a.data.stride(0), 0, _ptr(a.inv_scale), a.cols, a.scale_block, _ptr(b.data),
-            b.data.stride(0), 0, _ptr(b.inv_scale), _ptr(self.out), gr, sg, sr, sc, int(self.accumulate),
-            ctypes.c_void_p(self.ws.data_ptr() + off), self.ws.numel() - off, _stream()))
-
-    def product(self):
-        cur = torch.cuda.current_stream()
-        cur.wait_event(self.ev_factors)
-        self._phase(2)
-        self.ev_product = cur.record_event()
-
-    def finish(self):
-        self.side.wait_event(self.ev_product)
-        with torch.cuda.stream(self.side):
-            self._phase(4)
-            _aux_pending.append(self.side.record_event())
-        torch.autograd.graph.increment_version(self.out)
 
 
 def tensor_inv_scale(bound: torch.Tensor) -> torch.Tensor:
@@ -2172,48 +2021,6 @@ def _weight_checksum(w: torch.Tensor):
     return (float(v.sum()), float(v.abs().sum()))
 
 
-def sp_split_weights(stacks) -> None:
-    """Split the stacked kernels [L, D, H] of several layers (one shape) into both operand forms with ONE launch
-    (tfgnn_sp_split_weights) and put them where ``sp_weight_operand(W, "cols" | "rows", ...)`` finds them.  Stacks whose
-    current value is already split are skipped."""
-    import weakref
-
-    todo = []
-    for w in stacks:
-        hits = [_sp_weight_cache.get(_weight_key(w, kind)) for kind in ("cols", "rows")]
-        if not all(h is not None and h[0] == w._version and h[2]() is not None for h in hits):
-            todo.append(w)
-    if not todo:
-        return
-    lib = _lib.load()
-    L, D, H = todo[0].shape
-    for w in todo:
-        if tuple(w.shape) != (L, D, H) or not w.is_contiguous():
-            raise ValueError("sp_split_weights: contiguous [L, D, H] stacks of one shape")
-        _require_dev(w, torch.float32, "kernel stack")
-    for start in range(0, len(todo), 16):
-        group = todo[start : start + 16]
-        n = len(group)
-        dev = group[0].device
-        cols = [SplitOperand(torch.empty((H, L * D * 4), dtype=torch.uint8, device=dev), torch.empty((H, 1), dtype=torch.float32, device=dev),
-                             H, L * D, L * D) for _ in group]
-        rows = [SplitOperand(torch.empty((D, L * H * 4), dtype=torch.uint8, device=dev), torch.empty((D, 1), dtype=torch.float32, device=dev),
-                             D, L * H, L * H) for _ in group]
-
-        def ptrs(ts):
-            return (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
-
-        _lib.check(lib.tfgnn_sp_split_weights(n, ptrs(group), L, D, H, ptrs([c.data for c in cols]), ptrs([c.inv_scale for c in cols]),
-                                              ptrs([r.data for r in rows]), ptrs([r.inv_scale for r in rows]), _stream()))
-        if len(_sp_weight_cache) > 256:
-            _sp_weight_cache.clear()
-        for w, c, r in zip(group, cols, rows):
-            base = w._base if w._base is not None else w
-            chk = _weight_checksum(w)
-            _sp_weight_cache[_weight_key(w, "cols")] = (w._version, c, weakref.ref(base), chk)
-            _sp_weight_cache[_weight_key(w, "rows")] = (w._version, r, weakref.ref(base), chk)
-
-
 def sp_weight_operand(w: torch.Tensor, kind: str, build):
     """A derived form of a weight tensor (its SP16 operands; also the transposed / re-stacked fp32 copies the bf16x3 products
     take), built once per value: keyed on the tensor's storage and version (an in-place torch update bumps the version;
@@ -2221,20 +2028,30 @@ def sp_weight_operand(w: torch.Tensor, kind: str, build):
     and every step of an evaluation loop - share it.  ``build()`` makes the operand.  Updates torch cannot see
     (``var.value.data.add_(...)``, raw-pointer kernels) MUST be followed by ``Variable.mark_updated()`` /
     ``notify_weights_changed``; TFGNN_CHECK_WEIGHT_CACHE=1 verifies every hit against a checksum of the weight."""
-    key = _weight_key(w, kind)
-    hit = _sp_weight_cache.get(key)
+    op = _cached_weight_operand(w, kind)
+    if op is None:
+        op = build()
+        _cache_weight_operand(w, kind, op)
+    return op
+
+
+def _cached_weight_operand(w: torch.Tensor, kind: str):
+    """The cached form ``kind`` of the current value of ``w``, or None."""
+    hit = _sp_weight_cache.get(_weight_key(w, kind))
     if hit is not None and hit[0] == w._version and hit[2]() is not None:
         if hit[3] is not None and hit[3] != _weight_checksum(w):
             raise RuntimeError("a weight tensor changed without a version bump (update through .data or a raw pointer?): "
                                "call Variable.mark_updated() / ops.notify_weights_changed() after such an update")
         return hit[1]
-    import weakref
-
     if hit is not None:
         aux_flush()  # the stale form may still have its (deferred) conversion pending: launch it before the new one is queued
-    op = build()
+    return None
+
+
+def _cache_weight_operand(w: torch.Tensor, kind: str, op) -> None:
+    import weakref
+
     if len(_sp_weight_cache) > 256:
         _sp_weight_cache.clear()
     base = w._base if w._base is not None else w  # views are temporaries: the entry lives as long as the parameter buffer
-    _sp_weight_cache[key] = (w._version, op, weakref.ref(base), _weight_checksum(w))
-    return op
+    _sp_weight_cache[_weight_key(w, kind)] = (w._version, op, weakref.ref(base), _weight_checksum(w))

@@ -156,8 +156,7 @@ class Optimizer:
                 live.append((var, grad))
         if not live:
             raise ValueError("No gradients provided for any variable.")
-        ops.aux_flush()  # deferred split-K reductions complete the weight gradients of earlier layers
-        ops.join_aux_stream()  # and so do the passes handed to the library's second stream
+        ops.aux_flush()  # deferred weight splits read the weights when they are launched: before the update writes them
         dev = live[0][0].value.device
         state = self._ensure_state(dev)
         rows = np.empty((len(live), 8), dtype=np.int64)
