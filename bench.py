@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the message-passing hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--workload NAME]
+  python bench.py --gpus N --steps K --warmup W [--workload NAME] [--full]
 
 Headline (default workload ``rmat30k``): BASELINE.json's metric - edges/sec (fwd+bwd), RGCN H=320 L=4 on an R-MAT batch
 shaped like configs[1] (30k nodes, 900k edges, 4 edge types) with the PPI_RGCN.json hyper-parameters.  The other
@@ -25,11 +25,15 @@ the script re-executes itself under ``python -m torch.distributed.run --nnodes=1
     nodes) for the metric; --allreduce-grads adds the training-step exchange (one bucketed all-reduce of the weight
     gradients, parallel.allreduce_gradients).
 
-Prints ONE JSON line (rank 0).  ``roofline`` describes the dominant kernel of the workload, timed live with HIP events on
-the launch stream; ``cpu_baseline`` times the CPU oracle (the reference's op sequence, torch-CPU, the workload's own model)
-on rank 0 at N == 1 on a bounded sample; the non-headline workloads also carry ``step_breakdown`` - every library op of the
-real step between HIP events, priced against its roof; the default run (rmat30k, N == 1) times the other four BASELINE
-workloads briefly in processes of their own and reports them under ``other_configs`` (--no-other-configs skips that).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the
+line: nothing else.  --full then measures what the headline does not need (--no-alt-mode, --no-roofline,
+--no-cpu-baseline and --no-other-configs drop parts of it): ``config.alt_gemm_mode`` times the same job in a second GEMM
+mode; ``roofline`` describes the dominant kernel of the workload, timed live with HIP events on the launch stream;
+``cpu_baseline`` times the CPU oracle (the reference's op sequence, torch-CPU, the workload's own model) on rank 0 at
+N == 1 on a bounded sample; the non-headline workloads also carry ``step_breakdown`` - every library op of the real step
+between HIP events, priced against its roof; rmat30k at N == 1 times the other BASELINE workloads briefly in --full runs
+of their own and reports them under ``other_configs``; ppi adds the host time of a step and the step replayed from one
+hipGraph.
 """
 from __future__ import annotations
 
@@ -495,8 +499,8 @@ def run_ppi(args, wl):
     a full training step of tf2_gnn_train RGCN PPI minus the optimizer update on the synthetic stand-in - batch finalisation
     on the device (process_adjacency_lists: self loops + backward edges -> 3 edge types, data/utils.py:9-58), edge bucketing,
     NodeMulticlassTask forward (RGCN H=320 L=4 + Dense(121)), sigmoid cross-entropy + micro-F1, full backward.  At V = 7110
-    the step is ~200 launches of a few microseconds: the line separates the HOST time of a step (Python + ctypes, measured as
-    the time to enqueue it) from the device-bound step time."""
+    the step is ~200 launches of a few microseconds: with --full the line separates the HOST time of a step (Python + ctypes,
+    measured as the time to enqueue it) from the device-bound step time and adds the step replayed from one hipGraph."""
     import torch
 
     from tf2_gnn_amd import ops
@@ -582,26 +586,54 @@ def run_ppi(args, wl):
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, {"per_node_logits": last_step["output"].cpu(), "loss": last_step["loss"].cpu().reshape(1),
                                          **grads_of(model.trainable_variables)})
-    # host time: how long the enqueue of a step takes (each step timed on an idle queue, then waited for)
-    host = []
-    for _ in range(min(args.steps, 10)):
-        torch.cuda.synchronize()
-        h0 = time.perf_counter()
-        step()
-        host.append(time.perf_counter() - h0)
-        torch.cuda.synchronize()
-    host_ms = 1000.0 * float(np.median(host))
-    # device time of one step in isolation: events around it
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    a.record()
-    m = step()
-    b.record()
-    torch.cuda.synchronize()
     G = wl["num_graphs"]
-    eager = {"ms_per_step": 1000.0 * dt, "host_ms_per_step": host_ms, "device_ms_one_step_alone": a.elapsed_time(b),
-             "edges_per_s": E[0] / dt, "graphs_per_s": G / dt,
-             "what": "every step driven from Python: finalisation + bucketing + forward + loss + backward (~190 launches through ctypes)"}
+    # The line's `value` is the EAGER step: a stream of distinct batches - what PPI training is and what the reference's
+    # tf.function step serves (layers/gnn.py:220-232) - cannot be replayed from a graph frozen to one adjacency (ADVICE r5).
+    # The replayed step of a static batch (full-batch training, revisited batches, inference) is reported beside it (--full).
+    result = {
+        "metric": "graphs/sec and edges/sec (batch finalisation + fwd + loss + bwd) RGCN H=320 L=4 + NodeMulticlassTask, PPI stand-in (BASELINE configs[0])",
+        "value": E[0] / dt,
+        "unit": "edges/s",
+        "graphs_per_s": G / dt,
+        "n_gpus": 1,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1000.0 * dt,
+        "step": f"every step another batch ({K_batches} distinct batches take turns): finalisation + bucketing of the next batch "
+                f"{'on the compute stream' if args.serial_bucketing else '(2nd stream, overlapped)'} + forward + loss + backward, driven from Python (eager)",
+        "batches": K_batches,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "reference_published": {"graphs_per_s_epoch_1": 2.63, "graphs_per_s_later_epochs": 4.01,
+                                "source": "tf2-gnn README.md:47-48 (TensorFlow, real PPI, hardware not stated) - not this stand-in, no ratio taken"},
+        "dtype": "f32",
+        "data": "synthetic: 3 R-MAT graphs x 2370 nodes, 14 forward edges per node, N(0,1) features [V, 50], Bernoulli(0.3) labels [V, 121], Glorot weights",
+        "config": {"workload": f"ppi: V={V} E={E[0]} (3 edge types after finalisation) D_in=50 H=320 L=4 labels=121",
+                   "gemm_mode": args.gemm_mode, "gemm_mode_name": args.gemm_mode, "products_per_step": products},
+    }
+    if args.full:
+        # host time: how long the enqueue of a step takes (each step timed on an idle queue, then waited for)
+        host = []
+        for _ in range(min(args.steps, 10)):
+            torch.cuda.synchronize()
+            h0 = time.perf_counter()
+            step()
+            host.append(time.perf_counter() - h0)
+            torch.cuda.synchronize()
+        host_ms = 1000.0 * float(np.median(host))
+        # device time of one step in isolation: events around it
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        step()
+        b.record()
+        torch.cuda.synchronize()
+        result["host_ms_per_step"] = host_ms
+        result["eager"] = {"ms_per_step": 1000.0 * dt, "host_ms_per_step": host_ms, "device_ms_one_step_alone": a.elapsed_time(b),
+                           "edges_per_s": E[0] / dt, "graphs_per_s": G / dt,
+                           "what": "every step driven from Python: finalisation + bucketing + forward + loss + backward (~190 launches through ctypes)"}
+        result["bound"] = "host" if host_ms > 0.9 * 1000.0 * dt else "device"
 
     for b_, _ in ready:  # the batch prepared for the step after the last one
         g_ = b_.get("bucketed_graph")
@@ -611,15 +643,26 @@ def run_ppi(args, wl):
     ready.clear()
     torch.cuda.synchronize()
 
-    # ---- the same training step replayed from ONE hipGraph (tf2_gnn_amd.capture.CapturedStep; the reference traces its step
-    # into one tf.function graph: models/graph_task_model.py:327-357).  The forward + loss + backward of the finalised, bucketed
-    # batch is captured once; a replay is one hipGraphLaunch.  The input pipeline's share of a step - finalisation and
-    # bucketing of the NEXT batch - still runs per step, eagerly on a second stream (like the headline workload), so the
-    # step keeps the work it had in the eager measurement; `replay_only` is the step without it.
+    if args.full:
+        replay, loss = ppi_replay(args, model, ops, X, fwd_dev, n2g_dev, labels_dev, V, G, E[0])
+        result.update(replay)
+        result["config"]["loss"] = loss
+    result["config"]["guard"] = model._gnn.guard_state()
+    emit(result, "ppi")
+
+
+def ppi_replay(args, model, ops, X, fwd_dev, n2g_dev, labels_dev, V, G, E):
+    """The ppi workload's --full part -> (fields of the line, loss of the last replay): the same training step replayed from
+    ONE hipGraph (tf2_gnn_amd.capture.CapturedStep; the reference traces its step into one tf.function graph:
+    models/graph_task_model.py:327-357).  The forward + loss + backward of the finalised, bucketed batch is captured once; a
+    replay is one hipGraphLaunch.  The input pipeline's share of a step - finalisation and bucketing of the NEXT batch - still
+    runs per step, eagerly on a second stream (like the headline workload), so the step keeps the work it had in the eager
+    measurement; `replay_only` is the step without it."""
     from tf2_gnn_amd import CapturedStep
+    from tf2_gnn_amd.data import process_adjacency_lists
 
     adjs_static, _ = process_adjacency_lists([fwd_dev], V, add_self_loop_edges=True, tied_fwd_bkwd_edge_types=set())
-    batch_static = {"node_features": X, "node_to_graph_map": n2g_dev, "num_graphs_in_batch": wl["num_graphs"],
+    batch_static = {"node_features": X, "node_to_graph_map": n2g_dev, "num_graphs_in_batch": G,
                     **{f"adjacency_list_{i}": t for i, t in enumerate(adjs_static)}}
     edges_per_type = [int(t.shape[0]) for t in adjs_static]
 
@@ -679,43 +722,16 @@ def run_ppi(args, wl):
     m, _ = cap.replay()
     torch.cuda.synchronize()
     assert not cap.guard_tripped(), "the spread guard tripped during the replayed steps"
-    # The line's `value` is the EAGER step: a stream of distinct batches - what PPI training is and what the reference's
-    # tf.function step serves (layers/gnn.py:220-232) - cannot be replayed from a graph frozen to one adjacency (ADVICE r5).
-    # The replayed step of a static batch (full-batch training, revisited batches, inference) is reported beside it.
-    result = {
-        "metric": "graphs/sec and edges/sec (batch finalisation + fwd + loss + bwd) RGCN H=320 L=4 + NodeMulticlassTask, PPI stand-in (BASELINE configs[0])",
-        "value": E[0] / dt,
-        "unit": "edges/s",
-        "graphs_per_s": G / dt,
-        "n_gpus": 1,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": 1000.0 * dt,
-        "host_ms_per_step": host_ms,
-        "step": f"every step another batch ({K_batches} distinct batches take turns): finalisation + bucketing of the next batch "
-                f"{'on the compute stream' if args.serial_bucketing else '(2nd stream, overlapped)'} + forward + loss + backward, driven from Python (eager)",
-        "batches": K_batches,
-        "eager": eager,
-        "replay_static_batch": {"ms_per_step": 1000.0 * dt_cap, "host_ms_per_step": host_cap, "edges_per_s": E[0] / dt_cap,
+    replay = {
+        "replay_static_batch": {"ms_per_step": 1000.0 * dt_cap, "host_ms_per_step": host_cap, "edges_per_s": E / dt_cap,
                                 "graphs_per_s": G / dt_cap,
                                 "what": "the SAME batch every step: forward + loss + backward replayed from one hipGraph (CapturedStep) + "
                                         "finalisation and bucketing of a next batch on a second stream (built, not trained on)"},
-        "replay_only": {"ms_per_step": 1000.0 * dt_replay, "host_ms_per_step": host_replay, "edges_per_s": E[0] / dt_replay,
+        "replay_only": {"ms_per_step": 1000.0 * dt_replay, "host_ms_per_step": host_replay, "edges_per_s": E / dt_replay,
                         "graphs_per_s": G / dt_replay,
                         "what": "forward + loss + backward of the finalised, bucketed batch: one hipGraphLaunch per step"},
-        "bound": "host" if host_ms > 0.9 * 1000.0 * dt else "device",
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "reference_published": {"graphs_per_s_epoch_1": 2.63, "graphs_per_s_later_epochs": 4.01,
-                                "source": "tf2-gnn README.md:47-48 (TensorFlow, real PPI, hardware not stated) - not this stand-in, no ratio taken"},
-        "dtype": "f32",
-        "data": "synthetic: 3 R-MAT graphs x 2370 nodes, 14 forward edges per node, N(0,1) features [V, 50], Bernoulli(0.3) labels [V, 121], Glorot weights",
-        "config": {"workload": f"ppi: V={V} E={E[0]} (3 edge types after finalisation) D_in=50 H=320 L=4 labels=121",
-                   "gemm_mode": args.gemm_mode, "gemm_mode_name": args.gemm_mode, "products_per_step": products,
-                   "guard": model._gnn.guard_state(), "loss": float(m["loss"])},
     }
-    emit(result, "ppi")
+    return replay, float(m["loss"])
 
 
 def main():
@@ -726,6 +742,10 @@ def main():
     ap.add_argument("--workload", default="rmat30k", choices=sorted(WORKLOADS))
     ap.add_argument("--reuse-graph", action="store_true", help="bucket the edges once, outside the timed steps")
     ap.add_argument("--serial-bucketing", action="store_true", help="bucket each batch on the compute stream (no overlap)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what the line does not need: the other GEMM mode, the rooflines, the "
+                         "step breakdown, the CPU baseline, the other BASELINE workloads (rmat30k) and the replayed step (ppi); "
+                         "--no-alt-mode, --no-roofline, --no-cpu-baseline and --no-other-configs drop parts of it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=36.0, help="host time budget of the cpu_baseline leg")
     ap.add_argument("--no-roofline", action="store_true")
@@ -741,7 +761,7 @@ def main():
                          "whose source rows are then warm in the Infinity Cache - the optimistic case)")
     ap.add_argument("--no-settle", action="store_true", help="skip the untimed settle loop (launch-path tests)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short timings of the other BASELINE workloads that the default run reports under `other_configs`")
+                    help="skip the short timings of the other BASELINE workloads that a --full run reports under `other_configs`")
     ap.add_argument("--plumbing-only", action="store_true",
                     help="no device work: spawn / rendezvous (gloo) / sharding / collectives only - the CPU test of the N > 1 launch path")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -1049,7 +1069,7 @@ def main():
             "allreduce_ms_per_step_per_rank": allreduce_ms_per_rank,
         },
     }
-    if not args.no_alt_mode:
+    if args.full and not args.no_alt_mode:
         # the same job with the products in another evaluation mode, for reference (not the headline value)
         alt = "bf16x3" if args.gemm_mode != "bf16x3" else "fp32"
         ops.set_gemm_mode(alt)
@@ -1061,7 +1081,7 @@ def main():
             "value": total_edges_per_step * alt_steps / alt_elapsed,
         }
 
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         roofs = roofline_blocks(args, wl, ops, dev, adj_dev, V, E, L, H, NL, ms_per_step)
         roofs.sort(key=lambda r: -r["share_of_step"])
         result["roofline_blocks_share_of_step"] = float(sum(r["share_of_step"] for r in roofs))
@@ -1071,7 +1091,7 @@ def main():
         if len(roofs) > 2:
             result["roofline_other"] = roofs[2:]
 
-    if rank == 0 and world == 1 and not args.no_roofline and args.workload != "rmat30k":
+    if args.full and rank == 0 and world == 1 and not args.no_roofline and args.workload != "rmat30k":
         # the non-headline workloads spread their step over many kernels: the per-op breakdown of the REAL step (HIP events
         # around every library op) says where the step goes and prices each op against its roof
         ops.set_gemm_mode(args.gemm_mode)
@@ -1081,10 +1101,10 @@ def main():
             g_.close()
         pending.clear()
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(wl, batch, params, budget_seconds=args.cpu_baseline_seconds)
 
-    if rank == 0 and world == 1 and args.workload == "rmat30k" and not args.no_other_configs:
+    if args.full and rank == 0 and world == 1 and args.workload == "rmat30k" and not args.no_other_configs:
         result["other_configs"] = other_configs(args)
 
     if rank == 0:
@@ -1098,13 +1118,13 @@ OTHER_CONFIGS = (("ppi", 30), ("rgat", 10), ("qm9-ggnn", 3), ("qm9-edgemlp", 3),
 
 
 def other_configs(args):
-    """The other BASELINE configs, timed briefly (a few steps each, own process: fresh allocator and weight caches) so that
-    the driver's line carries them next to the headline: ms/step, edges/s, the dominant kernel's roofline fraction and the
-    CPU baseline of the same model.  They are reported, not part of `value`."""
+    """The other BASELINE configs, timed briefly (a few steps each, a --full run in a process of its own: fresh allocator and
+    weight caches) so that the driver's line carries them next to the headline: ms/step, edges/s, the dominant kernel's
+    roofline fraction and the CPU baseline of the same model.  They are reported, not part of `value`."""
     out = {}
     for name, steps in OTHER_CONFIGS:
-        cmd = [sys.executable, os.path.abspath(__file__), "--workload", name, "--steps", str(steps), "--warmup", "1", "--no-alt-mode",
-               "--no-other-configs", "--gemm-mode", args.gemm_mode, "--cpu-baseline-seconds", "8"]
+        cmd = [sys.executable, os.path.abspath(__file__), "--workload", name, "--steps", str(steps), "--warmup", "1", "--full",
+               "--no-alt-mode", "--no-other-configs", "--gemm-mode", args.gemm_mode, "--cpu-baseline-seconds", "8"]
         if args.no_cpu_baseline:
             cmd.append("--no-cpu-baseline")
         if args.no_roofline:

@@ -48,7 +48,7 @@ def test_two_ranks_shard_the_molecule_batch_through_the_hip_path():
 
 
 def test_two_replica_ranks_for_the_single_graph_workload():
-    r = _bench(["--gpus", "2", "--workload", "tiny"])
+    r = _bench(["--gpus", "2", "--workload", "tiny", "--full"])  # --full: the roofline block
     assert r["n_gpus"] == 2 and r["scaling"] == "weak"
     assert r["config"]["edges_per_rank"] == [40000.0, 40000.0]
     assert r["roofline"]["bound"] in ("hbm", "mfma") and 0 < r["roofline"]["frac"] <= 1.0

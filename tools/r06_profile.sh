@@ -9,7 +9,7 @@ STAGES=${@:-bench stats pmc mfma res}
 WLS="rmat30k rgat qm9-ggnn qm9-edgemlp arxiv-rgin"
 for S in $STAGES; do case $S in
   bench)
-    python bench.py > $O/bench_default.out 2> $O/bench_default.err
+    python bench.py --full > $O/bench_default.out 2> $O/bench_default.err
     grep "^BENCH_DETAIL " $O/bench_default.out | sed 's/^BENCH_DETAIL //' > $O/r06_bench_default_detail.json
     tail -1 $O/bench_default.out > $O/r06_bench_default.json
     wc -c $O/r06_bench_default.json ;;
