@@ -55,8 +55,7 @@ static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // they get two workgroups per CU with chunks of at least 512 rows.
 static inline int64_t splitk_want(int64_t tiles, int64_t K) {
   if (tiles < 1) tiles = 1;
-  static const bool long_k = [] { const char* e = getenv("TFGNN_LONG_K_SPLITS"); return !e || atoi(e) != 0; }();  // 0: A/B probe
-  if (long_k && tiles <= 8 && K >= 131072) {
+  if (tiles <= 8 && K >= 131072) {
     const int64_t want = std::min<int64_t>(512 / tiles, K / 512);
     return std::min<int64_t>(want, 512);
   }

@@ -913,23 +913,20 @@ static void launch_x3_splitk_reduce(const X3Args& g, unsigned groups, hipStream_
 // producer waves cannot keep up with the register transposes: 185 vs 207 us).
 // NT products on the pipelined kernel: the narrow tile only (106 registers there: two workgroups per CU and all eight
 // waves of each multiplying - the QM9-sized shapes run ~10 % faster than on the specialised kernel; on the wide tiles the
-// two kernels take the same time).  TFGNN_X3_NT_PIPELINED = 0 / 1 forces never / always.
-template <int TN>
-static bool pipelined_nt() {
-  static const int knob = [] { const char* e = getenv("TFGNN_X3_NT_PIPELINED"); return e ? atoi(e) : -1; }();
-  return knob < 0 ? TN == 2 : knob != 0;
-}
-
+// two kernels take the same time).
 template <int TN>
 static void launch_x3(const X3Args& g, dim3 grid, int nprod, int trans_a, int trans_b, hipStream_t s) {
+  constexpr bool pipelined_nt = TN == 2;
   const bool nine = nprod >= 9;
   count_launch(TFGNN_KFAM_GEMM_BF16X3);
   if (trans_a) {
     if (nine) hipLaunchKernelGGL((gemm_x3p_kernel<9, TN>), grid, dim3(X3_NT), 0, s, g);
     else hipLaunchKernelGGL((gemm_x3p_kernel<6, TN>), grid, dim3(X3_NT), 0, s, g);
-  } else if (trans_b && g.group_mode == 0 && pipelined_nt<TN>()) {
-    if (nine) hipLaunchKernelGGL((gemm_x3p_kernel<9, TN, true>), grid, dim3(X3_NT), 0, s, g);
-    else hipLaunchKernelGGL((gemm_x3p_kernel<6, TN, true>), grid, dim3(X3_NT), 0, s, g);
+  } else if (pipelined_nt && trans_b && g.group_mode == 0) {
+    if constexpr (pipelined_nt) {
+      if (nine) hipLaunchKernelGGL((gemm_x3p_kernel<9, TN, true>), grid, dim3(X3_NT), 0, s, g);
+      else hipLaunchKernelGGL((gemm_x3p_kernel<6, TN, true>), grid, dim3(X3_NT), 0, s, g);
+    }
   } else if (trans_b) {
     if (nine) hipLaunchKernelGGL((gemm_x3s_kernel<false, 9, TN>), grid, dim3(X3_NT), 0, s, g);
     else hipLaunchKernelGGL((gemm_x3s_kernel<false, 6, TN>), grid, dim3(X3_NT), 0, s, g);
@@ -1655,21 +1652,14 @@ static void launch_x3k_ks(const X3Args& g, int ks, int b_kmajor, int ncb, int sp
 }
 
 int gemm_f16x2_mode();
-// mode f16x2 (while its guard has not demoted it): the streaming kernel multiplies in the f16x2 arithmetic, 3 products instead of
-// 6 (TFGNN_X3K_F16=0: the exact bf16x3 form, for A/B runs)
-static bool x3k_f16_arithmetic(int nprod) {
-  static const bool on = [] { const char* e = getenv("TFGNN_X3K_F16"); return !e || atoi(e) != 0; }();
-  return on && nprod == 6 && gemm_f16x2_mode() == 1;
-}
+// mode f16x2 (while its guard has not demoted it): the streaming kernel multiplies in the f16x2 arithmetic, 3 products instead of 6
+static bool x3k_f16_arithmetic(int nprod) { return nprod == 6 && gemm_f16x2_mode() == 1; }
 
-static int64_t x3k_min_rows() {
-  static const int64_t min_rows = [] { const char* e = getenv("TFGNN_X3_STREAM_MIN_ROWS"); return e ? atoll(e) : 65536ll; }();
-  return min_rows;
-}
+constexpr int64_t kX3kMinRows = 65536;
 // shape limits shared by the forms of the streaming kernel: K in {32, 64, 96, 128}, many rows, 32-bit byte offsets and 24-bit
 // factors for the streamed operand
 static bool x3k_shape_ok(const X3Args& g) {
-  if (x3k_min_rows() <= 0 || g.M < x3k_min_rows() || g.K % 32 || g.K < 32 || g.K > 128) return false;
+  if (g.M < kX3kMinRows || g.K % 32 || g.K < 32 || g.K > 128) return false;
   const int64_t src_rows = g.a_index ? g.a_rows : g.M;
   return src_rows * g.lda < (1ll << 30) - 2048 && src_rows < (1 << 24) && g.M < (1ll << 31) - 64 && g.lda < (1 << 22);
 }
@@ -1701,9 +1691,8 @@ static int gemm_x3k_try(int nprod, int trans_b, const X3Args& g, hipStream_t s) 
 
 // the GRU form (g filled by gemm_x3_gru: B = the regrouped kernel [3H, K], C = h' [M, H]): one workgroup per 32 units
 static int gemm_x3k_gru_try(int nprod, const X3Args& g, hipStream_t s) {
-  static const bool on = [] { const char* e = getenv("TFGNN_X3_STREAM_GRU"); return !e || atoi(e) != 0; }();  // 0: A/B probe
   const int H = g.gru_H;
-  if (!on || !x3k_shape_ok(g) || H % 64 || H / 32 > 32 || g.ldc % 4) return 0;
+  if (!x3k_shape_ok(g) || H % 64 || H / 32 > 32 || g.ldc % 4) return 0;
   const int ncb = H / 32, spx = 32 / ncb;
   const bool f16 = x3k_f16_arithmetic(nprod);
   count_launch(f16 ? TFGNN_KFAM_STREAM_F16X2 : TFGNN_KFAM_GEMM_BF16X3);
@@ -1764,8 +1753,7 @@ int gemm_x3_try(int nprod, int trans_a, int trans_b, int64_t M, int64_t N, int64
   int bn = N % 320 == 0 ? 320 : (N % 256 == 0 ? 256 : (N % 128 == 0 ? 128 : 0));
   // short K, many row blocks (QM9-sized batches): the 128-wide tile runs two workgroups per CU, which overlaps one's
   // prologue / output burst with the other's few K tiles
-  static const int narrow_k = [] { const char* e = getenv("TFGNN_X3_NARROW_K"); return e ? atoi(e) : 256; }();
-  if (!trans_a && K <= narrow_k && N % 128 == 0 && M >= 128 * 1024) bn = 128;
+  if (!trans_a && K <= 256 && N % 128 == 0 && M >= 128 * 1024) bn = 128;
   if (!bn || K < 64 || M < 1) return 0;
   const bool a16 = ((uintptr_t)A % 16 == 0) && (lda % 4 == 0);
   const bool b16 = ((uintptr_t)B % 16 == 0) && (ldb % 4 == 0);
@@ -1886,8 +1874,7 @@ int gemm_x3_gru(int nprod, int64_t M, int H, int64_t K, const float* A, int64_t 
 // QM9-sized row counts (x3k_shape_ok).
 int gemm_x3_gru2(int nprod, int64_t M, int H, int64_t K, const float* A, int64_t lda, const float* Bt, const float* bias, const float* h,
                  const float* B2t, const float* bias2, float* h_new, float* gates, float* mh_out, hipStream_t s) {
-  static const bool on = [] { const char* e = getenv("TFGNN_X3_STREAM_GRU2"); return !e || atoi(e) != 0; }();  // 0: A/B probe
-  if (!on || !x3k_f16_arithmetic(nprod) || K != H || (H != 64 && H != 128) || M < 1 || lda % 4 != 0) return 0;
+  if (!x3k_f16_arithmetic(nprod) || K != H || (H != 64 && H != 128) || M < 1 || lda % 4 != 0) return 0;
   for (const void* ptr : {(const void*)A, (const void*)Bt, (const void*)B2t, (const void*)h, (const void*)h_new})
     if ((uintptr_t)ptr % 16) return 0;
   if ((bias && (uintptr_t)bias % 16) || (bias2 && (uintptr_t)bias2 % 16) || (gates && (uintptr_t)gates % 16) || (mh_out && (uintptr_t)mh_out % 16))

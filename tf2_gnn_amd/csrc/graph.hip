@@ -808,23 +808,15 @@ using namespace tfgnn;
 constexpr unsigned kPartsAll = TFGNN_GRAPH_PART_PLAN_TYPED | TFGNN_GRAPH_PART_PLAN_NODE | TFGNN_GRAPH_PART_COMPACT |
                                TFGNN_GRAPH_PART_EDGE_MAPS | TFGNN_GRAPH_PART_EDGE_IDS | TFGNN_GRAPH_PART_DST_PATTERN;
 
-// long-row plan parameters per view (tools/gather_probe.py sweeps at cfg-2, rows ordered by length): typed
-// views 91 us at (48, 512) vs 104 us at (16, 192) (134 us in natural row order at (16, 128)); the node views -
-// all edge types of a node in one row - 121 us at (32, 512) vs 128 us at (64, 512) (138 us in natural order).  TFGNN_LONG_ROW / TFGNN_ITEM_CHUNK override the typed views, TFGNN_LONG_ROW_NODE /
-// TFGNN_ITEM_CHUNK_NODE the node views, for probing.
+// long-row plan parameters per view (swept at cfg-2, rows ordered by length): typed views 91 us at (48, 512) vs 104 us at
+// (16, 192) (134 us in natural row order at (16, 128)); the node views - all edge types of a node in one row - 121 us at
+// (32, 512) vs 128 us at (64, 512) (138 us in natural order).
 void view_plan_parameters(int view_long[4], int view_chunk[4]) {
-  static const int env_long = [] { const char* e = getenv("TFGNN_LONG_ROW"); return e ? atoi(e) : 0; }();
-  static const int env_chunk = [] { const char* e = getenv("TFGNN_ITEM_CHUNK"); return e ? atoi(e) : 0; }();
-  static const int env_long_n = [] { const char* e = getenv("TFGNN_LONG_ROW_NODE"); return e ? atoi(e) : 0; }();
-  static const int env_chunk_n = [] { const char* e = getenv("TFGNN_ITEM_CHUNK_NODE"); return e ? atoi(e) : 0; }();
   const int dl[4] = {LONG_ROW_THRESHOLD_TYPED, LONG_ROW_THRESHOLD, LONG_ROW_THRESHOLD_TYPED, LONG_ROW_THRESHOLD};
   const int dc[4] = {ITEM_CHUNK_TYPED, ITEM_CHUNK, ITEM_CHUNK_TYPED, ITEM_CHUNK};
   for (int v = 0; v < 4; ++v) {
-    const bool node_view = v & 1;
     view_long[v] = dl[v];
     view_chunk[v] = dc[v];
-    if ((node_view ? env_long_n : env_long) > 0) view_long[v] = node_view ? env_long_n : env_long;
-    if ((node_view ? env_chunk_n : env_chunk) > 0) view_chunk[v] = node_view ? env_chunk_n : env_chunk;
     if (view_long[v] > SHORT_BINS - 1) view_long[v] = SHORT_BINS - 1;
     if (view_chunk[v] < view_long[v]) view_chunk[v] = view_long[v];
   }

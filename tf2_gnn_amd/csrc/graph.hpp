@@ -15,7 +15,7 @@ constexpr int LONG_ROW_THRESHOLD_TYPED = 48;  // typed views (one row per (node,
 constexpr int ITEM_CHUNK_TYPED = 512;
 
 struct CsrPlan {
-  int32_t long_threshold = LONG_ROW_THRESHOLD;  // values the plan was built with (env-tunable for probes)
+  int32_t long_threshold = LONG_ROW_THRESHOLD;  // values the plan was built with (view_plan_parameters)
   int32_t item_chunk_edges = ITEM_CHUNK;
   int32_t num_items = 0;     // host copies of the device counters
   int32_t num_multi = 0;     // rows with more than one item

@@ -157,7 +157,6 @@ struct GatherArgs {
   int64_t ld_out;
   int pre_act;
   int post_act;
-  int64_t num_src_rows;  // rows of `in` (0 = unknown): drives the L2-slicing heuristic
   int is_max;
   int ew_heads;    // K (MODE_HEADS)
   int head_width;  // floats per head (MODE_HEADS)
@@ -170,8 +169,6 @@ struct GatherArgs {
   int dot_lph_log2;
   int long_threshold;  // rows longer than this are left to the item kernels (0 = never)
   const int32_t* out_row_map;  // nullable: output row of CSR row r is out_row_map[r]; < 0 = no output
-  unsigned xcd_units_pad;      // != 0: 1-D XCD-aware grid over (window, unit); set by the launcher
-  unsigned total_units;
   // item pass
   const int32_t* item_row;
   const int32_t* item_chunk;
@@ -190,7 +187,7 @@ struct GatherArgs {
   float* inv_out;          // [rows] 2^-e of every output row (not written when fixed_inv is given)
   const float* fixed_inv;  // nullable: one caller-chosen 2^-e for the whole tensor
   tfgnn_aux_job* combine_job;  // host pointer, nullable: receive the combine pass as a job instead of launching it
-  int multi_code;  // host only: 10 R + U = the short rows go R to a lane group, U edges of each per round (gather_rows_block_multi: 21); 0: one row per group
+  bool multi_pairs;  // host only: the short rows go two to a lane group, one edge of each per round (gather_rows_block_multi)
 };
 
 // scale of one output row from the maximum over its LANES lanes (lanes of one group are contiguous)
@@ -659,20 +656,7 @@ __global__ void __launch_bounds__(256) csr_gather_combine_sp_kernel(AuxCombineSp
 template <int LPR, int VPL, int VEC, int UNROLL, int MODE, bool SP = false>
 __global__ void __launch_bounds__(256) csr_gather_reduce_kernel(GatherArgs a, int num_items) {
   __shared__ float red[256 / LPR][LPR * VPL * VEC];
-  unsigned unit, window;
-  if (a.xcd_units_pad) {
-    // XCD-aware order (workgroup b runs on XCD b % 8): every XCD walks the feature windows one after the
-    // other over its share of the work units, so the source slice in[:, window] (V * window bytes)
-    // it is gathering from stays resident in that XCD's 4 MiB L2
-    const unsigned xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
-    const unsigned per = a.xcd_units_pad >> 3;
-    window = j / per;
-    unit = (j % per) * 8u + xcd;
-    if (unit >= a.total_units) return;
-  } else {
-    unit = blockIdx.x;
-    window = blockIdx.y;
-  }
+  const unsigned unit = blockIdx.x, window = blockIdx.y;
   if ((int)unit < num_items)
     gather_item_block<LPR, VPL, VEC, UNROLL, MODE, SP>(a, (int)unit, window, red);
   else
@@ -693,7 +677,6 @@ __global__ void __launch_bounds__(256) csr_gather_reduce_multi_kernel(GatherArgs
 template <int LPR, int VPL, int VEC, int UNROLL, bool SP, int R, int U>
 static void launch_multi(GatherArgs a, int num_items, hipStream_t s) {
   const unsigned units = (unsigned)(num_items + ceil_div(a.short_rows ? a.num_short : a.num_rows, (256 / LPR) * R));
-  a.total_units = units;
   hipLaunchKernelGGL((csr_gather_reduce_multi_kernel<LPR, VPL, VEC, UNROLL, SP, R, U>), dim3(units, 1), dim3(256), 0, s, a, num_items);
 }
 
@@ -704,16 +687,11 @@ static int launch_mode(GatherArgs a, int num_items, hipStream_t s) {
   const unsigned windows = (unsigned)ceil_div(a.width, WINDOW);
   const unsigned units = (unsigned)(num_items + ceil_div(a.short_rows ? a.num_short : a.num_rows, GROUPS_PER_BLOCK));
   dim3 block(256);
-  a.total_units = units;
   bool multi_done = false;
   if constexpr (MODE == MODE_SUM && VEC == 4 && LPR * VPL <= 128) {
-    if (a.multi_code > 10 && windows == 1 && (!SP || a.width <= 2048)) {
-      a.xcd_units_pad = 0;
+    if (a.multi_pairs && windows == 1 && (!SP || a.width <= 2048)) {
+      launch_multi<LPR, VPL, VEC, UNROLL, SP, 2, 1>(a, num_items, s);
       multi_done = true;
-      switch (a.multi_code) {
-        case 21: launch_multi<LPR, VPL, VEC, UNROLL, SP, 2, 1>(a, num_items, s); break;
-        default: multi_done = false; break;
-      }
     }
   }
   if constexpr (SP) {
@@ -721,7 +699,6 @@ static int launch_mode(GatherArgs a, int num_items, hipStream_t s) {
       set_error("SP16 gather output needs the whole row in one feature window (width %d)", a.width);
       return TFGNN_ERR_UNSUPPORTED;
     }
-    a.xcd_units_pad = 0;
     if (!multi_done)
       hipLaunchKernelGGL((csr_gather_reduce_kernel<LPR, VPL, VEC, UNROLL, MODE, true>), dim3(units, 1), block, 0, s, a, num_items);
     TFGNN_LAUNCH_CHECK();
@@ -735,16 +712,9 @@ static int launch_mode(GatherArgs a, int num_items, hipStream_t s) {
     }
     return TFGNN_OK;
   }
-  if (multi_done) {
-  } else if (a.xcd_units_pad && windows > 1) {
-    a.xcd_units_pad = (units + 7u) & ~7u;
-    hipLaunchKernelGGL((csr_gather_reduce_kernel<LPR, VPL, VEC, UNROLL, MODE>), dim3(a.xcd_units_pad * windows), block, 0, s,
-                       a, num_items);
-  } else {
-    a.xcd_units_pad = 0;
+  if (!multi_done)
     hipLaunchKernelGGL((csr_gather_reduce_kernel<LPR, VPL, VEC, UNROLL, MODE>), dim3(units, windows), block, 0, s, a,
                        num_items);
-  }
   TFGNN_LAUNCH_CHECK();
   if (a.num_multi > 0) {
     const int64_t total = (int64_t)a.num_multi * a.width;
@@ -806,29 +776,13 @@ static int gather_dispatch(GatherArgs a, int num_items, hipStream_t s) {
     if (chunks <= 80) return launch_mode<16, 5, 4, 2, MODE_SUM, true>(a, num_items, s);  // UNROLL 1 / 4 and 32 lanes per row measured slower (tools/gather_l2_probe.py)
     return launch_mode<32, 4, 4, 2, MODE_SUM, true>(a, num_items, s);
   }
-  // L2-resident slicing: gather 32-float (128 B) windows of the rows, XCD by XCD, when one window of
-  // ALL source rows fits an XCD's 4 MiB L2 but the full rows do not (cfg-2: 3.84 MB vs 38 MB).
-  static const int sliced_knob = [] { const char* e = getenv("TFGNN_GATHER_SLICED"); return e ? atoi(e) : -1; }();
-  const bool can_slice = a.num_src_rows > 0 && chunks > 16 && !mode_heads(mode);
-  // Measured at cfg-2 (tools/gather_probe.py): 322 us sliced vs 160 us whole-row - ten passes over the
-  // index arrays with 128-byte requests lose more than the L2 hits win.  Off unless TFGNN_GATHER_SLICED=1.
-  const bool want_slice = sliced_knob > 0;
-  if (can_slice && want_slice) {
-    a.xcd_units_pad = 1;
-    return launch_variant<8, 1, 4, 8>(a, mode, num_items, s);
-  }
   // (rows of 8 floats - RGAT's per-head logit gradients summed per bucket - leave six of the eight lanes of the next variant
   // idle; a two-lane variant measured SLOWER, 28 vs 23 us at configs[2]: the launch is bound by the walk along the rows)
   if (chunks <= 8) return launch_variant<8, 1, 4, 8>(a, mode, num_items, s);
   if (chunks <= 16) return launch_variant<16, 1, 4, 8>(a, mode, num_items, s);
   if (chunks <= 32) return launch_variant<16, 2, 4, 4>(a, mode, num_items, s);
   if (chunks <= 64) return launch_variant<16, 4, 4, 2>(a, mode, num_items, s);
-  static const int unroll_knob = [] { const char* e = getenv("TFGNN_GATHER_UNROLL"); return e ? atoi(e) : 0; }();
-  if (chunks % 80 == 0 || chunks <= 80) {
-    if (unroll_knob == 4) return launch_variant<16, 5, 4, 4>(a, mode, num_items, s);
-    if (unroll_knob == 1) return launch_variant<16, 5, 4, 1>(a, mode, num_items, s);
-    return launch_variant<16, 5, 4, 2>(a, mode, num_items, s);
-  }
+  if (chunks % 80 == 0 || chunks <= 80) return launch_variant<16, 5, 4, 2>(a, mode, num_items, s);
   return launch_variant<32, 4, 4, 2>(a, mode, num_items, s);
 }
 
@@ -925,19 +879,14 @@ static int graph_gather_impl(const tfgnn_graph* g, int view, const int32_t* d_co
     a.dot_rows = d_dot_rows; a.ld_dot = ld_dot; a.dot_out = d_dot_out; a.dot_pos = d_dot_pos;
     a.dot_lph_log2 = 31 - __builtin_clz((unsigned)lph);
   }
-  a.num_src_rows = d_col_override ? 0 : ((view == 1 || view == 3) ? g->R : g->V);  // rows of `in`
   a.item_row = p.item_row; a.item_chunk = p.item_chunk; a.item_slot = p.item_slot;
   a.partial = (float*)d_workspace; a.item_chunk_edges = p.item_chunk_edges;
   a.multi_row = p.multi_row; a.multi_base = p.multi_base; a.multi_n = p.multi_n; a.num_multi = p.num_multi;
-  // bit 0: typed views, bit 1: node views keep the natural row order (probing)
-  static const int natural_order = [] { const char* e = getenv("TFGNN_GATHER_NATURAL_ORDER"); return e ? atoi(e) : 0; }();
-  if (!(natural_order & ((view & 1) ? 2 : 1))) {
-    a.short_rows = p.short_rows;
-    a.num_short = p.num_short;
-    // compact output: the empty buckets have no row, and they close the length-ordered list - no lane groups for them
-    // (configs[4]: 452 517 of 6.8 M by-source buckets are non-empty; walking all of them was 0.85 M workgroups with nothing to do)
-    if (compact_nz >= 0) a.num_short = std::max<int64_t>(0, (int64_t)p.num_short - (gv.num_rows - compact_nz));
-  }
+  a.short_rows = p.short_rows;
+  a.num_short = p.num_short;
+  // compact output: the empty buckets have no row, and they close the length-ordered list - no lane groups for them
+  // (configs[4]: 452 517 of 6.8 M by-source buckets are non-empty; walking all of them was 0.85 M workgroups with nothing to do)
+  if (compact_nz >= 0) a.num_short = std::max<int64_t>(0, (int64_t)p.num_short - (gv.num_rows - compact_nz));
   {
     // short rows side by side (gather_rows_block_multi) when the rows the row workgroups walk hold <= 1.5 edges on average -
     // the (node, type) buckets of a molecule batch (0.6): tools/gather_short_probe.py, 128k molecules, H = 128: typed by-target
@@ -948,9 +897,8 @@ static int graph_gather_impl(const tfgnn_graph* g, int view, const int32_t* d_co
     const char* multi_env = getenv("TFGNN_GATHER_MULTI");  // (read per call: the tests compare the two shapes in one process)
     const int multi_knob = multi_env ? atoi(multi_env) : 0;
     const int64_t nslots = a.short_rows ? a.num_short : a.num_rows;
-    a.multi_code = 0;
-    if (multi_knob > 10) a.multi_code = multi_knob;
-    else if (multi_knob == 0 && nslots > 0 && !a.is_max && ew_heads == 1 && (double)g->E <= kMultiAvgLen * (double)nslots) a.multi_code = 21;
+    if (multi_knob == 21) a.multi_pairs = true;
+    else if (multi_knob == 0) a.multi_pairs = nslots > 0 && !a.is_max && ew_heads == 1 && (double)g->E <= kMultiAvgLen * (double)nslots;
   }
   count_launch(d_out_sp ? TFGNN_KFAM_GATHER_SP : TFGNN_KFAM_GATHER);
   return gather_dispatch(a, p.num_items, (hipStream_t)stream);

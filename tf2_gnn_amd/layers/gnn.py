@@ -281,7 +281,7 @@ class GNN:
         """May the dropout at the input of layer ``layer_idx`` be applied by the op that produces that input?  Only where the
         backward pass hands the mask to an input-gradient product as well (no residual sum at this layer) and nothing but a
         Dense / the projection / a message passing layer precedes it."""
-        if ops.env("TFGNN_FUSED_DROPOUT", "1") == "0" or ops.get_gemm_mode() != ops.GEMM_F16X2:
+        if ops.get_gemm_mode() != ops.GEMM_F16X2:
             return False
         if layer_idx % self._residual_every_num_layers == 0 and not (layer_idx == 0 and self._residual_every_num_layers >= self._num_layers):
             return False
@@ -549,7 +549,7 @@ class GNN:
         -> what was demoted, or None when nothing is left to demote."""
         if self._dense_split_ok and self._dense_f16x2(self._hidden_dim, self._hidden_dim):
             self._dense_demoted_epoch = ops.REARM_EPOCH[0]
-            if not self._dense_tn_wide and ops.env("TFGNN_DENSE_TN_WIDE", "1") == "1":
+            if not self._dense_tn_wide:
                 self._dense_tn_wide = True
                 return "the Dense / projection weight gradients (now on the two-factor split-operand product)"
             self._dense_split_ok = False

@@ -50,8 +50,6 @@ def _skip_empty_blocks(L: int, Din: int) -> bool:
     """Does the forward product of path A run over the nodes in pattern order and skip the all-zero type blocks of a row tile
     (tfgnn_sp_gemm_nt_dropout d_tile_kmask)?  One edge type has nothing to skip; the library takes at most 8 blocks of at
     most 1024 columns.  TFGNN_NT_SKIP_EMPTY=0 keeps the node order (A/B measurements)."""
-    import os
-
     return 2 <= L <= 8 and Din % 16 == 0 and Din <= 1024 and ops.env("TFGNN_NT_SKIP_EMPTY", "1") == "1"
 
 
@@ -186,7 +184,6 @@ class GNN_Edge_MLP(MessagePassing):
     def graph_parts(self, num_nodes: int, edges_per_type, in_dim: int) -> int:
         """path A without target states reads the typed views only (forward: buckets by target, backward: by source); with
         one message per edge (molecule-sized batches) the node view as well.  Everything else: all parts."""
-        import os
         from types import SimpleNamespace
 
         if not self._user_message_function() and self._path() == "C":
@@ -194,8 +191,7 @@ class GNN_Edge_MLP(MessagePassing):
             L, H0 = len(edges_per_type), int(self._edge_type_mlps.kernels[0].shape[2])
             if self._first_layer_grads_split_ok(int(num_nodes), int(in_dim), L, H0) and _skip_empty_blocks(L, H0):
                 return ops.G_PARTS_DEFAULT | ops.G_PART_DST_PATTERN
-        if (self._user_message_function() or self._path() != "A" or self._use_target_state_as_input or self._compact_opt_in
-                or ops.env("TFGNN_COMPACT_BUCKETS") == "1"):
+        if self._user_message_function() or self._path() != "A" or self._use_target_state_as_input or self._compact_opt_in:
             return ops.G_PARTS_DEFAULT
         shape = SimpleNamespace(num_edge_types=len(edges_per_type), num_edges=int(sum(edges_per_type)), num_nodes=int(num_nodes),
                                 edges_per_type=tuple(int(c) for c in edges_per_type))
@@ -328,13 +324,11 @@ class GNN_Edge_MLP(MessagePassing):
     # rows).  Measured on MI355X (profiles/r01e_compact_kernel_stats.csv): 45 % fewer FLOPs buy only
     # ~12 % on the forward GEMM because the per-relation groups have K = D (10 K-tiles) and the
     # workgroup prologue / store-burst epilogue dominates; with the extra combine passes the step time
-    # is unchanged.  Kept opt-in (hyper-parameter "use_compact_buckets" or TFGNN_COMPACT_BUCKETS=1).
+    # is unchanged.  Kept opt-in (hyper-parameter "use_compact_buckets").
     SPARSE_BUCKET_THRESHOLD = 0.85
 
     def _use_compact_buckets(self, g) -> bool:
-        import os
-
-        if not (self._compact_opt_in or ops.env("TFGNN_COMPACT_BUCKETS") == "1"):
+        if not self._compact_opt_in:
             return False
         if self._use_target_state_as_input or g.num_edge_types == 0 or g.num_edges == 0:
             return False
@@ -602,9 +596,7 @@ class GNN_Edge_MLP(MessagePassing):
     GROUPED_SPLIT_MIN_ROWS = 4096  # (tests lower it: below this the grouped bf16x3 kernels are as good)
 
     def _grouped_split_ok(self, X, g) -> bool:
-        import os
-
-        if ops.get_gemm_mode() != ops.GEMM_F16X2 or ops.env("TFGNN_GROUPED_F16X2", "1") == "0":
+        if ops.get_gemm_mode() != ops.GEMM_F16X2:
             return False
         dims = [X.shape[1]] + [int(W.shape[2]) for W in self._edge_type_mlps.kernels]
         # every width a column tile of the split-operand product and a multiple of its scale blocks; rows x bytes below 4 GB

@@ -114,8 +114,6 @@ _AUX_LOCK = threading.RLock()
 
 
 def aux_enabled() -> bool:
-    import os
-
     return env("TFGNN_AUX_MERGE", "1") != "0"
 
 
@@ -605,8 +603,6 @@ def _f16x2_on() -> bool:
     the spread guard of the split weight-gradient product trips (tfgnn_gemm_get_mode); this mirror only warns once."""
     if (_GUARD_HOLD[0] or _in_late_trip[0]) and _f16x2[0]:
         return True  # a caller that checks the guard synchronously at the end of its pass decides what a trip demotes
-    if _f16x2[0] and env("TFGNN_GUARD_IGNORE", "0") == "1":
-        return True  # PROBING ONLY (what would a workload cost if its products stayed on split operands): results unguarded
     lib = _lib.load()
     on = lib.tfgnn_gemm_get_mode() == GEMM_F16X2  # (the library takes the mode off - sticky - when it finds the flag up)
     if _f16x2[0] and not on and _LATE_TRIP_POLICIES and lib.tfgnn_sp_spread_flag(0) and not capturing():

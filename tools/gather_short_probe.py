@@ -1,6 +1,6 @@
 """Gathers over short rows (configs[3]: a bucket of a molecule batch holds 0 - 4 edges): kernel time by lane-group shape.
-   python tools/gather_short_probe.py            runs itself once per TFGNN_GATHER_MULTI / TFGNN_GATHER_GRID setting
-(the knobs are read once per process), prints us per launch and the bytes moved."""
+   python tools/gather_short_probe.py            runs itself once per TFGNN_GATHER_MULTI setting
+(one child process each), prints us per launch and the bytes moved."""
 import os
 import subprocess
 import sys
@@ -33,7 +33,7 @@ def child():
     res["typed by-source view, SP16 out [V,L*128]"] = (time_kernel(lambda: ops.graph_gather_sp(g, ops.VIEW_BY_SRC_TYPED, X, rows_per_operand_row=L)), E * H * 4 + V * L * H * 4)
     A = torch.empty((V * L, H), device=dev)
     res["typed by-target view, fp32 out [V*L,128]"] = (time_kernel(lambda: ops.graph_gather(g, ops.VIEW_BY_DST_TYPED, X, out=A)), E * H * 4 + V * L * H * 4)
-    print(f"V={V} E={E} L={L}  multi={os.environ.get('TFGNN_GATHER_MULTI', '0')} grid={os.environ.get('TFGNN_GATHER_GRID', '0')}")
+    print(f"V={V} E={E} L={L}  multi={os.environ.get('TFGNN_GATHER_MULTI', '0')}")
     for k, (ms, b) in res.items():
         print(f"  {k:48s} {1000 * ms:8.1f} us  {b / ms / 1e9:7.2f} TB/s")
 
@@ -42,6 +42,6 @@ if __name__ == "__main__":
     if os.environ.get("PROBE_CHILD"):
         child()
     else:
-        for multi, grid in ((1, 0), (21, 0), (0, 0)):
-            env = dict(os.environ, PROBE_CHILD="1", TFGNN_GATHER_MULTI=str(multi), TFGNN_GATHER_GRID=str(grid))
+        for multi in (1, 21, 0):
+            env = dict(os.environ, PROBE_CHILD="1", TFGNN_GATHER_MULTI=str(multi))
             subprocess.run([sys.executable, os.path.abspath(__file__)], env=env, check=False)

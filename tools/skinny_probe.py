@@ -1,6 +1,5 @@
 """Times the QM9-sized products (configs[3]: V = 1.15 M nodes, ~0.68 M edges per type, width 128) through ops.gemm /
-ops.gemm_grad in bf16x3 mode:  python tools/skinny_probe.py            (shipped routes)
-                               TFGNN_X3_STREAM_MIN_ROWS=0 TFGNN_LONG_K_SPLITS=0 python tools/skinny_probe.py   (tiled kernels, <= 64 splits)
+ops.gemm_grad in bf16x3 mode:  python tools/skinny_probe.py
 Prints one JSON object: shape -> microseconds and the fraction of the 8 TB/s HBM roof its compulsory bytes reach."""
 import json
 import sys

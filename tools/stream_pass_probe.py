@@ -1,7 +1,6 @@
 """The streaming passes of configs[3] (V = 1.15 M node rows, H = 128) one by one: us per launch and bytes moved per second.
    python tools/stream_pass_probe.py            (the kernels all sit at 5.0 - 5.3 TB/s: the ceiling of mixed read + write streams on this part)"""
 import os
-import subprocess
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -27,14 +26,10 @@ def child():
     rows.append(("mul [V,H]", time_kernel(lambda: ops.mul(h, dh)), 3 * arr))
     rows.append(("activation_backward tanh [V,H]", time_kernel(lambda: ops.activation_backward("tanh", dh, h)), 3 * arr))
     rows.append(("sp_split_rows [V,H]", time_kernel(lambda: ops.sp_split_rows(h)), 2 * arr))
-    print(f"V={V} H={H} TFGNN_GATES_GROUPS={os.environ.get('TFGNN_GATES_GROUPS', '-')}")
+    print(f"V={V} H={H}")
     for name, ms, b in rows:
         print(f"  {name:36s} {1000 * ms:8.1f} us  {b / ms / 1e9:6.2f} TB/s")
 
 
 if __name__ == "__main__":
-    if os.environ.get("PROBE_CHILD"):
-        child()
-    else:
-        for groups in ("-",):
-            subprocess.run([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, PROBE_CHILD="1", TFGNN_GATES_GROUPS=groups), check=False)
+    child()
