@@ -897,6 +897,18 @@ int tfgnn_transpose_batched(const float* d_src, int64_t batch, int64_t rows, int
  *   tfgnn_regression_metrics: tf.losses.mean_squared_error / mean_absolute_error of per-graph outputs
  *       (models/graph_regression_task.py:157-158, models/qm9_regression.py:122-123): d_metrics = {mse, mae};
  *       d_dpred (optional) = d mse / d pred = 2 (pred - target) / G.
+ *   tfgnn_binary_ce_metrics: GraphBinaryClassificationTask.compute_task_metrics
+ *       (models/graph_binary_classification_task.py:31-58) from the per-graph LOGITS x and targets y (0 / 1), [G] fp32.
+ *       p = sigmoid(x), pc = min(max(p, eps), hi) with eps = float32(1e-7), hi = float32(1) - eps;
+ *       d_metrics[0] = mean over graphs of -(y log(pc + eps) + (1 - y) log(1 - pc + eps)): [ext]
+ *       tf.keras.losses.binary_crossentropy(from_logits=False) as the Keras backend writes it for a probability
+ *       input, PARITY UNPINNED (some TF versions, inside tf.function, recognise the Sigmoid producer and evaluate
+ *       the logits form instead; the two differ only where p is clipped); d_metrics[1] = num_correct / G, where the
+ *       prediction rint(p) (half to even: a logit of exactly 0 predicts 0, as tf.math.round) equals y;
+ *       d_prob (optional, [G]) = p; d_counts (optional) = {true pos, false pos, true neg, false neg}, num_correct =
+ *       tp + tn; d_dlogits (optional, [G]) = d loss / d logit =
+ *       (-(y / (pc + eps)) + (1 - y) / (1 - pc + eps)) p (1 - p) / G where eps <= p <= hi and exactly 0 outside
+ *       (the gradient of clip_by_value).
  * ------------------------------------------------------------------------------------------ */
 size_t tfgnn_task_metrics_workspace_bytes(void);
 int tfgnn_sigmoid_ce_metrics(const float* d_logits, int64_t ld_logits, const float* d_labels, int64_t ld_labels,
@@ -904,6 +916,9 @@ int tfgnn_sigmoid_ce_metrics(const float* d_logits, int64_t ld_logits, const flo
                              void* d_workspace, size_t workspace_bytes, void* stream);
 int tfgnn_regression_metrics(const float* d_pred, const float* d_target, int64_t G, float* d_metrics,
                              float* d_dpred, void* d_workspace, size_t workspace_bytes, void* stream);
+int tfgnn_binary_ce_metrics(const float* d_logits, const float* d_target, int64_t G, float* d_prob, float* d_metrics,
+                            int64_t* d_counts, float* d_dlogits, void* d_workspace, size_t workspace_bytes,
+                            void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Layer-level entry points (round 6): one call per message-passing layer and pass.

@@ -3,7 +3,10 @@
 //   tfgnn_sigmoid_ce_metrics: NodeMulticlassTask._fast_task_metrics + micro_f1 (tf2_gnn/models/node_multiclass_task.py:10-23,62-70)
 //   tfgnn_regression_metrics: tf.losses.mean_squared_error / mean_absolute_error of the per-graph outputs
 //                             (tf2_gnn/models/graph_regression_task.py:157-158, tf2_gnn/models/qm9_regression.py:122-123)
-// Both are one streaming pass (HBM-bound, 8 - 12 bytes per element) with a two-stage, fixed-order reduction: stage 1 leaves
+//   tfgnn_binary_ce_metrics:  GraphBinaryClassificationTask.compute_task_metrics on the per-graph LOGITS
+//                             (tf2_gnn/models/graph_binary_classification_task.py:31-58): sigmoid, binary cross-entropy of the
+//                             probabilities, accuracy counts, d loss / d logit
+// All are one streaming pass (HBM-bound, 8 - 20 bytes per element) with a two-stage, fixed-order reduction: stage 1 leaves
 // one partial per workgroup, stage 2 (one workgroup) adds them in index order, so the loss is reproducible run to run.
 #include <algorithm>
 
@@ -14,9 +17,9 @@ namespace tfgnn {
 constexpr int TASK_BLOCKS = 1024;
 
 struct TaskPartial {
-  double a;              // CE: sum of element losses | regression: sum of squared errors
+  double a;              // CE, binary CE: sum of element losses | regression: sum of squared errors
   double b;              // regression: sum of absolute errors
-  long long tp, fp, fn;  // CE: micro-F1 counts
+  long long tp, fp, fn;  // CE: micro-F1 counts | binary CE: confusion counts (tn = G - tp - fp - fn)
 };
 
 __device__ __forceinline__ double wave_sum(double v) {
@@ -85,7 +88,44 @@ regression_partial_kernel(const float* __restrict__ pred, const float* __restric
   block_reduce_store(mine, partials + blockIdx.x);
 }
 
-// kind 0: metrics = {mean per-node loss, micro-F1}, counts = {tp, fp, fn};  kind 1: metrics = {mse, mae}
+// graph g: x = logit, y = target (0 / 1).  [ext] tf.keras.losses.binary_crossentropy(from_logits=False) as the Keras backend
+// writes it for a probability input - clip to [eps, 1 - eps], then "+ eps" inside both logs - on p = sigmoid(x), eps =
+// K.epsilon() = float32(1e-7), hi = float32(1) - eps (PARITY UNPINNED: TensorFlow cannot run beside this library).  Some TF
+// versions, inside tf.function, recognise the Sigmoid producer of y_pred and evaluate the logits form instead; the two differ
+// only where p is clipped.
+//   p     sigmoid(x);  pc = min(max(p, eps), hi)
+//   loss  -( y log(pc + eps) + (1 - y) log(1 - pc + eps) )
+//   pred  rint(p): round half to even (tf.math.round), a logit of exactly 0 predicts 0; correct where pred == y as floats
+//   grad  ( -(y / (pc + eps)) + (1 - y) / (1 - pc + eps) ) p (1 - p) / G  where eps <= p <= hi, 0 outside (clip_by_value)
+// 1 - p is evaluated as sigmoid(-x), not as the fp32 difference: at |x| = 12 the difference keeps 7 bits (1 - p = 6e-6 next
+// to a spacing of 6e-8 below 1), which would put an error of 1e-2 on a log of 12.  Inside the clip range 1 - pc IS 1 - p; at
+// the two clip values it is the fp32 difference the formula states (1 - hi = 2^-23 exactly).
+__global__ void __launch_bounds__(256)
+binary_ce_partial_kernel(const float* __restrict__ logits, const float* __restrict__ target, int64_t G, float inv_g,
+                         float* __restrict__ prob, float* __restrict__ dlogits, TaskPartial* __restrict__ partials) {
+  TaskPartial mine = {0.0, 0.0, 0, 0, 0};
+  const float eps = 1e-7f, hi = 1.0f - eps;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < G; i += (int64_t)gridDim.x * blockDim.x) {
+    const float x = logits[i], y = target[i];
+    const float p = 1.0f / (1.0f + expf(-x)), q = 1.0f / (1.0f + expf(x));  // q = 1 - p
+    const bool inside = p >= eps && p <= hi;
+    const float pc = fminf(fmaxf(p, eps), hi);
+    const float qc = inside ? q : 1.0f - pc;
+    const float a = pc + eps, b = qc + eps;
+    mine.a -= (double)(y * logf(a) + (1.0f - y) * logf(b));
+    const float pred = rintf(p);
+    // every graph lands in exactly one of the four; tp + tn = number of pred == y also for a target that is not 0 / 1
+    mine.tp += pred == 1.0f && y == 1.0f;
+    mine.fp += pred == 1.0f && y != 1.0f;
+    mine.fn += pred == 0.0f && y != 0.0f;
+    if (prob) prob[i] = p;
+    if (dlogits) dlogits[i] = inside ? ((1.0f - y) / b - y / a) * (p * q) * inv_g : 0.0f;
+  }
+  block_reduce_store(mine, partials + blockIdx.x);
+}
+
+// kind 0: metrics = {mean per-node loss, micro-F1}, counts = {tp, fp, fn};  kind 1: metrics = {mse, mae};
+// kind 2: metrics = {mean loss, accuracy}, counts = {tp, fp, tn, fn} (denom = G, an integer)
 __global__ void __launch_bounds__(256)
 task_final_kernel(const TaskPartial* __restrict__ partials, int n, int kind, double denom, float* __restrict__ metrics,
                   long long* __restrict__ counts) {
@@ -106,9 +146,14 @@ task_final_kernel(const TaskPartial* __restrict__ partials, int n, int kind, dou
       const double precision = tp / (tp + fp), recall = tp / (tp + fn);
       metrics[1] = (float)((2.0 * precision * recall) / (precision + recall));
       if (counts) { counts[0] = total.tp; counts[1] = total.fp; counts[2] = total.fn; }
-    } else {
+    } else if (kind == 1) {
       metrics[0] = (float)(total.a / denom);
       metrics[1] = (float)(total.b / denom);
+    } else {
+      const long long tn = (long long)denom - total.tp - total.fp - total.fn;
+      metrics[0] = (float)(total.a / denom);
+      metrics[1] = (float)((double)(total.tp + tn) / denom);
+      if (counts) { counts[0] = total.tp; counts[1] = total.fp; counts[2] = tn; counts[3] = total.fn; }
     }
   }
 }
@@ -152,6 +197,25 @@ extern "C" int tfgnn_regression_metrics(const float* d_pred, const float* d_targ
   hipLaunchKernelGGL(regression_partial_kernel, dim3(grid), dim3(256), 0, s, d_pred, d_target, G, 2.0f / (float)G, d_dpred, partials);
   TFGNN_LAUNCH_CHECK();
   hipLaunchKernelGGL(task_final_kernel, dim3(1), dim3(256), 0, s, partials, grid, 1, (double)G, d_metrics, (long long*)nullptr);
+  TFGNN_LAUNCH_CHECK();
+  return TFGNN_OK;
+}
+
+extern "C" int tfgnn_binary_ce_metrics(const float* d_logits, const float* d_target, int64_t G, float* d_prob, float* d_metrics,
+                                       int64_t* d_counts, float* d_dlogits, void* d_workspace, size_t workspace_bytes,
+                                       void* stream) {
+  using namespace tfgnn;
+  TFGNN_REQUIRE(G > 0, "binary_ce_metrics: empty batch (the reference's reduce_mean gives nan)");
+  TFGNN_REQUIRE(d_logits && d_target && d_metrics, "NULL pointer");
+  TFGNN_REQUIRE(d_workspace && workspace_bytes >= tfgnn_task_metrics_workspace_bytes() && (uintptr_t)d_workspace % 8 == 0,
+                "workspace of tfgnn_task_metrics_workspace_bytes() bytes required");
+  hipStream_t s = (hipStream_t)stream;
+  TaskPartial* partials = (TaskPartial*)d_workspace;
+  const int grid = task_grid(G);
+  hipLaunchKernelGGL(binary_ce_partial_kernel, dim3(grid), dim3(256), 0, s, d_logits, d_target, G, 1.0f / (float)G, d_prob,
+                     d_dlogits, partials);
+  TFGNN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(task_final_kernel, dim3(1), dim3(256), 0, s, partials, grid, 2, (double)G, d_metrics, (long long*)d_counts);
   TFGNN_LAUNCH_CHECK();
   return TFGNN_OK;
 }

@@ -1316,6 +1316,29 @@ def regression_metrics(pred: torch.Tensor, target: torch.Tensor, need_grad: bool
     return metrics, grad
 
 
+def binary_ce_metrics(logits: torch.Tensor, target: torch.Tensor, need_grad: bool = True, want_prob: bool = True):
+    """GraphBinaryClassificationTask.compute_task_metrics on the per-graph logits
+    (tf2_gnn/models/graph_binary_classification_task.py:31-58; the arithmetic: include/tfgnn.h tfgnn_binary_ce_metrics) ->
+    (metrics [2] = (loss, batch accuracy) on the device, counts [4] int64 = (tp, fp, tn, fn), sigmoid(logits) or None,
+    d loss / d logits or None)."""
+    lib = _lib.load()
+    _require_dev(logits, torch.float32, "logits")
+    _require_dev(target, torch.float32, "target")
+    logits = logits.contiguous().view(-1)
+    target = target.contiguous().view(-1)
+    if logits.shape != target.shape:
+        raise ValueError(f"logits {tuple(logits.shape)} and target {tuple(target.shape)} differ in shape")
+    metrics = torch.empty(2, dtype=torch.float32, device=logits.device)
+    counts = torch.empty(4, dtype=torch.int64, device=logits.device)
+    prob = torch.empty_like(logits) if want_prob else None
+    grad = torch.empty_like(logits) if need_grad else None
+    nbytes = lib.tfgnn_task_metrics_workspace_bytes()
+    ws = _workspace(logits.device, nbytes)
+    _lib.check(lib.tfgnn_binary_ce_metrics(_ptr(logits), _ptr(target), logits.numel(), _ptr(prob), _ptr(metrics), _ptr(counts),
+                                           _ptr(grad), _ptr(ws), ws.numel(), _stream()))
+    return metrics, counts, prob, grad
+
+
 # ---- split-operand ("f16x2") products: include/tfgnn.h tfgnn_sp_*, csrc/gemm_sp.hip ------------------------------
 class SplitOperand:
     """An fp32 matrix [rows, cols] in the SP16 operand format: ``data`` uint8 [rows, 4 * cols] (per row and 16 columns

@@ -8,7 +8,8 @@ of ``GraphDataset._finalise_batch``: "node_features", "adjacency_list_<i>", "nod
 ``tf.GradientTape`` of ``GraphTaskModel._run_step`` (tf2_gnn/models/graph_task_model.py:327-357): it fills ``.grad``
 of every trainable variable with d loss / d variable.  The parameter update of that step (``_make_optimizer``,
 ``_apply_gradients``: clipping + a Keras optimizer, optim.py) and the step / epoch methods around it (``_run_step``,
-``run_one_epoch``) are here too; the training CLI, datasets and checkpoint I/O stay out (out of scope).
+``run_one_epoch``) are here too, and so are the prediction loop and the evaluation metrics (``predict``, ``evaluate_model``);
+the training CLI, datasets and checkpoint I/O stay out (out of scope).
 
 MLP-input dropout of the heads (``regression_mlp_dropout``, ``graph_aggregation_dropout_rate``; QM9 hands
 ``out_layer_dropout_keep_prob`` over as a rate) is applied in training mode as in the pooling layers (layers/nodes_to_graph_representation.py MLP).
@@ -19,6 +20,7 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import time
 
+import numpy as np
 import torch
 
 from . import _lib, ops
@@ -32,6 +34,7 @@ from .layers.nodes_to_graph_representation import (
     WeightedSumGraphRepresentation,
     segment_offsets,
 )
+from .utils import eval_metrics
 
 
 class GraphTaskModel:
@@ -223,6 +226,28 @@ class GraphTaskModel:
             print("\r\x1b[K", end="")
         total_time = time.time() - epoch_time_start
         return float(total_loss) / float(total_num_graphs), float(total_num_graphs) / total_time, task_results
+
+    # ---- prediction loop (graph_task_model.py:401-420) ------------------------------------------------------------------
+    def predict(self, dataset) -> torch.Tensor:
+        """The task outputs of every batch of ``dataset`` (an iterable of ``(batch_features, batch_labels)``) in evaluation
+        mode, concatenated along axis 0 on the device.  A model whose output is a 1-tuple (NodeMulticlassTask:
+        ``(per_node_logits,)``) contributes the tuple's element, so the result is one tensor for every task model."""
+        task_outputs = []
+        for batch_features, _ in dataset:
+            task_output = self(batch_features, training=False)
+            task_outputs.append(task_output[0] if isinstance(task_output, tuple) else task_output)
+        return torch.cat(task_outputs, dim=0)
+
+    def evaluate_model(self, dataset) -> Dict[str, float]:
+        """Metrics that make sense for the model's application area, by name (e.g. "acc", "roc_auc"), over ``dataset`` in the
+        format of the training loop; the graph-level tasks implement it."""
+        raise NotImplementedError()
+
+    def _predictions_and_target_values(self, dataset) -> Tuple[np.ndarray, np.ndarray]:
+        """``predict(dataset)`` and the batches' "target_value" labels, each copied to the host once"""
+        predictions = self.predict(dataset)
+        labels = torch.cat([batch_labels["target_value"].reshape(-1) for _, batch_labels in dataset], dim=0)
+        return predictions.cpu().numpy(), labels.cpu().numpy()
 
 
 class NodeMulticlassTask(GraphTaskModel):
@@ -471,9 +496,18 @@ class GraphRegressionTask(GraphTaskModel):
         epoch_mse, epoch_mae = _regression_epoch_metrics(task_results)
         return epoch_mae, f" MSE = {epoch_mse:.3f} | MAE = {epoch_mae:.3f}"
 
+    def evaluate_model(self, dataset) -> Dict[str, float]:
+        """graph_regression_task.py:184-203 -> mae, mse, max_err, expl_var, r2_score (utils/eval_metrics.py)."""
+        predictions, labels = self._predictions_and_target_values(dataset)
+        return eval_metrics.regression_metrics(labels, predictions)
+
+    def _dloss_dresults(self) -> torch.Tensor:
+        """d loss / d (per-graph results of the regression MLP) [G]"""
+        return self._step["dloss"]
+
     def _task_backward(self):
         s = self._step
-        d_graph = self._regression_mlp.backward(s["dloss"].contiguous().view(-1, 1))  # [G, 2 GD]
+        d_graph = self._regression_mlp.backward(self._dloss_dresults().contiguous().view(-1, 1))  # [G, 2 GD]
         GD = s["GD"]
         d_nodes = ops.add_scale(
             self._weighted_avg_of_nodes_to_graph_repr.backward(d_graph[:, :GD].contiguous()),
@@ -489,3 +523,86 @@ class GraphRegressionTask(GraphTaskModel):
                 col += w
             return None, grads
         return d_nodes[:, widths[0] :], None
+
+
+def _float32_epsilon() -> Tuple[float, float]:
+    """K.epsilon() and 1 - K.epsilon() as the float32 values Keras clips with"""
+    eps = np.float32(1e-7)
+    return float(eps), float(np.float32(1.0) - eps)
+
+
+def _binary_ce_from_probabilities(prob: torch.Tensor, target: torch.Tensor):
+    """The arithmetic of tfgnn_binary_ce_metrics (include/tfgnn.h) for probabilities that did not come out of the last
+    forward pass, unfused -> (loss, batch accuracy, number of correct predictions, d loss / d probability)."""
+    ops._require_dev(prob, torch.float32, "task_output")
+    ops._require_dev(target, torch.float32, "target_value")
+    p, y = prob.reshape(-1), target.reshape(-1)
+    if p.shape != y.shape:
+        raise ValueError(f"task_output {tuple(prob.shape)} and target_value {tuple(target.shape)} differ in shape")
+    if p.numel() == 0:
+        raise ValueError("binary cross-entropy of an empty batch (the reference's reduce_mean gives nan)")
+    eps, hi = _float32_epsilon()
+    pc = p.clamp(eps, hi)
+    a, b = pc + eps, (1.0 - pc) + eps
+    loss = -(y * torch.log(a) + (1.0 - y) * torch.log(b)).mean()
+    num_correct = (torch.round(p) == y).sum()  # torch.round: half to even, as tf.math.round
+    inside = (p >= eps) & (p <= hi)
+    dprob = torch.where(inside, (1.0 - y) / b - y / a, torch.zeros_like(p)) / float(p.numel())
+    return loss, num_correct.to(torch.float32) / float(p.numel()), num_correct, dprob
+
+
+class GraphBinaryClassificationTask(GraphRegressionTask):
+    """tf2_gnn/models/graph_binary_classification_task.py:11-101: the graph regression model with a sigmoid on its per-graph
+    results, binary cross-entropy of the probabilities against "target_value" (0 / 1), accuracy.
+
+    What ``_step`` holds, beside the parent's entries.  After a forward pass: ``"logits"`` (the parent's per-graph results)
+    and ``"prob"`` (the task output, sigmoid(logits)).  ``"dloss"`` is, as for every task model, the gradient with respect to
+    the task OUTPUT - here the probabilities - or ``None``; ``"dlogits"`` is the gradient with respect to the logits.
+    ``compute_task_metrics`` on the output of the last forward pass runs the fused kernel, which differentiates through the
+    sigmoid itself: it stores ``"dlogits"`` and sets ``"dloss"`` to ``None``.  Whoever has a gradient with respect to the
+    probabilities - ``TorchGraphTaskModel.back``, or ``compute_task_metrics`` on probabilities of the caller's own - stores it
+    under ``"dloss"``.  ``backward()`` uses ``"dloss"`` times p (1 - p) when it is not ``None``, and ``"dlogits"`` otherwise:
+    the last writer decides."""
+
+    def compute_task_output(self, batch_features, final_node_representations, training: bool):
+        logits = super().compute_task_output(batch_features, final_node_representations, training)
+        prob = ops.activation_forward("sigmoid", logits)  # :31
+        self._step["logits"], self._step["prob"] = logits, prob
+        return prob
+
+    def compute_task_metrics(self, batch_features, task_output, batch_labels) -> Dict[str, Any]:
+        """:33-58 -> "loss", "batch_acc", "num_correct" (device tensors; the count is int64), "num_graphs" (a float)."""
+        target = batch_labels["target_value"]
+        step = self._step
+        if step is not None and task_output is step.get("prob"):
+            metrics, counts, _, dlogits = ops.binary_ce_metrics(step["logits"], target, want_prob=False)
+            loss, batch_acc, num_correct = metrics[0], metrics[1], counts[0] + counts[2]
+            step["dlogits"], step["dloss"] = dlogits, None
+        else:
+            loss, batch_acc, num_correct, dprob = _binary_ce_from_probabilities(task_output, target)
+            if step is not None:
+                step["dloss"] = dprob
+        return {
+            "loss": loss,
+            "batch_acc": batch_acc,
+            "num_correct": num_correct,
+            "num_graphs": float(int(batch_features["num_graphs_in_batch"])),
+        }
+
+    def compute_epoch_metrics(self, task_results: List[Any]) -> Tuple[float, str]:
+        """:60-68."""
+        total_num_graphs = sum(r["num_graphs"] for r in task_results)
+        total_num_correct = sum(int(r["num_correct"]) for r in task_results)
+        epoch_acc = float(total_num_correct) / float(total_num_graphs)
+        return -epoch_acc, f"Accuracy = {epoch_acc:.3f}"
+
+    def evaluate_model(self, dataset) -> Dict[str, float]:
+        """:70-101 -> acc, balanced_acc, precision, recall, f1_score, roc_auc, average_precision (utils/eval_metrics.py)."""
+        predictions, labels = self._predictions_and_target_values(dataset)
+        return eval_metrics.binary_classification_metrics(labels, predictions)
+
+    def _dloss_dresults(self) -> torch.Tensor:
+        s = self._step
+        if s["dloss"] is not None:  # with respect to the probabilities: through the sigmoid
+            return ops.activation_backward("sigmoid", s["dloss"].reshape(-1), s["prob"])
+        return s["dlogits"]
