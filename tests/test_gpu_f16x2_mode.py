@@ -372,7 +372,7 @@ def test_rearming_the_mode_restores_both_demotion_stages_of_a_stack(dev, monkeyp
     inp = GNNInput(X, to_dev(random_graph(V, 900, L, seed=6), dev), torch.zeros(V, dtype=torch.int32, device=dev), 1)
     gnn(inp, training=True)
     gnn.backward(dOut)
-    assert any(getattr(mp, "_grouped_tn_used", False) for mp in gnn._mp_layers)
+    assert any(mp._grouped_tn_used for mp in gnn._mp_layers)
     stages = []
     while True:
         what = gnn._demote_fragile_weight_gradients()
@@ -381,12 +381,12 @@ def test_rearming_the_mode_restores_both_demotion_stages_of_a_stack(dev, monkeyp
         stages.append(what)
     assert stages[-1].startswith("the per-relation MLP weight gradients") and len(stages) <= 3
     assert not gnn._dense_split_ok or not gnn._dense_f16x2(128, 128)
-    assert all(mp._grouped_tn_split_ok is False for mp in gnn._mp_layers if getattr(mp, "_grouped_tn_used", False))
+    assert all(mp._grouped_tn_split_ok is False for mp in gnn._mp_layers if mp._grouped_tn_used)
     gnn._guard_sync_passes = 0
     ops.set_gemm_mode("f16x2")  # re-arm
     gnn(inp, training=True)
     assert gnn._tn_demoted_epoch is None and gnn._guard_sync_passes == gnn._guard_sync_passes_init and not gnn._dense_tn_wide
-    assert all(getattr(mp, "_grouped_tn_split_ok", True) for mp in gnn._mp_layers)
+    assert all(mp._grouped_tn_split_ok for mp in gnn._mp_layers)
     gnn.backward(dOut)
     _assert_mode_kept()
 

@@ -376,3 +376,61 @@ def test_layer_input_dropout_without_a_stored_mask_equals_the_stored_one(dev, mo
     close(dX1, dX0, "d node_features")
     for n, a, b in zip(names, g1, g0):
         close(a, b, "d " + n)
+
+
+# ---- the gradient epilogue of GNN_Edge_MLP.backward_with_epilogue, route by route ---------------------------------------
+_LINEAR = {"num_edge_MLP_hidden_layers": 0, "use_target_state_as_input": False}
+# id, GEMM mode, overrides, L, V, E, TFGNN_MP_ENTRY, the route: (ctx path, split-operand path A, a grouped / two-factor TN product
+# ran), does the route fold the factors into its input-gradient product(s)?
+EPILOGUE_ROUTES = [
+    ("A_f16x2_one_call", "f16x2", _LINEAR, 4, 384, 4200, "1", ("A", True, False), True),
+    ("A_f16x2_op_level", "f16x2", _LINEAR, 4, 384, 4200, "0", ("A", True, False), True),
+    ("A_bf16x3", "bf16x3", _LINEAR, 4, 384, 4200, "1", ("A", False, False), True),
+    ("C_exact_kernels", "bf16x3", {}, 5, 384, 4200, "1", ("C", False, False), True),
+    ("C_first_layer_split", "f16x2", {}, 5, 384, 4200, "1", ("C", False, True), True),
+    ("Bc", "bf16x3", {"use_target_state_as_input": False}, 8, 400, 900, "1", ("Bc", False, False), False),
+    ("Bc_grouped_split", "f16x2", {"use_target_state_as_input": False}, 8, 3000, 7000, "1", ("Bc", False, True), False),
+]
+
+
+@pytest.mark.parametrize("name,gemm_mode,over,L,V,E,mp_entry,route,folded", EPILOGUE_ROUTES, ids=[c[0] for c in EPILOGUE_ROUTES],
+                         indirect=["gemm_mode"])
+def test_edge_mlp_gradient_epilogue_is_applied_exactly_once_on_every_route(dev, monkeypatch, name, gemm_mode, over, L, V, E,
+                                                                           mp_entry, route, folded):
+    """backward_with_epilogue(g, out_mul=m, out_act_grad=("tanh", saved)) == apply_gradient_epilogue(backward(g), m, ("tanh",
+    saved)) on every backward route of GNN_Edge_MLP: bit for bit where the route has no product to fold the factors into (the
+    layer then runs the very same kernels), within this file's bound (tests.helpers.assert_close, 1e-5 scaled) where its
+    input-gradient product applies them in its epilogue.  A route that applied them twice, or dropped them, is off by O(1).
+    The kernel gradients do not see the factors: bit-equal on every route."""
+    from tests.test_gpu_layers import _build
+    from tf2_gnn_amd import ops
+    from tf2_gnn_amd.layers import MessagePassingInput
+    from tf2_gnn_amd.layers.message_passing.message_passing import apply_gradient_epilogue
+
+    H = 128
+    monkeypatch.setenv("TFGNN_MP_ENTRY", mp_entry)
+    layer, _ = _build("GNN_Edge_MLP", dict(over, hidden_dim=H, message_activation_function="tanh"), H, L)
+    gen = torch.Generator().manual_seed(29)
+    X = torch.randn((V, H), generator=gen).to(dev)
+    g = torch.randn((V, H), generator=gen).to(dev)
+    m = ((torch.rand((V, H), generator=gen) >= 0.1).float() / 0.9).to(dev)  # a dropout mask of the layer's input
+    saved = torch.tanh(torch.randn((V, H), generator=gen)).to(dev)         # the tanh output of the op below
+    adj = to_dev(random_graph(V, E, L, seed=4), dev)
+    one_call, real = [], ops.mp_backward
+    monkeypatch.setattr(ops, "mp_backward", lambda *a, **k: (one_call.append(1), real(*a, **k))[1])
+    layer(MessagePassingInput(X, adj), training=True)
+    want = apply_gradient_epilogue(layer.backward(g), m, ("tanh", saved)).clone()
+    want_grads = [v.grad.clone() for v in layer.trainable_variables]
+    got = layer.backward_with_epilogue(g, out_mul=m, out_act_grad=("tanh", saved))
+    torch.cuda.synchronize()
+    ctx = layer._ctx
+    assert (ctx["path"], bool(ctx.get("f16x2")), layer._grouped_tn_used) == route
+    # both backward passes of split-operand path A went through the one library call, or neither (TFGNN_MP_ENTRY=0)
+    assert len(one_call) == (2 if route[:2] == ("A", True) and mp_entry == "1" else 0), one_call
+    assert float(want.abs().max()) > 0.0
+    if folded:
+        assert_close(got, want, what=f"gradient epilogue {name} dX")
+    else:
+        assert torch.equal(got, want)
+    for v, a in zip(layer.trainable_variables, want_grads):
+        assert torch.equal(v.grad, a), v.name

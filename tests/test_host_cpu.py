@@ -378,3 +378,36 @@ def test_layer_entry_points_validate_their_arguments_without_a_gpu():
         a.kind = 0
         assert fn(ctypes.byref(a), None) == -1 and b"NULL pointer" in lib.tfgnn_last_error()
         assert fn(None, None) == -1
+
+
+def test_stack_entry_points_of_the_base_layer_and_the_guard_policy_defaults():
+    """MessagePassing.call_with_epilogue, generic form: builds the layer as ``__call__`` does, ignores both requests and reports
+    that no dropout was applied; backward_with_epilogue accepts (and ignores) the split-gradient wish.  The two pieces of
+    per-layer state the stack's spread-guard policy keeps are declared on the class; so are the width predicates in ops."""
+    from tf2_gnn_amd import ops
+    from tf2_gnn_amd.layers.message_passing import GGNN, GNN_Edge_MLP, MessagePassing, MessagePassingInput
+
+    class Stub(MessagePassing):
+        def _message_function(self, *args):
+            raise AssertionError("not used")
+
+        def call(self, inputs, training=False):
+            return ("called", inputs.node_embeddings, training)
+
+        def backward(self, grad_output):
+            return grad_output
+
+    layer = Stub(MessagePassing.get_default_hyperparameters())
+    inputs = MessagePassingInput(torch.zeros((5, 7)), (torch.zeros((3, 2), dtype=torch.int32),))
+    out, dropped = layer.call_with_epilogue(inputs, training=True, want_split_output=True, output_dropout=(0.5, 1))
+    assert layer.built and dropped is False
+    assert out == layer(inputs, training=True) and out[0] == "called" and out[1] is inputs.node_embeddings and out[2] is True
+    assert layer.call_with_epilogue(inputs) == (layer(inputs), False)
+    g = torch.ones((5, 7))
+    assert layer.backward_with_epilogue(g, want_split_input_grad=True) is g
+    assert MessagePassing._grouped_tn_split_ok is True and MessagePassing._grouped_tn_used is False
+    assert layer._grouped_tn_split_ok is True and layer._grouped_tn_used is False
+    assert GNN_Edge_MLP._always_split_output is False and GGNN._always_split_output is True
+    for n in (0, 16, 96, 128, 256, 320, 384, 512, 640, 960, 1280):
+        assert ops.sp_one_tile(n) == (n in (128, 256, 320)), n
+        assert ops.sp_tiles(n) == (ops.sp_tile_width(n) != 0) == (n % 128 == 0 or n % 320 == 0), n

@@ -13,8 +13,6 @@ from __future__ import annotations
 
 from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
-import os
-
 import torch
 
 from .. import ops
@@ -215,16 +213,10 @@ class GNN:
             parts |= mp.graph_parts(num_nodes, edges_per_type, self._hidden_dim)
         return parts
 
-    @staticmethod
-    def _tiles(n: int) -> bool:
-        return n % 128 == 0 or n % 320 == 0  # output widths the split-operand products tile
-
     def _dense_f16x2(self, in_dim: int, out_dim: int) -> bool:
         """Dense products on split operands (mode f16x2): the operands come split from their producers - the epilogue of
         the product before (tfgnn_sp_gemm_nt_sp), the dropout kernel, the input pipeline (ops.split_rows_remembered) -
         or from one split pass where no producer wrote them."""
-        import os
-
         # On by default since round 4 (TFGNN_DENSE_F16X2=0 turns it off).  Round 3 measured a break-even (2.66 vs 2.65 ms per
         # step): the three K = 320 products got 26 us faster each, the per-step splits of two more weight matrices and the
         # factor and reduce passes of two more weight-gradient products took it back.  With the weight splits riding in the
@@ -239,7 +231,7 @@ class GNN:
             self._guard_sync_passes = max(self._guard_sync_passes, self._guard_sync_passes_init)
         if ops.env("TFGNN_DENSE_F16X2", "1") == "0" or not self._dense_split_ok:
             return False
-        return ops.get_gemm_mode() == ops.GEMM_F16X2 and in_dim % 16 == 0 and in_dim >= 32 and self._tiles(out_dim)
+        return ops.get_gemm_mode() == ops.GEMM_F16X2 and in_dim % 16 == 0 and in_dim >= 32 and ops.sp_tiles(out_dim)
 
     def _dense(self, x, w: Variable, act_name, drop=None):
         """bias-free Dense + activation (gnn.py:136-141,163-170); gelu keeps its pre-activation.  ``drop`` = (rate, seed) of
@@ -250,7 +242,7 @@ class GNN:
             if act_name == "gelu":
                 pre = ops.sp_gemm_nt(ops.sp_rows_of(x), wt)
                 return ops.activation_forward("gelu", pre), pre, False
-            if drop is not None and w.value.shape[1] in (128, 256, 320):
+            if drop is not None and ops.sp_one_tile(w.value.shape[1]):
                 out, _ = ops.sp_gemm_nt_split(ops.sp_rows_of(x), wt, act=act_name, dropout=drop)  # dropped, fp32 + split form
                 return out, None, True
             return ops.sp_gemm_nt(ops.sp_rows_of(x), wt, act=act_name), None, False
@@ -270,7 +262,7 @@ class GNN:
                 w.grad = ops.sp_gemm_tn(ops.sp_rows_of(x), g_sp)  # [in, out] = x^T gpre
             if not need_input_grad:
                 return None
-            if self._tiles(d_in):
+            if ops.sp_tiles(d_in):
                 wr = ops.sp_weight_operand(w.value, "rows", lambda: ops.sp_split_rows(w.value, defer=True))
                 return ops.sp_gemm_nt(g_sp, wr, act_grad=act_grad)
             return ops.gemm_grad(gpre, w.value, trans_b=True, act_grad=act_grad)
@@ -312,7 +304,7 @@ class GNN:
             # the mode was re-armed (ops.set_gemm_mode("f16x2")) after stage 2 of the guard policy took the per-relation weight
             # gradients of this stack's layers off the split operands: they try again, under the synchronous check
             for mp in self._mp_layers:
-                if getattr(mp, "_grouped_tn_split_ok", True) is False:
+                if mp._grouped_tn_split_ok is False:
                     mp._grouped_tn_split_ok = True
             self._tn_demoted_epoch = None
             self._guard_sync_passes = max(self._guard_sync_passes, self._guard_sync_passes_init)
@@ -366,17 +358,13 @@ class GNN:
             dense_here = layer_idx % self._dense_every_num_layers == 0
             has_ex = str(layer_idx) in self._global_exchange_layers
             # a Dense right behind this layer takes its input as a split operand: let the layer's product write it
-            mp_layer._want_split_output = bool(getattr(mp_layer, "_always_split_output", False)) or (
-                dense_here and not has_ex
-                and not self._use_inter_layer_layernorm and self._dense_f16x2(self._hidden_dim, self._hidden_dim)
-            )
+            want_split = (dense_here and not has_ex
+                          and not self._use_inter_layer_layernorm and self._dense_f16x2(self._hidden_dim, self._hidden_dim))
             # ... and the next layer's input dropout, when this layer's output goes straight into it
             direct = not (dense_here or has_ex or self._use_inter_layer_layernorm)
-            mp_layer._fused_output_dropout = drop_for(layer_idx + 1, need_all_representations) if direct else None
-            mp_layer._fused_output_dropout_done = False
-            cur = mp_layer(MessagePassingInput(node_embeddings=cur, adjacency_lists=graph), training=training)
-            dropped = bool(mp_layer._fused_output_dropout_done)
-            mp_layer._fused_output_dropout = None
+            cur, dropped = mp_layer.call_with_epilogue(
+                MessagePassingInput(node_embeddings=cur, adjacency_lists=graph), training=training, want_split_output=want_split,
+                output_dropout=drop_for(layer_idx + 1, need_all_representations) if direct else None)
             all_reprs.append(cur)
             if has_ex:  # gnn.py:307-315
                 ex = self._global_exchange_layers[str(layer_idx)]
@@ -556,7 +544,7 @@ class GNN:
             return "the Dense / projection products (now on the exact bf16x3 kernels)"
         did = False
         for mp in self._mp_layers:
-            if getattr(mp, "_grouped_tn_used", False) and getattr(mp, "_grouped_tn_split_ok", True):
+            if mp._grouped_tn_used and mp._grouped_tn_split_ok:
                 mp._grouped_tn_split_ok = False
                 did = True
         if did:
@@ -598,8 +586,9 @@ class GNN:
                 # the gradient this layer hands down goes straight into a Dense / projection weight-gradient product when
                 # the op below is one and its activation derivative is folded in here: ask for it as a split operand too
                 below_is_dense = layer_idx == 0 or (layer_idx - 1) % self._dense_every_num_layers == 0
-                mp._want_split_input_grad = nxt is not None and below_is_dense and self._dense_f16x2(self._hidden_dim, self._hidden_dim)
-                g = mp.backward_with_epilogue(g, grad_is_pre_activation=g_is_pre, out_mul=mask, out_act_grad=nxt)
+                want_split = nxt is not None and below_is_dense and self._dense_f16x2(self._hidden_dim, self._hidden_dim)
+                g = mp.backward_with_epilogue(g, grad_is_pre_activation=g_is_pre, out_mul=mask, out_act_grad=nxt,
+                                              want_split_input_grad=want_split)
                 g_is_pre = nxt is not None
             else:
                 g = mp.backward_with_epilogue(g, grad_is_pre_activation=g_is_pre)

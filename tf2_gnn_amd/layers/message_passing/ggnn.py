@@ -8,6 +8,7 @@ from .gnn_edge_mlp import GNN_Edge_MLP
 from .message_passing import (
     MessagePassingInput,
     _INIT_GEN,
+    apply_gradient_epilogue,
     default_device,
     glorot_uniform,
     register_message_passing_implementation,
@@ -57,8 +58,8 @@ class GGNN(GNN_Edge_MLP):
     def _uses_base_aggregation(self) -> bool:
         return False
 
-    # f16x2: the aggregate [V, H] is the K operand of the GRU kernel's gradient product - let the forward product's epilogue
-    # write its split form (tfgnn_sp_gemm_nt_sp) instead of splitting it in a pass of its own
+    # f16x2: the aggregate [V, H] is the K operand of the GRU kernel's gradient product - the forward product's epilogue
+    # always writes its split form (tfgnn_sp_gemm_nt_sp) instead of splitting it in a pass of its own
     _always_split_output = True
 
     def _post_activation_name(self):
@@ -100,7 +101,7 @@ class GGNN(GNN_Edge_MLP):
         ru["bias"].grad = torch.stack([ops.colsum(dmx), ops.colsum(dmh)], dim=0)
         d_agg = ops.gemm(dmx, ru["kernel"].value, trans_b=True)
         dX_state = ops.gemm(dmh, ru["recurrent_kernel"].value, trans_b=True, out=dh_direct, accumulate=True)
-        dX_msgs = self._backward_messages(d_agg, ctx)
+        dX_msgs, _ = self._backward_messages(d_agg, ctx)
         return ops.add_scale(dX_msgs, dX_state, 1.0)
 
     def recomputes_input_dropout(self, num_nodes: int, in_dim: int, num_edge_types: int) -> bool:
@@ -109,13 +110,12 @@ class GGNN(GNN_Edge_MLP):
         return (type(self).backward is GGNN.backward and H % 64 == 0 and H <= 512 and in_dim == H and not self._user_message_function()
                 and self._path() == "A" and self._f16x2_eligible(num_nodes, in_dim, num_edge_types, H))
 
-    def backward_with_epilogue(self, grad_output, grad_is_pre_activation=False, out_mul=None, out_act_grad=None):
+    def backward_with_epilogue(self, grad_output, grad_is_pre_activation=False, out_mul=None, out_act_grad=None,
+                               want_split_input_grad=False):
         """With a DropoutSpec as ``out_mul`` (a layer input dropped without a stored mask) the mask is recomputed in the epilogues
         of the three terms of d(node_embeddings) - the gate-gradient kernel's dh_new * z and the two accumulating products -
         instead of a pass over [V, H] afterwards (a STORED mask costs three more reads there: measured slower, so tensors keep
         the generic route)."""
-        from .message_passing import apply_gradient_epilogue
-
         ctx = self._ctx
         if (grad_is_pre_activation or ctx is None or not isinstance(out_mul, ops.DropoutSpec) or type(self).backward is not GGNN.backward
                 or not (ctx.get("f16x2") and ops.get_gemm_mode() == ops.GEMM_F16X2)):
@@ -146,14 +146,10 @@ class GGNN(GNN_Edge_MLP):
         d_agg = ops.sp_gemm_nt(dmx_sp, ops.sp_weight_operand(Wk, "rows", lambda: ops.sp_split_rows(Wk, defer=True)))
         dX = ops.sp_gemm_nt(dmh_sp, ops.sp_weight_operand(Wr, "rows", lambda: ops.sp_split_rows(Wr, defer=True)), out=dh_direct,
                             accumulate=True, out_mul=out_mul)
-        # the message path adds its term into the same buffer (GNN_Edge_MLP._backward_A_f16x2 consumes the request)
-        self._dx_accumulate = (dX, out_mul)
-        try:
-            dX_msgs = self._backward_messages(d_agg, ctx)
-            if self._dx_accumulate is None:
-                return dX_msgs  # == dX, accumulated in place
-        finally:
-            self._dx_accumulate = None
+        # the message path adds its term into the same buffer where its route has an accumulating product
+        dX_msgs, accumulated = self._backward_messages(d_agg, ctx, accumulate=(dX, out_mul))
+        if accumulated:
+            return dX_msgs  # == dX, accumulated in place
         if out_mul is not None:  # the message path took a route without an accumulating product
             dX_msgs = ops.mul(dX_msgs, out_mul.mask() if isinstance(out_mul, ops.DropoutSpec) else out_mul)
         return ops.add_scale(dX_msgs, dX, 1.0)

@@ -53,14 +53,14 @@ def _skip_empty_blocks(L: int, Din: int) -> bool:
     return 2 <= L <= 8 and Din % 16 == 0 and Din <= 1024 and ops.env("TFGNN_NT_SKIP_EMPTY", "1") == "1"
 
 
-def messages_per_edge(layer, g, D, H) -> bool:
-    """one product row per EDGE (rows of X read through an index) rather than per (node, type) bucket?  Pays when edges are
-    fewer than buckets and the fused gathered product (tfgnn_gemm_gathered) takes every edge type's product - the library is
-    asked (tfgnn_gemm_gathered_supported), the shape conditions are not restated here."""
+def per_edge_products_supported(g, D, N) -> bool:
+    """one product row per EDGE (rows of X [V, D] read through an index, N output columns) rather than per (node, type) bucket?
+    Pays when edges are fewer than buckets and the fused gathered product (tfgnn_gemm_gathered) takes every edge type's
+    product - the library is asked (tfgnn_gemm_gathered_supported), the shape conditions are not restated here."""
     if ops.get_gemm_mode() == ops.GEMM_FP32:
         return False
     L, E, V = g.num_edge_types, g.num_edges, g.num_nodes
-    if E == 0 or E >= V * L or layer._aggregation_name == "max" or layer._pre_activation():
+    if E == 0 or E >= V * L:
         return False
     lib = _lib.load()
     forced = PER_EDGE_MIN_ROWS < 65536  # the layer-logic tests run the formulation on small graphs (separate gather + product)
@@ -68,11 +68,16 @@ def messages_per_edge(layer, g, D, H) -> bool:
         if c == 0:
             continue
         if forced:
-            if c < PER_EDGE_MIN_ROWS or D not in (64, 96, 128) or H % 128 != 0:
+            if c < PER_EDGE_MIN_ROWS or D not in (64, 96, 128) or N % 128 != 0:
                 return False
-        elif not lib.tfgnn_gemm_gathered_supported(int(c), int(H), int(D), int(D), int(V)):
+        elif not lib.tfgnn_gemm_gathered_supported(int(c), int(N), int(D), int(D), int(V)):
             return False
     return True
+
+
+def messages_per_edge(layer, g, D, H) -> bool:
+    """path A with one message per edge?  (sum-like aggregation of plain messages only)"""
+    return layer._aggregation_name != "max" and not layer._pre_activation() and per_edge_products_supported(g, D, H)
 
 
 def _relu_input_grad(d_out, W, layer_input, out):
@@ -237,14 +242,30 @@ class GNN_Edge_MLP(MessagePassing):
         return graph_scales(g, bool(self._normalize_by_num_incoming), self._aggregation_name)
 
     # ---- forward ----------------------------------------------------------------------------
+    # Does the layer read its own aggregate as a split operand (GGNN: the GRU kernel's gradient product)?  Then path A's
+    # product writes that form whether or not the stack asks for it.
+    _always_split_output = False
+
     def call(self, inputs: MessagePassingInput, training: bool = False):
+        return self._forward(inputs, training, False, None)[0]
+
+    def call_with_epilogue(self, inputs: MessagePassingInput, training: bool = False, *, want_split_output: bool = False,
+                           output_dropout=None):
+        """Path A on split operands honours both requests in its product's epilogue; every other path ignores them."""
+        if type(self).call is not GNN_Edge_MLP.call:  # a subclass with a forward pass of its own
+            return super().call_with_epilogue(inputs, training, want_split_output=want_split_output, output_dropout=output_dropout)
+        self._build_for(inputs)
+        return self._forward(inputs, training, want_split_output, output_dropout)
+
+    def _forward(self, inputs: MessagePassingInput, training, want_split, drop):
+        """-> (output, ``drop`` applied?)"""
         if self._user_message_function():
             if not self._uses_base_aggregation():
                 raise NotImplementedError(
                     f"{type(self).__name__} overrides _message_function on a layer whose aggregation is not the base class's "
                     "(RGIN / GGNN): override call() and backward() as well"
                 )
-            return MessagePassing.call(self, inputs, training)
+            return MessagePassing.call(self, inputs, training), False
         X = inputs.node_embeddings
         V = X.shape[0]
         g = get_graph(inputs.adjacency_lists, V)
@@ -252,25 +273,26 @@ class GNN_Edge_MLP(MessagePassing):
             raise ValueError(
                 f"layer was built for {self._num_edge_types} edge types, got {g.num_edge_types}"
             )
-        agg, ctx = self._aggregate_messages(X, g, fuse_act=self._post_activation_name())
+        agg, ctx, dropped = self._aggregate_messages(X, g, self._post_activation_name(), want_split, drop)
         ctx["graph"] = g
         ctx["X"] = X
         self._ctx = ctx
-        return self._finish(agg, X, ctx, training)
+        return self._finish(agg, X, ctx, training), dropped
 
     def _finish(self, agg, X, ctx, training):
         """base class: the activation was fused into the aggregation step."""
         ctx["out"] = agg
         return agg
 
-    def _aggregate_messages(self, X, g, fuse_act):
-        """-> (act?(aggregated messages) [V, H], ctx)"""
+    def _aggregate_messages(self, X, g, fuse_act, want_split=False, drop=None):
+        """-> (act?(aggregated messages) [V, H], ctx, ``drop`` applied?).  ``want_split``: write the result as a split operand
+        as well; ``drop`` = (rate, seed): the dropout the result is only ever read through (call_with_epilogue)."""
         path = self._path()
         if path == "A":
-            return self._forward_A(X, g, fuse_act)
+            return self._forward_A(X, g, fuse_act, want_split, drop)
         if path == "B":
-            return self._forward_B(X, g, fuse_act)
-        return self._forward_C(X, g, fuse_act)
+            return (*self._forward_B(X, g, fuse_act), False)
+        return (*self._forward_C(X, g, fuse_act), False)
 
     # ---- general aggregation (max / activation before aggregation) ----------------------------------
     def _agg_general(self) -> bool:
@@ -318,6 +340,24 @@ class GNN_Edge_MLP(MessagePassing):
             ident = torch.arange(g.num_edges + 1, dtype=torch.int32, device=g.device)
             g._cache["ident_e"] = ident
         return ident
+
+    @staticmethod
+    def _ident_nz(g, nz):
+        """identity row pointer over ``nz`` compact rows (one index per output row of a gather)"""
+        ident = g._cache.get(("ident_nz", nz))
+        if ident is None:
+            ident = torch.arange(nz + 1, dtype=torch.int32, device=g.device)
+            g._cache[("ident_nz", nz)] = ident
+        return ident
+
+    @staticmethod
+    def _orig_src_node(g, src_l):
+        """source node of every edge in edge-list order, from ``_original_order``'s source rows (u, l)"""
+        src_node = g._cache.get("orig_src_node")
+        if src_node is None:
+            src_node = torch.div(src_l, g.num_edge_types, rounding_mode="floor").to(torch.int32)
+            g._cache["orig_src_node"] = src_node
+        return src_node
 
     # Buckets (node, type) that received no edge contribute nothing: 45 % of them are empty on an R-MAT
     # batch, and the dense multiply can run over the non-empty ones only (grouped GEMMs over compact
@@ -368,26 +408,19 @@ class GNN_Edge_MLP(MessagePassing):
         Gc = ops.graph_gather(g, ops.VIEW_BY_SRC_TYPED_COMPACT, d_agg, edge_weight=ew_s)  # [nz, H]
         Zc = ops.gemm_grouped_rows(Gc, off_d, off_h, W, trans_b=True)  # [nz, D] = G_c,l @ W_l^T
         dX = ops.gather_reduce(g.array(ops.G_NZ_NODEPTR_BY_SRC), g.array(ops.G_NZ_COL_BY_SRC), Zc)
-        ident = g._cache.get(("ident_nz", nz))
-        if ident is None:
-            ident = torch.arange(nz + 1, dtype=torch.int32, device=X.device)
-            g._cache[("ident_nz", nz)] = ident
-        Xc = ops.gather_reduce(ident, g.array(ops.G_NZ_NODE_BY_SRC), X)  # source states of the compact rows
+        Xc = ops.gather_reduce(self._ident_nz(g, nz), g.array(ops.G_NZ_NODE_BY_SRC), X)  # source states of the compact rows
         mlps.grads = [ops.gemm_grouped_k(Xc, Gc, off_d, off_h, L)]  # dW_l = X_c,l^T @ G_c,l
         mlps.publish_grads()
         return dX
 
     def _f16x2_eligible(self, V, D, L, H) -> bool:
         """path A without target states on shapes the split-operand kernels tile (include/tfgnn.h tfgnn_sp_gemm_*)."""
-        def tiles(n):  # output widths the kernels tile: 320 / 256 / 128 columns
-            return n % 128 == 0 or n % 320 == 0
-
         return (ops.get_gemm_mode() == ops.GEMM_F16X2 and not self._use_target_state_as_input and L > 0 and V > 0
-                and D % 16 == 0 and D <= 512 and 32 <= H <= 512 and tiles(H) and tiles(D))
+                and D % 16 == 0 and D <= 512 and 32 <= H <= 512 and ops.sp_tiles(H) and ops.sp_tiles(D))
 
-    def _forward_A(self, X, g, fuse_act):
+    def _forward_A(self, X, g, fuse_act, want_split=False, drop=None):
         if self._use_compact_buckets(g):
-            return self._forward_A_compact(X, g, fuse_act)
+            return (*self._forward_A_compact(X, g, fuse_act), False)
         V, D = X.shape
         L, H = g.num_edge_types, self._hidden_dim
         T = self._use_target_state_as_input
@@ -400,16 +433,13 @@ class GNN_Edge_MLP(MessagePassing):
             # source index - summed per target by the node-view gather (the machinery of path C)
             _, ew_d, _, node_scale = self._scales(g)
             src_l, _, _, _, off, _ = self._original_order(g, ew_d)
-            src_node = g._cache.get("orig_src_node")
-            if src_node is None:
-                src_node = torch.div(src_l, L, rounding_mode="floor").to(torch.int32)
-                g._cache["orig_src_node"] = src_node
+            src_node = self._orig_src_node(g, src_l)
             msgs = torch.empty((g.num_edges, H), dtype=torch.float32, device=X.device)
             for l in range(L):
                 if off[l + 1] > off[l]:
                     ops.gemm_gathered(X, src_node[off[l] : off[l + 1]], W[l], out=msgs[off[l] : off[l + 1]])
             ctx = {"path": "A", "A": None, "fused_act": fuse_act, "f16x2": self._f16x2_eligible(V, D, L, H)}
-            return self._gather_messages(g, msgs, g.array(ops.G_EID_BY_DST), ew_d, node_scale, fuse_act, ctx), ctx
+            return self._gather_messages(g, msgs, g.array(ops.G_EID_BY_DST), ew_d, node_scale, fuse_act, ctx), ctx, False
         if self._f16x2_eligible(V, D, L, H):
             # f16x2: the gather writes [A_0 | ... | A_{L-1}] directly as the split operand (one scale per (node, type)
             # bucket), the kernels are split once per value, the product only moves data and multiplies
@@ -423,14 +453,14 @@ class GNN_Edge_MLP(MessagePassing):
             #  batch - measured no gain in round 5, 2.370 vs 2.368 ms per step: the gather's time is its reads.  Removed.)
             view = ops.VIEW_BY_DST_TYPED_PATTERN if skip else ops.VIEW_BY_DST_TYPED
             gelu_split = fuse_act == "gelu"
-            want_split = getattr(self, "_want_split_output", False) or getattr(self, "_always_split_output", False)
-            drop = getattr(self, "_fused_output_dropout", None)  # (rate, seed) of the NEXT layer's input dropout (GNN stack)
+            want_split = want_split or self._always_split_output
             out_scale = 1.0
-            # this layer's output is only ever read through that dropout: apply the mask in the product's epilogue and write the
-            # dropped result in both forms (fp32 for the next gather, SP16 for its weight-gradient product)
-            fuse_drop = drop is not None and not gelu_split and H in (128, 256, 320) and type(self)._finish is GNN_Edge_MLP._finish
+            # ``drop``: (rate, seed) of the NEXT layer's input dropout (GNN stack).  This layer's output is only ever read through
+            # it: apply the mask in the product's epilogue and write the dropped result in both forms (fp32 for the next gather,
+            # SP16 for its weight-gradient product)
+            fuse_drop = drop is not None and not gelu_split and ops.sp_one_tile(H) and type(self)._finish is GNN_Edge_MLP._finish
             # (a split result: the consumer finds it with sp_rows_of)
-            split_out = fuse_drop or (want_split and not gelu_split and H in (128, 256, 320))
+            split_out = fuse_drop or (want_split and not gelu_split and ops.sp_one_tile(H))
             if ops.mp_entry_enabled() and Din == D:
                 # round 6: gather + weight split + merged small passes + product in ONE library call (tfgnn_mp_forward) - the
                 # kernels and arguments of the op-level route below, without Python between the launches
@@ -446,13 +476,12 @@ class GNN_Edge_MLP(MessagePassing):
                 else:
                     pre = ops.sp_gemm_nt(A_sp, Wt_sp, act=None if gelu_split else fuse_act, tile_kmask=kmask, row_map=rmap)
             if fuse_drop:
-                self._fused_output_dropout_done = True
                 out_scale = 1.0 - float(drop[0])
             ctx = {"path": "A", "A": None, "fused_act": fuse_act, "f16x2": True, "out_scale": out_scale}
             if gelu_split:
                 ctx["pre"] = pre
-                return ops.activation_forward("gelu", pre), ctx
-            return pre, ctx
+                return ops.activation_forward("gelu", pre), ctx, False
+            return pre, ctx, fuse_drop
         A = torch.empty((V, L * Din), dtype=torch.float32, device=X.device)
         Arows = A.view(V * L, Din)
         ops.graph_gather(g, ops.VIEW_BY_DST_TYPED, X, row_scale=row_scale, out=Arows[:, :D])
@@ -473,43 +502,18 @@ class GNN_Edge_MLP(MessagePassing):
         ctx = {"path": "A", "A": A, "fused_act": fuse_act}
         if gelu_split:
             ctx["pre"] = pre
-            return ops.activation_forward("gelu", pre), ctx
-        return pre, ctx
+            return ops.activation_forward("gelu", pre), ctx, False
+        return pre, ctx, False
 
-    def _backward_A_f16x2(self, d_agg, ctx, g, X, ew_s):
+    def _backward_A_f16x2(self, d_agg, ctx, g, X, ew_s, epilogue=None, want_split=False, accumulate=None):
         """path A backward on split operands: the transposed gather writes G = [G_0 | ... | G_{L-1}] as an SP16 operand
         (one scale per (source, type) bucket) that serves both dX = G @ [W_0 | ... | W_{L-1}]^T (NT) and
-        dW_l = X^T G_l (TN, where the per-row scales become per-k factors: tfgnn_sp_gemm_tn)."""
+        dW_l = X^T G_l (TN, where the per-row scales become per-k factors: tfgnn_sp_gemm_tn).  The requests of
+        ``_backward_messages`` ride in the epilogue of the dX product.  -> (dX, a request was given: it was applied)"""
         V, D = X.shape
         L, H = g.num_edge_types, self._hidden_dim
         mlps = self._edge_type_mlps
         W = mlps.kernels[0]  # [L, D, H]
-        if ops.mp_entry_enabled():
-            # round 6: the whole pass in ONE library call (tfgnn_mp_backward): gather over the by-source buckets, the rows form of
-            # the kernels when stale, the merged small passes, dX = G W^T with its epilogue, dW = X^T G - the op-level sequence below
-            skip = {}
-            if _skip_empty_blocks(L, H) and V > 0:
-                node_at = g.array(ops.G_PATTERN_NODE_BY_SRC)
-                skip = dict(tile_kmask=g.array(ops.G_PATTERN_TILEMASK_BY_SRC), a_rows=node_at, row_map=node_at)
-            epi = getattr(self, "_out_epilogue", None)
-            acc = getattr(self, "_dx_accumulate", None)
-            kw = {}
-            if acc is not None:
-                kw = dict(out=acc[0], accumulate=True, out_mul=acc[1])
-                self._dx_accumulate = None  # consumed
-            elif epi is not None:
-                kw = dict(out_mul=epi[0], act_grad=epi[1], want_split=bool(getattr(self, "_want_split_input_grad", False)) and D in (128, 256, 320))
-                self._out_epilogue = None  # consumed
-            X_sp = ops.sp_rows_of(X)  # written by the dropout kernel when X came out of one
-            dX, _, dW = ops.mp_backward(g, d_agg.contiguous(), W, X_sp, edge_weight=ew_s, skip=skip, **kw)
-            mlps.grads = [dW]
-            mlps.publish_grads()
-            return dX
-        G_sp = ops.graph_gather_sp(g, ops.VIEW_BY_SRC_TYPED, d_agg.contiguous(), edge_weight=ew_s, rows_per_operand_row=L,
-                                   defer_combine=True)
-        Wh_sp = ops.sp_weight_operand(W, "rows", lambda: ops.sp_split_rows(W[0], segments=(H, D * H, L * H), defer=True))
-        epi = getattr(self, "_out_epilogue", None)
-        acc = getattr(self, "_dx_accumulate", None)
         # Round 5: the by-source buckets are as sparse as the by-target ones (45 % empty on the R-MAT batch).  G stays in node
         # order - the weight-gradient product below pairs its rows with X's -, the input-gradient product reads its rows in the
         # order of the by-source emptiness patterns (a_rows), skips the all-zero type blocks of a row tile and writes node order
@@ -518,25 +522,37 @@ class GNN_Edge_MLP(MessagePassing):
         if _skip_empty_blocks(L, H) and V > 0:
             node_at = g.array(ops.G_PATTERN_NODE_BY_SRC)
             skip = dict(tile_kmask=g.array(ops.G_PATTERN_TILEMASK_BY_SRC), a_rows=node_at, row_map=node_at)
-        if acc is not None:
+        # the request, decoded once for both routes below
+        applied = accumulate is not None or epilogue is not None
+        split = False
+        if accumulate is not None:
             # a subclass (GGNN) already holds other terms of d(node_embeddings): add this one in the product's epilogue
-            dX = ops.sp_gemm_nt(G_sp, Wh_sp, out=acc[0], accumulate=True, out_mul=acc[1], **skip)
-            self._dx_accumulate = None  # consumed
-        elif epi is not None:
-            if getattr(self, "_want_split_input_grad", False) and D in (128, 256, 320):
-                dX, _ = ops.sp_gemm_nt_split(G_sp, Wh_sp, out_mul=epi[0], act_grad=epi[1], **skip)
-            else:
-                dX = ops.sp_gemm_nt(G_sp, Wh_sp, out_mul=epi[0], act_grad=epi[1], **skip)
-            self._out_epilogue = None  # consumed
+            kw = dict(out=accumulate[0], accumulate=True, out_mul=accumulate[1])
+        elif epilogue is not None:
+            kw = dict(out_mul=epilogue[0], act_grad=epilogue[1])
+            split = bool(want_split) and ops.sp_one_tile(D)
         else:
-            dX = ops.sp_gemm_nt(G_sp, Wh_sp, **skip)
-        X_sp = ops.sp_rows_of(X)  # written by the dropout kernel when X came out of one
-        dW = torch.empty_like(W)
-        # element ((l, h), d) -> dW[l, d, h]  (the split reduction stays right behind the product: NOTEBOOK.md 4.4)
-        ops.sp_gemm_tn(G_sp, X_sp, out=dW, scatter=(H, D * H, 1, H))
+            kw = {}
+        if ops.mp_entry_enabled():
+            # round 6: the whole pass in ONE library call (tfgnn_mp_backward): gather over the by-source buckets, the rows form of
+            # the kernels when stale, the merged small passes, dX = G W^T with its epilogue, dW = X^T G - the op-level sequence below
+            X_sp = ops.sp_rows_of(X)  # written by the dropout kernel when X came out of one
+            dX, _, dW = ops.mp_backward(g, d_agg.contiguous(), W, X_sp, edge_weight=ew_s, skip=skip, want_split=split, **kw)
+        else:
+            G_sp = ops.graph_gather_sp(g, ops.VIEW_BY_SRC_TYPED, d_agg.contiguous(), edge_weight=ew_s, rows_per_operand_row=L,
+                                       defer_combine=True)
+            Wh_sp = ops.sp_weight_operand(W, "rows", lambda: ops.sp_split_rows(W[0], segments=(H, D * H, L * H), defer=True))
+            if split:
+                dX, _ = ops.sp_gemm_nt_split(G_sp, Wh_sp, **kw, **skip)
+            else:
+                dX = ops.sp_gemm_nt(G_sp, Wh_sp, **kw, **skip)
+            X_sp = ops.sp_rows_of(X)
+            dW = torch.empty_like(W)
+            # element ((l, h), d) -> dW[l, d, h]  (the split reduction stays right behind the product: NOTEBOOK.md 4.4)
+            ops.sp_gemm_tn(G_sp, X_sp, out=dW, scatter=(H, D * H, 1, H))
         mlps.grads = [dW]
         mlps.publish_grads()
-        return dX
+        return dX, applied
 
     def _mlp_all_types(self, X, L, ctx, mlps=None, key="mlp_acts"):
         """Y[:, l, :] = MLP_l(X) for all nodes -> [V, L, H]; hidden activations saved in ctx[key]."""
@@ -614,7 +630,7 @@ class GNN_Edge_MLP(MessagePassing):
     def _grouped_tn_route(self, g) -> bool:
         """kernel gradients of the compact-row MLPs on the grouped two-factor TN product?  Not after the stack's guard policy
         handed them back (``_grouped_tn_split_ok``), and not for more K ranges than one launch takes (~10^6 compact rows)."""
-        return bool(getattr(self, "_grouped_tn_split_ok", True)) and self._row_groups(g).tn_tables()[2] <= ops.TN_GROUPED_MAX_RANGES
+        return bool(self._grouped_tn_split_ok) and self._row_groups(g).tn_tables()[2] <= ops.TN_GROUPED_MAX_RANGES
 
     @staticmethod
     def _stacked_transposed_operand(W):
@@ -669,12 +685,7 @@ class GNN_Edge_MLP(MessagePassing):
                 if j > 0:
                     inp32 = acts[j - 1]
                 else:  # the expanded node states, as the bf16x3 path keeps them
-                    nz = groups.num_rows
-                    ident = g._cache.get(("ident_nz", nz))
-                    if ident is None:
-                        ident = torch.arange(nz + 1, dtype=torch.int32, device=dcur.device)
-                        g._cache[("ident_nz", nz)] = ident
-                    inp32 = ops.gather_reduce(ident, g.array(ops.G_NZ_NODE_BY_SRC), ctx["X"])
+                    inp32 = ops.gather_reduce(self._ident_nz(g, groups.num_rows), g.array(ops.G_NZ_NODE_BY_SRC), ctx["X"])
                 grads[j] = ops.gemm_grouped_k(inp32, d32, g.array(ops.G_NZ_OFF_BY_SRC), off, groups.num_groups)
             else:
                 self._grouped_tn_used = True  # (what the stack's guard policy demotes if the spread guard trips: GNN.backward)
@@ -716,11 +727,7 @@ class GNN_Edge_MLP(MessagePassing):
         off_h = g.nonempty_offsets(True)
         nz = off_h[-1]
         off_dev = g.array(ops.G_NZ_OFF_BY_SRC)
-        ident = g._cache.get(("ident_nz", nz))
-        if ident is None:
-            ident = torch.arange(nz + 1, dtype=torch.int32, device=X.device)
-            g._cache[("ident_nz", nz)] = ident
-        Xc = ops.gather_reduce(ident, g.array(ops.G_NZ_NODE_BY_SRC), X)  # states of the non-empty (source, type) pairs
+        Xc = ops.gather_reduce(self._ident_nz(g, nz), g.array(ops.G_NZ_NODE_BY_SRC), X)  # states of the non-empty (source, type) pairs
         acts, cur = [], Xc
         for j, W in enumerate(mlps.kernels):
             last = j == mlps.num_layers - 1
@@ -779,8 +786,6 @@ class GNN_Edge_MLP(MessagePassing):
 
     def _original_order(self, g, ew_d):
         """index arrays in concatenated-adjacency-list order (type-contiguous), cached on the Graph."""
-        from ... import _lib
-
         key = ("orig", None if ew_d is None else ew_d.data_ptr())
         cached = g._cache.get(key)
         if cached is None:
@@ -805,22 +810,17 @@ class GNN_Edge_MLP(MessagePassing):
 
     def _edge_messages_C(self, X, g, ew_d):
         """per-edge MLP outputs [E, H] in edge-list order (target states + hidden layers); see csrc/edge.hip."""
-        from ... import _lib
-
         V, D = X.shape
         L, E = g.num_edge_types, g.num_edges
         mlps = self._edge_type_mlps
         src_l, tgt_l, tgt_node, _, off, _ = self._original_order(g, ew_d)
         H0 = mlps.kernels[0].shape[2]
         first_act = "relu" if mlps.num_layers > 1 else None
-        if self._first_layer_per_edge(g, D, H0, off):
+        if per_edge_products_supported(g, D, H0):
             # few edges per (node, type) pair (molecules: E < V L): the first layer runs once per EDGE on rows of X read
             # through the edge's source / target index - x_u W_s, then act(. + x_v W_t) - instead of once per (node, type)
             # pair followed by a pass that adds the two gathered rows
-            src_node = g._cache.get("orig_src_node")
-            if src_node is None:
-                src_node = torch.div(src_l, L, rounding_mode="floor").to(torch.int32)
-                g._cache["orig_src_node"] = src_node
+            src_node = self._orig_src_node(g, src_l)
             W0 = mlps.kernels[0]  # [L, 2D, H0]
             Z = torch.empty((E, H0), dtype=torch.float32, device=X.device)
             for l in range(L):
@@ -859,24 +859,6 @@ class GNN_Edge_MLP(MessagePassing):
             cur = nxt
         return cur, acts
 
-    def _first_layer_per_edge(self, g, D, H0, off) -> bool:
-        """the first layer of path C once per edge (two gathered products)?  The same question as ``messages_per_edge`` with the
-        hidden width as the output width (one predicate, asked of the library)."""
-        if g.num_edges == 0 or g.num_edges >= g.num_nodes * g.num_edge_types or ops.get_gemm_mode() == ops.GEMM_FP32:
-            return False
-        lib = _lib.load()
-        forced = PER_EDGE_MIN_ROWS < 65536
-        for l in range(g.num_edge_types):
-            c = off[l + 1] - off[l]
-            if c == 0:
-                continue
-            if forced:
-                if c < PER_EDGE_MIN_ROWS or D not in (64, 96, 128) or H0 % 128 != 0:
-                    return False
-            elif not lib.tfgnn_gemm_gathered_supported(int(c), int(H0), int(D), int(D), int(g.num_nodes)):
-                return False
-        return True
-
     def _aggregate_nothing(self, V, X, fuse_act, ctx):
         """aggregation over zero edges: zeros (sum-like) / the float minimum (max), then the activation."""
         out = torch.zeros((V, self._hidden_dim), dtype=torch.float32, device=X.device)
@@ -899,8 +881,9 @@ class GNN_Edge_MLP(MessagePassing):
             return self._aggregate_nothing(V, X, fuse_act, ctx), ctx
         return self._gather_messages(g, cur, g.array(ops.G_EID_BY_DST), ew_d, node_scale, fuse_act, ctx), ctx
 
-    def _backward_C(self, d_agg, ctx, dcur=None):
-        """``dcur``: d(per-edge MLP outputs) [E, H] in edge-list order when the caller already has it (GNN_FiLM)."""
+    def _backward_C(self, d_agg, ctx, dcur=None, epilogue=None):
+        """``dcur``: d(per-edge MLP outputs) [E, H] in edge-list order when the caller already has it (GNN_FiLM).
+        -> (dX, ``epilogue`` applied?) as ``_backward_messages``."""
         g, X = ctx["graph"], ctx["X"]
         V, D = X.shape
         L, E = g.num_edge_types, g.num_edges
@@ -908,7 +891,7 @@ class GNN_Edge_MLP(MessagePassing):
         if E == 0:
             mlps.grads = [torch.zeros_like(W) for W in mlps.kernels]
             mlps.publish_grads()
-            return torch.zeros_like(X)
+            return torch.zeros_like(X), False
         _, ew_d, _, node_scale = self._scales(g)
         general = self._agg_general()
         acts = ctx["edge_acts"]
@@ -944,58 +927,51 @@ class GNN_Edge_MLP(MessagePassing):
         # first layer: z0[e] = relu(P[(src,l)] + Q[(tgt,l)]); dcur is d(P+Q) per edge
         H0 = mlps.kernels[0].shape[2]
         if self._first_layer_grads_split_ok(V, D, L, H0):
-            grads[0], dX = self._backward_C_first_layer_split(dcur, g, X, L, H0)
+            grads[0], dX = self._backward_C_first_layer_split(dcur, g, X, L, H0, epilogue)
             mlps.grads = grads
             mlps.publish_grads()
-            return dX
+            return dX, epilogue is not None
         dP = ops.graph_gather(g, ops.VIEW_BY_SRC_TYPED, dcur, col=g.array(ops.G_EID_BY_SRC)).view(V, L * H0)
         dQ = ops.graph_gather(g, ops.VIEW_BY_DST_TYPED, dcur, col=g.array(ops.G_EID_BY_DST)).view(V, L * H0)
         Wh = ops.permute_021(mlps.kernels[0])  # [2D, L, H0]
         dWh = torch.empty_like(Wh)
         ops.gemm(X, dP, trans_a=True, out=dWh[:D].view(D, L * H0))
         ops.gemm(X, dQ, trans_a=True, out=dWh[D:].view(D, L * H0))
-        epi = getattr(self, "_out_epilogue", None)
-        if epi is not None:
+        if epilogue is not None:
             # the factors of the next backward step (dropout mask, activation derivative of the layer below) distribute over
             # the two terms: both products apply them in their epilogues, the second one adds into the first's result
-            dX = ops.gemm_grad(dP, Wh[:D].view(D, L * H0), trans_b=True, out_mul=epi[0], act_grad=epi[1])
-            dX = ops.gemm_grad(dQ, Wh[D:].view(D, L * H0), trans_b=True, out=dX, accumulate=True, out_mul=epi[0], act_grad=epi[1])
-            self._out_epilogue = None  # consumed
+            out_mul, act_grad = epilogue
+            dX = ops.gemm_grad(dP, Wh[:D].view(D, L * H0), trans_b=True, out_mul=out_mul, act_grad=act_grad)
+            dX = ops.gemm_grad(dQ, Wh[D:].view(D, L * H0), trans_b=True, out=dX, accumulate=True, out_mul=out_mul, act_grad=act_grad)
         else:
             dX = ops.gemm(dP, Wh[:D].view(D, L * H0), trans_b=True)
             ops.gemm(dQ, Wh[D:].view(D, L * H0), trans_b=True, out=dX, accumulate=True)
         grads[0] = ops.permute_021(dWh)
         mlps.grads = grads
         mlps.publish_grads()
-        return dX
+        return dX, epilogue is not None
 
     def _first_layer_grads_split_ok(self, V, D, L, H0) -> bool:
         """path C, gradients of the first MLP layer on split operands?  (widths the split-operand kernels tile; the stack's guard
         policy may have handed these weight gradients back to the exact kernels: GNN._demote_fragile_weight_gradients)"""
-        import os
-
-        def tiles(n):
-            return n % 128 == 0 or n % 320 == 0
-
         return (ops.get_gemm_mode() == ops.GEMM_F16X2 and ops.env("TFGNN_EDGE_FIRST_LAYER_F16X2", "1") == "1"
-                and getattr(self, "_grouped_tn_split_ok", True) and V > 0 and L > 0 and H0 % 16 == 0 and H0 <= 512
-                and 32 <= D <= 512 and tiles(D) and tiles(H0))
+                and self._grouped_tn_split_ok and V > 0 and L > 0 and H0 % 16 == 0 and H0 <= 512
+                and 32 <= D <= 512 and ops.sp_tiles(D) and ops.sp_tiles(H0))
 
-    def _backward_C_first_layer_split(self, dcur, g, X, L, H0):
+    def _backward_C_first_layer_split(self, dcur, g, X, L, H0, epilogue=None):
         """d(first-layer pre-activations) per edge [E, H0] -> (d kernels[0] [L, 2D, H0], dX [V, D]) on split operands (f16x2), the
         two halves of the layer - source states, target states - alike (as _backward_A_f16x2 does for linear messages):
           G = [G_0 | .. | G_{L-1}], G_l[u] = sum of dcur over the edges of type l that leave (enter) u: the typed gather writes
               it as an SP16 operand, one scale per (node, type) bucket;
           dX += G @ [W_0 | .. | W_{L-1}]^T   split-operand NT product over the nodes in the order of their emptiness patterns
-              (all-zero type blocks of a row tile skipped), the factors of the next backward step in its epilogue;
+              (all-zero type blocks of a row tile skipped), the factors of the next backward step (``epilogue``) in its epilogue;
           dW_l = X^T G_l                      the two-factor TN product (both operands are un-normalised sums).
         Replaces two fp32 typed gathers + four bf16x3 products over [V, L H0] (QM9-sized batches: 2.4 -> 1.9 ms per half)."""
         V, D = X.shape
         W0 = self._edge_type_mlps.kernels[0]  # [L, 2D, H0]
         X_sp = ops.sp_rows_of(X)
         gW0 = torch.empty_like(W0)
-        epi = getattr(self, "_out_epilogue", None)
-        kw = dict(out_mul=epi[0], act_grad=epi[1]) if epi is not None else {}
+        kw = dict(out_mul=epilogue[0], act_grad=epilogue[1]) if epilogue is not None else {}
         self._grouped_tn_used = True  # (what the stack's guard policy demotes if the spread guard trips: GNN.backward)
         dX = None
         halves = ((ops.VIEW_BY_SRC_TYPED, ops.G_EID_BY_SRC, ops.G_PATTERN_NODE_BY_SRC, ops.G_PATTERN_TILEMASK_BY_SRC, 0),
@@ -1015,7 +991,6 @@ class GNN_Edge_MLP(MessagePassing):
             dWh = torch.empty((L, D, H0), dtype=torch.float32, device=X.device)
             ops.sp_gemm_tn(G_sp, X_sp, out=dWh, scatter=(H0, D * H0, 1, H0), wide=True)  # element ((l, h), d) -> dWh[l, d, h]
             gW0[:, d0:d0 + D].copy_(dWh)
-        self._out_epilogue = None  # consumed
         return gW0, dX
 
     # ---- backward ---------------------------------------------------------------------------
@@ -1026,7 +1001,7 @@ class GNN_Edge_MLP(MessagePassing):
         if ctx.get("generic"):  # the forward pass ran a user message function on the generic path
             return MessagePassing.backward(self, grad_output)
         d_agg = self._backward_finish(grad_output, ctx)
-        return self._backward_messages(d_agg, ctx)
+        return self._backward_messages(d_agg, ctx)[0]
 
     def _plain_base_backward(self) -> bool:
         cls = type(self)
@@ -1048,20 +1023,17 @@ class GNN_Edge_MLP(MessagePassing):
             return False
         return True
 
-    def backward_with_epilogue(self, grad_output, grad_is_pre_activation=False, out_mul=None, out_act_grad=None):
+    def backward_with_epilogue(self, grad_output, grad_is_pre_activation=False, out_mul=None, out_act_grad=None,
+                               want_split_input_grad=False):
         if not self._plain_base_backward() or (self._ctx is not None and self._ctx.get("generic")):
             return super().backward_with_epilogue(grad_output, grad_is_pre_activation, out_mul, out_act_grad)
         ctx = self._ctx
         if ctx is None:
             raise RuntimeError("backward called before a forward pass")
         d_agg = grad_output if grad_is_pre_activation else self._backward_finish(grad_output, ctx)
-        self._out_epilogue = (out_mul, out_act_grad)
-        try:
-            dX = self._backward_messages(d_agg, ctx)
-            if self._out_epilogue is not None:  # the path taken had no GEMM to fold the factors into
-                dX = apply_gradient_epilogue(dX, out_mul, out_act_grad)
-        finally:
-            self._out_epilogue = None
+        dX, applied = self._backward_messages(d_agg, ctx, epilogue=(out_mul, out_act_grad), want_split=want_split_input_grad)
+        if not applied:  # the path taken had no GEMM to fold the factors into
+            dX = apply_gradient_epilogue(dX, out_mul, out_act_grad)
         return dX
 
     def _backward_finish(self, grad_output, ctx):
@@ -1073,14 +1045,20 @@ class GNN_Edge_MLP(MessagePassing):
         _, spec = ops.plain_epilogue(None, (act, saved, 1.0 if act == "gelu" else ctx.get("out_scale", 1.0)))
         return ops.activation_backward(act, grad_output, spec[1])
 
-    def _backward_messages(self, d_agg, ctx):
-        """d(aggregated messages) [V, H] -> dX [V, D]; fills the edge-MLP kernel gradients."""
+    def _backward_messages(self, d_agg, ctx, epilogue=None, want_split=False, accumulate=None):
+        """d(aggregated messages) [V, H] -> dX [V, D]; fills the edge-MLP kernel gradients.  What the caller would do to dX next
+        may ride in the epilogue of the product that writes it - one of
+          ``epilogue`` = (out_mul, act_grad): dX * out_mul * act'(saved) (backward_with_epilogue), with ``want_split``: written
+              as a split operand as well, where the product can;
+          ``accumulate`` = (buffer, out_mul): buffer += dX * out_mul, the buffer returned (GGNN's other terms of dX).
+        -> (dX, request applied?): a route without such a product returns the plain dX and False, and the caller does it."""
+        assert epilogue is None or accumulate is None
         if ctx["path"] == "C":
-            return self._backward_C(d_agg, ctx)
+            return self._backward_C(d_agg, ctx, epilogue=epilogue)
         if ctx["path"] == "Bc":
-            return self._backward_B_compact(d_agg, ctx)
+            return self._backward_B_compact(d_agg, ctx), False
         if ctx["path"] == "Ac":
-            return self._backward_A_compact(d_agg, ctx)
+            return self._backward_A_compact(d_agg, ctx), False
         g = ctx["graph"]
         X = ctx["X"]
         V, D = X.shape
@@ -1094,7 +1072,7 @@ class GNN_Edge_MLP(MessagePassing):
                                      node_scale, self._ident_e(g)[: g.num_edges])
             G = ops.graph_gather(g, ops.VIEW_BY_SRC_TYPED, dM, col=g.array(ops.G_SRC2DST_POS)).view(V, L, H)
         elif ctx.get("f16x2") and ops.get_gemm_mode() == ops.GEMM_F16X2:  # (not after the spread guard demoted the mode)
-            return self._backward_A_f16x2(d_agg, ctx, g, X, ew_s)
+            return self._backward_A_f16x2(d_agg, ctx, g, X, ew_s, epilogue, want_split, accumulate)
         else:
             # G[u, l, :] = sum over edges (u -> v) of type l of w_e * d_agg[v, :]
             G = ops.graph_gather(g, ops.VIEW_BY_SRC_TYPED, d_agg, edge_weight=ew_s).view(V, L, H)
@@ -1108,15 +1086,13 @@ class GNN_Edge_MLP(MessagePassing):
             G2 = G.view(V, L * H)
             if L > 0 and not self._use_target_state_as_input:
                 # dW^T = G^T X [L*H, D]: ten full 128-row output tiles instead of the 2.5 x 4 ragged ones of X^T G
-                epi = getattr(self, "_out_epilogue", None)
-                if epi is not None:
-                    dX = ops.gemm_grad(G2, Wh.view(D, L * H), trans_b=True, out=dX, out_mul=epi[0], act_grad=epi[1])
-                    self._out_epilogue = None  # consumed
+                if epilogue is not None:
+                    dX = ops.gemm_grad(G2, Wh.view(D, L * H), trans_b=True, out=dX, out_mul=epilogue[0], act_grad=epilogue[1])
                 else:
                     ops.gemm(G2, Wh.view(D, L * H), trans_b=True, out=dX)
                 mlps.grads = [ops.transpose_batched(ops.gemm(G2, X, trans_a=True).view(L, H, D))]
                 mlps.publish_grads()
-                return dX
+                return dX, epilogue is not None
             dWh = torch.empty((Din, L, H), dtype=torch.float32, device=X.device)
             if L == 0:
                 dX.zero_()
@@ -1138,4 +1114,4 @@ class GNN_Edge_MLP(MessagePassing):
         else:
             self._mlp_all_types_backward(mlps, X, ctx["mlp_acts"], G, dX, accumulate=False)
         mlps.publish_grads()
-        return dX
+        return dX, False

@@ -144,7 +144,7 @@ class GNN_FiLM(GNN_Edge_MLP):
         self._mlp_all_types_backward(self._film_mlps, X, ctx["film_acts"], dfilm, dX, accumulate=False)
         self._film_mlps.publish_grads()
         if self._use_target_state_as_input:
-            dX = ops.add_scale(dX, self._backward_C(None, ctx, dcur=dmsg), 1.0)
+            dX = ops.add_scale(dX, self._backward_C(None, ctx, dcur=dmsg)[0], 1.0)
         else:
             # MLP_l(x_u) was used by every edge leaving (u, l)
             G = ops.graph_gather(g, ops.VIEW_BY_SRC_TYPED, dmsg, col=g.array(ops.G_EID_BY_SRC)).view(V, L, H)

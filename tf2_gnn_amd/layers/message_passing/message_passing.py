@@ -169,6 +169,11 @@ class MessagePassing:
             "hidden_dim": 7,
         }
 
+    # Defaults of the per-layer state of the stack's spread-guard policy (GNN._demote_fragile_weight_gradients); __init__ copies
+    # them into the instance, where they live across passes:
+    _grouped_tn_split_ok = True  # the per-relation weight gradients may run on the split-operand TN products (stage 2 clears it)
+    _grouped_tn_used = False     # a backward pass of this layer ran such a product (what stage 2 can demote)
+
     def graph_parts(self, num_nodes: int, edges_per_type, in_dim: int) -> int:
         """Which derived tables of the batch's graph handle this layer reads (ops.G_PART_*), for a batch of that shape: a
         stack whose layers need only some of them skips the preparation kernels of the rest (include/tfgnn.h
@@ -194,6 +199,8 @@ class MessagePassing:
         self.built = False
         self._variables: List[Variable] = []
         self._ctx = None  # saved tensors of the last recorded forward
+        self._grouped_tn_split_ok = type(self)._grouped_tn_split_ok
+        self._grouped_tn_used = type(self)._grouped_tn_used
 
     # ---- Keras-like plumbing ----------------------------------------------------------------
     @property
@@ -216,7 +223,7 @@ class MessagePassing:
     def build(self, input_shapes: MessagePassingInput):
         self.built = True
 
-    def __call__(self, inputs: MessagePassingInput, training: bool = False):
+    def _build_for(self, inputs: MessagePassingInput):
         if not self.built:
             self.build(
                 MessagePassingInput(
@@ -224,6 +231,9 @@ class MessagePassing:
                     tuple((None, 2) for _ in range(_num_edge_types(inputs.adjacency_lists))),
                 )
             )
+
+    def __call__(self, inputs: MessagePassingInput, training: bool = False):
+        self._build_for(inputs)
         return self.call(inputs, training=training)
 
     # ---- the reference's extension points ---------------------------------------------------
@@ -419,10 +429,21 @@ class MessagePassing:
         (ops.plain_epilogue): correct, one pass slower."""
         return False
 
-    def backward_with_epilogue(self, grad_output, grad_is_pre_activation=False, out_mul=None, out_act_grad=None):
+    def call_with_epilogue(self, inputs: MessagePassingInput, training: bool = False, *, want_split_output: bool = False,
+                           output_dropout=None):
+        """``__call__`` for the layer stack, with what the stack would do to the output next handed in as requests:
+        ``want_split_output`` - the consumer reads the output as a split operand as well (a Dense right behind the layer);
+        ``output_dropout`` = (rate, seed) - the output is only read through that dropout (the next layer's input).
+        -> (output, dropout applied?).  A layer may ignore either request; one that applied the dropout says so, and the
+        stack then does not drop again.  Generic form: a plain call, nothing applied."""
+        return self(inputs, training=training), False
+
+    def backward_with_epilogue(self, grad_output, grad_is_pre_activation=False, out_mul=None, out_act_grad=None,
+                               want_split_input_grad=False):
         """backward(), then d(node_embeddings) * out_mul * act'(saved) - the element-wise factors the caller would
         apply next (dropout mask of this layer's input, activation derivative of the layer below).  Generic form:
-        separate kernels; GNN_Edge_MLP folds them into its input-gradient GEMM."""
+        separate kernels; GNN_Edge_MLP folds them into its input-gradient GEMM.  ``want_split_input_grad``: the caller reads
+        the result as a split operand as well (a layer whose product can write it does; ignored here)."""
         if grad_is_pre_activation:
             raise ValueError(f"{type(self).__name__} does not accept an already activation-multiplied gradient")
         return apply_gradient_epilogue(self.backward(grad_output), out_mul, out_act_grad)

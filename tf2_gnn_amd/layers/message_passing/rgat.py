@@ -1,5 +1,4 @@
 """Relational Graph Attention Network layer - mirror of tf2_gnn/layers/message_passing/rgat.py."""
-import os
 from typing import Any, Dict
 
 import torch
@@ -8,6 +7,7 @@ from ... import _lib, ops
 from .message_passing import (
     MessagePassing,
     MessagePassingInput,
+    apply_gradient_epilogue,
     default_device,
     get_graph,
     glorot_uniform,
@@ -129,11 +129,8 @@ class RGAT(MessagePassing):
 
     def _f16x2_eligible(self, V, D, L, H) -> bool:
         """the three products of the layer (Y = X W, dX = dY W^T, dW = X^T dY) on split operands: widths the kernels tile"""
-        def tiles(n):
-            return n % 128 == 0 or n % 320 == 0
-
-        return (ops.get_gemm_mode() == ops.GEMM_F16X2 and V > 0 and L > 0 and D % 16 == 0 and 32 <= D <= 512 and tiles(D)
-                and tiles(L * H) and L * H <= 2048 and (H // self._num_heads) % 4 == 0)
+        return (ops.get_gemm_mode() == ops.GEMM_F16X2 and V > 0 and L > 0 and D % 16 == 0 and 32 <= D <= 512 and ops.sp_tiles(D)
+                and ops.sp_tiles(L * H) and L * H <= 2048 and (H // self._num_heads) % 4 == 0)
 
     @staticmethod
     def _ident(g, n):
@@ -180,7 +177,7 @@ class RGAT(MessagePassing):
 
     def backward(self, grad_output: torch.Tensor) -> torch.Tensor:
         """d(loss)/d(out) -> d(loss)/d(node_embeddings); fills the kernel / attention gradients."""
-        return self._backward(grad_output, False, None, None)
+        return self._backward(grad_output, False, None, None, False)
 
     def activation_backward_spec(self):
         ctx = self._ctx
@@ -193,17 +190,16 @@ class RGAT(MessagePassing):
         return (type(self).backward is RGAT.backward and num_edge_types == self._num_edge_types
                 and self._f16x2_eligible(num_nodes, in_dim, num_edge_types, self._hidden_dim))
 
-    def backward_with_epilogue(self, grad_output, grad_is_pre_activation=False, out_mul=None, out_act_grad=None):
+    def backward_with_epilogue(self, grad_output, grad_is_pre_activation=False, out_mul=None, out_act_grad=None,
+                               want_split_input_grad=False):
         """backward() whose input-gradient product dX = dY W^T applies the caller's next element-wise steps (dropout mask of
-        this layer's input, activation derivative of the layer below) in its epilogue, and which takes a gradient the layer
-        above already multiplied by this layer's activation derivative."""
+        this layer's input, activation derivative of the layer below) in its epilogue - and writes dX as a split operand as well
+        when asked -, and which takes a gradient the layer above already multiplied by this layer's activation derivative."""
         if type(self).backward is not RGAT.backward:
             return super().backward_with_epilogue(grad_output, grad_is_pre_activation, out_mul, out_act_grad)
-        return self._backward(grad_output, grad_is_pre_activation, out_mul, out_act_grad)
+        return self._backward(grad_output, grad_is_pre_activation, out_mul, out_act_grad, want_split_input_grad)
 
-    def _backward(self, grad_output, grad_is_pre_activation, out_mul, out_act_grad) -> torch.Tensor:
-        from .message_passing import apply_gradient_epilogue
-
+    def _backward(self, grad_output, grad_is_pre_activation, out_mul, out_act_grad, want_split_input_grad) -> torch.Tensor:
         ctx = self._ctx
         if ctx is None:
             raise RuntimeError("backward called before a forward pass")
@@ -289,7 +285,7 @@ class RGAT(MessagePassing):
             if rc == 0:
                 d_kernels = ops.gemm(X, dY.view(V, L * H), trans_a=True)  # X^T dY  [D, L*H]
                 Wr = ops.sp_weight_operand(self._kernels, "rows", lambda: ops.sp_split_rows(self._kernels, defer=True))
-                if getattr(self, "_want_split_input_grad", False) and D in (128, 256, 320):
+                if want_split_input_grad and ops.sp_one_tile(D):
                     dX, _ = ops.sp_gemm_nt_split(dY_sp, Wr, out_mul=out_mul, act_grad=out_act_grad)
                 else:
                     dX = ops.sp_gemm_nt(dY_sp, Wr, out_mul=out_mul, act_grad=out_act_grad)

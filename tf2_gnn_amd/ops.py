@@ -1492,6 +1492,16 @@ def sp_tile_width(N: int) -> int:
     return 320 if N % 320 == 0 else (256 if N % 256 == 0 else (128 if N % 128 == 0 else 0))
 
 
+def sp_tiles(N: int) -> bool:
+    """Do the split-operand products tile N output columns (320 / 256 / 128 wide tiles)?"""
+    return N % 128 == 0 or N % 320 == 0
+
+
+def sp_one_tile(N: int) -> bool:
+    """Is N exactly one column tile of the split-operand NT product (128, 256 or 320: what ``sp_gemm_nt_split`` takes)?"""
+    return sp_tile_width(N) == N
+
+
 class RowGroups:
     """Consecutive row groups (rows of group g: [offsets[g], offsets[g + 1])) cut into the row tiles of the grouped product
     (tfgnn_sp_gemm_nt_grouped d_tile_table): int32 [tiles, 4] = (first row, rows, group, 0) on the device, built once per
