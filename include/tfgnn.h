@@ -1019,6 +1019,83 @@ int tfgnn_mp_forward(const tfgnn_mp_forward_args* args, void* stream);
 int tfgnn_mp_backward(const tfgnn_mp_backward_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Graph readout (csrc/pool_fused.hip): the tail of WeightedSumGraphRepresentation.call behind its two MLPs
+ * (nodes_to_graph_representation.py:170-229) - per-graph softmax of the scores (:178-186), clip of the transformed nodes
+ * (:194-197), weighted segment sum (:204-227) - and its share of tape.gradient, one call each.  With h(f) = f / (GD / heads):
+ *   out[g, f] = sum over the nodes v of graph g of  w[v, h(f)] * min(max(T[v, f], lo), hi)          (an empty graph: a zero row)
+ *   TFGNN_POOL_SOFTMAX  w = exp(S - m_g) / (sum_g exp(S - m_g) + 1e-7) per (graph, head), what tfgnn_segment_softmax computes;
+ *                       written to `w` (the backward call reads it)
+ *   TFGNN_POOL_SIGMOID  w = S: the scoring MLP's final activation already applied the sigmoid; `w` is not written
+ *   TFGNN_POOL_NONE     w = 1;   TFGNN_POOL_AVERAGE  w = 1 / max(number of nodes of g, 1)
+ * backward:
+ *   dT[v, f] = w[v, h(f)] * dOut[g, f] where lo <= T[v, f] <= hi, else 0                             (tfgnn_clip_backward's mask)
+ *   dw[v, h] = sum over the features f of head h of clip(T[v, f]) * dOut[g, f]                       (never written to memory)
+ *   SOFTMAX  dS[v, h] = w * (dw - sum over the graph of w * dw);   SIGMOID  dS = dw (pass w = S);   dS NULL: not computed
+ * lo / hi: -INFINITY / +INFINITY for an absent bound.  T, S, w, dT, dS have leading dimensions (floats); out and dOut are
+ * contiguous [G, GD]; ptr [G + 1] comes from tfgnn_segment_offsets*.
+ *
+ * The nodes are cut into tiles of TFGNN_POOL_CHUNK_NODES; a graph with more nodes than that is reduced chunk by chunk by
+ * several workgroups, whose partial results (in `workspace`) a second launch combines in ascending chunk order - no float
+ * atomics, results independent of the grid and the run.  At most two launches per call; the second one only when
+ * V > TFGNN_POOL_CHUNK_NODES (otherwise no graph can have been cut; workgroups whose tile holds no chunk leave at once), and
+ * in the backward call only for SOFTMAX with dS.  No allocation, no synchronisation: capturable as they are.
+ * Rejected on the host before any HIP call: a struct of another size, an unknown kind, negative sizes, heads that do not
+ * divide GD, lo > hi, a workspace smaller than tfgnn_pool_workspace_bytes (which needs no device; 0 when
+ * V <= TFGNN_POOL_CHUNK_NODES).  V == 0, G == 0 or GD == 0: nothing is launched (and nothing written), TFGNN_OK.
+ * GD > 1024: TFGNN_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------ */
+#define TFGNN_POOL_CHUNK_NODES 128
+typedef enum { TFGNN_POOL_SOFTMAX = 0, TFGNN_POOL_SIGMOID = 1, TFGNN_POOL_NONE = 2, TFGNN_POOL_AVERAGE = 3 } tfgnn_pool_kind;
+
+typedef struct tfgnn_pool_forward_args {
+  size_t struct_size;
+  int kind; /* tfgnn_pool_kind */
+  int64_t V, G;
+  int GD, heads;
+  const int32_t* ptr; /* [G + 1] */
+  const float* T;     /* [V, GD], row pitch ldT: the transformation MLP's output after its activation, not clipped */
+  int64_t ldT;
+  const float* S;     /* [V, heads], row pitch ldS: scores (SOFTMAX) / sigmoid weights (SIGMOID); NULL for NONE, AVERAGE */
+  int64_t ldS;
+  float lo, hi;
+  float* out;         /* [G, GD] */
+  float* w;           /* [V, heads], row pitch ldw: written for SOFTMAX, otherwise unused (may be NULL) */
+  int64_t ldw;
+  void* workspace;    /* tfgnn_pool_workspace_bytes(V, G, GD, heads, kind) bytes, 16-byte aligned */
+  size_t workspace_bytes;
+} tfgnn_pool_forward_args;
+
+typedef struct tfgnn_pool_backward_args {
+  size_t struct_size;
+  int kind;
+  int64_t V, G;
+  int GD, heads;
+  const int32_t* ptr;
+  const int32_t* ids; /* [V] node -> graph; the kernels find a node's graph through ptr, so this may be NULL */
+  const float* dOut;  /* [G, GD] */
+  const float* T;
+  int64_t ldT;
+  const float* w;     /* SOFTMAX: what the forward call wrote; SIGMOID: S; NULL for NONE, AVERAGE */
+  int64_t ldw;
+  float lo, hi;
+  float* dT;          /* [V, GD], row pitch lddT */
+  int64_t lddT;
+  float* dS;          /* [V, heads], row pitch lddS; NULL = not wanted (must be NULL for NONE, AVERAGE) */
+  int64_t lddS;
+  void* workspace;    /* the same query as the forward call */
+  size_t workspace_bytes;
+} tfgnn_pool_backward_args;
+
+size_t tfgnn_pool_workspace_bytes(int64_t V, int64_t G, int GD, int heads, int kind);
+/* = tfgnn_segment_softmax + tfgnn_clip + tfgnn_segment_weighted_sum, on kernels of its own */
+int tfgnn_pool_forward(const tfgnn_pool_forward_args* args, void* stream);
+/* = tfgnn_segment_weighted_sum_backward + tfgnn_clip_backward + tfgnn_segment_softmax_backward, on kernels of its own */
+int tfgnn_pool_backward(const tfgnn_pool_backward_args* args, void* stream);
+/* host-side counts of the kernel launches the two calls have enqueued in this process: out[0] forward ("pool_fwd"),
+ * out[1] backward ("pool_bwd"), the combining launches included; further slots are zero */
+int tfgnn_pool_launch_counts(int64_t* out_counts, int n);
+
+/* ------------------------------------------------------------------------------------------
  * Optimizer step (csrc/optim.hip): GraphTaskModel._apply_gradients (models/graph_task_model.py:279-324) with the optimizers
  * of _make_optimizer (:224-277) - [ext] TF 2.x optimizer_v2 arithmetic, fp32:
  *   SGD      momentum > 0: accum = accum * mu - lr * g;  w += accum          momentum 0: w -= lr * g

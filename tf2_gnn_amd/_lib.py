@@ -318,6 +318,16 @@ _SIGNATURES += [
     ("tfgnn_mp_backward", c_int, [c_void_p, c_void_p]),
 ]
 
+# graph readout (include/tfgnn.h "Graph readout", csrc/pool_fused.hip)
+_SIGNATURES += [
+    ("tfgnn_pool_workspace_bytes", c_size_t, [c_int64, c_int64, c_int, c_int, c_int]),
+    ("tfgnn_pool_forward", c_int, [c_void_p, c_void_p]),
+    ("tfgnn_pool_backward", c_int, [c_void_p, c_void_p]),
+    ("tfgnn_pool_launch_counts", c_int, [POINTER(c_int64), c_int]),
+]
+POOL_SOFTMAX, POOL_SIGMOID, POOL_NONE, POOL_AVERAGE = range(4)  # tfgnn_pool_kind
+POOL_CHUNK_NODES = 128  # TFGNN_POOL_CHUNK_NODES
+
 # optimizer step (include/tfgnn.h "Optimizer step", csrc/optim.hip): descriptors and config travel by pointer
 _SIGNATURES += [
     ("tfgnn_optimizer_workspace_bytes", c_size_t, [c_void_p, c_int, c_int]),
@@ -363,6 +373,27 @@ class MpBackwardArgs(ctypes.Structure):
         ("row_map", c_void_p), ("dw", c_void_p), ("x_sp", c_void_p), ("ld_x_sp_bytes", c_int64), ("x_inv_scale", c_void_p),
         ("tn_workspace", c_void_p), ("tn_workspace_bytes", ctypes.c_size_t), ("workspace", c_void_p),
         ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
+class PoolForwardArgs(ctypes.Structure):
+    """tfgnn_pool_forward_args (include/tfgnn.h), field for field"""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t), ("kind", c_int), ("V", c_int64), ("G", c_int64), ("GD", c_int), ("heads", c_int),
+        ("ptr", c_void_p), ("T", c_void_p), ("ldT", c_int64), ("S", c_void_p), ("ldS", c_int64), ("lo", c_float), ("hi", c_float),
+        ("out", c_void_p), ("w", c_void_p), ("ldw", c_int64), ("workspace", c_void_p), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
+class PoolBackwardArgs(ctypes.Structure):
+    """tfgnn_pool_backward_args (include/tfgnn.h), field for field"""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t), ("kind", c_int), ("V", c_int64), ("G", c_int64), ("GD", c_int), ("heads", c_int),
+        ("ptr", c_void_p), ("ids", c_void_p), ("dOut", c_void_p), ("T", c_void_p), ("ldT", c_int64), ("w", c_void_p),
+        ("ldw", c_int64), ("lo", c_float), ("hi", c_float), ("dT", c_void_p), ("lddT", c_int64), ("dS", c_void_p),
+        ("lddS", c_int64), ("workspace", c_void_p), ("workspace_bytes", ctypes.c_size_t),
     ]
 
 

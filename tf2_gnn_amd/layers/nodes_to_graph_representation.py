@@ -269,68 +269,32 @@ class WeightedSumGraphRepresentation(NodesToGraphRepresentation):
         X = inputs.node_embeddings
         V = X.shape[0]
         G = int(inputs.num_graphs)
-        GD, heads = self._graph_representation_size, self._num_heads
-        lib = _lib.load()
+        heads = self._num_heads
         ids = inputs.node_to_graph_map.to(torch.int32).contiguous()
         ptr = segment_offsets(ids, G)
         masks = self.dropout_masks or {}
-        w = None
+        S = None
         if self._weighting_fun == "sigmoid":
-            w = self._scoring_mlp(X, final_act="sigmoid", training=training, dropout_masks=masks.get("scoring"))  # [V, heads]
+            S = self._scoring_mlp(X, final_act="sigmoid", training=training, dropout_masks=masks.get("scoring"))  # [V, heads]
         elif self._weighting_fun == "softmax":
-            scores = self._scoring_mlp(X, training=training, dropout_masks=masks.get("scoring"))
-            w = torch.empty_like(scores)
-            _lib.check(
-                lib.tfgnn_segment_softmax(ops._ptr(scores), heads, heads, ops._ptr(ptr), G, ops._ptr(w), heads, ops._stream())
-            )
+            S = self._scoring_mlp(X, training=training, dropout_masks=masks.get("scoring"))
         # nodes_to_graph_representation.py:191-193: the activation is applied to the MLP *output* too
-        R = self._transformation_mlp(X, final_act=self._transformation_mlp_activation_fun, training=training,
+        T = self._transformation_mlp(X, final_act=self._transformation_mlp_activation_fun, training=training,
                                      dropout_masks=masks.get("transformation"))  # [V, GD]
-        lo, hi = self._transformation_mlp_result_lower_bound, self._transformation_mlp_result_upper_bound
-        R_unclipped = None
-        if lo is not None or hi is not None:  # :194-197
-            R_unclipped = R
-            R = ops.clip(R, lo, hi)
-        out = torch.empty((G, GD), dtype=torch.float32, device=X.device)
-        _lib.check(
-            lib.tfgnn_segment_weighted_sum(
-                ops._ptr(R), ops._ptr(w), ops._ptr(ptr), G, GD, heads, int(self._weighting_fun == "average"),
-                ops._ptr(out), ops._stream(),
-            )
-        )
-        self._ctx = {"ids": ids, "ptr": ptr, "w": w, "R": R, "V": V, "G": G, "R_unclipped": R_unclipped}
+        # softmax (:178-186), clip (:194-197) and the weighted sum (:204-227) in one call
+        out, w = ops.pool_forward(self._weighting_fun, ptr, T, S, heads, self._transformation_mlp_result_lower_bound,
+                                  self._transformation_mlp_result_upper_bound)
+        self._ctx = {"ids": ids, "ptr": ptr, "w": w if self._weighting_fun == "softmax" else S, "T": T, "V": V, "G": G}
         return out
 
     def backward(self, grad_output: torch.Tensor) -> torch.Tensor:
         """d(loss)/d(graph representations) [G, GD] -> d(loss)/d(node_embeddings) [V, VD]."""
         c = self._ctx
-        lib = _lib.load()
-        GD, heads = self._graph_representation_size, self._num_heads
-        V, G = c["V"], c["G"]
-        g = grad_output.contiguous()
-        dR = torch.empty((V, GD), dtype=torch.float32, device=g.device)
-        w = c["w"]
-        dW = torch.empty((V, heads), dtype=torch.float32, device=g.device) if w is not None else None
-        _lib.check(
-            lib.tfgnn_segment_weighted_sum_backward(
-                ops._ptr(g), ops._ptr(c["R"]) if w is not None else None, ops._ptr(w), ops._ptr(c["ids"]),
-                ops._ptr(c["ptr"]), V, GD, heads, int(self._weighting_fun == "average"), ops._ptr(dR), ops._ptr(dW),
-                ops._stream(),
-            )
-        )
-        if c["R_unclipped"] is not None:
-            dR = ops.clip_backward(dR, c["R_unclipped"], self._transformation_mlp_result_lower_bound,
-                                   self._transformation_mlp_result_upper_bound)
-        dX = self._transformation_mlp.backward(dR)
-        if self._weighting_fun == "sigmoid":
-            dXs = self._scoring_mlp.backward(dW)  # sigmoid handled as the MLP's final activation
-            dX = ops.add_scale(dX, dXs, 1.0)
-        elif self._weighting_fun == "softmax":
-            ds = torch.empty_like(dW)
-            _lib.check(
-                lib.tfgnn_segment_softmax_backward(ops._ptr(w), ops._ptr(dW), heads, ops._ptr(c["ptr"]), G, ops._ptr(ds), ops._stream())
-            )
-            dXs = self._scoring_mlp.backward(ds)
+        dT, dS = ops.pool_backward(self._weighting_fun, c["ptr"], c["ids"], grad_output, c["T"], c["w"], self._num_heads,
+                                   self._transformation_mlp_result_lower_bound, self._transformation_mlp_result_upper_bound)
+        dX = self._transformation_mlp.backward(dT)
+        if dS is not None:  # softmax: d(scores); sigmoid: d(weights), the sigmoid is the MLP's final activation
+            dXs = self._scoring_mlp.backward(dS)
             dX = ops.add_scale(dX, dXs, 1.0)
         return dX
 

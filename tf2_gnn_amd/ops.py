@@ -1129,6 +1129,86 @@ def clip_backward(dy: torch.Tensor, x: torch.Tensor, lower: Optional[float], upp
     return dx
 
 
+_POOL_KINDS = {"softmax": _lib.POOL_SOFTMAX, "sigmoid": _lib.POOL_SIGMOID, "none": _lib.POOL_NONE, "average": _lib.POOL_AVERAGE}
+
+
+def _pool_common(a, kind: str, ptr: torch.Tensor, T: torch.Tensor, heads: int, lower, upper):
+    """Fills the fields the two graph-readout argument structs share; -> (T as passed, workspace tensor or None)."""
+    lib = _lib.load()
+    _require_dev(T, torch.float32, "T")
+    T, ldT = _rowmajor(T, "T")
+    V, GD = (int(v) for v in T.shape)
+    G = int(ptr.numel()) - 1
+    a.struct_size = ctypes.sizeof(type(a))
+    a.kind = _POOL_KINDS[kind]
+    a.V, a.G, a.GD, a.heads = V, G, GD, int(heads)
+    a.ptr = ptr.data_ptr()
+    a.T, a.ldT = T.data_ptr(), ldT
+    a.lo = float("-inf") if lower is None else float(lower)
+    a.hi = float("inf") if upper is None else float(upper)
+    ws_bytes = lib.tfgnn_pool_workspace_bytes(V, G, GD, int(heads), a.kind)
+    ws = _workspace(T.device, ws_bytes) if ws_bytes else None
+    a.workspace, a.workspace_bytes = (ws.data_ptr(), ws.numel()) if ws is not None else (None, 0)
+    return T, ws
+
+
+def pool_forward(kind: str, ptr: torch.Tensor, T: torch.Tensor, S: Optional[torch.Tensor], heads: int, lower=None, upper=None):
+    """Graph readout forward in ONE library call (tfgnn_pool_forward): per-graph softmax of the scores S [V, heads] (kind
+    "softmax"; "sigmoid": S already holds the weights; "none" / "average": S is None), clip of T [V, GD] to [lower, upper]
+    (None = no bound) and the weighted sum per graph of ptr [G + 1].  -> (out [G, GD], w [V, heads] for "softmax" else None)."""
+    a = _lib.PoolForwardArgs()
+    T, ws = _pool_common(a, kind, ptr, T, heads, lower, upper)
+    out = (torch.empty if a.V else torch.zeros)((a.G, a.GD), dtype=torch.float32, device=T.device)
+    w = None
+    if S is not None:
+        _require_dev(S, torch.float32, "S")
+        S, ldS = _rowmajor(S, "S")
+        a.S, a.ldS = S.data_ptr(), ldS
+        if kind == "softmax":
+            w = torch.empty((a.V, int(heads)), dtype=torch.float32, device=T.device)
+            a.w, a.ldw = w.data_ptr(), int(heads)
+    a.out = out.data_ptr()
+    stream = _stream()
+    with op_scope("pool_forward", T, S, out):
+        _lib.check(_lib.load().tfgnn_pool_forward(ctypes.byref(a), stream))
+    return out, w
+
+
+def pool_backward(kind: str, ptr: torch.Tensor, ids: Optional[torch.Tensor], grad_out: torch.Tensor, T: torch.Tensor,
+                  w: Optional[torch.Tensor], heads: int, lower=None, upper=None, want_scores_grad: bool = True):
+    """Gradient of ``pool_forward`` in ONE library call (tfgnn_pool_backward).  ``w``: what the forward returned ("softmax") or
+    the sigmoid weights S ("sigmoid").  -> (dT [V, GD], dS [V, heads] or None): dS is the gradient with respect to the scores
+    ("softmax") or to the sigmoid weights ("sigmoid")."""
+    a = _lib.PoolBackwardArgs()
+    T, ws = _pool_common(a, kind, ptr, T, heads, lower, upper)
+    _require_dev(grad_out, torch.float32, "grad_out")
+    grad_out = grad_out.contiguous()
+    if tuple(grad_out.shape) != (a.G, a.GD):
+        raise ValueError(f"pool_backward: grad_out must be [{a.G}, {a.GD}], got {tuple(grad_out.shape)}")
+    dT = torch.empty((a.V, a.GD), dtype=torch.float32, device=T.device)
+    dS = None
+    if w is not None:
+        w, ldw = _rowmajor(w, "w")
+        a.w, a.ldw = w.data_ptr(), ldw
+        if want_scores_grad:
+            dS = torch.empty((a.V, int(heads)), dtype=torch.float32, device=T.device)
+            a.dS, a.lddS = dS.data_ptr(), int(heads)
+    a.ids = ids.data_ptr() if ids is not None else None
+    a.dOut = grad_out.data_ptr()
+    a.dT, a.lddT = dT.data_ptr(), a.GD
+    stream = _stream()
+    with op_scope("pool_backward", T, grad_out, dT):
+        _lib.check(_lib.load().tfgnn_pool_backward(ctypes.byref(a), stream))
+    return dT, dS
+
+
+def pool_launch_counts() -> dict:
+    """tfgnn_pool_launch_counts: kernel launches of the two graph-readout calls so far (host counters)."""
+    buf = (ctypes.c_int64 * 2)()
+    _lib.check(_lib.load().tfgnn_pool_launch_counts(buf, 2))
+    return {"pool_fwd": int(buf[0]), "pool_bwd": int(buf[1])}
+
+
 def mul(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     lib = _lib.load()
     a = a.contiguous()
