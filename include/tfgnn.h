@@ -549,7 +549,8 @@ int tfgnn_rgat_scores_backward_sp(const float* d_ds_src, const float* d_ds_tgt, 
  *   forward:  att[e, k] = softmax over the in-edges e of v of leaky_relu(s_src[(src_e, l_e), k] + s_tgt[(v, l_e), k])   [E, K], by-dst order;
  *             d_att_by_src (nullable): the same weights in the by-source edge order (for the backward pass's weighted gather)
  *   backward: dz[e, k]  = att (da - sum_{e' into v} att da) leaky_relu'(z)                  (the gradient w.r.t. the logits)
- * num_heads must be a power of two <= 64 (TFGNN_ERR_UNSUPPORTED otherwise: callers keep the piecewise kernels above).
+ * 1 <= num_heads <= 64 (TFGNN_ERR_UNSUPPORTED otherwise); a head count that is not a power of two runs on the lane layout
+ * of the next power of two with the surplus lanes idle (3 heads: a quarter of them).  The arrays keep their stride num_heads.
  * Short rows take one wave, single-item rows of the long-row plan one workgroup, hub rows one workgroup PER ITEM with an
  * in-order combine of the items' (max, sum) pairs in between (d_workspace: tfgnn_rgat_attention_workspace_bytes); online
  * softmax, fixed reduction trees and orders: deterministic. */

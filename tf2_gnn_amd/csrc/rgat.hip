@@ -211,8 +211,13 @@ rgat_scores_backward_kernel(const float* __restrict__ ds_src, const float* __res
 // ------------------------------------------------------------------------------------------------------
 // Row-centric softmax over all edges entering a node (round 3): the five launches above (edge scores, segment max, exp,
 // segment sum, divide) in one pass structure over the CSR rows of the node view, and its backward (t = sum a da, dz) likewise.
-// A row's (edge, head) pairs are laid out lane = slot * K + head (K a power of two): a step covers T / K consecutive edges,
-// i.e. T consecutive floats of the [E, K] arrays, U steps in flight per lane.  Work units follow the view's long-row plan:
+// A row's (edge, head) pairs are laid out lane = slot * KP + head, KP the next power of two at or above the head count K
+// (1 <= K <= 64): a step covers T / KP consecutive edges, U steps in flight per lane.  The arrays keep their stride K; lanes
+// with head >= K are padding - they form no address, load and store nothing, and stay in every shuffle and barrier of the
+// reductions with the identity (-FLT_MAX / 0).  For a power of two KP == K: T consecutive floats of the [E, K] arrays per
+// step and no padding; K = 3 idles a quarter of the lanes, K = 5 three eighths.  The kernels are compiled twice: PAD = false
+// (K a power of two) is the code without any of the padding tests - guarding the passes costs the backward kernels 8 VGPRs
+// and a wave of occupancy, 2.7 % of the 8-head rgat workload's step.  Work units follow the view's long-row plan:
 //   * rows of at most long_threshold edges (short-row list, longest first): one wave each, both passes;
 //   * rows that are ONE item of the plan (up to item_chunk edges): one 256-thread workgroup, both passes;
 //   * rows cut into several items (a 15 000-edge R-MAT hub: 30 items): every item is a workgroup - pass 1 leaves the item's
@@ -224,8 +229,8 @@ rgat_scores_backward_kernel(const float* __restrict__ ds_src, const float* __res
 // by-source edge order (att_s[dst2src[e]]) for the backward pass's weighted gather.
 // ------------------------------------------------------------------------------------------------------
 template <int T>
-__device__ __forceinline__ float row_reduce(float v, bool is_max, int K, float* red /* [T / 64][64] */) {
-  for (int d = K; d < 64; d <<= 1) {
+__device__ __forceinline__ float row_reduce(float v, bool is_max, int KP, float* red /* [T / 64][64] */) {
+  for (int d = KP; d < 64; d <<= 1) {
     const float o = __shfl_xor(v, d, 64);
     v = is_max ? fmaxf(v, o) : v + o;
   }
@@ -259,10 +264,12 @@ struct RowSoftmaxArgs {
   const float* da;  // backward
   float* dz;        // backward
   float* part;      // [num_partials][K][2] scratch of the multi-item rows
+  int KP;           // lanes per edge: the next power of two >= K (read by the PAD kernels only)
 };
 
 constexpr int RS_U = 8;  // edges per lane and step, loads issued together
 
+// (both passes are for lanes with k < K only: a padding lane's k would address the next edge's / node's heads)
 // pass 1 over edges [beg, end) of node v: forward -> scores parked in att, running (max, sum of exp) in (m, d);
 // backward -> t += att * da
 template <bool BWD>
@@ -374,58 +381,60 @@ __device__ __forceinline__ void row_pass2(const RowSoftmaxArgs& a, int64_t v, in
 }
 
 // a whole row with T threads: both passes
-template <int T, bool BWD>
+template <int T, bool BWD, bool PAD>
 __device__ __forceinline__ void row_softmax_whole(const RowSoftmaxArgs& a, int64_t v, int tid, float* red) {
-  const int K = a.K, epi = T / K, slot = tid / K, k = tid & (K - 1);
+  const int KP = PAD ? a.KP : a.K, epi = T / KP, slot = tid / KP, k = tid & (KP - 1);
+  const bool live = !PAD || k < a.K;  // padding lanes keep (m, d) = (-FLT_MAX, 0) and take part in the reductions only
   const int32_t beg = a.nodeptr[v], end = a.nodeptr[v + 1];
   float m = -3.402823466e+38f, d = 0.f;
-  row_pass1<BWD>(a, v, beg, end, slot, k, epi, m, d);
+  if (live) row_pass1<BWD>(a, v, beg, end, slot, k, epi, m, d);
   if (!BWD) {
-    const float M = row_reduce<T>(m, true, K, red);
-    const float D = row_reduce<T>(d * expf(m - M), false, K, red);  // lanes without an edge: d = 0
-    row_pass2<false>(a, v, beg, end, slot, k, epi, M, D);
+    const float M = row_reduce<T>(m, true, KP, red);
+    const float D = row_reduce<T>(d * expf(m - M), false, KP, red);  // lanes without an edge: d = 0
+    if (live) row_pass2<false>(a, v, beg, end, slot, k, epi, M, D);
   } else {
-    const float t = row_reduce<T>(d, false, K, red);
-    row_pass2<true>(a, v, beg, end, slot, k, epi, 0.f, t);
+    const float t = row_reduce<T>(d, false, KP, red);
+    if (live) row_pass2<true>(a, v, beg, end, slot, k, epi, 0.f, t);
   }
 }
 
-template <bool BWD>
+template <bool BWD, bool PAD>
 __global__ void __launch_bounds__(256) rgat_row_softmax_wave_kernel(RowSoftmaxArgs a) {
   const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (w >= a.num_rows) return;
-  row_softmax_whole<64, BWD>(a, a.rows[w], threadIdx.x & 63, nullptr);
+  row_softmax_whole<64, BWD, PAD>(a, a.rows[w], threadIdx.x & 63, nullptr);
 }
 
 // one workgroup per item of the long-row plan.  PHASE 1: whole-row items do both passes; items of multi-item rows pass 1 and
 // leave their pair in part[slot].  PHASE 2 (after the combine kernel): items of multi-item rows normalise.
-template <bool BWD, int PHASE>
+template <bool BWD, int PHASE, bool PAD>
 __global__ void __launch_bounds__(256) rgat_row_softmax_item_kernel(RowSoftmaxArgs a) {
   __shared__ float red[4 * 64];
   const int item = blockIdx.x;
   const int32_t sl = a.item_slot[item];
   const int64_t v = a.rows[item];
   if (sl < 0) {
-    if (PHASE == 1) row_softmax_whole<256, BWD>(a, v, threadIdx.x, red);
+    if (PHASE == 1) row_softmax_whole<256, BWD, PAD>(a, v, threadIdx.x, red);
     return;
   }
-  const int K = a.K, epi = 256 / K, slot = threadIdx.x / K, k = threadIdx.x & (K - 1);
+  const int K = a.K, KP = PAD ? a.KP : K, epi = 256 / KP, slot = threadIdx.x / KP, k = threadIdx.x & (KP - 1);
+  const bool live = !PAD || k < K;
   const int32_t rbeg = a.nodeptr[v], rend = a.nodeptr[v + 1];
   const int32_t beg = rbeg + a.item_chunk[item] * a.chunk_edges;
   const int32_t end = beg + a.chunk_edges < rend ? beg + a.chunk_edges : rend;
-  float* pr = a.part + ((int64_t)sl * K + k) * 2;
+  float* pr = a.part + ((int64_t)sl * K + (live ? k : 0)) * 2;  // read and written by the lanes of a head only
   if (PHASE == 1) {
     float m = -3.402823466e+38f, d = 0.f;
-    row_pass1<BWD>(a, v, beg, end, slot, k, epi, m, d);
+    if (live) row_pass1<BWD>(a, v, beg, end, slot, k, epi, m, d);
     if (!BWD) {
-      const float M = row_reduce<256>(m, true, K, red);
-      const float D = row_reduce<256>(d * expf(m - M), false, K, red);
-      if (slot == 0) { pr[0] = M; pr[1] = D; }
+      const float M = row_reduce<256>(m, true, KP, red);
+      const float D = row_reduce<256>(d * expf(m - M), false, KP, red);
+      if (slot == 0 && live) { pr[0] = M; pr[1] = D; }
     } else {
-      const float t = row_reduce<256>(d, false, K, red);
-      if (slot == 0) pr[0] = t;
+      const float t = row_reduce<256>(d, false, KP, red);
+      if (slot == 0 && live) pr[0] = t;
     }
-  } else {
+  } else if (live) {
     row_pass2<BWD>(a, v, beg, end, slot, k, epi, pr[0], BWD ? pr[0] : pr[1]);
   }
 }
@@ -745,7 +754,7 @@ static int rgat_row_softmax(const tfgnn_graph* g, const float* s_src, const floa
                             const float* da, float* dz, bool bwd, void* workspace, size_t workspace_bytes, hipStream_t s) {
   using namespace tfgnn;
   TFGNN_REQUIRE(g != nullptr, "graph is NULL");
-  if (K <= 0 || K > MAX_HEADS || (K & (K - 1))) return TFGNN_ERR_UNSUPPORTED;  // lane = slot * K + head needs a power of two
+  if (K <= 0 || K > MAX_HEADS) return TFGNN_ERR_UNSUPPORTED;  // MAX_HEADS lanes of a wave hold the heads of one edge
   if (g->E == 0) return TFGNN_OK;
   TFGNN_REQUIRE(s_src && s_tgt && att && (!bwd || (da && dz)), "NULL pointer");
   {
@@ -758,26 +767,28 @@ static int rgat_row_softmax(const tfgnn_graph* g, const float* s_src, const floa
   TFGNN_REQUIRE(pl.num_partials == 0 || (workspace && workspace_bytes >= need), "workspace too small: need %zu bytes", need);
   RowSoftmaxArgs a{};
   a.nodeptr = gv.rowptr; a.coll = gv.col; a.dst2src = g->dst2src; a.s_src = s_src; a.s_tgt = s_tgt; a.L = g->L > 0 ? g->L : 1; a.K = K;
+  const bool pad = (K & (K - 1)) != 0;
+  a.KP = 1;
+  while (a.KP < K) a.KP <<= 1;
   a.att = att; a.att_s = att_s; a.da = da; a.dz = dz; a.part = (float*)workspace; a.chunk_edges = pl.item_chunk_edges;
+  const auto wave = bwd ? (pad ? rgat_row_softmax_wave_kernel<true, true> : rgat_row_softmax_wave_kernel<true, false>)
+                        : (pad ? rgat_row_softmax_wave_kernel<false, true> : rgat_row_softmax_wave_kernel<false, false>);
+  const auto item1 = bwd ? (pad ? rgat_row_softmax_item_kernel<true, 1, true> : rgat_row_softmax_item_kernel<true, 1, false>)
+                         : (pad ? rgat_row_softmax_item_kernel<false, 1, true> : rgat_row_softmax_item_kernel<false, 1, false>);
+  const auto item2 = bwd ? (pad ? rgat_row_softmax_item_kernel<true, 2, true> : rgat_row_softmax_item_kernel<true, 2, false>)
+                         : (pad ? rgat_row_softmax_item_kernel<false, 2, true> : rgat_row_softmax_item_kernel<false, 2, false>);
   if (pl.num_short > 0) {
     a.rows = pl.short_rows; a.num_rows = pl.num_short;
-    const dim3 grid((unsigned)ceil_div(pl.num_short, 4));
-    if (bwd) hipLaunchKernelGGL(rgat_row_softmax_wave_kernel<true>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(rgat_row_softmax_wave_kernel<false>, grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(wave, dim3((unsigned)ceil_div(pl.num_short, 4)), dim3(256), 0, s, a);
   }
   if (pl.num_items > 0) {
     a.rows = pl.item_row; a.num_rows = pl.num_items; a.item_chunk = pl.item_chunk; a.item_slot = pl.item_slot;
     const dim3 grid((unsigned)pl.num_items);
-    if (bwd) hipLaunchKernelGGL((rgat_row_softmax_item_kernel<true, 1>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((rgat_row_softmax_item_kernel<false, 1>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(item1, grid, dim3(256), 0, s, a);
     if (pl.num_multi > 0) {
-      if (bwd) {
-        hipLaunchKernelGGL(rgat_row_softmax_combine_kernel<true>, dim3((unsigned)pl.num_multi), dim3(64), 0, s, pl.multi_base, pl.multi_n, K, a.part);
-        hipLaunchKernelGGL((rgat_row_softmax_item_kernel<true, 2>), grid, dim3(256), 0, s, a);
-      } else {
-        hipLaunchKernelGGL(rgat_row_softmax_combine_kernel<false>, dim3((unsigned)pl.num_multi), dim3(64), 0, s, pl.multi_base, pl.multi_n, K, a.part);
-        hipLaunchKernelGGL((rgat_row_softmax_item_kernel<false, 2>), grid, dim3(256), 0, s, a);
-      }
+      if (bwd) hipLaunchKernelGGL(rgat_row_softmax_combine_kernel<true>, dim3((unsigned)pl.num_multi), dim3(64), 0, s, pl.multi_base, pl.multi_n, K, a.part);
+      else hipLaunchKernelGGL(rgat_row_softmax_combine_kernel<false>, dim3((unsigned)pl.num_multi), dim3(64), 0, s, pl.multi_base, pl.multi_n, K, a.part);
+      hipLaunchKernelGGL(item2, grid, dim3(256), 0, s, a);
     }
   }
   TFGNN_LAUNCH_CHECK();

@@ -143,8 +143,10 @@ class RGAT(MessagePassing):
     def _edge_attention(self, g, s_src, s_tgt, K, training=True):
         """a[e,k]: per head, softmax over all edges entering the target (rgat.py:142-151) -> (a in by-target edge order,
         the same weights in by-source order or None).  One pass structure per CSR row (csrc/rgat.hip,
-        tfgnn_rgat_attention_forward) when the head count is a power of two; otherwise edge-parallel kernels + two generic
-        segment reductions over the node view (identity columns)."""
+        tfgnn_rgat_attention_forward) at every head count the layer can have (1 .. 64).  The branch behind ``rc == -4``
+        - edge-parallel kernels + two generic segment reductions over the node view (identity columns) - is the form the row
+        kernels replaced; no head count reaches it any more, its C entries stay as the op-level cross-check of the row kernels
+        (tests/test_gpu_rgat_heads.py)."""
         lib = _lib.load()
         E, V, L = g.num_edges, g.num_nodes, g.num_edge_types
         dev = s_src.device
@@ -247,7 +249,7 @@ class RGAT(MessagePassing):
         with ops.op_scope("rgat_attention_backward", s_src, s_tgt, att, da, dz):
             rc = lib.tfgnn_rgat_attention_backward(g._h, ops._ptr(s_src), ops._ptr(s_tgt), ops._ptr(att), ops._ptr(da), K, ops._ptr(dz),
                                                    ops._ptr(ws), ws.numel() if ws is not None else 0, ops._stream())
-        if rc == -4:  # head count not a power of two: the piecewise form
+        if rc == -4:  # the piecewise form (see _edge_attention: not reached at any head count the row kernels take, 1 .. 64)
             t = ops.graph_gather(g, ops.VIEW_BY_DST_NODE, ops.mul(att, da), col=ident_e[:E])  # [V, K] sum of a * da
             _lib.check(
                 lib.tfgnn_rgat_edge_softmax_backward(
