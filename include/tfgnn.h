@@ -1154,6 +1154,73 @@ int tfgnn_optimizer_iterations_set(int64_t* state, int64_t value, void* stream);
 /* host-side count of the kernel launches tfgnn_optimizer_apply has enqueued in this process (tests) */
 int64_t tfgnn_optimizer_launch_count(void);
 
+/* ------------------------------------------------------------------------------------------
+ * Batch assembly from a device-resident fold (csrc/batch.hip): GraphDataset.graph_batch_iterator_from_graph_iterator
+ * (data/graph_dataset.py:161-246) for a fold whose graphs were packed onto the device once.
+ *
+ * Fold store (N graphs, laid end to end in file order; plain device arrays the caller owns):
+ *   node_ptr [N + 1]              nodes before graph i;  features [store_nodes, F] fp32, store_nodes = node_ptr[N] < 2^31
+ *   per processed edge type t:    edge_ptr[t] [N + 1] edges of type t before graph i;  edges[t] [edge_ptr[t][N], 2] int32,
+ *                                 rows (src, dst) with graph-LOCAL node ids, in the order the reference gives them
+ *   per column c:                 columns[c] [N] fp32, one value per graph (target_value, ...)
+ * Epoch arrays (uploaded once per epoch; P = order_len positions):
+ *   order [P]                     graph id at position p (any ids in [0, N), repeats allowed)
+ *   pos_node_ptr [P + 1]          nodes of the graphs at positions 0 .. p-1;  pos_edge_ptr[t] [P + 1] likewise per type
+ * The call assembles the batch of positions [p0, p1), G = p1 - p0 graphs, with i = p - p0:
+ *   node_features[pos_node_ptr[p] - pos_node_ptr[p0] + j, :] = features[node_ptr[order[p]] + j, :]
+ *   node_to_graph_map[the same row]                           = i
+ *   adjacency_lists[t][pos_edge_ptr[t][p] - pos_edge_ptr[t][p0] + k] = edges[t][edge_ptr[t][order[p]] + k] + (that node offset)
+ *   column_out[c][i]                                          = columns[c][order[p]]
+ * The caller keeps the per-graph counts on the host, so it knows - and passes - the output sizes: num_nodes = V and
+ * num_edges[t] = E_t; it allocates the outputs.  The kernel never writes past them: a size that disagrees with the device's
+ * prefix sums, a graph id outside [0, N) or a local node id outside its graph sets *bad_flag (nullable, zeroed by the caller)
+ * and the element is skipped or, for a bad local id, written as computed - what tfgnn_batch_offset_edges does.
+ *
+ * ONE launch per call, its grid partitioned over the parts (feature tiles, which also write node_to_graph_map; every edge
+ * type; the columns); none when the batch is empty (G == 0).  No copy, no allocation, no synchronisation.  Feature rows
+ * are copied with consecutive lanes on consecutive floats (float4 when F % 4 == 0 and both buffers are 16-byte aligned);
+ * element offsets into `features` are 64-bit.  Zero-length segments (no edges of a type, no nodes) cost nothing.
+ * The pointer tables (edge_ptr, edges, pos_edge_ptr, adjacency_lists, num_edges, columns, column_out) are HOST arrays of
+ * num_edge_types / num_columns entries, read during the call.
+ * Rejected on the host before any HIP call: NULL args, another struct_size, negative sizes, p0 > p1 or p1 > order_len,
+ * feature_dim < 1 or >= 2^31, store_nodes or num_nodes >= 2^31, num_edges[t] >= 2^31, NULL pointers where the size is not
+ * zero, edge buffers that are not 8-byte aligned.  More than TFGNN_BATCH_MAX_EDGE_TYPES types or TFGNN_BATCH_MAX_COLUMNS
+ * columns: TFGNN_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------ */
+#define TFGNN_BATCH_MAX_EDGE_TYPES 48
+#define TFGNN_BATCH_MAX_COLUMNS 8
+typedef struct tfgnn_batch_assemble_args {
+  size_t struct_size;
+  int num_edge_types;
+  int num_columns;
+  int64_t num_graphs;  /* N */
+  int64_t store_nodes; /* node_ptr[N] */
+  int64_t feature_dim; /* F */
+  /* fold store */
+  const int32_t* node_ptr;
+  const float* features;
+  const int32_t* const* edge_ptr;
+  const int32_t* const* edges;
+  const float* const* columns;
+  /* epoch */
+  int64_t order_len; /* P */
+  const int32_t* order;
+  const int32_t* pos_node_ptr;
+  const int32_t* const* pos_edge_ptr;
+  /* batch */
+  int64_t p0, p1;
+  int64_t num_nodes;        /* V */
+  const int64_t* num_edges; /* E_t */
+  float* node_features;     /* [V, F] contiguous */
+  int32_t* node_to_graph_map;
+  int32_t* const* adjacency_lists; /* [E_t, 2] each */
+  float* const* column_out;        /* [G] each */
+  int* bad_flag;
+} tfgnn_batch_assemble_args;
+int tfgnn_batch_assemble(const tfgnn_batch_assemble_args* args, void* stream);
+/* host-side count of the kernel launches tfgnn_batch_assemble has enqueued in this process: out[0]; further slots are zero */
+int tfgnn_batch_assemble_launch_counts(int64_t* out_counts, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -337,6 +337,14 @@ _SIGNATURES += [
     ("tfgnn_optimizer_launch_count", c_int64, []),
 ]
 
+# batch assembly from a device-resident fold (include/tfgnn.h, csrc/batch.hip): the argument struct travels by pointer
+_SIGNATURES += [
+    ("tfgnn_batch_assemble", c_int, [c_void_p, c_void_p]),
+    ("tfgnn_batch_assemble_launch_counts", c_int, [POINTER(c_int64), c_int]),
+]
+BATCH_MAX_EDGE_TYPES = 48  # TFGNN_BATCH_MAX_EDGE_TYPES
+BATCH_MAX_COLUMNS = 8  # TFGNN_BATCH_MAX_COLUMNS
+
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
 ABI_VERSION = 5  # include/tfgnn.h TFGNN_ABI_VERSION
 
@@ -394,6 +402,20 @@ class PoolBackwardArgs(ctypes.Structure):
         ("ptr", c_void_p), ("ids", c_void_p), ("dOut", c_void_p), ("T", c_void_p), ("ldT", c_int64), ("w", c_void_p),
         ("ldw", c_int64), ("lo", c_float), ("hi", c_float), ("dT", c_void_p), ("lddT", c_int64), ("dS", c_void_p),
         ("lddS", c_int64), ("workspace", c_void_p), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
+class BatchAssembleArgs(ctypes.Structure):
+    """tfgnn_batch_assemble_args (include/tfgnn.h), field for field.  The pointer tables are host arrays (c_void_p * n,
+    c_int64 * n) that the caller keeps alive for the duration of the call."""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t), ("num_edge_types", c_int), ("num_columns", c_int), ("num_graphs", c_int64),
+        ("store_nodes", c_int64), ("feature_dim", c_int64), ("node_ptr", c_void_p), ("features", c_void_p), ("edge_ptr", c_void_p),
+        ("edges", c_void_p), ("columns", c_void_p), ("order_len", c_int64), ("order", c_void_p), ("pos_node_ptr", c_void_p),
+        ("pos_edge_ptr", c_void_p), ("p0", c_int64), ("p1", c_int64), ("num_nodes", c_int64), ("num_edges", c_void_p),
+        ("node_features", c_void_p), ("node_to_graph_map", c_void_p), ("adjacency_lists", c_void_p), ("column_out", c_void_p),
+        ("bad_flag", c_void_p),
     ]
 
 
