@@ -357,6 +357,24 @@ def test_gemm_nt_split_result_equals_a_split_pass_over_the_fp32_result(dev, M, N
     assert np.array_equal(decode_sp16(op), decode_sp16(ref))
 
 
+def test_both_nt_front_ends_hand_the_kernel_the_same_arguments(dev):
+    """``sp_gemm_nt`` and ``sp_gemm_nt_split`` are front ends of one call of tfgnn_sp_gemm_nt_rows: with an activation AND a
+    multiplier in the epilogue, over one full 128-row tile plus a ragged one, the fp32 results are the same bits, and the
+    fp32 tensor of the split front end remembers its split form."""
+    from tf2_gnn_amd import ops
+
+    M, K, N = 130, 64, 128
+    g = torch.Generator().manual_seed(130)
+    a_op = ops.sp_split_rows(torch.randn((M, K), generator=g).to(dev))
+    b_op = ops.sp_split_rows((torch.randn((N, K), generator=g) * 0.05).to(dev))
+    mul = ((torch.rand((M, N), generator=g) > 0.2).float() * 1.25).to(dev)
+    plain = ops.sp_gemm_nt(a_op, b_op, act="relu", out_mul=mul)
+    out, op = ops.sp_gemm_nt_split(a_op, b_op, act="relu", out_mul=mul, want_fp32=True)
+    assert tuple(plain.shape) == (M, N) and bool((plain > 0).any())
+    assert torch.equal(out, plain)
+    assert ops.sp_rows_of(out) is op
+
+
 def test_gemm_nt_split_result_over_several_column_tiles_carries_one_scale_per_tile(dev):
     """Round 5: N = 512 = two column tiles of 256 - the split form of the result has scale blocks of 256 columns and equals a
     split pass over the fp32 result with that block size; it feeds the next product as an operand with per-block scales."""

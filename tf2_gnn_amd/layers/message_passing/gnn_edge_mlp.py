@@ -29,6 +29,7 @@ from .message_passing import (
     MessagePassing,
     MessagePassingInput,
     Variable,
+    _edge_identity,
     default_device,
     get_graph,
     glorot_uniform,
@@ -80,6 +81,13 @@ def messages_per_edge(layer, g, D, H) -> bool:
     return layer._aggregation_name != "max" and not layer._pre_activation() and per_edge_products_supported(g, D, H)
 
 
+def _type_slices(off):
+    """(l, rows of edge type l) for every type that has edges, in type-contiguous edge order; ``off``: host offsets [L + 1]"""
+    for l in range(len(off) - 1):
+        if off[l + 1] > off[l]:
+            yield l, slice(off[l], off[l + 1])
+
+
 def _relu_input_grad(d_out, W, layer_input, out):
     """out = (d_out @ W^T) * relu'(layer_input), the gradient w.r.t. the pre-activation of the layer below, with the
     factor applied in the product's epilogue when the active kernel has one (one pass over [rows, width] less)."""
@@ -120,6 +128,10 @@ class StackedEdgeMLPs:
         for j, g in enumerate(self.grads):
             for l in range(self.L):
                 self.vars[l][j].grad = None if g is None else g[l]
+
+    def set_grads(self, grads):
+        self.grads = grads
+        self.publish_grads()
 
 
 @register_message_passing_implementation
@@ -290,9 +302,7 @@ class GNN_Edge_MLP(MessagePassing):
         path = self._path()
         if path == "A":
             return self._forward_A(X, g, fuse_act, want_split, drop)
-        if path == "B":
-            return (*self._forward_B(X, g, fuse_act), False)
-        return (*self._forward_C(X, g, fuse_act), False)
+        return (self._forward_B if path == "B" else self._forward_C)(X, g, fuse_act)
 
     # ---- general aggregation (max / activation before aggregation) ----------------------------------
     def _agg_general(self) -> bool:
@@ -303,7 +313,7 @@ class GNN_Edge_MLP(MessagePassing):
         the backward pass of a max aggregation needs (the raw maxima)."""
         is_max = self._aggregation_name == "max"
         pre = self._activation_name if self._pre_activation() else None
-        gelu_split = fuse_act == "gelu"
+        gelu_split = fuse_act == "gelu"  # (applied by ``_split_gelu``)
         separate_post = is_max and fuse_act is not None and not gelu_split
         out = ops.graph_gather(
             g, ops.VIEW_BY_DST_NODE, msgs, col=col, edge_weight=ew_d, row_scale=node_scale,
@@ -312,12 +322,18 @@ class GNN_Edge_MLP(MessagePassing):
         )
         if is_max:
             ctx["agg_max"] = out
-        if gelu_split:
-            ctx["pre"] = out
-            return ops.activation_forward("gelu", out)
         if separate_post:
             return ops.activation_forward(fuse_act, out)
-        return out
+        return self._split_gelu(out, fuse_act, ctx)
+
+    @staticmethod
+    def _split_gelu(pre, fuse_act, ctx):
+        """gelu is never fused into the kernel that wrote ``pre`` (its derivative needs the pre-activation): keep ``pre`` for the
+        backward pass and apply it here; every other activation has been applied already"""
+        if fuse_act != "gelu":
+            return pre
+        ctx["pre"] = pre
+        return ops.activation_forward("gelu", pre)
 
     def _message_grads(self, g, d_agg, ctx, msgs, msg_row, target, ew, node_scale, sel_col):
         """d(loss)/d(message of every edge) [E, H], in the edge order of msg_row / target / ew
@@ -332,14 +348,6 @@ class GNN_Edge_MLP(MessagePassing):
                                                reduce=ops.REDUCE_MAX, agg_max=ctx["agg_max"], num_selected=nsel)
         return ops.edge_aggregate_backward(msgs, target, d_agg, msg_row=msg_row, edge_weight=ew, node_scale=node_scale,
                                            pre_act=pre, reduce=ops.REDUCE_SUM)
-
-    @staticmethod
-    def _ident_e(g):
-        ident = g._cache.get("ident_e")
-        if ident is None or ident.numel() < g.num_edges + 1:
-            ident = torch.arange(g.num_edges + 1, dtype=torch.int32, device=g.device)
-            g._cache["ident_e"] = ident
-        return ident
 
     @staticmethod
     def _ident_nz(g, nz):
@@ -390,10 +398,7 @@ class GNN_Edge_MLP(MessagePassing):
             g.array(ops.G_NZ_NODEPTR_BY_DST), g.array(ops.G_NZ_COL_BY_DST), Yc, post_act=None if gelu_split else fuse_act
         )
         ctx = {"path": "Ac", "fused_act": fuse_act}
-        if gelu_split:
-            ctx["pre"] = pre
-            return ops.activation_forward("gelu", pre), ctx
-        return pre, ctx
+        return self._split_gelu(pre, fuse_act, ctx), ctx, False
 
     def _backward_A_compact(self, d_agg, ctx):
         g, X = ctx["graph"], ctx["X"]
@@ -409,8 +414,7 @@ class GNN_Edge_MLP(MessagePassing):
         Zc = ops.gemm_grouped_rows(Gc, off_d, off_h, W, trans_b=True)  # [nz, D] = G_c,l @ W_l^T
         dX = ops.gather_reduce(g.array(ops.G_NZ_NODEPTR_BY_SRC), g.array(ops.G_NZ_COL_BY_SRC), Zc)
         Xc = ops.gather_reduce(self._ident_nz(g, nz), g.array(ops.G_NZ_NODE_BY_SRC), X)  # source states of the compact rows
-        mlps.grads = [ops.gemm_grouped_k(Xc, Gc, off_d, off_h, L)]  # dW_l = X_c,l^T @ G_c,l
-        mlps.publish_grads()
+        mlps.set_grads([ops.gemm_grouped_k(Xc, Gc, off_d, off_h, L)])  # dW_l = X_c,l^T @ G_c,l
         return dX
 
     def _f16x2_eligible(self, V, D, L, H) -> bool:
@@ -420,7 +424,7 @@ class GNN_Edge_MLP(MessagePassing):
 
     def _forward_A(self, X, g, fuse_act, want_split=False, drop=None):
         if self._use_compact_buckets(g):
-            return (*self._forward_A_compact(X, g, fuse_act), False)
+            return self._forward_A_compact(X, g, fuse_act)
         V, D = X.shape
         L, H = g.num_edge_types, self._hidden_dim
         T = self._use_target_state_as_input
@@ -435,9 +439,8 @@ class GNN_Edge_MLP(MessagePassing):
             src_l, _, _, _, off, _ = self._original_order(g, ew_d)
             src_node = self._orig_src_node(g, src_l)
             msgs = torch.empty((g.num_edges, H), dtype=torch.float32, device=X.device)
-            for l in range(L):
-                if off[l + 1] > off[l]:
-                    ops.gemm_gathered(X, src_node[off[l] : off[l + 1]], W[l], out=msgs[off[l] : off[l + 1]])
+            for l, sl in _type_slices(off):
+                ops.gemm_gathered(X, src_node[sl], W[l], out=msgs[sl])
             ctx = {"path": "A", "A": None, "fused_act": fuse_act, "f16x2": self._f16x2_eligible(V, D, L, H)}
             return self._gather_messages(g, msgs, g.array(ops.G_EID_BY_DST), ew_d, node_scale, fuse_act, ctx), ctx, False
         if self._f16x2_eligible(V, D, L, H):
@@ -469,19 +472,15 @@ class GNN_Edge_MLP(MessagePassing):
             else:
                 A_sp = ops.graph_gather_sp(g, view, X, row_scale=row_scale, rows_per_operand_row=L, defer_combine=True)
                 Wt_sp = ops.sp_weight_operand(W, "cols", lambda: ops.sp_split_cols(W.view(L * Din, H), defer=True))
-                if fuse_drop:
-                    pre, _ = ops.sp_gemm_nt_split(A_sp, Wt_sp, act=fuse_act, dropout=drop, tile_kmask=kmask, row_map=rmap)
-                elif split_out:
-                    pre, _ = ops.sp_gemm_nt_split(A_sp, Wt_sp, act=fuse_act, tile_kmask=kmask, row_map=rmap)
+                if split_out:  # (never with a split gelu)
+                    pre, _ = ops.sp_gemm_nt_split(A_sp, Wt_sp, act=fuse_act, dropout=drop if fuse_drop else None, tile_kmask=kmask,
+                                                  row_map=rmap)
                 else:
                     pre = ops.sp_gemm_nt(A_sp, Wt_sp, act=None if gelu_split else fuse_act, tile_kmask=kmask, row_map=rmap)
             if fuse_drop:
                 out_scale = 1.0 - float(drop[0])
             ctx = {"path": "A", "A": None, "fused_act": fuse_act, "f16x2": True, "out_scale": out_scale}
-            if gelu_split:
-                ctx["pre"] = pre
-                return ops.activation_forward("gelu", pre), ctx, False
-            return pre, ctx, fuse_drop
+            return self._split_gelu(pre, fuse_act, ctx), ctx, fuse_drop  # (fuse_drop: never with a split gelu)
         A = torch.empty((V, L * Din), dtype=torch.float32, device=X.device)
         Arows = A.view(V * L, Din)
         ops.graph_gather(g, ops.VIEW_BY_DST_TYPED, X, row_scale=row_scale, out=Arows[:, :D])
@@ -491,8 +490,7 @@ class GNN_Edge_MLP(MessagePassing):
 
             k, ident_ptr, node_of_row = target_multiplier(g, row_scale)
             ops.gather_reduce(ident_ptr, node_of_row, X, edge_weight=k, out=Arows[:, D:])
-        gelu_split = fuse_act == "gelu"
-        act = None if gelu_split else fuse_act
+        act = None if fuse_act == "gelu" else fuse_act
         if ops.get_gemm_mode() != ops.GEMM_FP32:
             # the split-operand kernel stages K-contiguous operands fastest: hand it W^T ([H, L*Din], 1.6 MB copy)
             Wt = ops.sp_weight_operand(W, "transposed", lambda: ops.transpose_batched(W.view(L * Din, H)))  # once per weight value
@@ -500,10 +498,18 @@ class GNN_Edge_MLP(MessagePassing):
         else:
             pre = ops.gemm(A, W.view(L * Din, H), act=act)
         ctx = {"path": "A", "A": A, "fused_act": fuse_act}
-        if gelu_split:
-            ctx["pre"] = pre
-            return ops.activation_forward("gelu", pre), ctx, False
-        return pre, ctx, False
+        return self._split_gelu(pre, fuse_act, ctx), ctx, False
+
+    @staticmethod
+    def _skip_args(g, L, width, by_src):
+        """the arguments that let a split-operand NT product over [V, L * width] bucket rows skip the all-zero type blocks of a
+        row tile: it reads its rows in the order of the nodes' emptiness patterns (a_rows) and writes node order again (row_map;
+        mask, saved activation and dropout index follow it).  {} where nothing is skipped (``_skip_empty_blocks``)."""
+        if not _skip_empty_blocks(L, width):
+            return {}
+        node_at = g.array(ops.G_PATTERN_NODE_BY_SRC if by_src else ops.G_PATTERN_NODE_BY_DST)
+        kmask = g.array(ops.G_PATTERN_TILEMASK_BY_SRC if by_src else ops.G_PATTERN_TILEMASK_BY_DST)
+        return dict(tile_kmask=kmask, a_rows=node_at, row_map=node_at)
 
     def _backward_A_f16x2(self, d_agg, ctx, g, X, ew_s, epilogue=None, want_split=False, accumulate=None):
         """path A backward on split operands: the transposed gather writes G = [G_0 | ... | G_{L-1}] as an SP16 operand
@@ -516,12 +522,9 @@ class GNN_Edge_MLP(MessagePassing):
         W = mlps.kernels[0]  # [L, D, H]
         # Round 5: the by-source buckets are as sparse as the by-target ones (45 % empty on the R-MAT batch).  G stays in node
         # order - the weight-gradient product below pairs its rows with X's -, the input-gradient product reads its rows in the
-        # order of the by-source emptiness patterns (a_rows), skips the all-zero type blocks of a row tile and writes node order
-        # again (row_map; mask, saved activation and dropout index follow it).  Skipped terms are exact zeros: bit-equal.
-        skip = {}
-        if _skip_empty_blocks(L, H) and V > 0:
-            node_at = g.array(ops.G_PATTERN_NODE_BY_SRC)
-            skip = dict(tile_kmask=g.array(ops.G_PATTERN_TILEMASK_BY_SRC), a_rows=node_at, row_map=node_at)
+        # order of the by-source emptiness patterns and skips the all-zero type blocks of a row tile.  Skipped terms are exact
+        # zeros: bit-equal.
+        skip = self._skip_args(g, L, H, True) if V > 0 else {}
         # the request, decoded once for both routes below
         applied = accumulate is not None or epilogue is not None
         split = False
@@ -550,8 +553,7 @@ class GNN_Edge_MLP(MessagePassing):
             dW = torch.empty_like(W)
             # element ((l, h), d) -> dW[l, d, h]  (the split reduction stays right behind the product: NOTEBOOK.md 4.4)
             ops.sp_gemm_tn(G_sp, X_sp, out=dW, scatter=(H, D * H, 1, H))
-        mlps.grads = [dW]
-        mlps.publish_grads()
+        mlps.set_grads([dW])
         return dX, applied
 
     def _mlp_all_types(self, X, L, ctx, mlps=None, key="mlp_acts"):
@@ -627,6 +629,15 @@ class GNN_Edge_MLP(MessagePassing):
             g._cache["row_groups_by_src"] = rg
         return rg
 
+    @staticmethod
+    def _compact_src_col(g):
+        """column of every bucketed edge (by-dst order) in the table of compact (source, type) rows: cpos_src[source * L + type]"""
+        colc = g._cache.get("compact_src_col_by_dst")
+        if colc is None:
+            colc = g.array(ops.G_NZ_CPOS_BY_SRC)[g.array(ops.G_COLL_BY_DST).long()].contiguous()
+            g._cache["compact_src_col_by_dst"] = colc
+        return colc
+
     def _grouped_tn_route(self, g) -> bool:
         """kernel gradients of the compact-row MLPs on the grouped two-factor TN product?  Not after the stack's guard policy
         handed them back (``_grouped_tn_split_ok``), and not for more K ranges than one launch takes (~10^6 compact rows)."""
@@ -653,12 +664,9 @@ class GNN_Edge_MLP(MessagePassing):
                                                    act=None if last else "relu", want_split=not last, b_column_blocks=True)
             acts.append(cur32)
             cur_sp = nxt_sp
-        colc = g._cache.get("compact_src_col_by_dst")
-        if colc is None:
-            colc = g.array(ops.G_NZ_CPOS_BY_SRC)[g.array(ops.G_COLL_BY_DST).long()].contiguous()
-            g._cache["compact_src_col_by_dst"] = colc
+        colc = self._compact_src_col(g)
         ctx = {"path": "Bc", "fused_act": fuse_act, "Xc": None, "x_sp": x_sp, "mlp_acts": acts, "colc": colc, "grouped_split": True}
-        return self._gather_messages(g, cur32, colc, ew_d, node_scale, fuse_act, ctx), ctx
+        return self._gather_messages(g, cur32, colc, ew_d, node_scale, fuse_act, ctx), ctx, False
 
     def _backward_B_compact_split(self, dcur, ctx, g):
         """d(MLP outputs) [nz, H] -> d(compact inputs) [nz, D]; fills the kernel gradients (see _forward_B_compact_split).
@@ -714,8 +722,7 @@ class GNN_Edge_MLP(MessagePassing):
             dcur32, d_sp = ops.sp_gemm_nt_grouped(d_sp, wr, groups, act_grad=("relu", acts[j - 1]) if j > 0 else None,
                                                   want_fp32=(j == 0 or not tn_split or resplit_below), want_split=(j > 0))
             d32 = dcur32
-        mlps.grads = grads
-        mlps.publish_grads()
+        mlps.set_grads(grads)
         return dcur32
 
     def _forward_B_compact(self, X, g, fuse_act):
@@ -733,13 +740,9 @@ class GNN_Edge_MLP(MessagePassing):
             last = j == mlps.num_layers - 1
             cur = ops.gemm_grouped_rows(cur, off_dev, off_h, W, act=None if last else "relu")
             acts.append(cur)
-        # column of every bucketed edge (by-dst order) in the compact table: cpos_src[source * L + type]
-        colc = g._cache.get("compact_src_col_by_dst")
-        if colc is None:
-            colc = g.array(ops.G_NZ_CPOS_BY_SRC)[g.array(ops.G_COLL_BY_DST).long()].contiguous()
-            g._cache["compact_src_col_by_dst"] = colc
+        colc = self._compact_src_col(g)
         ctx = {"path": "Bc", "fused_act": fuse_act, "Xc": Xc, "mlp_acts": acts, "colc": colc}
-        return self._gather_messages(g, cur, colc, ew_d, node_scale, fuse_act, ctx), ctx
+        return self._gather_messages(g, cur, colc, ew_d, node_scale, fuse_act, ctx), ctx, False
 
     def _backward_B_compact(self, d_agg, ctx):
         g = ctx["graph"]
@@ -752,7 +755,7 @@ class GNN_Edge_MLP(MessagePassing):
         if self._agg_general():
             _, ew_d, _, node_scale = self._scales(g)
             dM = self._message_grads(g, d_agg, ctx, acts[-1], ctx["colc"], g.array(ops.G_TARGET_BY_DST), ew_d, node_scale,
-                                     self._ident_e(g)[: g.num_edges])
+                                     _edge_identity(g)[: g.num_edges])
             dcur = ops.graph_gather(g, ops.VIEW_BY_SRC_TYPED_COMPACT, dM, col=g.array(ops.G_SRC2DST_POS))
         elif ctx.get("grouped_split") and self._grouped_tn_route(g) and d_agg.shape[1] % 16 == 0:
             # every consumer of d(MLP outputs) takes the split form: the gather writes it (no fp32 [nz, H], no split pass)
@@ -769,8 +772,7 @@ class GNN_Edge_MLP(MessagePassing):
             # (hidden layers: relu' of the layer below rides in the product's epilogue)
             dcur = ops.gemm_grouped_rows(dcur, off_dev, off_h, mlps.kernels[j], trans_b=True,
                                          act_grad=("relu", inp) if j > 0 else None)
-        mlps.grads = grads
-        mlps.publish_grads()
+        mlps.set_grads(grads)
         # dX[u] = sum over the non-empty (u, l) pairs
         return ops.gather_reduce(g.array(ops.G_NZ_NODEPTR_BY_SRC), g.array(ops.G_NZ_COL_BY_SRC), dcur)
 
@@ -782,7 +784,7 @@ class GNN_Edge_MLP(MessagePassing):
         _, ew_d, _, node_scale = self._scales(g)
         ctx = {"path": "B", "fused_act": fuse_act}
         Y = self._mlp_all_types(X, L, ctx)
-        return self._gather_messages(g, Y.view(V * L, H), None, ew_d, node_scale, fuse_act, ctx), ctx
+        return self._gather_messages(g, Y.view(V * L, H), None, ew_d, node_scale, fuse_act, ctx), ctx, False
 
     def _original_order(self, g, ew_d):
         """index arrays in concatenated-adjacency-list order (type-contiguous), cached on the Graph."""
@@ -823,12 +825,10 @@ class GNN_Edge_MLP(MessagePassing):
             src_node = self._orig_src_node(g, src_l)
             W0 = mlps.kernels[0]  # [L, 2D, H0]
             Z = torch.empty((E, H0), dtype=torch.float32, device=X.device)
-            for l in range(L):
-                if off[l + 1] > off[l]:
-                    sl = slice(off[l], off[l + 1])
-                    ops.gemm_gathered(X, src_node[sl], W0[l, :D], out=Z[sl])
-                    ops.gemm_gathered(X, tgt_node[sl], W0[l, D:], out=Z[sl], act=first_act, accumulate="before")
-            return self._edge_hidden_layers_C(Z, off, L)
+            for l, sl in _type_slices(off):
+                ops.gemm_gathered(X, src_node[sl], W0[l, :D], out=Z[sl])
+                ops.gemm_gathered(X, tgt_node[sl], W0[l, D:], out=Z[sl], act=first_act, accumulate="before")
+            return self._edge_hidden_layers_C(Z, off)
         Wh = ops.permute_021(mlps.kernels[0])  # [2D, L, H0]
         P = ops.gemm(X, Wh[:D].view(D, L * H0))  # x_u W_s for every (node, type)
         Q = ops.gemm(X, Wh[D:].view(D, L * H0))  # x_v W_t
@@ -840,9 +840,9 @@ class GNN_Edge_MLP(MessagePassing):
                 ops._stream(),
             )
         )
-        return self._edge_hidden_layers_C(Z, off, L)
+        return self._edge_hidden_layers_C(Z, off)
 
-    def _edge_hidden_layers_C(self, Z, off, L):
+    def _edge_hidden_layers_C(self, Z, off):
         """layers 1 .. of the per-edge MLPs on the first layer's activations Z [E, H0] (edge-list order) -> (outputs, acts)."""
         mlps = self._edge_type_mlps
         E = Z.shape[0]
@@ -852,9 +852,8 @@ class GNN_Edge_MLP(MessagePassing):
             W = mlps.kernels[j]
             last = j == mlps.num_layers - 1
             nxt = torch.empty((E, W.shape[2]), dtype=torch.float32, device=Z.device)
-            for l in range(L):
-                if off[l + 1] > off[l]:
-                    ops.gemm(cur[off[l] : off[l + 1]], W[l], act=None if last else "relu", out=nxt[off[l] : off[l + 1]])
+            for l, sl in _type_slices(off):
+                ops.gemm(cur[sl], W[l], act=None if last else "relu", out=nxt[sl])
             acts.append(nxt)
             cur = nxt
         return cur, acts
@@ -864,12 +863,9 @@ class GNN_Edge_MLP(MessagePassing):
         out = torch.zeros((V, self._hidden_dim), dtype=torch.float32, device=X.device)
         if self._aggregation_name == "max":
             out.fill_(torch.finfo(torch.float32).min)
-        if fuse_act == "gelu":
-            ctx["pre"] = out
-            return ops.activation_forward("gelu", out)
-        if fuse_act is not None:
+        if fuse_act not in (None, "gelu"):
             out = ops.activation_forward(fuse_act, out)
-        return out
+        return self._split_gelu(out, fuse_act, ctx)
 
     def _forward_C(self, X, g, fuse_act):
         V = X.shape[0]
@@ -878,8 +874,8 @@ class GNN_Edge_MLP(MessagePassing):
         H0 = self._edge_type_mlps.kernels[0].shape[2]
         ctx = {"path": "C", "fused_act": fuse_act, "edge_acts": acts, "P_shape": (V, g.num_edge_types * H0)}
         if g.num_edges == 0:
-            return self._aggregate_nothing(V, X, fuse_act, ctx), ctx
-        return self._gather_messages(g, cur, g.array(ops.G_EID_BY_DST), ew_d, node_scale, fuse_act, ctx), ctx
+            return self._aggregate_nothing(V, X, fuse_act, ctx), ctx, False
+        return self._gather_messages(g, cur, g.array(ops.G_EID_BY_DST), ew_d, node_scale, fuse_act, ctx), ctx, False
 
     def _backward_C(self, d_agg, ctx, dcur=None, epilogue=None):
         """``dcur``: d(per-edge MLP outputs) [E, H] in edge-list order when the caller already has it (GNN_FiLM).
@@ -889,8 +885,7 @@ class GNN_Edge_MLP(MessagePassing):
         L, E = g.num_edge_types, g.num_edges
         mlps = self._edge_type_mlps
         if E == 0:
-            mlps.grads = [torch.zeros_like(W) for W in mlps.kernels]
-            mlps.publish_grads()
+            mlps.set_grads([torch.zeros_like(W) for W in mlps.kernels])
             return torch.zeros_like(X), False
         _, ew_d, _, node_scale = self._scales(g)
         general = self._agg_general()
@@ -904,7 +899,7 @@ class GNN_Edge_MLP(MessagePassing):
         else:
             # per-edge weight of the aggregation in by-dst order, including the mean / sqrt_n factor
             if node_scale is not None:
-                m_e = ops.gather_reduce(self._ident_e(g), g.array(ops.G_TARGET_BY_DST), node_scale.view(-1, 1)).view(-1)
+                m_e = ops.gather_reduce(_edge_identity(g), g.array(ops.G_TARGET_BY_DST), node_scale.view(-1, 1)).view(-1)
                 w_full = m_e if ew_d is None else ops.mul(m_e, ew_d)
             else:
                 w_full = ew_d
@@ -917,19 +912,16 @@ class GNN_Edge_MLP(MessagePassing):
             inp = acts[j - 1]
             gW = torch.zeros_like(W)
             dprev = torch.empty_like(inp)
-            for l in range(L):
-                if off[l + 1] > off[l]:
-                    sl = slice(off[l], off[l + 1])
-                    ops.gemm(inp[sl], dcur[sl], trans_a=True, out=gW[l])
-                    _relu_input_grad(dcur[sl], W[l], inp[sl], dprev[sl])  # hidden layers are relu (dpu_utils MLP)
+            for l, sl in _type_slices(off):
+                ops.gemm(inp[sl], dcur[sl], trans_a=True, out=gW[l])
+                _relu_input_grad(dcur[sl], W[l], inp[sl], dprev[sl])  # hidden layers are relu (dpu_utils MLP)
             grads[j] = gW
             dcur = dprev
         # first layer: z0[e] = relu(P[(src,l)] + Q[(tgt,l)]); dcur is d(P+Q) per edge
         H0 = mlps.kernels[0].shape[2]
         if self._first_layer_grads_split_ok(V, D, L, H0):
             grads[0], dX = self._backward_C_first_layer_split(dcur, g, X, L, H0, epilogue)
-            mlps.grads = grads
-            mlps.publish_grads()
+            mlps.set_grads(grads)
             return dX, epilogue is not None
         dP = ops.graph_gather(g, ops.VIEW_BY_SRC_TYPED, dcur, col=g.array(ops.G_EID_BY_SRC)).view(V, L * H0)
         dQ = ops.graph_gather(g, ops.VIEW_BY_DST_TYPED, dcur, col=g.array(ops.G_EID_BY_DST)).view(V, L * H0)
@@ -947,8 +939,7 @@ class GNN_Edge_MLP(MessagePassing):
             dX = ops.gemm(dP, Wh[:D].view(D, L * H0), trans_b=True)
             ops.gemm(dQ, Wh[D:].view(D, L * H0), trans_b=True, out=dX, accumulate=True)
         grads[0] = ops.permute_021(dWh)
-        mlps.grads = grads
-        mlps.publish_grads()
+        mlps.set_grads(grads)
         return dX, epilogue is not None
 
     def _first_layer_grads_split_ok(self, V, D, L, H0) -> bool:
@@ -974,16 +965,12 @@ class GNN_Edge_MLP(MessagePassing):
         kw = dict(out_mul=epilogue[0], act_grad=epilogue[1]) if epilogue is not None else {}
         self._grouped_tn_used = True  # (what the stack's guard policy demotes if the spread guard trips: GNN.backward)
         dX = None
-        halves = ((ops.VIEW_BY_SRC_TYPED, ops.G_EID_BY_SRC, ops.G_PATTERN_NODE_BY_SRC, ops.G_PATTERN_TILEMASK_BY_SRC, 0),
-                  (ops.VIEW_BY_DST_TYPED, ops.G_EID_BY_DST, ops.G_PATTERN_NODE_BY_DST, ops.G_PATTERN_TILEMASK_BY_DST, D))
-        for view, eid, pat_node, pat_mask, d0 in halves:
+        halves = ((ops.VIEW_BY_SRC_TYPED, ops.G_EID_BY_SRC, True, 0), (ops.VIEW_BY_DST_TYPED, ops.G_EID_BY_DST, False, D))
+        for view, eid, by_src, d0 in halves:
             G_sp = ops.graph_gather_sp(g, view, dcur, col=g.array(eid), rows_per_operand_row=L, defer_combine=True)
             Wh_sp = ops.sp_weight_operand(W0, f"rows_half{d0}", lambda d0=d0: ops.sp_split_rows(
                 W0[0, d0:d0 + D], segments=(H0, 2 * D * H0, L * H0), defer=True))  # row d = [W_0[d0 + d, :] | W_1[d0 + d, :] | ..]
-            skip = {}
-            if _skip_empty_blocks(L, H0):
-                node_at = g.array(pat_node)
-                skip = dict(tile_kmask=g.array(pat_mask), a_rows=node_at, row_map=node_at)
+            skip = self._skip_args(g, L, H0, by_src)
             if dX is None:
                 dX = ops.sp_gemm_nt(G_sp, Wh_sp, **kw, **skip)
             else:  # the factors distribute over the two terms: the second product adds into the first's result
@@ -1069,7 +1056,7 @@ class GNN_Edge_MLP(MessagePassing):
             # max / activation before aggregation: per-edge gradients first, then the sum over every (source, type) bucket
             Y = ctx["mlp_acts"][-1].view(V * L, H)
             dM = self._message_grads(g, d_agg, ctx, Y, g.array(ops.G_COLL_BY_DST), g.array(ops.G_TARGET_BY_DST), ew_d,
-                                     node_scale, self._ident_e(g)[: g.num_edges])
+                                     node_scale, _edge_identity(g)[: g.num_edges])
             G = ops.graph_gather(g, ops.VIEW_BY_SRC_TYPED, dM, col=g.array(ops.G_SRC2DST_POS)).view(V, L, H)
         elif ctx.get("f16x2") and ops.get_gemm_mode() == ops.GEMM_F16X2:  # (not after the spread guard demoted the mode)
             return self._backward_A_f16x2(d_agg, ctx, g, X, ew_s, epilogue, want_split, accumulate)
@@ -1090,8 +1077,7 @@ class GNN_Edge_MLP(MessagePassing):
                     dX = ops.gemm_grad(G2, Wh.view(D, L * H), trans_b=True, out=dX, out_mul=epilogue[0], act_grad=epilogue[1])
                 else:
                     ops.gemm(G2, Wh.view(D, L * H), trans_b=True, out=dX)
-                mlps.grads = [ops.transpose_batched(ops.gemm(G2, X, trans_a=True).view(L, H, D))]
-                mlps.publish_grads()
+                mlps.set_grads([ops.transpose_batched(ops.gemm(G2, X, trans_a=True).view(L, H, D))])
                 return dX, epilogue is not None
             dWh = torch.empty((Din, L, H), dtype=torch.float32, device=X.device)
             if L == 0:
@@ -1110,8 +1096,8 @@ class GNN_Edge_MLP(MessagePassing):
                 # dX_v += sum_l k_{l,v} * (d_agg[v] @ W_t[l]^T)
                 kd = ops.gather_reduce(ident_ptr, node_of_row, d_agg, edge_weight=k).view(V, L * H)
                 ops.gemm(kd, Wh[D:].view(D, L * H), trans_b=True, out=dX, accumulate=True)
-            mlps.grads = [ops.permute_021(dWh)]
+            mlps.set_grads([ops.permute_021(dWh)])
         else:
             self._mlp_all_types_backward(mlps, X, ctx["mlp_acts"], G, dX, accumulate=False)
-        mlps.publish_grads()
+            mlps.publish_grads()
         return dX, False

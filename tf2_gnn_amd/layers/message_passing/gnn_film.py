@@ -126,8 +126,7 @@ class GNN_FiLM(GNN_Edge_MLP):
             dfilm = torch.zeros((V, L, 2 * H), dtype=torch.float32, device=X.device)
             self._mlp_all_types_backward(self._film_mlps, X, ctx["film_acts"], dfilm, dX, accumulate=False)
             self._film_mlps.publish_grads()
-            mlps.grads = [torch.zeros_like(W) for W in mlps.kernels]
-            mlps.publish_grads()
+            mlps.set_grads([torch.zeros_like(W) for W in mlps.kernels])
             return dX
         d_agg = self._backward_finish(grad_output, ctx)
         _, ew_d, _, node_scale = self._scales(g)

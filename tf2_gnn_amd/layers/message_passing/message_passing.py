@@ -141,6 +141,16 @@ def get_graph(adjacency_lists, num_nodes: int, parts: int = ops.G_PARTS_DEFAULT)
     return g
 
 
+def _edge_identity(g: "ops.Graph") -> torch.Tensor:
+    """int32 [E + 1] = 0 .. E, cached on the Graph: the row pointer of a gather with one row per edge (its first E entries:
+    the identity column index)"""
+    ident = g._cache.get("ident_e")
+    if ident is None or ident.numel() < g.num_edges + 1:
+        ident = torch.arange(g.num_edges + 1, dtype=torch.int32, device=g.device)
+        g._cache["ident_e"] = ident
+    return ident
+
+
 def clear_graph_cache():
     _GRAPH_CACHE.clear()
 

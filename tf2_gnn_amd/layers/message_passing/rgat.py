@@ -7,6 +7,7 @@ from ... import _lib, ops
 from .message_passing import (
     MessagePassing,
     MessagePassingInput,
+    _edge_identity,
     apply_gradient_epilogue,
     default_device,
     get_graph,
@@ -132,23 +133,14 @@ class RGAT(MessagePassing):
         return (ops.get_gemm_mode() == ops.GEMM_F16X2 and V > 0 and L > 0 and D % 16 == 0 and 32 <= D <= 512 and ops.sp_tiles(D)
                 and ops.sp_tiles(L * H) and L * H <= 2048 and (H // self._num_heads) % 4 == 0)
 
-    @staticmethod
-    def _ident(g, n):
-        ident = g._cache.get("ident_e")
-        if ident is None or ident.numel() < n + 1:
-            ident = torch.arange(n + 1, dtype=torch.int32, device=g.device)
-            g._cache["ident_e"] = ident
-        return ident
-
     def _edge_attention(self, g, s_src, s_tgt, K, training=True):
         """a[e,k]: per head, softmax over all edges entering the target (rgat.py:142-151) -> (a in by-target edge order,
-        the same weights in by-source order or None).  One pass structure per CSR row (csrc/rgat.hip,
-        tfgnn_rgat_attention_forward) at every head count the layer can have (1 .. 64).  The branch behind ``rc == -4``
-        - edge-parallel kernels + two generic segment reductions over the node view (identity columns) - is the form the row
-        kernels replaced; no head count reaches it any more, its C entries stay as the op-level cross-check of the row kernels
+        the same weights in by-source order, or None when not training).  One pass structure per CSR row (csrc/rgat.hip,
+        tfgnn_rgat_attention_forward) at every head count the layer can have (1 .. 64: tfgnn_rgat_node_scores has refused any
+        other).  The edge-parallel form the row kernels replaced stays in the library as their op-level cross-check
         (tests/test_gpu_rgat_heads.py)."""
         lib = _lib.load()
-        E, V, L = g.num_edges, g.num_nodes, g.num_edge_types
+        E = g.num_edges
         dev = s_src.device
         att = torch.empty((E, K), dtype=torch.float32, device=dev)
         if E == 0:
@@ -160,22 +152,8 @@ class RGAT(MessagePassing):
         with ops.op_scope("rgat_attention_forward", s_src, s_tgt, att, att_by_src):
             rc = lib.tfgnn_rgat_attention_forward(g._h, ops._ptr(s_src), ops._ptr(s_tgt), K, ops._ptr(att), ops._ptr(att_by_src),
                                                   ops._ptr(ws), ws.numel() if ws is not None else 0, ops._stream())
-        if rc == 0:
-            return att, att_by_src
-        if rc != -4:
-            _lib.check(rc)
-        coll, tgt = g.array(ops.G_COLL_BY_DST), g.array(ops.G_TARGET_BY_DST)
-        ident = self._ident(g, E)[:E]
-        scores = torch.empty((E, K), dtype=torch.float32, device=dev)
-        _lib.check(lib.tfgnn_rgat_edge_scores(ops._ptr(coll), ops._ptr(tgt), ops._ptr(s_src), ops._ptr(s_tgt), E, L, K,
-                                              ops._ptr(scores), ops._stream()))
-        m = ops.graph_gather(g, ops.VIEW_BY_DST_NODE, scores, col=ident, reduce=ops.REDUCE_MAX)  # [V, K]
-        _lib.check(lib.tfgnn_rgat_edge_node_op(ops._ptr(scores), ops._ptr(tgt), ops._ptr(m), E, K, 0, ops._ptr(scores),
-                                               ops._stream()))  # in place: p = exp(score - m[tgt])
-        den = ops.graph_gather(g, ops.VIEW_BY_DST_NODE, scores, col=ident)  # [V, K]
-        _lib.check(lib.tfgnn_rgat_edge_node_op(ops._ptr(scores), ops._ptr(tgt), ops._ptr(den), E, K, 1, ops._ptr(att),
-                                               ops._stream()))
-        return att, None
+        _lib.check(rc)
+        return att, att_by_src
 
     def backward(self, grad_output: torch.Tensor) -> torch.Tensor:
         """d(loss)/d(out) -> d(loss)/d(node_embeddings); fills the kernel / attention gradients."""
@@ -222,9 +200,9 @@ class RGAT(MessagePassing):
                 v.grad = torch.zeros_like(v.value)
             return torch.zeros_like(X)  # (zero times the caller's factors)
         s2d = g.array(ops.G_SRC2DST_POS)
-        ident_e = self._ident(g, E)
+        ident_e = _edge_identity(g)
         # (1) dY[(u,l),k,:] = sum over out-edges e of (u,l): a_ek * d_agg[tgt_e, k, :]
-        att_s = ctx.get("att_by_src")  # written by the forward row kernels in training mode
+        att_s = ctx.get("att_by_src")  # written by the forward pass in training mode
         if att_s is None:
             att_s = ops.gather_reduce(ident_e[: E + 1], s2d, att)  # attention re-ordered to the by-src edge order
         # (2) gradient w.r.t. the attention values: da[e,k] = <Y[(src_e, l_e)], d_agg[tgt_e]>_k.  The gather of (1) reads
@@ -249,16 +227,7 @@ class RGAT(MessagePassing):
         with ops.op_scope("rgat_attention_backward", s_src, s_tgt, att, da, dz):
             rc = lib.tfgnn_rgat_attention_backward(g._h, ops._ptr(s_src), ops._ptr(s_tgt), ops._ptr(att), ops._ptr(da), K, ops._ptr(dz),
                                                    ops._ptr(ws), ws.numel() if ws is not None else 0, ops._stream())
-        if rc == -4:  # the piecewise form (see _edge_attention: not reached at any head count the row kernels take, 1 .. 64)
-            t = ops.graph_gather(g, ops.VIEW_BY_DST_NODE, ops.mul(att, da), col=ident_e[:E])  # [V, K] sum of a * da
-            _lib.check(
-                lib.tfgnn_rgat_edge_softmax_backward(
-                    ops._ptr(g.array(ops.G_COLL_BY_DST)), ops._ptr(g.array(ops.G_TARGET_BY_DST)), ops._ptr(s_src),
-                    ops._ptr(s_tgt), ops._ptr(att), ops._ptr(da), ops._ptr(t), E, L, K, ops._ptr(dz), ops._stream(),
-                )
-            )
-        else:
-            _lib.check(rc)
+        _lib.check(rc)
         # (3) logits are s_src[(src,l)] + s_tgt[(tgt,l)]: segment sums of dz over both bucketings
         ds_tgt = ops.graph_gather(g, ops.VIEW_BY_DST_TYPED, dz, col=ident_e[:E])  # [V*L, K]
         ds_src = ops.graph_gather(g, ops.VIEW_BY_SRC_TYPED, dz, col=s2d)  # [V*L, K]
@@ -279,8 +248,7 @@ class RGAT(MessagePassing):
             # the score terms are added while dY is ALSO written as the split operand of dX = dY W^T.  The weight gradient stays
             # on the exact bf16x3 kernel: dY's rows carry attention weights (1e-9 into a hub) - beyond the spread guard of the
             # split-operand TN product (measured: it trips on the first step of the rgat workload)
-            dY_sp = ops.SplitOperand(torch.empty((V, L * H * 4), dtype=torch.uint8, device=dev),
-                                     torch.empty((V, 1), dtype=torch.float32, device=dev), V, L * H, L * H)
+            dY_sp = ops._empty_split(V, L * H, dev, per_row=True)
             with ops.op_scope("rgat_scores_backward", ds_src, ds_tgt, dY, dY_sp.data):
                 rc = lib.tfgnn_rgat_scores_backward_sp(ops._ptr(ds_src), ops._ptr(ds_tgt), ops._ptr(self._attn), ops._ptr(dY), 1, V, L, K, H,
                                                        ops._ptr(dY_sp.data), ops._ptr(dY_sp.inv_scale), ops._stream())

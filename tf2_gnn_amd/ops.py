@@ -1582,6 +1582,35 @@ def sp_one_tile(N: int) -> bool:
     return sp_tile_width(N) == N
 
 
+def _empty_split(rows: int, cols: int, device, per_row: bool = False) -> SplitOperand:
+    """An unwritten SP16 operand [rows, cols] for a kernel to fill: a product's split result, which carries one scale per row
+    and COLUMN TILE (cols = 512: blocks of 256 columns), or - per_row - an operand with one scale per row."""
+    bn = cols if per_row else sp_tile_width(cols)
+    return SplitOperand(torch.empty((rows, cols * 4), dtype=torch.uint8, device=device),
+                        torch.empty((rows, max(1, cols // max(bn, 1))), dtype=torch.float32, device=device), rows, cols, bn if bn else cols)
+
+
+def _c_epilogue(out_mul, act_grad, dropout, saved_scale):
+    """The epilogue specs of a split-operand product as the C ABI takes them
+    -> (out_mul tensor | None, activation id of ``saved``, saved tensor | None, saved_scale, dropout rate, dropout seed)."""
+    out_mul, act_grad, dropout, saved_scale = _native_epilogue(out_mul, act_grad, dropout, saved_scale)
+    act_name, saved = act_grad if act_grad is not None else (None, None)
+    rate, seed = dropout if dropout is not None else (0.0, 0)
+    return out_mul, act_id(act_name), saved, float(saved_scale), float(rate), int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def _product_out(out, M: int, N: int, accumulate, device):
+    """-> (out, leading dimension): the fp32 result [M, N] of a product, the caller's tensor checked or a new one"""
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate=True needs out")
+        out = torch.empty((M, N), dtype=torch.float32, device=device)
+    out2, ldc = _rowmajor(out, "out")
+    if out2 is not out or tuple(out.shape) != (M, N):
+        raise ValueError(f"out must be [{M},{N}] with unit inner stride")
+    return out, ldc
+
+
 class RowGroups:
     """Consecutive row groups (rows of group g: [offsets[g], offsets[g + 1])) cut into the row tiles of the grouped product
     (tfgnn_sp_gemm_nt_grouped d_tile_table): int32 [tiles, 4] = (first row, rows, group, 0) on the device, built once per
@@ -1649,20 +1678,15 @@ def sp_gemm_nt_grouped(a: SplitOperand, b: SplitOperand, groups: RowGroups, *, a
         a_rows = _row_map(a_rows, M)
     dev = a.data.device
     out = torch.empty((M, N), dtype=torch.float32, device=dev) if want_fp32 else None
-    op = None
-    if want_split:
-        bn = sp_tile_width(N)
-        op = SplitOperand(torch.empty((M, N * 4), dtype=torch.uint8, device=dev),
-                          torch.empty((M, max(1, N // max(bn, 1))), dtype=torch.float32, device=dev), M, N, bn if bn else N)
+    op = _empty_split(M, N, dev) if want_split else None
     if M == 0:
         return out, op
-    _, act_grad, _, _ = _native_epilogue(None, act_grad, None, 1.0)
-    act_name, saved = act_grad if act_grad is not None else (None, None)
+    _, act_of_saved, saved, _, _, _ = _c_epilogue(None, act_grad, None, 1.0)
     _lib.check(
         lib.tfgnn_sp_gemm_nt_grouped(
             M, N, K, _ptr(a.data), a.data.stride(0), _ptr(a.inv_scale), a.scale_block if a.scale_block else -1, _ptr(a_rows), a.rows,
             _ptr(groups.table), groups.num_tiles, G, _ptr(b.data), b.data.stride(0), stride_b, _ptr(b.inv_scale), stride_scale,
-            _ptr(out), N, None, act_id(act), None, 0, act_id(act_name), _ptr(saved), saved.stride(0) if saved is not None else 0,
+            _ptr(out), N, None, act_id(act), None, 0, act_of_saved, _ptr(saved), saved.stride(0) if saved is not None else 0,
             _ptr(op.data) if op is not None else None, op.data.stride(0) if op is not None else 0,
             _ptr(op.inv_scale) if op is not None else None, _stream(),
         )
@@ -1714,6 +1738,36 @@ def sp_gather_rows(a: SplitOperand, index: torch.Tensor) -> SplitOperand:
     return out
 
 
+def _nt_shape(who: str, a: SplitOperand, b: SplitOperand):
+    """-> (M, K, N) of a [M, K] @ b [N, K]^T, after the operand checks of the NT product"""
+    M, K, N = a.rows, a.cols, b.rows
+    if b.cols != K:
+        raise ValueError(f"{who}: inner dimensions differ ({K} vs {b.cols})")
+    if b.scale_block != K:
+        raise ValueError(f"{who}: the right operand must carry one scale per row")
+    return M, K, N
+
+
+def _sp_gemm_nt_rows(a, b, M, N, K, out, ldc, op, bias, act, accumulate, epilogue, tile_kmask, row_map, a_rows) -> None:
+    """The one call of tfgnn_sp_gemm_nt_rows: ``out`` (fp32 [M, N], leading dimension ldc) and ``op`` (the split result) may
+    each be None; ``epilogue`` as ``_c_epilogue`` returns it."""
+    out_mul, act_of_saved, saved, saved_scale, rate, seed = epilogue
+    if bias is not None:
+        bias = bias.contiguous()
+    _ensure_splitk_workspace(a.data.device, M)
+    _lib.check(
+        _lib.load().tfgnn_sp_gemm_nt_rows(
+            M, N, K, _ptr(a.data), a.data.stride(0), _ptr(a.inv_scale), a.scale_block if a.scale_block else -1,
+            _ptr(_row_map(a_rows, M)), _ptr(b.data), b.data.stride(0),
+            _ptr(b.inv_scale), _ptr(out), ldc, _ptr(bias), act_id(act), int(accumulate), _ptr(out_mul),
+            out_mul.stride(0) if out_mul is not None else 0, act_of_saved, _ptr(saved),
+            saved.stride(0) if saved is not None else 0, saved_scale, _ptr(op.data) if op is not None else None,
+            op.data.stride(0) if op is not None else 0, _ptr(op.inv_scale) if op is not None else None, rate, seed,
+            _ptr(_tile_kmask(tile_kmask, M)), _ptr(_row_map(row_map, M)), _stream(),
+        )
+    )
+
+
 @_writes_out
 def sp_gemm_nt(a: SplitOperand, b: SplitOperand, *, bias=None, act=ACT_NONE, out=None, accumulate=False, out_mul=None,
                act_grad=None, dropout=None, saved_scale: float = 1.0, tile_kmask=None, row_map=None, a_rows=None) -> torch.Tensor:
@@ -1724,35 +1778,10 @@ def sp_gemm_nt(a: SplitOperand, b: SplitOperand, *, bias=None, act=ACT_NONE, out
     (forward: the next layer's input dropout; gradient product: the recomputed forward mask).  saved_scale: the derivative
     of ``act_grad`` is taken at saved * saved_scale (saved is a dropped activation).  a_rows (int32 [M]): product row r reads
     row a_rows[r] of ``a`` (tfgnn_sp_gemm_nt_rows: the by-source pattern order of the input-gradient product)."""
-    lib = _lib.load()
-    M, K, N = a.rows, a.cols, b.rows
-    if b.cols != K:
-        raise ValueError(f"sp_gemm_nt: inner dimensions differ ({K} vs {b.cols})")
-    if b.scale_block != K:
-        raise ValueError("sp_gemm_nt: the right operand must carry one scale per row")
-    if out is None:
-        if accumulate:
-            raise ValueError("accumulate=True needs out")
-        out = torch.empty((M, N), dtype=torch.float32, device=a.data.device)
-    out2, ldc = _rowmajor(out, "out")
-    if out2 is not out or tuple(out.shape) != (M, N):
-        raise ValueError(f"out must be [{M},{N}] with unit inner stride")
-    out_mul, act_grad, dropout, saved_scale = _native_epilogue(out_mul, act_grad, dropout, saved_scale)
-    act_name, saved = act_grad if act_grad is not None else (None, None)
-    if bias is not None:
-        bias = bias.contiguous()
-    rate, seed = dropout if dropout is not None else (0.0, 0)
-    _ensure_splitk_workspace(a.data.device, M)
-    _lib.check(
-        lib.tfgnn_sp_gemm_nt_rows(
-            M, N, K, _ptr(a.data), a.data.stride(0), _ptr(a.inv_scale), a.scale_block if a.scale_block else -1,
-            _ptr(_row_map(a_rows, M)), _ptr(b.data), b.data.stride(0),
-            _ptr(b.inv_scale), _ptr(out), ldc, _ptr(bias), act_id(act), int(accumulate), _ptr(out_mul),
-            out_mul.stride(0) if out_mul is not None else 0, act_id(act_name), _ptr(saved),
-            saved.stride(0) if saved is not None else 0, float(saved_scale), None, 0, None, float(rate),
-            int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(_tile_kmask(tile_kmask, M)), _ptr(_row_map(row_map, M)), _stream(),
-        )
-    )
+    M, K, N = _nt_shape("sp_gemm_nt", a, b)
+    out, ldc = _product_out(out, M, N, accumulate, a.data.device)
+    _sp_gemm_nt_rows(a, b, M, N, K, out, ldc, None, bias, act, accumulate, _c_epilogue(out_mul, act_grad, dropout, saved_scale),
+                     tile_kmask, row_map, a_rows)
     return out
 
 
@@ -1762,33 +1791,12 @@ def sp_gemm_nt_split(a: SplitOperand, b: SplitOperand, *, bias=None, act=ACT_NON
     by the product's epilogue (tfgnn_sp_gemm_nt_sp): the next product's operand without a split pass.  N must be one
     column tile (128, 256 or 320).  -> (fp32 [M, N] | None, SplitOperand); the fp32 tensor remembers its split form
     (``sp_rows_of``)."""
-    lib = _lib.load()
-    M, K, N = a.rows, a.cols, b.rows
-    if b.cols != K:
-        raise ValueError(f"sp_gemm_nt_split: inner dimensions differ ({K} vs {b.cols})")
-    if b.scale_block != K:
-        raise ValueError("sp_gemm_nt_split: the right operand must carry one scale per row")
+    M, K, N = _nt_shape("sp_gemm_nt_split", a, b)
     dev = a.data.device
     out = torch.empty((M, N), dtype=torch.float32, device=dev) if want_fp32 else None
-    bn = sp_tile_width(N)  # the result carries one scale per row and COLUMN TILE (N = 512: blocks of 256 columns)
-    op = SplitOperand(torch.empty((M, N * 4), dtype=torch.uint8, device=dev),
-                      torch.empty((M, max(1, N // max(bn, 1))), dtype=torch.float32, device=dev), M, N, bn if bn else N)
-    out_mul, act_grad, dropout, saved_scale = _native_epilogue(out_mul, act_grad, dropout, saved_scale)
-    act_name, saved = act_grad if act_grad is not None else (None, None)
-    if bias is not None:
-        bias = bias.contiguous()
-    rate, seed = dropout if dropout is not None else (0.0, 0)
-    _ensure_splitk_workspace(dev, M)
-    _lib.check(
-        lib.tfgnn_sp_gemm_nt_rows(
-            M, N, K, _ptr(a.data), a.data.stride(0), _ptr(a.inv_scale), a.scale_block if a.scale_block else -1,
-            _ptr(_row_map(a_rows, M)), _ptr(b.data),
-            b.data.stride(0), _ptr(b.inv_scale), _ptr(out), N, _ptr(bias), act_id(act), 0, _ptr(out_mul),
-            out_mul.stride(0) if out_mul is not None else 0, act_id(act_name), _ptr(saved),
-            saved.stride(0) if saved is not None else 0, float(saved_scale), _ptr(op.data), op.data.stride(0), _ptr(op.inv_scale),
-            float(rate), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(_tile_kmask(tile_kmask, M)), _ptr(_row_map(row_map, M)), _stream(),
-        )
-    )
+    op = _empty_split(M, N, dev)
+    _sp_gemm_nt_rows(a, b, M, N, K, out, N, op, bias, act, False, _c_epilogue(out_mul, act_grad, dropout, saved_scale),
+                     tile_kmask, row_map, a_rows)
     if out is not None:
         _remember_split_rows(out, op)
     return out, op
@@ -1868,8 +1876,7 @@ def _weight_operand_for_call(w: torch.Tensor, kind: str, rows: int, cols: int):
     op = _cached_weight_operand(w, kind)
     if op is not None:
         return op, False
-    return SplitOperand(torch.empty((rows, cols * 4), dtype=torch.uint8, device=w.device),
-                        torch.empty((rows, 1), dtype=torch.float32, device=w.device), rows, cols, cols), True
+    return _empty_split(rows, cols, w.device, per_row=True), True
 
 
 def mp_forward(graph: "Graph", view: int, x: torch.Tensor, W: torch.Tensor, *, row_scale=None, act=ACT_NONE, dropout=None,
@@ -1890,11 +1897,7 @@ def mp_forward(graph: "Graph", view: int, x: torch.Tensor, W: torch.Tensor, *, r
     agg = torch.empty((V, L * D * 4), dtype=torch.uint8, device=dev)
     agg_inv = torch.empty((V, L), dtype=torch.float32, device=dev)
     out = torch.empty((V, H), dtype=torch.float32, device=dev) if want_fp32 else None
-    op = None
-    if want_split:
-        bn = sp_tile_width(H)
-        op = SplitOperand(torch.empty((V, H * 4), dtype=torch.uint8, device=dev),
-                          torch.empty((V, max(1, H // max(bn, 1))), dtype=torch.float32, device=dev), V, H, bn if bn else H)
+    op = _empty_split(V, H, dev) if want_split else None
     ws_bytes = lib.tfgnn_graph_gather_workspace_bytes(graph._h, view, D)
     ws = _workspace(dev, ws_bytes) if ws_bytes else None
     rate, seed = dropout if dropout is not None else (0.0, 0)
@@ -1947,23 +1950,11 @@ def mp_backward(graph: "Graph", d_pre: torch.Tensor, W: torch.Tensor, x_sp: Opti
     wh, stale = _weight_operand_for_call(W, "rows", D, L * H)
     g_sp = torch.empty((V, L * H * 4), dtype=torch.uint8, device=dev)
     g_inv = torch.empty((V, L), dtype=torch.float32, device=dev)
-    if out is None:
-        if accumulate:
-            raise ValueError("accumulate=True needs out")
-        out = torch.empty((V, D), dtype=torch.float32, device=dev)
-    out2, ldc = _rowmajor(out, "out")
-    if out2 is not out or tuple(out.shape) != (V, D):
-        raise ValueError(f"out must be [{V},{D}] with unit inner stride")
-    op = None
-    if want_split:
-        if accumulate:
-            raise ValueError("mp_backward: the split result needs no accumulation")
-        bn = sp_tile_width(D)
-        op = SplitOperand(torch.empty((V, D * 4), dtype=torch.uint8, device=dev),
-                          torch.empty((V, max(1, D // max(bn, 1))), dtype=torch.float32, device=dev), V, D, bn if bn else D)
-    out_mul, act_grad, dropout, saved_scale = _native_epilogue(out_mul, act_grad, None, 1.0)
-    act_name, saved = act_grad if act_grad is not None else (None, None)
-    rate, seed = dropout if dropout is not None else (0.0, 0)
+    out, ldc = _product_out(out, V, D, accumulate, dev)
+    if want_split and accumulate:
+        raise ValueError("mp_backward: the split result needs no accumulation")
+    op = _empty_split(V, D, dev) if want_split else None
+    out_mul, act_of_saved, saved, saved_scale, rate, seed = _c_epilogue(out_mul, act_grad, None, 1.0)
     dW = torch.empty_like(W) if need_weight_grad else None
     ws_bytes = lib.tfgnn_graph_gather_workspace_bytes(graph._h, VIEW_BY_SRC_TYPED, H)
     ws = _workspace(dev, ws_bytes) if ws_bytes else None
@@ -1992,11 +1983,11 @@ def mp_backward(graph: "Graph", d_pre: torch.Tensor, W: torch.Tensor, x_sp: Opti
     a.dx, a.ld_dx, a.accumulate = out.data_ptr(), ldc, int(bool(accumulate))
     if out_mul is not None:
         a.mul, a.ld_mul = out_mul.data_ptr(), out_mul.stride(0)
-    a.act_of_saved = act_id(act_name)
+    a.act_of_saved = act_of_saved
     if saved is not None:
         a.saved, a.ld_saved = saved.data_ptr(), saved.stride(0)
-    a.saved_scale = float(saved_scale)
-    a.dropout_rate, a.dropout_seed = float(rate), int(seed) & 0xFFFFFFFFFFFFFFFF
+    a.saved_scale = saved_scale
+    a.dropout_rate, a.dropout_seed = rate, seed
     if op is not None:
         a.dx_sp, a.ld_dx_sp_bytes, a.dx_inv_scale = op.data.data_ptr(), op.data.stride(0), op.inv_scale.data_ptr()
     for name, check in (("tile_kmask", _tile_kmask), ("a_rows", _row_map), ("row_map", _row_map)):

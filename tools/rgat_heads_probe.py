@@ -6,6 +6,8 @@
                sum, divide; backward mul + segment sum + edge kernel, and the re-ordering gather for the by-source weights.
                It is forced by answering -4 for the two entries without calling them, which is what the library did for
                these head counts before the row kernels took them.
+               (The layer no longer has that branch: NOTEBOOK.md §17 keeps the measurement, and this leg runs only in a checkout
+               of the commit that recorded it.)
 
     python tools/rgat_heads_probe.py --heads 3 [--hidden 192] [--repeats 30]
 
