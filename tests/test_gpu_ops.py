@@ -255,6 +255,9 @@ def test_gemm_split_k_weight_gradient_shape(dev):
 @pytest.mark.parametrize("width", [3, 4, 7, 8, 12, 32, 64, 128, 256, 320, 512, 1280])
 @pytest.mark.parametrize("reduce", ["sum", "max"])
 def test_gather_reduce_matches_oracle(dev, width, reduce):
+    """The plan-less entry only (tfgnn_csr_gather_reduce: no items, no length-ordered short rows, no combine pass, no output
+    row map).  The planned entry the layers call, tfgnn_graph_gather_reduce, is held to the same bound on every work unit of
+    its plan in tests/test_gpu_graph_gather.py."""
     from tf2_gnn_amd import ops
 
     V, L = 200, 3

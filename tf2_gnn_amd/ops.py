@@ -424,8 +424,11 @@ def graph_gather(
         num_rows = graph.nonempty_offsets(False)[-1]
     elif view == VIEW_BY_SRC_TYPED_COMPACT:
         num_rows = graph.nonempty_offsets(True)[-1]
-    else:
-        num_rows = graph.num_nodes * (graph.num_edge_types if view in (VIEW_BY_DST_TYPED, VIEW_BY_SRC_TYPED) else 1)
+    else:  # (the pattern view writes every (node, type) bucket, like the typed views)
+        typed = view in (VIEW_BY_DST_TYPED, VIEW_BY_SRC_TYPED, VIEW_BY_DST_TYPED_PATTERN)
+        num_rows = graph.num_nodes * (graph.num_edge_types if typed else 1)
+    if view == VIEW_BY_DST_TYPED_PATTERN and graph.num_edge_types > 8:
+        raise ValueError("graph_gather: the pattern order exists for at most 8 edge types")
     inp, ld_in = _rowmajor(inp, "inp")
     width = inp.shape[1]
     if out is None:
