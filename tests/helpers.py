@@ -29,6 +29,17 @@ def to_dev(arrs, dev):
     return tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in arrs)
 
 
+def decode_sp16(op):
+    """SP16 -> float64 matrix (h + l) * inv_scale, on the host."""
+    data = op.data.cpu().numpy()
+    R, C = op.rows, op.cols
+    gran = data[:, : 4 * C].reshape(R, C // 16, 2, 32).copy()
+    planes = gran.view(np.float16).reshape(R, C // 16, 2, 16).astype(np.float64)
+    x = (planes[:, :, 0, :] + planes[:, :, 1, :]).reshape(R, C)
+    inv = op.inv_scale.cpu().numpy().astype(np.float64).reshape(R, -1)
+    return x * np.repeat(inv, op.scale_block, axis=1)
+
+
 def edge_mlp_weights_from_layer(layer):
     """HIP GNN_Edge_MLP-family layer -> oracle weights dict (CPU tensors, same values)."""
     mlps = layer._edge_type_mlps

@@ -392,23 +392,93 @@ def test_gru_gates_forward_backward(dev):
     assert_close(dh.cpu(), gh.float(), tol=5e-6, what="gru dh")
 
 
-def test_layernorm_forward_backward(dev):
+def _layernorm_case(rows, H, seed=1):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn((rows, H), generator=g, dtype=torch.float64)
+    gamma = torch.randn(H, generator=g, dtype=torch.float64)
+    beta = torch.randn(H, generator=g, dtype=torch.float64)
+    dy = torch.randn((rows, H), generator=g, dtype=torch.float64)
+    return x, gamma, beta, dy
+
+
+def _layernorm_reference(x, gamma, beta, dy):
+    x, gamma, beta = (t.clone().requires_grad_(True) for t in (x, gamma, beta))
+    y = orc.layer_norm(x, gamma, beta, 1e-3)
+    return (y.detach(),) + torch.autograd.grad((y * dy).sum(), [x, gamma, beta])
+
+
+@pytest.mark.parametrize("rows,H", [(1, 1), (3, 63), (4, 64), (5, 65), (33, 70), (257, 320)])
+def test_layernorm_forward_backward(dev, rows, H):
+    """One wave per row, four rows per workgroup, lane j owns columns j, j + 64, ...: row counts that are no multiple of four, a
+    last workgroup of one row, and one, two and five strides per lane with a ragged last stride."""
     from tf2_gnn_amd import ops
 
-    g = torch.Generator().manual_seed(1)
-    x = torch.randn((33, 70), generator=g, dtype=torch.float64).requires_grad_(True)
-    gamma = torch.randn(70, generator=g, dtype=torch.float64).requires_grad_(True)
-    beta = torch.randn(70, generator=g, dtype=torch.float64).requires_grad_(True)
-    y = orc.layer_norm(x, gamma, beta, 1e-3)
-    dy = torch.randn((33, 70), generator=g, dtype=torch.float64)
-    gx, gg, gb = torch.autograd.grad((y * dy).sum(), [x, gamma, beta])
+    x, gamma, beta, dy = _layernorm_case(rows, H)
+    y, gx, gg, gb = _layernorm_reference(x, gamma, beta, dy)
     f = lambda t: t.detach().float().to(dev)
     yd, mean, rstd = ops.layernorm_forward(f(x), f(gamma), f(beta), 1e-3)
-    assert_close(yd.cpu(), y.detach().float(), tol=5e-6, what="ln fwd")
+    assert_close(yd.cpu(), y.float(), tol=5e-6, what="ln fwd")
+    assert_close(mean.cpu(), x.mean(dim=1).float(), tol=5e-6, what="ln mean")
     dx, dgam, dbet = ops.layernorm_backward(f(dy), f(x), f(gamma), mean, rstd)
     assert_close(dx.cpu(), gx.float(), tol=1e-5, what="ln dx")
     assert_close(dgam.cpu(), gg.float(), tol=1e-5, what="ln dgamma")
     assert_close(dbet.cpu(), gb.float(), tol=1e-5, what="ln dbeta")
+
+
+def test_layernorm_constant_row(dev):
+    """A row of one value: the variance is 0, rstd = 1 / sqrt(eps), y = beta, and dx = rstd * gamma-weighted dy less its mean."""
+    from tf2_gnn_amd import ops
+
+    x, gamma, beta, dy = _layernorm_case(6, 70, seed=2)
+    x[2] = 3.25
+    y, gx, gg, gb = _layernorm_reference(x, gamma, beta, dy)
+    f = lambda t: t.detach().float().to(dev)
+    yd, mean, rstd = ops.layernorm_forward(f(x), f(gamma), f(beta), 1e-3)
+    assert float(mean[2]) == 3.25
+    assert abs(float(rstd[2]) * 1e-3 ** 0.5 - 1.0) <= 2e-6
+    assert torch.equal(yd[2].cpu(), beta.float())
+    assert_close(yd.cpu(), y.float(), tol=5e-6, what="ln fwd, constant row")
+    dx, dgam, dbet = ops.layernorm_backward(f(dy), f(x), f(gamma), mean, rstd)
+    assert_close(dx.cpu(), gx.float(), tol=1e-5, what="ln dx, constant row")
+    assert_close(dgam.cpu(), gg.float(), tol=1e-5, what="ln dgamma, constant row")
+    assert_close(dbet.cpu(), gb.float(), tol=1e-5, what="ln dbeta, constant row")
+
+
+def test_layernorm_large_row_mean(dev):
+    """Rows offset by +-1e3 from a unit spread: what the two-pass variance is for.  The fp32 input is the common starting point
+    (the reference takes it cast up).  Tolerances are those of test_layernorm_forward_backward plus the conditioning of x - mean in
+    fp32: one rounding of a 1e3-sized mean, delta = 1e3 * 2^-24 in units of x, is delta * rstd in xhat = (x - mean) * rstd, and
+    reaches the outputs through their first derivatives with respect to xhat:
+        y = xhat gamma + beta                          -> delta rstd |gamma|
+        dx = rstd (g - mean(g) - xhat mean(g xhat))    -> delta rstd^2 (|mean(g xhat)| + |xhat| mean|g|),  g = dy gamma
+        dgamma = sum_rows dy xhat                      -> sum_rows |dy| delta rstd
+    (dbeta does not depend on x).  The bound comes from the number format, not from what the kernel gives."""
+    from tf2_gnn_amd import ops
+
+    rows, H = 33, 70
+    x, gamma, beta, dy = _layernorm_case(rows, H, seed=3)
+    offset = torch.where(torch.arange(rows) % 2 == 0, 1e3, -1e3).double().unsqueeze(1)
+    x = (x + offset).float().double()
+    y, gx, gg, gb = _layernorm_reference(x, gamma, beta, dy)
+    f = lambda t: t.detach().float().to(dev)
+    yd, mean, rstd = ops.layernorm_forward(f(x), f(gamma), f(beta), 1e-3)
+    dx, dgam, dbet = ops.layernorm_backward(f(dy), f(x), f(gamma), mean, rstd)
+    delta = 1e3 * 2.0 ** -24
+    mu = x.mean(dim=1, keepdim=True)
+    rs = 1.0 / torch.sqrt(((x - mu) ** 2).mean(dim=1, keepdim=True) + 1e-3)
+    xhat = (x - mu) * rs
+    g = dy * gamma
+    extra_y = delta * rs * gamma.abs()
+    extra_dx = delta * rs * rs * ((g * xhat).mean(dim=1, keepdim=True).abs() + xhat.abs() * g.abs().mean(dim=1, keepdim=True))
+    extra_dgamma = (dy.abs() * delta * rs).sum(dim=0)
+    for what, got, ref, tol, extra in (("y", yd, y, 5e-6, extra_y), ("dx", dx, gx, 1e-5, extra_dx), ("dgamma", dgam, gg, 1e-5, extra_dgamma),
+                                       ("dbeta", dbet, gb, 1e-5, torch.zeros(H, dtype=torch.float64))):
+        err = (got.cpu().double() - ref).abs()
+        bound = tol * ref.abs().clamp(min=1.0) + extra
+        worst = float((err / bound).max())
+        print(f"ln large mean {what}: max error {float(err.max()):.3e}, worst error / bound {worst:.3f}")
+        assert worst <= 1.0, (what, worst)
+    assert float((mean.cpu().double() - mu.view(-1)).abs().max()) <= delta
 
 
 @pytest.mark.parametrize("M", [1, 200, 256, 257, 4097, 7110, 150001])

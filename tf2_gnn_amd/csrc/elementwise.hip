@@ -111,7 +111,7 @@ gru_gates_backward_kernel(const float* __restrict__ dh_new, const float* __restr
     const float g = dh_new[i];
     const float dc = g * (1.f - z);
     const float dz = g * (h[i] - c);
-    const float dpc = dc * (1.f - c * c);
+    const float dpc = dc * fmaf(-c, c, 1.f);  // 1 - c^2 in one rounding: c * c rounded first loses a saturated unit's derivative
     const float dpz = dz * z * (1.f - z);
     const float dpr = dpc * hh * r * (1.f - r);
     float* ox = dmx + v * 3 * H;
@@ -160,7 +160,7 @@ gru_gates_backward_sp_kernel(const float* __restrict__ dh_new, const float* __re
       const float g = dh_new[v * H + j];
       const float dc = g * (1.f - z);
       const float dz = g * (h[v * H + j] - c);
-      const float dpc = dc * (1.f - c * c);
+      const float dpc = dc * fmaf(-c, c, 1.f);  // (as gru_gates_backward_kernel: one rounding)
       const float dpz = dz * z * (1.f - z);
       const float dpr = dpc * hh * r * (1.f - r);
       x[0][u] = dpz; x[1][u] = dpr; x[2][u] = dpc; y[u] = dpc * r;
@@ -173,6 +173,11 @@ gru_gates_backward_sp_kernel(const float* __restrict__ dh_new, const float* __re
       const float m2 = fmaxf(fabsf(dpz), fabsf(dpr));
       mxx = fmaxf(mxx, fmaxf(m2, fabsf(dpc)));
       mxh = fmaxf(mxh, fmaxf(m2, fabsf(dpc * r)));
+      // fmaxf drops a NaN: a row of NaN would keep the maximum 0 and get the scale of an all-zero row, which the weight-gradient
+      // product skips (sp_row_holds) - finite gradients out of a diverged step.  NaN in the row -> inf -> scale 1, as every
+      // other producer of split operands does
+      if (dpz != dpz || dpr != dpr || dpc != dpc) mxx = __builtin_inff();
+      if (dpz != dpz || dpr != dpr || y[u] != y[u]) mxh = __builtin_inff();
     }
 #pragma unroll
     for (int o = 32; o; o >>= 1) {
@@ -380,13 +385,19 @@ layernorm_forward_kernel(const float* __restrict__ x, const float* __restrict__ 
   const float* xr = x + row * H;
   float s = 0.f;
   for (int j = lane; j < H; j += 64) s += xr[j];
-  const float mean = wave_sum(s) / (float)H;
-  float q = 0.f;
+  // The sum of a row around a large mean (1e3 against a unit spread) rounds at the size of the SUM: its mean is off by several
+  // ulp of the mean, which is not small against the spread.  The second pass measures that error - the deviations from the
+  // first mean are small, their sum is accurate - and takes it out of the mean and of the variance (corrected two-pass form).
+  const float mean0 = wave_sum(s) / (float)H;
+  float q = 0.f, e = 0.f;
   for (int j = lane; j < H; j += 64) {
-    const float d = xr[j] - mean;
+    const float d = xr[j] - mean0;
     q += d * d;
+    e += d;
   }
-  const float rstd = rsqrtf(wave_sum(q) / (float)H + eps);
+  const float corr = wave_sum(e) / (float)H;
+  const float mean = mean0 + corr;
+  const float rstd = rsqrtf(fmaxf(wave_sum(q) / (float)H - corr * corr, 0.f) + eps);
   float* yr = y + row * H;
   for (int j = lane; j < H; j += 64) yr[j] = (xr[j] - mean) * rstd * gamma[j] + beta[j];
   if (lane == 0) {
