@@ -1163,6 +1163,8 @@ int64_t tfgnn_optimizer_launch_count(void);
  *   per processed edge type t:    edge_ptr[t] [N + 1] edges of type t before graph i;  edges[t] [edge_ptr[t][N], 2] int32,
  *                                 rows (src, dst) with graph-LOCAL node ids, in the order the reference gives them
  *   per column c:                 columns[c] [N] fp32, one value per graph (target_value, ...)
+ *   per node column c:            node_columns[c] [store_nodes, W_c] fp32, one row per node, laid out like `features`, every
+ *                                 column with its own width W_c = node_column_widths[c] (node_labels, ...)
  * Epoch arrays (uploaded once per epoch; P = order_len positions):
  *   order [P]                     graph id at position p (any ids in [0, N), repeats allowed)
  *   pos_node_ptr [P + 1]          nodes of the graphs at positions 0 .. p-1;  pos_edge_ptr[t] [P + 1] likewise per type
@@ -1171,24 +1173,33 @@ int64_t tfgnn_optimizer_launch_count(void);
  *   node_to_graph_map[the same row]                           = i
  *   adjacency_lists[t][pos_edge_ptr[t][p] - pos_edge_ptr[t][p0] + k] = edges[t][edge_ptr[t][order[p]] + k] + (that node offset)
  *   column_out[c][i]                                          = columns[c][order[p]]
+ *   node_column_out[c][pos_node_ptr[p] - pos_node_ptr[p0] + j, :] = node_columns[c][node_ptr[order[p]] + j, :]
  * The caller keeps the per-graph counts on the host, so it knows - and passes - the output sizes: num_nodes = V and
  * num_edges[t] = E_t; it allocates the outputs.  The kernel never writes past them: a size that disagrees with the device's
  * prefix sums, a graph id outside [0, N) or a local node id outside its graph sets *bad_flag (nullable, zeroed by the caller)
  * and the element is skipped or, for a bad local id, written as computed - what tfgnn_batch_offset_edges does.
  *
- * ONE launch per call, its grid partitioned over the parts (feature tiles, which also write node_to_graph_map; every edge
- * type; the columns); none when the batch is empty (G == 0).  No copy, no allocation, no synchronisation.  Feature rows
- * are copied with consecutive lanes on consecutive floats (float4 when F % 4 == 0 and both buffers are 16-byte aligned);
- * element offsets into `features` are 64-bit.  Zero-length segments (no edges of a type, no nodes) cost nothing.
- * The pointer tables (edge_ptr, edges, pos_edge_ptr, adjacency_lists, num_edges, columns, column_out) are HOST arrays of
- * num_edge_types / num_columns entries, read during the call.
+ * ONE launch per call, its grid partitioned over the parts (feature tiles, which also write node_to_graph_map; the tiles
+ * of every node column; every edge type; the columns); none when the batch is empty (G == 0).  No copy, no allocation, no
+ * synchronisation.  Feature and node column rows are copied with consecutive lanes on consecutive floats (per array: float4
+ * when its width % 4 == 0 and both of its buffers are 16-byte aligned), rows_per_tile = clamp(8192 / width, 1, 256) rows to a
+ * workgroup; element offsets into the store are 64-bit.  A node column row whose source disagrees with the store sizes is
+ * skipped and sets *bad_flag, like a feature row; nothing is written beyond num_nodes rows.  Zero-length segments (no edges
+ * of a type, no nodes) cost nothing.  With num_node_columns == 0 the grid and every output are what they are without them.
+ * The pointer tables (edge_ptr, edges, pos_edge_ptr, adjacency_lists, num_edges, columns, column_out, node_column_widths,
+ * node_columns, node_column_out) are HOST arrays of num_edge_types / num_columns / num_node_columns entries, read during the
+ * call.
  * Rejected on the host before any HIP call: NULL args, another struct_size, negative sizes, p0 > p1 or p1 > order_len,
  * feature_dim < 1 or >= 2^31, store_nodes or num_nodes >= 2^31, num_edges[t] >= 2^31, NULL pointers where the size is not
- * zero, edge buffers that are not 8-byte aligned.  More than TFGNN_BATCH_MAX_EDGE_TYPES types or TFGNN_BATCH_MAX_COLUMNS
- * columns: TFGNN_ERR_UNSUPPORTED.
+ * zero, edge buffers that are not 8-byte aligned, a negative num_node_columns, a NULL node column table when there are node
+ * columns, a node column width < 1 or >= 2^31, a NULL node column when num_nodes > 0.  More than TFGNN_BATCH_MAX_EDGE_TYPES
+ * types, TFGNN_BATCH_MAX_COLUMNS columns or TFGNN_BATCH_MAX_NODE_COLUMNS node columns: TFGNN_ERR_UNSUPPORTED.
+ * The node column fields were appended behind bad_flag: no earlier field moved, and struct_size tells a caller built against
+ * the shorter struct apart.
  * ------------------------------------------------------------------------------------------ */
 #define TFGNN_BATCH_MAX_EDGE_TYPES 48
 #define TFGNN_BATCH_MAX_COLUMNS 8
+#define TFGNN_BATCH_MAX_NODE_COLUMNS 4
 typedef struct tfgnn_batch_assemble_args {
   size_t struct_size;
   int num_edge_types;
@@ -1216,6 +1227,11 @@ typedef struct tfgnn_batch_assemble_args {
   int32_t* const* adjacency_lists; /* [E_t, 2] each */
   float* const* column_out;        /* [G] each */
   int* bad_flag;
+  /* per-node columns */
+  int num_node_columns;
+  const int64_t* node_column_widths; /* W_c */
+  const float* const* node_columns;  /* store [store_nodes, W_c] each */
+  float* const* node_column_out;     /* [V, W_c] contiguous each */
 } tfgnn_batch_assemble_args;
 int tfgnn_batch_assemble(const tfgnn_batch_assemble_args* args, void* stream);
 /* host-side count of the kernel launches tfgnn_batch_assemble has enqueued in this process: out[0]; further slots are zero */

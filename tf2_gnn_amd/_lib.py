@@ -344,6 +344,7 @@ _SIGNATURES += [
 ]
 BATCH_MAX_EDGE_TYPES = 48  # TFGNN_BATCH_MAX_EDGE_TYPES
 BATCH_MAX_COLUMNS = 8  # TFGNN_BATCH_MAX_COLUMNS
+BATCH_MAX_NODE_COLUMNS = 4  # TFGNN_BATCH_MAX_NODE_COLUMNS
 
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
 ABI_VERSION = 5  # include/tfgnn.h TFGNN_ABI_VERSION
@@ -415,7 +416,8 @@ class BatchAssembleArgs(ctypes.Structure):
         ("edges", c_void_p), ("columns", c_void_p), ("order_len", c_int64), ("order", c_void_p), ("pos_node_ptr", c_void_p),
         ("pos_edge_ptr", c_void_p), ("p0", c_int64), ("p1", c_int64), ("num_nodes", c_int64), ("num_edges", c_void_p),
         ("node_features", c_void_p), ("node_to_graph_map", c_void_p), ("adjacency_lists", c_void_p), ("column_out", c_void_p),
-        ("bad_flag", c_void_p),
+        ("bad_flag", c_void_p), ("num_node_columns", c_int), ("node_column_widths", c_void_p), ("node_columns", c_void_p),
+        ("node_column_out", c_void_p),
     ]
 
 

@@ -5,3 +5,5 @@ from .graph_dataset import (DataFold, EpochPlan, FoldStore, GraphDataset, Packed
                             plan_batches)
 from .jsonl_graph_dataset import JsonLGraphDataset
 from .jsonl_graph_property_dataset import GraphWithPropertySample, JsonLGraphPropertyDataset
+from .ppi_dataset import PPIDataset, PPIGraphSample
+from .qm9_dataset import QM9Dataset, QM9GraphSample

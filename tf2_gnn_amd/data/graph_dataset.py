@@ -46,9 +46,10 @@ class PackedFold:
 
     ``node_counts`` int64 [N]; ``features`` float32 [sum V, F]; per processed edge type ``edge_counts[t]`` int64 [N] and
     ``edges[t]`` int32 [sum E_t, 2] (graph-local node ids, each graph's edges in the reference's order); ``columns``: name ->
-    float32 [N], one value per graph (labels)."""
+    float32 [N], one value per graph (labels); ``node_columns``: name -> float32 [sum V, W], one row per node, laid out like
+    ``features``, every column with its own width (per-node labels)."""
 
-    def __init__(self, node_counts, features, edge_counts, edges, columns=None):
+    def __init__(self, node_counts, features, edge_counts, edges, columns=None, node_columns=None):
         self.node_counts = np.asarray(node_counts, dtype=np.int64).reshape(-1)
         self.features = np.ascontiguousarray(features, dtype=np.float32)
         if self.features.ndim != 2:
@@ -56,6 +57,10 @@ class PackedFold:
         self.edge_counts = [np.asarray(c, dtype=np.int64).reshape(-1) for c in edge_counts]
         self.edges = [np.ascontiguousarray(e, dtype=np.int32).reshape(-1, 2) for e in edges]
         self.columns = {k: np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for k, v in (columns or {}).items()}
+        self.node_columns = {}
+        for k, v in (node_columns or {}).items():
+            v = np.ascontiguousarray(v, dtype=np.float32)
+            self.node_columns[k] = v.reshape(-1, 1) if v.ndim == 1 else v
         N = self.num_graphs
         self.node_ptr = _prefix(self.node_counts)
         self.edge_ptr = [_prefix(c) for c in self.edge_counts]
@@ -71,6 +76,13 @@ class PackedFold:
         for k, v in self.columns.items():
             if v.shape[0] != N:
                 raise ValueError(f"column {k!r} needs one value per graph")
+        for k, v in self.node_columns.items():
+            if k in self.columns:
+                raise ValueError(f"{k!r} is both a per-graph column and a node column")
+            if v.ndim != 2 or v.shape[0] != self.features.shape[0]:
+                raise ValueError(f"node column {k!r} needs one row per node: [{self.features.shape[0]}, W], not {list(v.shape)}")
+            if v.shape[1] < 1:
+                raise ValueError(f"node column {k!r} needs a width >= 1")
 
     @property
     def num_graphs(self) -> int:
@@ -85,8 +97,9 @@ class PackedFold:
 
     @classmethod
     def from_samples(cls, samples: Sequence[Any], num_edge_types: int, columns: Optional[Dict[str, Any]] = None,
-                     feature_dim: Optional[int] = None) -> "PackedFold":
-        """Pack already processed graph samples (anything with ``node_features`` and ``adjacency_lists``)."""
+                     feature_dim: Optional[int] = None, node_columns: Optional[Dict[str, Any]] = None) -> "PackedFold":
+        """Pack already processed graph samples (anything with ``node_features`` and ``adjacency_lists``).  ``node_columns``
+        are given for the whole fold, the graphs' rows end to end."""
         feats = [np.asarray(s.node_features, dtype=np.float32) for s in samples]
         node_counts = np.array([len(f) for f in feats], dtype=np.int64)
         if feature_dim is None:
@@ -98,12 +111,12 @@ class PackedFold:
             per_graph = [np.asarray(s.adjacency_lists[t], dtype=np.int32).reshape(-1, 2) for s in samples]
             edge_counts.append(np.array([a.shape[0] for a in per_graph], dtype=np.int64))
             edges.append(np.concatenate(per_graph) if per_graph else np.zeros((0, 2), dtype=np.int32))
-        return cls(node_counts, features, edge_counts, edges, columns)
+        return cls(node_counts, features, edge_counts, edges, columns, node_columns)
 
     @classmethod
     def from_raw_graphs(cls, node_features: Sequence[Any], raw_adjacency_lists: Sequence[Sequence[Any]], num_fwd_edge_types: int,
                         add_self_loop_edges: bool, tied_fwd_bkwd_edge_types: Set[int], columns: Optional[Dict[str, Any]] = None,
-                        feature_dim: Optional[int] = None) -> "PackedFold":
+                        feature_dim: Optional[int] = None, node_columns: Optional[Dict[str, Any]] = None) -> "PackedFold":
         """Pack raw graphs and process their edge lists for the whole fold at once - what process_adjacency_lists
         (tf2_gnn/data/utils.py:9-58) does per graph: a tied forward type is followed, within each graph, by its flipped
         edges; the other forward types get fresh backward types behind all forward types, in forward-type order; the self
@@ -144,7 +157,7 @@ class PackedFold:
             edge_counts.insert(0, node_counts.copy())
             edges.insert(0, np.stack([local, local], axis=1).astype(np.int32))
         assert len(node_counts) == N
-        return cls(node_counts, features, edge_counts, edges, columns)
+        return cls(node_counts, features, edge_counts, edges, columns, node_columns)
 
     @classmethod
     def concatenate(cls, folds: Sequence["PackedFold"]) -> "PackedFold":
@@ -156,12 +169,15 @@ class PackedFold:
         for f in folds:
             if f.num_edge_types != L or set(f.columns) != set(first.columns) or (f.features.shape[0] and f.features.shape[1] != F):
                 raise ValueError("the parts of a fold disagree on edge types, feature width or columns")
+            if {k: v.shape[1] for k, v in f.node_columns.items()} != {k: v.shape[1] for k, v in first.node_columns.items()}:
+                raise ValueError("the parts of a fold disagree on node columns or their widths")
         return cls(
             np.concatenate([f.node_counts for f in folds]),
             np.concatenate([f.features.reshape(f.features.shape[0], F) for f in folds]),
             [np.concatenate([f.edge_counts[t] for f in folds]) for t in range(L)],
             [np.concatenate([f.edges[t] for f in folds]) for t in range(L)],
             {k: np.concatenate([f.columns[k] for f in folds]) for k in first.columns},
+            {k: np.concatenate([f.node_columns[k] for f in folds]) for k in first.node_columns},
         )
 
     def sample(self, i: int) -> GraphSample:
@@ -182,13 +198,16 @@ class PackedFold:
 class FoldStore:
     """A PackedFold on the device - the fold store of tfgnn_batch_assemble (include/tfgnn.h): ``node_ptr`` int32 [N + 1],
     ``features`` float32 [sum V, F], per type ``edge_ptr[t]`` int32 [N + 1] and ``edges[t]`` int32 [sum E_t, 2], per column a
-    float32 [N].  The per-graph counts stay on the host (``fold``), so planning an epoch reads nothing back."""
+    float32 [N], per node column a float32 [sum V, W].  The per-graph counts stay on the host (``fold``), so planning an epoch
+    reads nothing back."""
 
     def __init__(self, fold: PackedFold, device=None):
         if fold.features.shape[1] < 1:
             raise ValueError("a fold store needs node features of width >= 1")
         if fold.num_edge_types > _lib.BATCH_MAX_EDGE_TYPES or len(fold.columns) > _lib.BATCH_MAX_COLUMNS:
             raise ValueError(f"at most {_lib.BATCH_MAX_EDGE_TYPES} edge types and {_lib.BATCH_MAX_COLUMNS} per-graph columns")
+        if len(fold.node_columns) > _lib.BATCH_MAX_NODE_COLUMNS:
+            raise ValueError(f"at most {_lib.BATCH_MAX_NODE_COLUMNS} node columns")
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.fold = fold
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
@@ -198,11 +217,16 @@ class FoldStore:
         self.edges = [up(e) for e in fold.edges]
         self.column_names = list(fold.columns)
         self.columns = [up(fold.columns[k]) for k in self.column_names]
-        L, C = len(self.edges), len(self.columns)
+        self.node_column_names = list(fold.node_columns)
+        self.node_columns = [up(fold.node_columns[k]) for k in self.node_column_names]
+        self.node_column_widths = [int(t.shape[1]) for t in self.node_columns]
+        L, C, NC = len(self.edges), len(self.columns), len(self.node_columns)
         # host pointer tables of the argument struct; they live as long as the store
         self._edge_ptr_tab = (ctypes.c_void_p * max(L, 1))(*[t.data_ptr() for t in self.edge_ptr])
         self._edges_tab = (ctypes.c_void_p * max(L, 1))(*[t.data_ptr() for t in self.edges])
         self._columns_tab = (ctypes.c_void_p * max(C, 1))(*[t.data_ptr() for t in self.columns])
+        self._node_columns_tab = (ctypes.c_void_p * max(NC, 1))(*[t.data_ptr() for t in self.node_columns])
+        self._node_column_widths_tab = (ctypes.c_int64 * max(NC, 1))(*self.node_column_widths)
 
     @property
     def num_graphs(self) -> int:
@@ -294,25 +318,30 @@ def assemble_batch(plan: EpochPlan, p0: int, p1: int, out: Optional[Dict[str, An
                    bad_flag: Optional[torch.Tensor] = None) -> Tuple[Dict[str, Any], Dict[str, Any]]:
     """The batch of positions [p0, p1) of ``plan`` -> (batch_features, batch_labels), by one tfgnn_batch_assemble call on the
     current stream.  ``out`` may bring the output tensors (node_features [V, F], node_to_graph_map [V], adjacency_list_<t>
-    [E_t, 2], one [G] per column name), ``bad_flag`` a zeroed int32 [1]; what is missing is allocated here (two allocations)."""
+    [E_t, 2], one [G] per column name, one [V, W] per node column name), ``bad_flag`` a zeroed int32 [1]; what is missing is
+    allocated here (two allocations).  The node columns come back in ``batch_labels`` next to the per-graph columns."""
     store = plan.store
     L, C, F = store.num_edge_types, len(store.columns), store.feature_dim
+    NC, widths = len(store.node_columns), store.node_column_widths
     V, E = plan.sizes(p0, p1)
     G = p1 - p0
     dev = store.device
     if out is None:
         ints = _carve([2 * e for e in E] + [V], torch.int32, dev)
-        floats = _carve([V * F] + [G] * C, torch.float32, dev)
+        floats = _carve([V * F] + [G] * C + [V * w for w in widths], torch.float32, dev)
         out = {"node_features": floats[0].view(V, F), "node_to_graph_map": ints[L]}
         for t in range(L):
             out[f"adjacency_list_{t}"] = ints[t].view(E[t], 2)
         for c, name in enumerate(store.column_names):
             out[name] = floats[1 + c]
+        for c, name in enumerate(store.node_column_names):
+            out[name] = floats[1 + C + c].view(V, widths[c])
     if bad_flag is None:
         bad_flag = torch.zeros(1, dtype=torch.int32, device=dev)
     nf, n2g = out["node_features"], out["node_to_graph_map"]
     adj = [out[f"adjacency_list_{t}"] for t in range(L)]
     cols = [out[name] for name in store.column_names]
+    node_cols = [out[name] for name in store.node_column_names]
     if tuple(nf.shape) != (V, F) or nf.dtype != torch.float32 or not nf.is_contiguous() or n2g.numel() != V or n2g.dtype != torch.int32:
         raise ValueError("node_features / node_to_graph_map outputs have the wrong shape or type")
     for t, a in enumerate(adj):
@@ -321,6 +350,9 @@ def assemble_batch(plan: EpochPlan, p0: int, p1: int, out: Optional[Dict[str, An
     for c in cols:
         if c.numel() != G or c.dtype != torch.float32 or not c.is_contiguous():
             raise ValueError("a column output must be a contiguous float32 [G]")
+    for name, w, c in zip(store.node_column_names, widths, node_cols):
+        if tuple(c.shape) != (V, w) or c.dtype != torch.float32 or not c.is_contiguous():
+            raise ValueError(f"the {name} output must be a contiguous float32 [{V}, {w}]")
     a = _lib.BatchAssembleArgs()
     a.struct_size = ctypes.sizeof(_lib.BatchAssembleArgs)
     a.num_edge_types, a.num_columns = L, C
@@ -338,12 +370,20 @@ def assemble_batch(plan: EpochPlan, p0: int, p1: int, out: Optional[Dict[str, An
     col_tab = (ctypes.c_void_p * max(C, 1))(*[t.data_ptr() for t in cols])
     a.num_edges, a.adjacency_lists, a.column_out = ctypes.addressof(num_edges), ctypes.addressof(adj_tab), ctypes.addressof(col_tab)
     a.node_features, a.node_to_graph_map, a.bad_flag = nf.data_ptr(), n2g.data_ptr(), bad_flag.data_ptr()
+    if NC:  # without node columns the four fields stay zero
+        node_col_tab = (ctypes.c_void_p * NC)(*[t.data_ptr() for t in node_cols])
+        a.num_node_columns = NC
+        a.node_column_widths = ctypes.addressof(store._node_column_widths_tab)
+        a.node_columns, a.node_column_out = ctypes.addressof(store._node_columns_tab), ctypes.addressof(node_col_tab)
     _lib.check(_lib.load().tfgnn_batch_assemble(ctypes.byref(a), ops._stream()))
     features: Dict[str, Any] = {"node_features": nf, "node_to_graph_map": n2g, "num_graphs_in_batch": G}
     for t in range(L):
         features[f"adjacency_list_{t}"] = adj[t]
     features["_bad_local_index"] = bad_flag  # device flag, read lazily by ``check_batch``
-    return features, dict(zip(store.column_names, cols))
+    labels = dict(zip(store.column_names, cols))
+    if NC:
+        labels.update(zip(store.node_column_names, node_cols))
+    return features, labels
 
 
 def batch_assemble_launch_counts() -> int:
@@ -369,9 +409,11 @@ class GraphDataset:
     """graph_dataset.py:56-311 on a fold store.  Subclasses load raw data into ``self._loaded_data[fold]`` (a PackedFold) and
     implement ``num_edge_types`` / ``node_feature_shape`` / ``load_data`` / ``load_data_from_list``.
 
-    Where the reference lets subclasses add labels through _new_batch / _add_graph_to_batch / _finalise_batch, there is ONE
-    hook here: ``_extra_graph_columns(datapoints)`` returns per-graph float32 columns (name -> [len(datapoints)]); they are
-    packed with the fold, gathered per batch like ``target_value`` and handed out in ``batch_labels`` under their names."""
+    Where the reference lets subclasses add labels through _new_batch / _add_graph_to_batch / _finalise_batch, there are TWO
+    hooks here.  ``_extra_graph_columns(datapoints)`` returns per-graph float32 columns (name -> [len(datapoints)]); they are
+    packed with the fold, gathered per batch like ``target_value`` and handed out in ``batch_labels`` under their names.
+    ``_extra_node_columns(datapoints)`` returns per-node float32 columns (name -> [sum V, W], the graphs' rows end to end);
+    they travel the same way and come out as [V, W] next to the per-graph columns.  A name appears in only one of the two."""
 
     @classmethod
     def get_default_hyperparameters(cls) -> Dict[str, Any]:
@@ -419,6 +461,10 @@ class GraphDataset:
         """Per-graph float32 label columns of these raw datapoints (see the class docstring); none by default."""
         return {}
 
+    def _extra_node_columns(self, datapoints: List[Dict[str, Any]]) -> Dict[str, np.ndarray]:
+        """Per-node float32 label columns of these raw datapoints, [sum V, W] each (see the class docstring); none by default."""
+        return {}
+
     # ---- folds --------------------------------------------------------------------------------------------------------------
     def _set_fold(self, data_fold: DataFold, fold: PackedFold) -> None:
         self._loaded_data[data_fold] = fold
@@ -464,7 +510,7 @@ class GraphDataset:
     def get_batches(self, data_fold: DataFold, device=None) -> _Batches:
         """Stands where the reference has get_tensorflow_dataset (graph_dataset.py:276-311): a re-iterable; every ``iter()``
         starts a new epoch of ``(batch_features, batch_labels)`` with the reference's keys - device tensors node_features,
-        node_to_graph_map, adjacency_list_<i> (int32 [E, 2]) and the label columns (float32 [G]), a Python int
+        node_to_graph_map, adjacency_list_<i> (int32 [E, 2]) and the label columns (float32 [G]; node columns [V, W]), a Python int
         num_graphs_in_batch, and the ``_bad_local_index`` flag that ``check_batch`` reads."""
         return _Batches(self, data_fold, device)
 

@@ -95,5 +95,6 @@ class JsonLGraphDataset(GraphDataset):
             add_self_loop_edges=self.params["add_self_loop_edges"],
             tied_fwd_bkwd_edge_types=self._tied_fwd_bkwd_edge_types,
             columns=self._extra_graph_columns(datapoints),
+            node_columns=self._extra_node_columns(datapoints),
             feature_dim=None if shape is None else int(shape[0]),
         )

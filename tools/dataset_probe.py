@@ -8,7 +8,11 @@ order, planning and the upload).  Both routes shuffle per epoch.  ``--warmup`` e
 measured; median, minimum and maximum over the measured epochs are printed, and the verdict line compares the medians with
 the per-batch route's own epoch-to-epoch spread.  Packing and uploading the fold is timed once and reported apart.
 
-    python tools/dataset_probe.py [--epochs 9] [--warmup 3] [--out profiles/dataset_probe.txt]
+``--node-column-width W`` gives every node of the PPI-shaped fold W float32 labels (PPI has 121): the fold store carries them as
+the node column ``node_labels`` and assembles them in the same launch; the per-batch route concatenates the batch's label rows
+on the host and uploads them, one more copy per batch - what the reference's _finalise_batch plus a transfer would do.
+
+    python tools/dataset_probe.py [--epochs 9] [--warmup 3] [--node-column-width 121] [--out profiles/dataset_probe.txt]
 """
 from __future__ import annotations
 
@@ -56,10 +60,10 @@ def ppi_fold(num_graphs, seed=0):
 class _SampleDataset(GraphDataset):
     """a GraphDataset over processed samples: all the probe needs"""
 
-    def __init__(self, params, samples, num_edge_types):
+    def __init__(self, params, samples, num_edge_types, node_columns=None):
         super().__init__(params)
         self._num_edge_types = num_edge_types
-        self._set_fold(DataFold.TRAIN, PackedFold.from_samples(samples, num_edge_types))
+        self._set_fold(DataFold.TRAIN, PackedFold.from_samples(samples, num_edge_types, node_columns=node_columns))
 
     @property
     def num_edge_types(self):
@@ -106,15 +110,34 @@ def _fmt(xs, scale, unit):
     return f"median {statistics.median(xs) * scale:9.3f} {unit}  min {min(xs) * scale:9.3f}  max {max(xs) * scale:9.3f}"
 
 
-def probe(name, samples, num_edge_types, max_nodes, warmup, epochs, dev, out):
+def _with_node_labels(batches, labels, width, dev):
+    """the per-batch route's batches with the label rows of their graphs, concatenated on the host and uploaded"""
+    g = 0
+    for features in batches:
+        G = features["num_graphs_in_batch"]
+        rows = np.concatenate(labels[g:g + G]) if G else np.zeros((0, width), dtype=np.float32)
+        g += G
+        yield features, {"node_labels": torch.from_numpy(rows).to(dev)}
+
+
+def probe(name, samples, num_edge_types, max_nodes, warmup, epochs, dev, out, node_column_width=0):
     samples = list(samples)
+    node_labels = None
+    if node_column_width:
+        rng = np.random.default_rng(0)
+        node_labels = [rng.integers(0, 2, size=(len(s.node_features), node_column_width)).astype(np.float32) for s in samples]
 
     def old_route():
-        np.random.shuffle(samples)
-        return data.graph_batch_iterator_from_graph_iterator(iter(samples), num_edge_types, max_nodes, dev)
+        if node_labels is None:
+            np.random.shuffle(samples)
+            return data.graph_batch_iterator_from_graph_iterator(iter(samples), num_edge_types, max_nodes, dev)
+        order = np.random.permutation(len(samples))
+        batches = data.graph_batch_iterator_from_graph_iterator(iter([samples[i] for i in order]), num_edge_types, max_nodes, dev)
+        return _with_node_labels(batches, [node_labels[i] for i in order], node_column_width, dev)
 
     t0 = time.perf_counter()
-    ds = _SampleDataset({"max_nodes_per_batch": max_nodes}, samples, num_edge_types)
+    ds = _SampleDataset({"max_nodes_per_batch": max_nodes}, samples, num_edge_types,
+                        None if node_labels is None else {"node_labels": np.concatenate(node_labels)})
     ds.fold_store(DataFold.TRAIN, dev)
     torch.cuda.synchronize()
     pack = time.perf_counter() - t0
@@ -125,7 +148,8 @@ def probe(name, samples, num_edge_types, max_nodes, warmup, epochs, dev, out):
     fold = ds.packed_fold(DataFold.TRAIN)
     out(f"{name}: {fold.num_graphs} graphs, {int(fold.node_ptr[-1])} nodes, {num_edge_types} edge types, "
         f"{sum(int(p[-1]) for p in fold.edge_ptr)} edges, F = {fold.features.shape[1]}, max_nodes_per_batch = {max_nodes}, "
-        f"about {nb_old} batches per epoch; {warmup} warm-up + {epochs} measured epochs")
+        f"about {nb_old} batches per epoch; {warmup} warm-up + {epochs} measured epochs"
+        + (f"; node column node_labels of width {node_column_width}" if node_column_width else ""))
     out(f"  pack + upload of the fold, once:        {pack * 1e3:9.3f} ms")
     out(f"  per-batch route  host time per batch:   {_fmt(old_host, 1e6, 'us')}")
     out(f"  fold store       host time per batch:   {_fmt(new_host, 1e6, 'us')}")
@@ -144,6 +168,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--qm9-graphs", type=int, default=8192)
     ap.add_argument("--ppi-graphs", type=int, default=20)
+    ap.add_argument("--node-column-width", type=int, default=0,
+                    help="labels per node of the PPI-shaped fold, carried as a node column (0: none; PPI has 121)")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "dataset_probe needs a ROCm device"
@@ -159,7 +185,7 @@ def main():
     samples, L = qm9_fold(args.qm9_graphs)
     probe("QM9-shaped", samples, L, 10000, args.warmup, args.epochs, dev, out)
     samples, L = ppi_fold(args.ppi_graphs)
-    probe("PPI-shaped", samples, L, 8000, args.warmup, args.epochs, dev, out)
+    probe("PPI-shaped", samples, L, 8000, args.warmup, args.epochs, dev, out, node_column_width=args.node_column_width)
     if args.out:
         Path(args.out).parent.mkdir(parents=True, exist_ok=True)
         Path(args.out).write_text("\n".join(lines) + "\n")
