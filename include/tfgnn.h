@@ -183,7 +183,10 @@ typedef enum {
   /* the same order for the by-SOURCE buckets (also part DST_PATTERN; round 5): the input-gradient product over the by-source
    * sums reads its operand rows through NODE_BY_SRC (tfgnn_sp_gemm_nt_rows d_a_rows) and skips a tile's all-zero blocks */
   TFGNN_G_PATTERN_NODE_BY_SRC = 30,     /* int32 [V]: position -> node */
-  TFGNN_G_PATTERN_TILEMASK_BY_SRC = 31  /* uint8 [ceil(V/128)] */
+  TFGNN_G_PATTERN_TILEMASK_BY_SRC = 31, /* uint8 [ceil(V/128)] */
+  /* debugging aid: the arrival counters of the gathers over view v = id - 32 (tfgnn_graph_view 0 - 3), int32
+   * [multi-item rows of the view's plan x 8]; every entry is 0 whenever no gather over that view is in flight */
+  TFGNN_G_GATHER_ARRIVALS_VIEW0 = 32
 } tfgnn_graph_array_id;
 
 /* Borrow a device array owned by the handle (valid until tfgnn_graph_destroy). */
@@ -228,15 +231,21 @@ int tfgnn_csr_gather_reduce(const int32_t* d_rowptr, const int32_t* d_col,
                             void* stream);
 
 /* The same reduction over one of the graph handle's four bucketed views, with the handle's plan for
- * long rows (rows with more than 32 edges are cut into 256-edge items, one workgroup each, combined
- * deterministically) - the form the layers use:
+ * long rows (rows with more than 32 edges are cut into 512-edge items, one workgroup each; the partial sums of a row
+ * made of several items are added in item order by the item workgroup of the row that finishes last, inside the same
+ * launch) - the form the layers use:
  *   TFGNN_VIEW_BY_DST_TYPED  rows (v,l) -> col = source             (aggregate-first forward)
  *   TFGNN_VIEW_BY_DST_NODE   rows v     -> col = source*L + type    (transform-first forward, RGAT)
  *   TFGNN_VIEW_BY_SRC_TYPED  rows (u,l) -> col = target             (backward: scatter by source)
  *   TFGNN_VIEW_BY_SRC_NODE   rows u     -> col = target*L + type
  * d_col_override (nullable) replaces the view's column array (same edge order).  d_edge_weight is
  * [E] (ew_heads == 1) or [E, ew_heads] applied per head of width/ew_heads floats (RGAT attention,
- * rgat.py:154-160).  d_workspace must hold tfgnn_graph_gather_workspace_bytes(graph, view, width). */
+ * rgat.py:154-160).  d_workspace must hold tfgnn_graph_gather_workspace_bytes(graph, view, width).
+ * CONCURRENCY: the item workgroups of a long row count their arrivals in the handle (one counter set per view 0 - 3; views
+ * 4 - 6 use the counters of the typed view they are made of).  Two gathers over the same view of the same handle must
+ * therefore not be in flight at once on different streams; gathers on one stream, over different views, or over
+ * different handles need no care.  This holds for every tfgnn_graph_gather_* function and for tfgnn_mp_forward /
+ * tfgnn_mp_backward, which gather over views 0 / 6 and 2. */
 typedef enum {
   TFGNN_VIEW_BY_DST_TYPED = 0,
   TFGNN_VIEW_BY_DST_NODE = 1,
@@ -801,7 +810,7 @@ int tfgnn_sp_gemm_nt_dropout(int64_t M, int64_t N, int64_t K, const void* d_A_sp
  * tfgnn_sp_gemm_tn_workspace_bytes bytes. */
 /* ---- small passes that share a launch ------------------------------------------------------------------------------
  * Around the big kernels of a layer sit passes of 5-15 us each that are bound by launch and dependent-load latency, not by
- * work: weight matrices into SP16 form, the combine pass of the gather's long buckets.  A `tfgnn_aux_job` describes one of
+ * work: weight matrices into SP16 form, the column maxima of a long one.  A `tfgnn_aux_job` describes one of
  * them; tfgnn_aux_launch runs up to 8 per launch (more: several launches), every job on its own workgroups - the launch
  * takes as long as its longest job.  Jobs of one call must be independent of each other.  The *_job / *_deferred functions FILL a job (host memory, nothing is launched for it) with exactly the
  * work the function of the same name without the suffix would have launched; a job holds device pointers - keep the
@@ -826,7 +835,8 @@ size_t tfgnn_sp_split_cols_two_pass_bytes(int64_t K, int64_t N);
 int tfgnn_sp_split_cols_jobs(const float* d_src, int64_t ld, int64_t K, int64_t N, void* d_sp, int64_t ld_sp_bytes,
                              float* d_inv_scale, float* d_colmax_workspace, size_t workspace_bytes, tfgnn_aux_job* maxima_job,
                              tfgnn_aux_job* split_job);
-/* tfgnn_graph_gather_reduce_sp; the combine pass of the long buckets comes back in *combine_job (kind 0: none) */
+/* tfgnn_graph_gather_reduce_sp.  *combine_job used to receive the combine pass of the long buckets; the gather now combines
+ * them inside its own launch, so the job always comes back empty (kind 0).  Kept for callers written against that form. */
 int tfgnn_graph_gather_reduce_sp_deferred(const tfgnn_graph* graph, int view, const int32_t* d_col_override,
                                           const float* d_edge_weight, const float* d_row_scale, const float* d_in,
                                           int64_t ld_in, int width, void* d_out_sp, int64_t ld_out_sp_bytes,
@@ -948,7 +958,10 @@ typedef struct tfgnn_mp_forward_args {
   int64_t ldx;
   int in_dim, hidden_dim;
   const float* row_scale;   /* [V * L] factor per (node, type) bucket - 1 / (c + 1e-7), tfgnn_graph_scales - or NULL */
-  const float* w;           /* stacked kernels [L * D, H] row-major: non-NULL = (re)build the operand below from them */
+  const float* w;           /* stacked kernels [L * D, H] row-major: non-NULL = (re)build the operand below from them (a
+                             * small-pass launch between the gather and the product).  A stack of layers does better to
+                             * split all its stale weights in ONE tfgnn_aux_launch at the start of the pass - the weights do
+                             * not change before the optimizer update - and to pass NULL here */
   void* wt_sp;              /* W^T as SP16 [H, L * D] (row pitch ld_wt_sp_bytes) + wt_inv_scale [H]: kept by the caller */
   int64_t ld_wt_sp_bytes;   /*   across calls while the kernels do not change                                          */
   float* wt_inv_scale;

@@ -58,11 +58,6 @@ __global__ void __launch_bounds__(256) aux_jobs_kernel(AuxJobTable table) {
       col_absmax_body(a, b);
       break;
     }
-    case AUX_COMBINE_SP: {
-      const AuxCombineSp a = aux_payload<AuxCombineSp>(j);
-      combine_sp_body(a, b);
-      break;
-    }
     default:
       break;
   }
@@ -80,7 +75,7 @@ extern "C" int tfgnn_aux_launch(const tfgnn_aux_job* jobs, int num_jobs, void* s
     while (i < num_jobs && t.n < AUX_MAX_JOBS) {
       const tfgnn_aux_job& j = jobs[i++];
       if (j.kind == AUX_NONE || j.num_blocks == 0) continue;
-      TFGNN_REQUIRE(j.kind == AUX_SPLIT_ROWS || j.kind == AUX_SPLIT_COLS || j.kind == AUX_COMBINE_SP || j.kind == AUX_COL_ABSMAX,
+      TFGNN_REQUIRE(j.kind == AUX_SPLIT_ROWS || j.kind == AUX_SPLIT_COLS || j.kind == AUX_COL_ABSMAX,
                     "tfgnn_aux_launch: unknown job kind %d", j.kind);
       t.j[t.n++] = j;
       blocks += j.num_blocks;

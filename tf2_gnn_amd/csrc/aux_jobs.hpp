@@ -1,7 +1,6 @@
 // Small passes that ride together in ONE launch (tfgnn_aux_launch): the per-step preparation and finishing work around the
-// big kernels of a layer - splitting a weight matrix into SP16 operand form, combining the partial sums of the gather's
-// multi-item buckets - is a handful of kernels of 5-15 us each, every one
-// of them bound by launch + dependent-load latency, not by work.  Merged, the launch costs what its longest job costs.
+// big kernels of a layer - splitting a weight matrix into SP16 operand form, the column maxima of a long one - is a handful
+// of kernels of 5-15 us each, every one of them bound by launch + dependent-load latency, not by work.  Merged, the launch costs what its longest job costs.
 // A job = (kind, number of 256-thread workgroups, payload); the kernel finds a workgroup's job from blockIdx.x by walking the
 // table in the kernel-argument segment (scalar loads; no table in device memory, no copy command).
 #pragma once
@@ -15,8 +14,9 @@
 
 namespace tfgnn {
 
-// (3 and 5 were the reduction and factor pass of a weight-gradient product; they stay unused)
-enum AuxKind { AUX_NONE = 0, AUX_SPLIT_ROWS = 1, AUX_SPLIT_COLS = 2, AUX_COMBINE_SP = 4, AUX_COL_ABSMAX = 6 };
+// (3 and 5 were the reduction and factor pass of a weight-gradient product, 4 the combine pass of the gather's multi-item
+// buckets, which the gather now does inside its own launch - spmm.hip finish_multi_row; they stay unused)
+enum AuxKind { AUX_NONE = 0, AUX_SPLIT_ROWS = 1, AUX_SPLIT_COLS = 2, AUX_COL_ABSMAX = 6 };
 
 struct AuxSplitRows {
   const float* src;
@@ -63,20 +63,7 @@ struct AuxTnReduce {
   int64_t slab;
   int ref_ld;  // 0: one reference scale per block (ref[blk]); > 0: one per (split, block) at ref[z * ref_ld + blk]
 };
-struct AuxCombineSp {
-  const int32_t *multi_row, *multi_base, *multi_n;
-  int num_multi;
-  const float* row_scale;
-  const float* partial;
-  int width;
-  const int32_t* out_row_map;
-  uint8_t* out_sp;
-  int64_t ld_out_sp;
-  float* inv_out;
-  const float* fixed_inv;
-};
-static_assert(sizeof(AuxSplitRows) <= sizeof(((tfgnn_aux_job*)0)->payload) && sizeof(AuxSplitCols) <= sizeof(((tfgnn_aux_job*)0)->payload) &&
-                  sizeof(AuxCombineSp) <= sizeof(((tfgnn_aux_job*)0)->payload),
+static_assert(sizeof(AuxSplitRows) <= sizeof(((tfgnn_aux_job*)0)->payload) && sizeof(AuxSplitCols) <= sizeof(((tfgnn_aux_job*)0)->payload),
               "tfgnn_aux_job payload too small");
 
 template <class P>
@@ -305,56 +292,6 @@ __device__ __forceinline__ void sp_tn_reduce_body(const AuxTnReduce& a, unsigned
     const int64_t gi = m / a.group_rows, mi = m - gi * a.group_rows;
     float* dst = a.C + gi * a.stride_group + mi * a.stride_row + n * a.stride_col;
     *dst = a.accumulate ? *dst + s : s;
-  }
-}
-
-// ---- partial sums of the gather's multi-item buckets -> SP16 rows: one wave per bucket (width <= 2048 floats) ------------
-__device__ __forceinline__ void combine_sp_body(const AuxCombineSp& a, unsigned block) {
-  const int m = (int)block * 4 + (threadIdx.x >> 6);
-  if (m >= a.num_multi) return;
-  const int lane = threadIdx.x & 63;
-  const int64_t row = a.multi_row[m];
-  const int32_t base = a.multi_base[m], n = a.multi_n[m];
-  const float rs = a.row_scale ? a.row_scale[row] : 1.f;
-  float4 sum[8];
-  float mx = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int c = (lane + i * 64) * 4;
-    sum[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c < a.width) {
-      int k = 0;
-      for (; k + 4 <= n; k += 4) {  // four partial rows in flight; the sum stays in item order
-        float4 p[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) p[u] = *reinterpret_cast<const float4*>(a.partial + (int64_t)(base + k + u) * a.width + c);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { sum[i].x += p[u].x; sum[i].y += p[u].y; sum[i].z += p[u].z; sum[i].w += p[u].w; }
-      }
-      for (; k < n; ++k) {
-        const float4 p = *reinterpret_cast<const float4*>(a.partial + (int64_t)(base + k) * a.width + c);
-        sum[i].x += p.x; sum[i].y += p.y; sum[i].z += p.z; sum[i].w += p.w;
-      }
-      sum[i].x *= rs; sum[i].y *= rs; sum[i].z *= rs; sum[i].w *= rs;
-      mx = fmaxf(mx, fmaxf(fmaxf(fabsf(sum[i].x), fabsf(sum[i].y)), fmaxf(fabsf(sum[i].z), fabsf(sum[i].w))));
-    }
-  }
-  const int64_t orow = a.out_row_map ? a.out_row_map[row] : row;
-  float iv, sc;
-  if (a.fixed_inv) {
-    iv = a.fixed_inv[0];
-    sc = 1.f / iv;
-  } else {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    sc = sp_scale_for_max(mx, &iv);
-    if (lane == 0) a.inv_out[orow] = iv;
-  }
-  uint8_t* drow = a.out_sp + orow * a.ld_out_sp;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int c = (lane + i * 64) * 4;
-    if (c < a.width) sp_store4(drow, c, sum[i], sc);
   }
 }
 

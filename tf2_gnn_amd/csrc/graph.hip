@@ -400,7 +400,8 @@ struct PlanJob {
   int64_t R;
   int thr, chunk;
   int32_t* counters;  // {items, multi-item rows, partial slots, short rows}
-  int32_t *item_row, *item_chunk, *item_slot, *multi_row, *multi_base, *multi_n;
+  int32_t *item_row, *item_chunk, *item_slot, *item_multi, *multi_row, *multi_base, *multi_n;
+  uint32_t* arrive;
   int32_t *bin_count, *bin_cursor, *short_rows;
   int want_items;  // E > 0
 };
@@ -411,25 +412,28 @@ struct PlanJobs {
 __device__ __forceinline__ void plan_rows_body(const int32_t* __restrict__ rowptr, int64_t R, int long_threshold, int chunk_edges,
                                  int32_t* __restrict__ counters,
                                  int32_t* __restrict__ item_row, int32_t* __restrict__ item_chunk,
-                                 int32_t* __restrict__ item_slot, int32_t* __restrict__ multi_row,
-                                 int32_t* __restrict__ multi_base, int32_t* __restrict__ multi_n) {
+                                 int32_t* __restrict__ item_slot, int32_t* __restrict__ item_multi,
+                                 int32_t* __restrict__ multi_row, int32_t* __restrict__ multi_base,
+                                 int32_t* __restrict__ multi_n, uint32_t* __restrict__ arrive) {
   for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < R; r += (int64_t)gridDim.x * blockDim.x) {
     const int32_t len = rowptr[r + 1] - rowptr[r];
     if (len <= long_threshold) continue;
     const int32_t n = (len + chunk_edges - 1) / chunk_edges;
     const int32_t base = atomicAdd(&counters[0], n);
-    int32_t pb = -1;
+    int32_t pb = -1, m = -1;
     if (n > 1) {
-      const int32_t m = atomicAdd(&counters[1], 1);
+      m = atomicAdd(&counters[1], 1);
       pb = atomicAdd(&counters[2], n);
       multi_row[m] = (int32_t)r;
       multi_base[m] = pb;
       multi_n[m] = n;
+      for (int w = 0; w < ARRIVE_WINDOWS; ++w) arrive[(size_t)m * ARRIVE_WINDOWS + w] = 0u;  // the gathers' arrival counters
     }
     for (int32_t i = 0; i < n; ++i) {
       item_row[base + i] = (int32_t)r;
       item_chunk[base + i] = i;
       item_slot[base + i] = n > 1 ? pb + i : -1;
+      item_multi[base + i] = m;
     }
   }
 }
@@ -465,8 +469,8 @@ __global__ void __launch_bounds__(256) plan_hist_kernel(PlanJobs jobs) {
   if ((blockIdx.y >> 1) == 0) {
     short_hist_body(j.rowptr, j.R, j.thr, j.bin_count, j.counters + 3, h, n_short);
   } else if (j.want_items) {
-    plan_rows_body(j.rowptr, j.R, j.thr, j.chunk, j.counters, j.item_row, j.item_chunk, j.item_slot, j.multi_row, j.multi_base,
-                   j.multi_n);
+    plan_rows_body(j.rowptr, j.R, j.thr, j.chunk, j.counters, j.item_row, j.item_chunk, j.item_slot, j.item_multi, j.multi_row,
+                   j.multi_base, j.multi_n, j.arrive);
   }
 }
 
@@ -838,8 +842,8 @@ int build_plans(tfgnn_graph* g, int node_views, int32_t* counters, int32_t* bins
     j.thr = pl.long_threshold;
     j.chunk = pl.item_chunk_edges;
     j.counters = counters + 16 + 4 * v;
-    j.item_row = pl.item_row; j.item_chunk = pl.item_chunk; j.item_slot = pl.item_slot;
-    j.multi_row = pl.multi_row; j.multi_base = pl.multi_base; j.multi_n = pl.multi_n;
+    j.item_row = pl.item_row; j.item_chunk = pl.item_chunk; j.item_slot = pl.item_slot; j.item_multi = pl.item_multi;
+    j.multi_row = pl.multi_row; j.multi_base = pl.multi_base; j.multi_n = pl.multi_n; j.arrive = pl.arrive;
     j.bin_count = bins + (size_t)v * 2 * SHORT_BINS;
     j.bin_cursor = j.bin_count + SHORT_BINS;
     j.short_rows = pl.short_rows;
@@ -1080,10 +1084,11 @@ static int graph_create_impl(int num_edge_types, int64_t num_nodes, const int32_
   const int min_long = std::min(std::min(view_long[0], view_long[1]), std::min(view_long[2], view_long[3]));
   const int min_chunk = std::min(std::min(view_chunk[0], view_chunk[1]), std::min(view_chunk[2], view_chunk[3]));
   const size_t max_items = (size_t)(E / min_long + 1), max_multi = (size_t)(E / min_chunk + 1);
-  size_t o_item[4][3], o_multi[4][3];
+  size_t o_item[4][4], o_multi[4][3], o_arrive[4];
   for (int v = 0; v < 4; ++v) {
-    for (int k = 0; k < 3; ++k) o_item[v][k] = plan.take(max_items * 4);
+    for (int k = 0; k < 4; ++k) o_item[v][k] = plan.take(max_items * 4);
     for (int k = 0; k < 3; ++k) o_multi[v][k] = plan.take(max_multi * 4);
+    o_arrive[v] = plan.take(max_multi * ARRIVE_WINDOWS * 4);
   }
   size_t o_short[4];
   for (int v = 0; v < 4; ++v) o_short[v] = plan.take((size_t)((v & 1) ? V : R) * 4 + 4);
@@ -1170,6 +1175,8 @@ static int graph_create_impl(int num_edge_types, int64_t num_nodes, const int32_
     pl.item_row = (int32_t*)(slab + o_item[v][0]);
     pl.item_chunk = (int32_t*)(slab + o_item[v][1]);
     pl.item_slot = (int32_t*)(slab + o_item[v][2]);
+    pl.item_multi = (int32_t*)(slab + o_item[v][3]);
+    pl.arrive = (uint32_t*)(slab + o_arrive[v]);
     pl.multi_row = (int32_t*)(slab + o_multi[v][0]);
     pl.multi_base = (int32_t*)(slab + o_multi[v][1]);
     pl.multi_n = (int32_t*)(slab + o_multi[v][2]);
@@ -1479,6 +1486,8 @@ extern "C" int tfgnn_graph_array(const tfgnn_graph* g, int array_id, const void*
     if (array_id == TFGNN_G_EID_BY_DST || array_id == TFGNN_G_EID_BY_SRC) need = TFGNN_GRAPH_PART_EDGE_IDS;
     if (array_id >= TFGNN_G_PATTERN_POS_BY_DST && array_id <= TFGNN_G_PATTERN_TILEMASK_BY_SRC) need = TFGNN_GRAPH_PART_DST_PATTERN;
     if (array_id >= TFGNN_G_NZ_CPOS_BY_DST && array_id <= TFGNN_G_NZ_COL_BY_SRC) need = TFGNN_GRAPH_PART_COMPACT;
+    if (array_id >= TFGNN_G_GATHER_ARRIVALS_VIEW0 && array_id <= TFGNN_G_GATHER_ARRIVALS_VIEW0 + 3)
+      need = ((array_id - TFGNN_G_GATHER_ARRIVALS_VIEW0) & 1) ? TFGNN_GRAPH_PART_PLAN_NODE : TFGNN_GRAPH_PART_PLAN_TYPED;
     if (need) {
       const int rc = tfgnn::graph_require_parts(g, need, "tfgnn_graph_array");
       if (rc) return rc;
@@ -1517,6 +1526,11 @@ extern "C" int tfgnn_graph_array(const tfgnn_graph* g, int array_id, const void*
       *d_ptr = g->compact[array_id >= TFGNN_G_NZ_CPOS_BY_SRC].nodeptr_nz; *count = g->V + 1; break;
     case TFGNN_G_NZ_COL_BY_DST: case TFGNN_G_NZ_COL_BY_SRC:
       *d_ptr = g->compact[array_id >= TFGNN_G_NZ_CPOS_BY_SRC].col_nz; *count = g->compact[array_id >= TFGNN_G_NZ_CPOS_BY_SRC].num_nz; break;
+    case TFGNN_G_GATHER_ARRIVALS_VIEW0: case TFGNN_G_GATHER_ARRIVALS_VIEW0 + 1: case TFGNN_G_GATHER_ARRIVALS_VIEW0 + 2:
+    case TFGNN_G_GATHER_ARRIVALS_VIEW0 + 3: {
+      const tfgnn::CsrPlan& pl = g->views[array_id - TFGNN_G_GATHER_ARRIVALS_VIEW0].plan;
+      *d_ptr = pl.arrive; *count = (int64_t)pl.num_multi * tfgnn::ARRIVE_WINDOWS; break;
+    }
     default:
       tfgnn::set_error("unknown graph array id %d", array_id);
       return TFGNN_ERR_INVALID_ARGUMENT;

@@ -8,11 +8,14 @@ namespace tfgnn {
 
 // Rows longer than LONG_ROW_THRESHOLD edges are not walked by a single lane group: they are cut
 // into items of ITEM_CHUNK consecutive edges, one workgroup per item (deterministic partial sums,
-// combined in item order).  Keeps the tail of the gather kernel bounded on skewed (R-MAT) graphs.
+// combined in item order by the row's last-arriving item workgroup).  Keeps the tail of the gather
+// kernel bounded on skewed (R-MAT) graphs.
 constexpr int LONG_ROW_THRESHOLD = 32;        // node views (all edge types of a node in one row)
 constexpr int ITEM_CHUNK = 512;
 constexpr int LONG_ROW_THRESHOLD_TYPED = 48;  // typed views (one row per (node, type) bucket)
 constexpr int ITEM_CHUNK_TYPED = 512;
+// arrival counters per multi-item row: feature window w of a launch counts on counter w % ARRIVE_WINDOWS
+constexpr int ARRIVE_WINDOWS = 8;
 
 struct CsrPlan {
   int32_t long_threshold = LONG_ROW_THRESHOLD;  // values the plan was built with (view_plan_parameters)
@@ -23,9 +26,13 @@ struct CsrPlan {
   int32_t* item_row = nullptr;    // [num_items]
   int32_t* item_chunk = nullptr;  // [num_items] chunk index within the row
   int32_t* item_slot = nullptr;   // [num_items] scratch slot, or -1: the item is the whole row
+  int32_t* item_multi = nullptr;  // [num_items] index of the item's row in the multi_* tables, or -1
   int32_t* multi_row = nullptr;   // [num_multi]
   int32_t* multi_base = nullptr;  // [num_multi] first scratch slot
   int32_t* multi_n = nullptr;     // [num_multi] number of items
+  // [num_multi][ARRIVE_WINDOWS] item workgroups of the row that have stored their partial sums in the gather launch
+  // in flight (spmm.hip): zero between launches - written as zeros with the multi_* tables, set back by every launch
+  uint32_t* arrive = nullptr;
   // rows of at most long_threshold edges, longest first: the lane groups of a wave get rows of (almost) equal
   // length, so a wave is not held up by its longest row (65 % -> ~100 % lane use on an R-MAT batch)
   int32_t* short_rows = nullptr;  // [num_short]

@@ -12,7 +12,7 @@
 // i.e. the reference's message_passing.py:95-218 + gnn_edge_mlp.py:84-107 for one layer, and its share of
 // tf.GradientTape.gradient (models/graph_task_model.py:347-357).  Host code only: each function walks the launch sequence the
 // Python layer (tf2_gnn_amd/layers/message_passing/gnn_edge_mlp.py: _forward_A / _backward_A_f16x2) used to drive through
-// six to eight op-level calls - the same kernels with the same arguments, so results are bit-identical to the op-level route
+// four to six op-level calls - the same kernels with the same arguments, so results are bit-identical to the op-level route
 // (tests/test_gpu_mp_entry.py) - without Python in between.  A binding from another framework needs
 // these two calls per layer, the graph handle, and the loss.
 #include <cstring>
@@ -36,21 +36,23 @@ extern "C" int tfgnn_mp_forward(const tfgnn_mp_forward_args* a, void* stream) {
   if (rc) return rc;
   const int64_t D = a->in_dim, H = a->hidden_dim, K = (int64_t)L * D;
   TFGNN_REQUIRE(V > 0 && L > 0 && D > 0 && H > 0, "tfgnn_mp_forward: empty layer");
-  tfgnn_aux_job own[2];
-  std::memset(own, 0, sizeof(own));
-  // 1. the aggregate, one SP16 row of L blocks per node (one scale per (node, type) bucket)
-  rc = tfgnn_graph_gather_reduce_sp_deferred(a->graph, a->view, nullptr, nullptr, a->row_scale, a->x, a->ldx, (int)D, a->agg_sp,
-                                             D * 4, a->agg_inv_scale, nullptr, a->workspace, a->workspace_bytes, &own[0], stream);
+  // 1. the aggregate, one SP16 row of L blocks per node (one scale per (node, type) bucket); buckets cut into several items
+  //    are combined inside the gather's launch
+  rc = tfgnn_graph_gather_reduce_sp(a->graph, a->view, nullptr, nullptr, a->row_scale, a->x, a->ldx, (int)D, a->agg_sp, D * 4,
+                                    a->agg_inv_scale, nullptr, a->workspace, a->workspace_bytes, stream);
   if (rc) return rc;
-  // 2. W^T as the [H, L * D] operand, when the caller's copy is stale (once per weight value)
+  // 2. W^T as the [H, L * D] operand, when the caller's copy is stale: a small-pass launch of its own.  A layer stack
+  //    splits all its weights at the start of the pass instead (they do not change before the optimizer update) and hands
+  //    in w = NULL: nothing is launched between the gather and the product
   if (a->w) {
-    rc = tfgnn_sp_split_cols_job(a->w, H, K, H, a->wt_sp, a->ld_wt_sp_bytes, a->wt_inv_scale, &own[1]);
+    tfgnn_aux_job job;
+    std::memset(&job, 0, sizeof(job));
+    rc = tfgnn_sp_split_cols_job(a->w, H, K, H, a->wt_sp, a->ld_wt_sp_bytes, a->wt_inv_scale, &job);
+    if (rc) return rc;
+    rc = tfgnn_aux_launch(&job, 1, stream);
     if (rc) return rc;
   }
-  // 3. the small passes in one launch: the combine pass of the long buckets, the weight split
-  rc = tfgnn_aux_launch(own, 2, stream);  // (skips empty jobs: nothing is launched when both are)
-  if (rc) return rc;
-  // 4. the product with its epilogue
+  // 3. the product with its epilogue
   return tfgnn_sp_gemm_nt_rows(V, H, K, a->agg_sp, K * 4, a->agg_inv_scale, (int)D, nullptr, a->wt_sp, a->ld_wt_sp_bytes, a->wt_inv_scale,
                                a->out, a->ld_out, a->bias, a->act, 0, nullptr, 0, TFGNN_ACT_NONE, nullptr, 0, 1.f, a->out_sp,
                                a->ld_out_sp_bytes, a->out_inv_scale, a->dropout_rate, a->dropout_seed, a->tile_kmask, a->row_map, stream);
@@ -69,20 +71,19 @@ extern "C" int tfgnn_mp_backward(const tfgnn_mp_backward_args* a, void* stream) 
   if (rc) return rc;
   const int64_t D = a->in_dim, H = a->hidden_dim, K = (int64_t)L * H;
   TFGNN_REQUIRE(V > 0 && L > 0 && D > 0 && H > 0, "tfgnn_mp_backward: empty layer");
-  tfgnn_aux_job own[2];
-  std::memset(own, 0, sizeof(own));
   // 1. G = [G_0 | .. | G_{L-1}]: d_pre summed over the out-edges of every (source, type) bucket
-  rc = tfgnn_graph_gather_reduce_sp_deferred(a->graph, TFGNN_VIEW_BY_SRC_TYPED, nullptr, a->edge_weight, nullptr, a->d_pre, a->ld_d_pre,
-                                                 (int)H, a->g_sp, H * 4, a->g_inv_scale, nullptr, a->workspace, a->workspace_bytes, &own[0],
-                                                 stream);
+  rc = tfgnn_graph_gather_reduce_sp(a->graph, TFGNN_VIEW_BY_SRC_TYPED, nullptr, a->edge_weight, nullptr, a->d_pre, a->ld_d_pre, (int)H,
+                                    a->g_sp, H * 4, a->g_inv_scale, nullptr, a->workspace, a->workspace_bytes, stream);
   if (rc) return rc;
-  // 2. the kernels as rows [W_0[d, :] | W_1[d, :] | ..] of the [D, L * H] operand, when the caller's copy is stale
+  // 2. the kernels as rows [W_0[d, :] | W_1[d, :] | ..] of the [D, L * H] operand, when the caller's copy is stale (see above)
   if (a->w) {
-    rc = tfgnn_sp_split_rows_job(a->w, H, H, D * H, D, K, (int)K, a->wh_sp, a->ld_wh_sp_bytes, a->wh_inv_scale, nullptr, &own[1]);
+    tfgnn_aux_job job;
+    std::memset(&job, 0, sizeof(job));
+    rc = tfgnn_sp_split_rows_job(a->w, H, H, D * H, D, K, (int)K, a->wh_sp, a->ld_wh_sp_bytes, a->wh_inv_scale, nullptr, &job);
+    if (rc) return rc;
+    rc = tfgnn_aux_launch(&job, 1, stream);
     if (rc) return rc;
   }
-  rc = tfgnn_aux_launch(own, 2, stream);
-  if (rc) return rc;
   // 3. dX = G W^T with the gradient factors of the op below in the epilogue; rows in by-source pattern order when asked
   rc = tfgnn_sp_gemm_nt_rows(V, D, K, a->g_sp, K * 4, a->g_inv_scale, (int)H, a->a_rows, a->wh_sp, a->ld_wh_sp_bytes, a->wh_inv_scale, a->dx,
                              a->ld_dx, nullptr, TFGNN_ACT_NONE, a->accumulate, a->mul, a->ld_mul, a->act_of_saved, a->saved, a->ld_saved,

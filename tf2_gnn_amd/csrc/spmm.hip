@@ -20,14 +20,17 @@
 // Skew (R-MAT hubs): with a plan (graph views), rows longer than LONG_ROW_THRESHOLD are skipped by
 // the row kernel and cut into items of ITEM_CHUNK edges; one workgroup per item, its groups each
 // take a contiguous slice of the item, partial sums are combined through LDS in group order.  Rows
-// made of several items go through a scratch buffer and a third, tiny combine kernel (item order).
+// made of several items go through a scratch buffer: every item workgroup stores its partial row
+// (write-through), then counts its arrival on the row's counter in the graph handle; the workgroup that
+// arrives last adds the row's partial rows in item order and writes the result (finish_multi_row) - no second
+// launch, nobody waits, and the order of the sum does not depend on who arrives last.
 // Everything stays deterministic.
 //
 // blockIdx.y walks feature windows.
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 
-#include "aux_jobs.hpp"
 #include "common.hpp"
 #include "graph.hpp"
 #include "sp16.hpp"
@@ -173,20 +176,19 @@ struct GatherArgs {
   const int32_t* item_row;
   const int32_t* item_chunk;
   const int32_t* item_slot;
+  const int32_t* item_multi;
   float* partial;  // [num_partials, width]
   int item_chunk_edges;
-  // combine pass
-  const int32_t* multi_row;
+  // rows made of several items: combined by their last-arriving item workgroup
   const int32_t* multi_base;
   const int32_t* multi_n;
-  int num_multi;
+  uint32_t* arrive;  // [num_multi][ARRIVE_WINDOWS], zero between launches
   // SP16 output (kernels instantiated with SP = true; MODE_SUM, float4 path, one feature window): the row sums are
   // written as the split fp16 operand of the f16x2 products (csrc/gemm_sp.hip) instead of fp32
   uint8_t* out_sp;         // [rows] x ld_out_sp bytes
   int64_t ld_out_sp;
   float* inv_out;          // [rows] 2^-e of every output row (not written when fixed_inv is given)
   const float* fixed_inv;  // nullable: one caller-chosen 2^-e for the whole tensor
-  tfgnn_aux_job* combine_job;  // host pointer, nullable: receive the combine pass as a job instead of launching it
   bool multi_pairs;  // host only: the short rows go two to a lane group, one edge of each per round (gather_rows_block_multi)
 };
 
@@ -535,6 +537,116 @@ __device__ __forceinline__ void gather_rows_block_multi(const GatherArgs& a, uns
   }
 }
 
+// ---- rows made of several items -------------------------------------------------------------------------------------------
+typedef unsigned uint4v __attribute__((ext_vector_type(4)));
+// 16 bytes of partial row `slot` at float c, read past this XCD's caches (sc1): every load of a partial row goes this way
+__device__ __forceinline__ float4 load_partial4(const GatherArgs& a, int64_t slot, int c) {
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(a.partial + slot * a.width, (short)0, a.width * 4, 0x00020000);
+  const uint4v v = __builtin_amdgcn_raw_buffer_load_b128(rs, (unsigned)c * 4u, 0, 16 /* sc1 */);
+  return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+}
+__device__ __forceinline__ float load_partial1(const GatherArgs& a, int64_t slot, int f) {
+  return __hip_atomic_load(a.partial + slot * a.width + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The partial rows of a multi-item row (scratch slots base, base + 1, .. base + n - 1) -> its SP16 row: ONE WAVE, lane = its
+// lane (width <= 2048 floats).  Sums in item order, four partial rows in flight.
+__device__ __forceinline__ void combine_sp_row(const GatherArgs& a, int64_t row, int32_t base, int32_t n, float rs, int lane) {
+  float4 sum[8];
+  float mx = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int c = (lane + i * 64) * 4;
+    sum[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (c < a.width) {
+      int k = 0;
+      for (; k + 4 <= n; k += 4) {  // four partial rows in flight; the sum stays in item order
+        float4 p[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) p[u] = load_partial4(a, base + k + u, c);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { sum[i].x += p[u].x; sum[i].y += p[u].y; sum[i].z += p[u].z; sum[i].w += p[u].w; }
+      }
+      for (; k < n; ++k) {
+        const float4 p = load_partial4(a, base + k, c);
+        sum[i].x += p.x; sum[i].y += p.y; sum[i].z += p.z; sum[i].w += p.w;
+      }
+      sum[i].x *= rs; sum[i].y *= rs; sum[i].z *= rs; sum[i].w *= rs;
+      mx = fmaxf(mx, fmaxf(fmaxf(fabsf(sum[i].x), fabsf(sum[i].y)), fmaxf(fabsf(sum[i].z), fabsf(sum[i].w))));
+    }
+  }
+  const int64_t orow = a.out_row_map ? a.out_row_map[row] : row;
+  float iv, sc;
+  if (a.fixed_inv) {
+    iv = a.fixed_inv[0];
+    sc = 1.f / iv;
+  } else {
+#pragma unroll
+    for (int o = 32; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    sc = sp_scale_for_max(mx, &iv);
+    if (lane == 0) a.inv_out[orow] = iv;
+  }
+  uint8_t* drow = a.out_sp + orow * a.ld_out_sp;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int c = (lane + i * 64) * 4;
+    if (c < a.width) sp_store4(drow, c, sum[i], sc);
+  }
+}
+
+// ... -> floats [f0, f1) of its fp32 row: the whole workgroup, one float per thread and round
+__device__ __forceinline__ void combine_fp32_row(const GatherArgs& a, int64_t row, int32_t base, int32_t n, float rs, bool is_max,
+                                                 int f0, int f1) {
+  const int64_t orow = a.out_row_map ? a.out_row_map[row] : row;
+  for (int f = f0 + (int)threadIdx.x; f < f1; f += 256) {
+    float s = load_partial1(a, base, f);
+    for (int k = 1; k < n; ++k) {
+      const float p = load_partial1(a, base + k, f);
+      s = is_max ? fmaxf(s, p) : s + p;
+    }
+    a.out[orow * a.ld_out + f] = act_apply(a.post_act, s * rs);
+  }
+}
+
+// Called by every thread of an item workgroup that has just stored its partial row (slot >= 0), once per launch and
+// (item, feature window).  The hand-off between the workgroups of a row - they run on any CU of any XCD, and the XCDs' L2s
+// are not coherent for plain stores - is the one the K split inside the NT product uses (gemm_sp.hip):
+//   the partial rows are stored write-through (sc1); every wave waits for its stores, the workgroup meets at a barrier, and
+//   thread 0 adds 1 to the row's counter (agent scope); the workgroup that draws the last ticket sets the counter back to 0
+//   for the next launch and reads all partial rows of the row with loads that go past its own caches (sc1, every one of them).
+// No cache is written back or invalidated as a whole (a release / acquire fence pair at agent scope does both, in the middle
+// of a launch that streams 150 MB through the L2s: measured 9 us per gather, NOTEBOOK section 23).  Nobody waits for
+// anybody: a workgroup that is not the last one leaves.  Feature window w counts on counter w % ARRIVE_WINDOWS of the row;
+// with more windows than counters the windows of one residue class share a counter and the last of THEIR item workgroups
+// finishes all of them.  `flag`: one word of the workgroup's LDS array (free by now).
+template <int WINDOW, bool SP>
+__device__ __forceinline__ void finish_multi_row(const GatherArgs& a, int item, int64_t row, float rs, unsigned window, bool is_max,
+                                                 unsigned* flag) {
+  const int m = a.item_multi[item];
+  const int32_t n = a.multi_n[m];
+  const unsigned windows = gridDim.y;
+  const unsigned cls = window % ARRIVE_WINDOWS;
+  const unsigned sharing = (windows - cls + ARRIVE_WINDOWS - 1) / ARRIVE_WINDOWS;  // windows cls, cls + ARRIVE_WINDOWS, ..
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's partial stores have left
+  __syncthreads();                                   // ... every wave's (and every read of the LDS array is over)
+  if (threadIdx.x == 0) {
+    uint32_t* ctr = a.arrive + (size_t)m * ARRIVE_WINDOWS + cls;
+    const unsigned old = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool last = old == (unsigned)n * sharing - 1u;
+    if (last) __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // all tickets of this launch are drawn
+    *flag = last ? 1u : 0u;
+  }
+  __syncthreads();
+  if (*flag == 0u) return;
+  const int32_t base = a.multi_base[m];
+  if constexpr (SP) {  // (one feature window)
+    if (threadIdx.x < 64) combine_sp_row(a, row, base, n, rs, (int)threadIdx.x);
+  } else {
+    for (unsigned w = cls; w < windows; w += ARRIVE_WINDOWS)
+      combine_fp32_row(a, row, base, n, rs, is_max, (int)(w * WINDOW), min(a.width, (int)((w + 1) * WINDOW)));
+  }
+}
+
 // one workgroup per item (a run of <= item_chunk_edges edges of a long row)
 template <int LPR, int VPL, int VEC, int UNROLL, int MODE, bool SP = false>
 __device__ __forceinline__ void gather_item_block(const GatherArgs& a, int item, unsigned window,
@@ -617,39 +729,12 @@ __device__ __forceinline__ void gather_item_block(const GatherArgs& a, int item,
       const int64_t orow = a.out_row_map ? a.out_row_map[row] : row;
       a.out[orow * a.ld_out + w0 + f] = act_apply(a.post_act, s * rs);
     } else {
-      a.partial[(int64_t)slot * a.width + w0 + f] = s;
+      // write-through (sc1): the row's last-arriving workgroup may sit on another XCD, whose L2 never sees a plain store
+      __hip_atomic_store(a.partial + (int64_t)slot * a.width + w0 + f, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
+  if (slot >= 0) finish_multi_row<WINDOW, SP>(a, item, row, rs, window, is_max, reinterpret_cast<unsigned*>(&red[0][0]));
 }
-
-// rows made of several items: combine their partial results in item order
-__global__ void __launch_bounds__(256) csr_gather_combine_kernel(GatherArgs a) {
-  const int64_t total = (int64_t)a.num_multi * a.width;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int m = (int)(i / a.width);
-    const int f = (int)(i - (int64_t)m * a.width);
-    const int64_t row = a.multi_row[m];
-    const int32_t base = a.multi_base[m], n = a.multi_n[m];
-    float s = a.partial[(int64_t)base * a.width + f];
-    for (int k = 1; k < n; ++k) {
-      const float p = a.partial[(int64_t)(base + k) * a.width + f];
-      s = a.is_max ? fmaxf(s, p) : s + p;
-    }
-    const float rs = a.row_scale ? a.row_scale[row] : 1.f;
-    const int64_t orow = a.out_row_map ? a.out_row_map[row] : row;
-    a.out[orow * a.ld_out + f] = act_apply(a.post_act, s * rs);
-  }
-}
-
-// SP16 output: one wave per multi-item row (width <= 2048 floats); the body is shared with the merged small-pass launch
-static AuxCombineSp combine_sp_args(const GatherArgs& a) {
-  AuxCombineSp c{};
-  c.multi_row = a.multi_row; c.multi_base = a.multi_base; c.multi_n = a.multi_n; c.num_multi = a.num_multi;
-  c.row_scale = a.row_scale; c.partial = a.partial; c.width = a.width; c.out_row_map = a.out_row_map;
-  c.out_sp = a.out_sp; c.ld_out_sp = a.ld_out_sp; c.inv_out = a.inv_out; c.fixed_inv = a.fixed_inv;
-  return c;
-}
-__global__ void __launch_bounds__(256) csr_gather_combine_sp_kernel(AuxCombineSp a) { combine_sp_body(a, blockIdx.x); }
 
 // One launch covers both kinds of work: workgroups [0, num_items) each take one item of a long row
 // (longest work first), the remaining workgroups take 256/LPR short rows each.
@@ -702,25 +787,12 @@ static int launch_mode(GatherArgs a, int num_items, hipStream_t s) {
     if (!multi_done)
       hipLaunchKernelGGL((csr_gather_reduce_kernel<LPR, VPL, VEC, UNROLL, MODE, true>), dim3(units, 1), block, 0, s, a, num_items);
     TFGNN_LAUNCH_CHECK();
-    if (a.num_multi > 0) {
-      if (a.combine_job) {  // the caller launches the combine pass itself, together with other small passes
-        aux_job_set(a.combine_job, AUX_COMBINE_SP, (unsigned)ceil_div(a.num_multi, 4), combine_sp_args(a));
-      } else {
-        hipLaunchKernelGGL(csr_gather_combine_sp_kernel, dim3((unsigned)ceil_div(a.num_multi, 4)), block, 0, s, combine_sp_args(a));
-        TFGNN_LAUNCH_CHECK();
-      }
-    }
     return TFGNN_OK;
   }
   if (!multi_done)
     hipLaunchKernelGGL((csr_gather_reduce_kernel<LPR, VPL, VEC, UNROLL, MODE>), dim3(units, windows), block, 0, s, a,
                        num_items);
   TFGNN_LAUNCH_CHECK();
-  if (a.num_multi > 0) {
-    const int64_t total = (int64_t)a.num_multi * a.width;
-    hipLaunchKernelGGL(csr_gather_combine_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(total, 256), 4096)), block, 0, s, a);
-    TFGNN_LAUNCH_CHECK();
-  }
   return TFGNN_OK;
 }
 
@@ -866,8 +938,7 @@ static int graph_gather_impl(const tfgnn_graph* g, int view, const int32_t* d_co
   a.row_scale = d_row_scale; a.num_rows = gv.num_rows; a.in = d_in; a.ld_in = ld_in; a.width = width;
   a.out = d_out; a.ld_out = d_out_sp ? (int64_t)width : ld_out; a.pre_act = pre_act; a.post_act = post_act;
   a.out_sp = (uint8_t*)d_out_sp; a.ld_out_sp = ld_out_sp; a.inv_out = d_inv_scale; a.fixed_inv = d_fixed_inv;
-  a.combine_job = combine_job;
-  if (combine_job) combine_job->kind = 0, combine_job->num_blocks = 0;
+  if (combine_job) memset(combine_job, 0, sizeof(*combine_job));  // (kind 0: the gather combines its long rows itself)
   a.is_max = reduce_op == TFGNN_REDUCE_MAX; a.ew_heads = ew_heads; a.head_width = width / ew_heads;
   a.long_threshold = p.long_threshold;
   a.out_row_map = out_map;
@@ -879,9 +950,9 @@ static int graph_gather_impl(const tfgnn_graph* g, int view, const int32_t* d_co
     a.dot_rows = d_dot_rows; a.ld_dot = ld_dot; a.dot_out = d_dot_out; a.dot_pos = d_dot_pos;
     a.dot_lph_log2 = 31 - __builtin_clz((unsigned)lph);
   }
-  a.item_row = p.item_row; a.item_chunk = p.item_chunk; a.item_slot = p.item_slot;
+  a.item_row = p.item_row; a.item_chunk = p.item_chunk; a.item_slot = p.item_slot; a.item_multi = p.item_multi;
   a.partial = (float*)d_workspace; a.item_chunk_edges = p.item_chunk_edges;
-  a.multi_row = p.multi_row; a.multi_base = p.multi_base; a.multi_n = p.multi_n; a.num_multi = p.num_multi;
+  a.multi_base = p.multi_base; a.multi_n = p.multi_n; a.arrive = p.arrive;
   a.short_rows = p.short_rows;
   a.num_short = p.num_short;
   // compact output: the empty buckets have no row, and they close the length-ordered list - no lane groups for them
@@ -955,8 +1026,8 @@ extern "C" int tfgnn_graph_gather_reduce_sp(const tfgnn_graph* g, int view, cons
                            ld_out_sp_bytes, d_inv_scale, d_fixed_inv_scale);
 }
 
-/* tfgnn_graph_gather_reduce_sp whose combine pass (the partial sums of buckets cut into several items) comes back as a job
- * for tfgnn_aux_launch instead of being launched: kind 0 = there is nothing to combine. */
+/* tfgnn_graph_gather_reduce_sp in the form that used to hand the combine pass of the long buckets back as a job for
+ * tfgnn_aux_launch: the gather combines them in its own launch now, *combine_job always comes back empty (kind 0). */
 extern "C" int tfgnn_graph_gather_reduce_sp_deferred(const tfgnn_graph* g, int view, const int32_t* d_col_override,
                                                      const float* d_edge_weight, const float* d_row_scale, const float* d_in,
                                                      int64_t ld_in, int width, void* d_out_sp, int64_t ld_out_sp_bytes,

@@ -233,6 +233,30 @@ class GNN:
             return False
         return ops.get_gemm_mode() == ops.GEMM_F16X2 and in_dim % 16 == 0 and in_dim >= 32 and ops.sp_tiles(out_dim)
 
+    def _presplit_weights(self, graph, V: int, backward: bool, need_input_grad: bool = False) -> None:
+        """Split every weight operand the coming pass reads whose cached form is stale, all in ONE merged small-pass launch
+        (``ops.presplit_weight_operands``): the kernel stacks of the message passing layers, the Dense kernels and the
+        projection - forward as W^T, backward as rows.  The weights stay what they are until the end of the backward pass, so
+        nothing has to wait for its layer: the per-layer launches that carried one split each (8 - 10 us apiece, serial with
+        the layer's gather and product) are gone.  The layers still build what is not announced here.  TFGNN_PRESPLIT=0:
+        every consumer splits its own weights (A/B measurements)."""
+        if V <= 0 or ops.get_gemm_mode() != ops.GEMM_F16X2 or not ops.aux_enabled() or ops.env("TFGNN_PRESPLIT", "1") == "0":
+            return
+        H = self._hidden_dim
+        reqs = []
+        dense = [self._initial_projection_layer] + [self._dense_layers[k] for k in sorted(self._dense_layers, key=int)]
+        for i, w in enumerate(dense):
+            d_in, d_out = w.value.shape
+            if not self._dense_f16x2(d_in, d_out):
+                continue
+            if not backward:
+                reqs.append((w.value, "cols", lambda w=w: ops.sp_split_cols(w.value, defer=True)))
+            elif ops.sp_tiles(d_in) and (i > 0 or need_input_grad):  # (the projection's input gradient: on request only)
+                reqs.append((w.value, "rows", lambda w=w: ops.sp_split_rows(w.value, defer=True)))
+        for mp in self._mp_layers:
+            reqs.extend(mp.weight_operand_requests(graph, V, H, backward))
+        ops.presplit_weight_operands(reqs)
+
     def _dense(self, x, w: Variable, act_name, drop=None):
         """bias-free Dense + activation (gnn.py:136-141,163-170); gelu keeps its pre-activation.  ``drop`` = (rate, seed) of
         the layer-input dropout that follows: applied in the product's epilogue where the split-operand kernel runs it.
@@ -331,9 +355,10 @@ class GNN:
                 return None
             return (rate, drop_seed[i])
 
+        self._presplit_weights(graph, V, backward=False)
         cur, pre0, dropped = self._dense(X, self._initial_projection_layer, self._init_act,
                                          drop=drop_for(0, need_all_representations))
-        ctx = {"X": X, "h0": cur, "pre0": pre0, "steps": steps, "h0_scale": (1.0 - rate) if dropped else 1.0,
+        ctx = {"X": X, "graph": graph, "h0": cur, "pre0": pre0, "steps": steps, "h0_scale": (1.0 - rate) if dropped else 1.0,
                "all_representations": need_all_representations}
         last = cur
         all_reprs = [cur]
@@ -557,6 +582,7 @@ class GNN:
         return ops.activation_backward(act, g, spec[1])
 
     def _backward_walk(self, ctx, g, g_is_pre, g_last, extras, need_input_grad):
+        self._presplit_weights(ctx["graph"], int(ctx["X"].shape[0]), backward=True, need_input_grad=need_input_grad)
         for layer_idx in range(self._num_layers - 1, -1, -1):
             st = ctx["steps"][layer_idx]
             mp = self._mp_layers[layer_idx]

@@ -422,6 +422,22 @@ class GNN_Edge_MLP(MessagePassing):
         return (ops.get_gemm_mode() == ops.GEMM_F16X2 and not self._use_target_state_as_input and L > 0 and V > 0
                 and D % 16 == 0 and D <= 512 and 32 <= H <= 512 and ops.sp_tiles(H) and ops.sp_tiles(D))
 
+    def weight_operand_requests(self, graph, num_nodes: int, in_dim: int, backward: bool):
+        """path A on split operands: W^T as the [H, L * D] operand of the forward product, the rows [W_0[d] | W_1[d] | ..] of
+        the input-gradient product (the keys and builders of ``_forward_A`` / ``_backward_A_f16x2``)"""
+        if (not getattr(self, "built", False) or self._user_message_function() or self._path() != "A"
+                or self._use_target_state_as_input or self._compact_opt_in):
+            return []
+        W = self._edge_type_mlps.kernels[0]  # [L, Din, H]
+        L, Din, H = (int(v) for v in W.shape)
+        if L != graph.num_edge_types or Din != in_dim or not self._f16x2_eligible(num_nodes, in_dim, L, H):
+            return []
+        if backward:
+            return [(W, "rows", lambda: ops.sp_split_rows(W[0], segments=(H, Din * H, L * H), defer=True))]
+        if messages_per_edge(self, graph, in_dim, H):  # (one product per edge type on rows of X: no stacked operand)
+            return []
+        return [(W, "cols", lambda: ops.sp_split_cols(W.view(L * Din, H), defer=True))]
+
     def _forward_A(self, X, g, fuse_act, want_split=False, drop=None):
         if self._use_compact_buckets(g):
             return self._forward_A_compact(X, g, fuse_act)

@@ -439,6 +439,13 @@ class MessagePassing:
         (ops.plain_epilogue): correct, one pass slower."""
         return False
 
+    def weight_operand_requests(self, graph, num_nodes: int, in_dim: int, backward: bool):
+        """[(weight tensor, kind, build)] - the derived forms of this layer's weights (``ops.sp_weight_operand``) that its
+        forward (``backward``: backward) pass over ``graph`` will ask for, so that the layer stack can build the stale ones
+        of ALL its layers in one launch at the start of the pass (``ops.presplit_weight_operands``).  A hint only: a form that
+        is not announced is built by the layer itself, one that is announced and not used costs its split.  Generic: none."""
+        return []
+
     def call_with_epilogue(self, inputs: MessagePassingInput, training: bool = False, *, want_split_output: bool = False,
                            output_dropout=None):
         """``__call__`` for the layer stack, with what the stack would do to the output next handed in as requests:

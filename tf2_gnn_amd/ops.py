@@ -216,6 +216,7 @@ class _DevArray:
  G_NZ_OFF_BY_DST, G_NZ_NODEPTR_BY_DST, G_NZ_COL_BY_DST, G_NZ_CPOS_BY_SRC, G_NZ_ROW_BY_SRC, G_NZ_NODE_BY_SRC,
  G_NZ_OFF_BY_SRC, G_NZ_NODEPTR_BY_SRC, G_NZ_COL_BY_SRC, G_PATTERN_POS_BY_DST, G_PATTERN_NODE_BY_DST,
  G_PATTERN_TILEMASK_BY_DST, G_PATTERN_NODE_BY_SRC, G_PATTERN_TILEMASK_BY_SRC) = range(32)
+G_GATHER_ARRIVALS_VIEW0 = 32  # + view (0 - 3): the arrival counters of the gathers over that view (debugging aid; all zero at rest)
 _FLOAT_ARRAYS = {G_INVDEG_BY_DST, G_INVDEG_EDGE_BY_SRC, G_INVDEG_EDGE_BY_DST}
 _BYTE_ARRAYS = {G_PATTERN_TILEMASK_BY_DST, G_PATTERN_TILEMASK_BY_SRC}
 # parts of a graph handle beyond the two sorted edge orders (include/tfgnn.h tfgnn_graph_part)
@@ -233,6 +234,8 @@ def _array_parts(array_id: int) -> int:
         return G_PART_EDGE_IDS
     if G_PATTERN_POS_BY_DST <= array_id <= G_PATTERN_TILEMASK_BY_SRC:
         return G_PART_DST_PATTERN
+    if G_GATHER_ARRIVALS_VIEW0 <= array_id <= G_GATHER_ARRIVALS_VIEW0 + 3:
+        return _VIEW_PARTS[array_id - G_GATHER_ARRIVALS_VIEW0]
     return G_PART_COMPACT if G_NZ_CPOS_BY_DST <= array_id <= G_NZ_COL_BY_SRC else 0
 
 
@@ -1843,8 +1846,8 @@ def graph_gather_sp(graph: "Graph", view: int, inp: torch.Tensor, *, col=None, e
     ws_bytes = lib.tfgnn_graph_gather_workspace_bytes(graph._h, view, width)
     ws = _workspace(inp.device, ws_bytes) if ws_bytes else None
     if defer_combine and aux_enabled():
-        # the combine pass of the long buckets rides with whatever other small pass precedes the consumer (a weight split): the
-        # operand is complete once the next library call has been issued (or after aux_flush())
+        # (the form that used to get the combine pass of the long buckets back as a job of the next merged launch: the gather
+        # combines them inside its own launch now, the job comes back empty and nothing is queued)
         job = _lib.AuxJob()
         _lib.check(
             lib.tfgnn_graph_gather_reduce_sp_deferred(
@@ -2136,6 +2139,28 @@ def sp_weight_operand(w: torch.Tensor, kind: str, build):
         op = build()
         _cache_weight_operand(w, kind, op)
     return op
+
+
+def presplit_weight_operands(requests) -> int:
+    """Build every STALE derived form among ``requests`` = [(w, kind, build)] now, in one merged small-pass launch (one per
+    eight jobs): the start of a stack's forward or backward pass, where all the operands of the pass can be split at once -
+    the weights do not change between the optimizer update and the end of the backward pass - instead of one launch in
+    front of every layer's product.  ``build()`` is what the consumer would hand to ``sp_weight_operand`` (it defers its job);
+    the same jobs, launched earlier: bit-identical operands.  An operand enters the cache only after its job has been
+    launched, so a failure on the way leaves no entry behind that a later call could mistake for a built operand.
+    -> number of operands built."""
+    made, seen = [], set()
+    for w, kind, build in requests:
+        key = _weight_key(w, kind)
+        if key in seen or _cached_weight_operand(w, kind) is not None:
+            continue
+        seen.add(key)
+        made.append((w, kind, build()))
+    if made:
+        aux_flush()
+        for w, kind, op in made:
+            _cache_weight_operand(w, kind, op)
+    return len(made)
 
 
 def _cached_weight_operand(w: torch.Tensor, kind: str):
