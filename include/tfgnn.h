@@ -812,9 +812,10 @@ int tfgnn_sp_gemm_nt_dropout(int64_t M, int64_t N, int64_t K, const void* d_A_sp
  * Around the big kernels of a layer sit passes of 5-15 us each that are bound by launch and dependent-load latency, not by
  * work: weight matrices into SP16 form, the column maxima of a long one.  A `tfgnn_aux_job` describes one of
  * them; tfgnn_aux_launch runs up to 8 per launch (more: several launches), every job on its own workgroups - the launch
- * takes as long as its longest job.  Jobs of one call must be independent of each other.  The *_job / *_deferred functions FILL a job (host memory, nothing is launched for it) with exactly the
- * work the function of the same name without the suffix would have launched; a job holds device pointers - keep the
- * buffers alive until the launch has run.  (No reference counterpart: TensorFlow schedules these ops one kernel each.) */
+ * takes as long as its longest job.  Jobs of one call must be independent of each other.  The *_job / *_jobs functions FILL a
+ * job (host memory, nothing is launched for it) with exactly the work the function of the same name without the suffix would
+ * have launched; a job holds device pointers - keep the buffers alive until the launch has been issued.  The caller that
+ * fills jobs launches them itself, before the first kernel that reads their results: the library keeps no queue of them.  (No reference counterpart: TensorFlow schedules these ops one kernel each.) */
 typedef struct tfgnn_aux_job {
   int kind;            /* 0: nothing to do */
   unsigned num_blocks; /* workgroups of 256 threads */
@@ -836,7 +837,8 @@ int tfgnn_sp_split_cols_jobs(const float* d_src, int64_t ld, int64_t K, int64_t 
                              float* d_inv_scale, float* d_colmax_workspace, size_t workspace_bytes, tfgnn_aux_job* maxima_job,
                              tfgnn_aux_job* split_job);
 /* tfgnn_graph_gather_reduce_sp.  *combine_job used to receive the combine pass of the long buckets; the gather now combines
- * them inside its own launch, so the job always comes back empty (kind 0).  Kept for callers written against that form. */
+ * them inside its own launch, so the job always comes back empty (kind 0).  Kept for C callers written against that form:
+ * nothing in this package calls it any more (the Python wrappers and the layer-level entry points use the plain form). */
 int tfgnn_graph_gather_reduce_sp_deferred(const tfgnn_graph* graph, int view, const int32_t* d_col_override,
                                           const float* d_edge_weight, const float* d_row_scale, const float* d_in,
                                           int64_t ld_in, int width, void* d_out_sp, int64_t ld_out_sp_bytes,

@@ -587,9 +587,9 @@ def test_narrow_row_split_equals_the_general_kernel(dev, C):
 
 
 def test_small_passes_sharing_one_launch_equal_their_stand_alone_kernels(dev, monkeypatch):
-    """tfgnn_aux_launch (round 4): weight splits and the combine pass of the gather's long buckets, deferred and run as jobs of
-    ONE launch before the next library call, give bit-identical results to the kernels of their own."""
-    from tf2_gnn_amd import _lib, ops
+    """tfgnn_aux_launch (round 4): weight splits built as jobs and launched together in ONE launch (``ops.aux_flush``) give
+    bit-identical results to the kernels of their own - the operands, and everything the products around them compute."""
+    from tf2_gnn_amd import ops
     from tf2_gnn_amd.data import make_synthetic_batch
 
     g = torch.Generator().manual_seed(11)
@@ -600,26 +600,25 @@ def test_small_passes_sharing_one_launch_equal_their_stand_alone_kernels(dev, mo
     graph = ops.Graph(tuple(torch.from_numpy(a).to(dev) for a in adjs), V)
     dY = torch.randn((V, H), generator=g).to(dev)
 
-    def run():
-        cols = ops.sp_split_cols(W.view(4 * 320, 320), defer=True)
-        rows = ops.sp_split_rows(W[0], segments=(320, 320 * 320, 4 * 320), defer=True)
-        A = ops.graph_gather_sp(graph, ops.VIEW_BY_DST_TYPED, X, rows_per_operand_row=L, defer_combine=True)  # long buckets
-        Y = ops.sp_gemm_nt(A, cols, act="relu")                                                 # flushes the three jobs first
-        G = ops.graph_gather_sp(graph, ops.VIEW_BY_SRC_TYPED, dY, rows_per_operand_row=L, defer_combine=True)
+    def run(shared_launch):
+        if shared_launch:
+            cj = ops.sp_split_cols_jobs(W.view(4 * 320, 320))
+            rj = ops.sp_split_rows_jobs(W[0], segments=(320, 320 * 320, 4 * 320))
+            ops.aux_flush([cj, rj])
+            cols, rows = cj.operand, rj.operand
+        else:
+            cols = ops.sp_split_cols(W.view(4 * 320, 320))
+            rows = ops.sp_split_rows(W[0], segments=(320, 320 * 320, 4 * 320))
+        A = ops.graph_gather_sp(graph, ops.VIEW_BY_DST_TYPED, X, rows_per_operand_row=L)  # long buckets
+        Y = ops.sp_gemm_nt(A, cols, act="relu")
+        G = ops.graph_gather_sp(graph, ops.VIEW_BY_SRC_TYPED, dY, rows_per_operand_row=L)
         dW = torch.empty_like(W)
         ops.sp_gemm_tn(G, ops.sp_split_rows(X), out=dW, scatter=(H, 320 * H, 1, H))
         dX = ops.sp_gemm_nt(G, rows)
-        ops.aux_flush()
         return [cols.data, cols.inv_scale, rows.data, rows.inv_scale, A.data, A.inv_scale, Y, G.data, G.inv_scale, dW, dX]
 
-    monkeypatch.setenv("TFGNN_AUX_MERGE", "0")
-    ref = [t.clone() for t in run()]
-    monkeypatch.setenv("TFGNN_AUX_MERGE", "1")
-    assert ops.aux_enabled()
-    calls = []
-    real = _lib.load().tfgnn_aux_launch
-    got = [t.clone() for t in run()]
-    assert not ops._AUX_PENDING
+    ref = [t.clone() for t in run(False)]
+    got = [t.clone() for t in run(True)]
     names = ["W^T sp", "W^T inv", "W rows sp", "W rows inv", "A sp", "A inv", "Y", "G sp", "G inv", "dW", "dX"]
     for n, a, b in zip(names, got, ref):
         assert torch.equal(a, b), n
@@ -627,9 +626,10 @@ def test_small_passes_sharing_one_launch_equal_their_stand_alone_kernels(dev, mo
 
 
 def test_two_pass_weight_split_launches_on_the_stream_it_was_deferred_for(dev, monkeypatch):
-    """A long-K weight split deferred on one stream (the column maxima in one merged launch, the split in the next) and flushed
-    by a library call on ANOTHER stream: both launches go to the stream it was deferred for, and the operand is the one-pass
-    split's, bit for bit."""
+    """A long-K weight split launched under a side stream: exactly two launches (the column maxima, then the split), both on
+    that stream, and the operand is the one-pass split's, bit for bit.  Nothing is left behind: a library call on the main
+    stream afterwards launches no small pass.  (The jobs used to wait in a queue that a call from ANOTHER stream could flush;
+    they are launched where they are built now, so that cannot happen.)"""
     from tf2_gnn_amd import _lib, ops
 
     lib = _lib.load()
@@ -639,23 +639,29 @@ def test_two_pass_weight_split_launches_on_the_stream_it_was_deferred_for(dev, m
     w = (torch.randn((K, N), generator=g) * torch.exp(torch.randn((1, N), generator=g) * 3)).to(dev)
     ref = ops.sp_split_cols(w)
     torch.cuda.synchronize()
-    monkeypatch.setenv("TFGNN_AUX_MERGE", "1")
-    streams = []
+    launches = []
     real = lib.tfgnn_aux_launch
 
     def spy(jobs, n, stream):
-        streams.append(stream)
+        launches.append((getattr(stream, "value", stream), [int(jobs[i].kind) for i in range(n)]))
         return real(jobs, n, stream)
 
     monkeypatch.setattr(lib, "tfgnn_aux_launch", spy)
     main, side = torch.cuda.current_stream(), torch.cuda.Stream()
-    op = ops.sp_split_cols(w, defer=True)
-    assert not streams
     side.wait_stream(main)
     with torch.cuda.stream(side):
-        ops.absmax(w)  # a library call: launches what is deferred first
+        jobs = ops.sp_split_cols_jobs(w)
+        assert not launches  # building the jobs launches nothing
+        ops.aux_flush([jobs])
+    op = jobs.operand
+    assert side.cuda_stream != main.cuda_stream
+    assert [st for st, _ in launches] == [side.cuda_stream, side.cuda_stream], (launches, main.cuda_stream, side.cuda_stream)
+    assert [kinds for _, kinds in launches] == [[6], [2]], launches  # AUX_COL_ABSMAX, then AUX_SPLIT_COLS (csrc/aux_jobs.hpp)
+    main.wait_stream(side)
+    del launches[:]
+    ops.absmax(w)  # a library call on the main stream: there is nothing left for it to launch
     torch.cuda.synchronize()
-    assert streams == [main.cuda_stream, main.cuda_stream], (streams, main.cuda_stream, side.cuda_stream)
+    assert not launches, launches
     assert torch.equal(op.data, ref.data) and torch.equal(op.inv_scale, ref.inv_scale)
 
 
@@ -847,8 +853,8 @@ def test_tile_mask_needs_block_scales_that_tile_k(dev):
 
 @pytest.mark.parametrize("K,N", [(4096, 512), (20480, 512), (2560, 320), (1296, 128), (1280, 256)])
 def test_two_pass_split_of_a_long_kernel_stack_equals_the_one_pass_split(dev, K, N):
-    """Round 6 (BASELINE configs[4]): the deferred transposed split of a long [K, N] stack of kernels takes its column maxima in a
-    pass of its own (a job of one merged launch) and converts in the next launch - every byte read once instead of once per K
+    """Round 6 (BASELINE configs[4]): the transposed split of a long [K, N] stack of kernels as jobs takes its column maxima in a
+    pass of its own (a job of one shared launch) and converts in the next launch - every byte read once instead of once per K
     slice.  The operand and its scales must be the one-pass split's, bit for bit; K <= 1280 keeps the one-pass job."""
     from tf2_gnn_amd import _lib, ops
 
@@ -858,13 +864,17 @@ def test_two_pass_split_of_a_long_kernel_stack_equals_the_one_pass_split(dev, K,
     w[:, 8] = 0.0  # an all-zero column: the marker scale
     assert (_lib.load().tfgnn_sp_split_cols_two_pass_bytes(K, N) > 0) == (K > 1280)
     ref = ops.sp_split_cols(w)
-    got = ops.sp_split_cols(w, defer=True).synced()
+    jobs = ops.sp_split_cols_jobs(w)
+    assert bool(jobs.stage1) == (K > 1280)
+    ops.aux_flush([jobs])
+    got = jobs.operand
     torch.cuda.synchronize()
     assert torch.equal(got.inv_scale, ref.inv_scale) and torch.equal(got.data, ref.data)
-    # and as a consumer meets it: the product right behind the deferred split
+    # and as a consumer meets it: the product right behind the split that ``sp_weight_operand`` launches
     a = ops.sp_split_rows(torch.randn((300, K), generator=gen).to(dev))
     out_ref = ops.sp_gemm_nt(a, ref)
-    out = ops.sp_gemm_nt(a, ops.sp_split_cols(w, defer=True))
+    ops.clear_weight_operand_cache()
+    out = ops.sp_gemm_nt(a, ops.sp_weight_operand(w, "cols", lambda: ops.sp_split_cols_jobs(w)))
     assert torch.equal(out, out_ref)
 
 

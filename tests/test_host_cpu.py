@@ -411,3 +411,23 @@ def test_stack_entry_points_of_the_base_layer_and_the_guard_policy_defaults():
     for n in (0, 16, 96, 128, 256, 320, 384, 512, 640, 960, 1280):
         assert ops.sp_one_tile(n) == (n in (128, 256, 320)), n
         assert ops.sp_tiles(n) == (ops.sp_tile_width(n) != 0) == (n % 128 == 0 or n % 320 == 0), n
+
+
+def test_split_jobs_are_launched_by_their_builder_and_no_queue_is_left():
+    """The process-global queue of deferred small passes is gone: the wrappers take no ``defer`` arguments, the job builders and
+    the one launcher exist, and ``aux_flush`` keeps its module-level name (bench.py's step breakdown looks it up in _TIMED_OPS)."""
+    import inspect
+
+    import bench
+    from tf2_gnn_amd import ops
+
+    for name in ("aux_defer", "aux_enabled", "_AUX_PENDING", "_AUX_STREAM", "_AUX_LOCK"):
+        assert not hasattr(ops, name), name
+    assert not hasattr(ops.SplitOperand, "synced")
+    for fn, gone in ((ops.sp_split_rows, "defer"), (ops.sp_split_cols, "defer"), (ops.graph_gather_sp, "defer_combine")):
+        assert gone not in inspect.signature(fn).parameters, fn.__name__
+    assert "aux_flush" in bench._TIMED_OPS and callable(ops.aux_flush)
+    assert list(inspect.signature(ops.aux_flush).parameters) == ["batch"]
+    assert set(inspect.signature(ops.sp_split_rows_jobs).parameters) == set(inspect.signature(ops.sp_split_rows).parameters)
+    assert set(inspect.signature(ops.sp_split_cols_jobs).parameters) == set(inspect.signature(ops.sp_split_cols).parameters)
+    assert ops.SplitJobs.__slots__ == ("operand", "stage0", "stage1", "keep")

@@ -74,7 +74,6 @@ class CapturedStep:
         with torch.cuda.stream(side):
             for _ in range(self._warmup):
                 self._fn()
-            ops.aux_flush()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         if ops.get_gemm_mode() == ops.GEMM_F16X2 and ops.f16x2_guard_flag_async():
@@ -87,7 +86,6 @@ class CapturedStep:
             if self._advance:
                 ops.dropout_epoch_advance()
             out = self._fn()
-            ops.aux_flush()  # deferred small passes belong to the step
         self._graph, self._out, self._stream = graph, out, side
         # the derived-weight forms made during the capture live in the graph's memory pool and are rewritten by replays the
         # library's cache cannot see: eager calls after this must rebuild their own

@@ -1414,9 +1414,62 @@ __global__ void __launch_bounds__(SP_NT, 1) gemm_sp_tn_kernel(SpTnArgs g) {
   store_tile(std::integral_constant<int, 1>{});
 }
 
-__global__ void __launch_bounds__(256) sp_tn_reduce_kernel(AuxTnReduce a) { sp_tn_reduce_body(a, blockIdx.x, gridDim.x); }
+struct TnReduceArgs {
+  const float* partial;
+  int splits;
+  int64_t M, N;
+  const float* ref;
+  int64_t a_col0;
+  int a_sb;
+  float* C;
+  int64_t group_rows, stride_group, stride_row, stride_col;
+  int accumulate;
+  int64_t slab;
+  int ref_ld;  // 0: one reference scale per block (ref[blk]); > 0: one per (split, block) at ref[z * ref_ld + blk]
+};
+
+// ---- split-K partials of a weight gradient -> dW -----------------------------------------------------------------------
+// C[(m / group_rows) * stride_group + (m % group_rows) * stride_row + n * stride_col] (+)= ref[blk(m)] * sum_z partial[z][m][n]
+// (`block` of `nblocks` workgroups of 256 threads walk the M * N elements)
+__device__ __forceinline__ void sp_tn_reduce_body(const TnReduceArgs& a, unsigned block, unsigned nblocks) {
+  const int64_t total = a.M * a.N;  // slab >= total: floats per split (the product pads M to a multiple of 128)
+  for (int64_t i = (int64_t)block * 256 + threadIdx.x; i < total; i += (int64_t)nblocks * 256) {
+    const int64_t m = i / a.N, n = i - m * a.N;
+    const int64_t blk = (a.a_col0 + m) / a.a_sb;
+    float s = 0.f;
+    int z = 0;
+    if (a.ref_ld > 0) {  // every split carries its own reference scale (factors computed inside the product kernel)
+      for (; z + 8 <= a.splits; z += 8) {  // eight loads in flight; the sum stays in split order
+        float v[8], r[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          v[u] = a.partial[(int64_t)(z + u) * a.slab + i];
+          r[u] = a.ref[(int64_t)(z + u) * a.ref_ld + blk];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += v[u] * r[u];
+      }
+      for (; z < a.splits; ++z) s += a.partial[(int64_t)z * a.slab + i] * a.ref[(int64_t)z * a.ref_ld + blk];
+    } else {
+      for (; z + 8 <= a.splits; z += 8) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = a.partial[(int64_t)(z + u) * a.slab + i];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += v[u];
+      }
+      for (; z < a.splits; ++z) s += a.partial[(int64_t)z * a.slab + i];
+      s *= a.ref[blk];
+    }
+    const int64_t gi = m / a.group_rows, mi = m - gi * a.group_rows;
+    float* dst = a.C + gi * a.stride_group + mi * a.stride_row + n * a.stride_col;
+    *dst = a.accumulate ? *dst + s : s;
+  }
+}
+
+__global__ void __launch_bounds__(256) sp_tn_reduce_kernel(TnReduceArgs a) { sp_tn_reduce_body(a, blockIdx.x, gridDim.x); }
 // blockIdx.y = row group: the K ranges [split_off[g], split_off[g + 1]) of the grouped product belong to output g
-__global__ void __launch_bounds__(256) sp_tn_reduce_grouped_kernel(AuxTnReduce a, const int32_t* __restrict__ split_off,
+__global__ void __launch_bounds__(256) sp_tn_reduce_grouped_kernel(TnReduceArgs a, const int32_t* __restrict__ split_off,
                                                                    int64_t c_group_stride) {
   const int gq = blockIdx.y;
   const int s0 = split_off[gq], s1 = split_off[gq + 1];
@@ -1944,7 +1997,7 @@ static int sp_gemm_tn_impl(int64_t M, int64_t N, int64_t K, const void* d_A_sp, 
   TFGNN_LAUNCH_CHECK();
 #undef SP_LAUNCH_TN
   const int64_t total = M * N;
-  AuxTnReduce ra{};
+  TnReduceArgs ra{};
   ra.partial = g.partial; ra.splits = splits_used; ra.M = M; ra.N = N; ra.ref = fik ? ref_split : ref; ra.a_col0 = a_first_col; ra.a_sb = a_scale_block;
   ra.ref_ld = fik ? (int)nblk : 0;
   ra.C = d_C; ra.group_rows = group_rows; ra.stride_group = stride_group; ra.stride_row = stride_row; ra.stride_col = stride_col;
@@ -2033,7 +2086,7 @@ int tfgnn_sp_gemm_tn_grouped(int64_t M, int64_t N, const void* d_A_sp, int64_t l
 #undef SP_LAUNCH_TNG
     TFGNN_LAUNCH_CHECK();
   }
-  AuxTnReduce ra{};
+  TnReduceArgs ra{};
   ra.partial = g.partial; ra.splits = 0; ra.M = M; ra.N = N; ra.ref = ref_split; ra.a_col0 = 0; ra.a_sb = a_scale_block;
   ra.ref_ld = (int)nblk;
   ra.C = d_C; ra.group_rows = M; ra.stride_group = 0; ra.stride_row = stride_row; ra.stride_col = stride_col;

@@ -240,7 +240,7 @@ class GNN:
         nothing has to wait for its layer: the per-layer launches that carried one split each (8 - 10 us apiece, serial with
         the layer's gather and product) are gone.  The layers still build what is not announced here.  TFGNN_PRESPLIT=0:
         every consumer splits its own weights (A/B measurements)."""
-        if V <= 0 or ops.get_gemm_mode() != ops.GEMM_F16X2 or not ops.aux_enabled() or ops.env("TFGNN_PRESPLIT", "1") == "0":
+        if V <= 0 or ops.get_gemm_mode() != ops.GEMM_F16X2 or ops.env("TFGNN_PRESPLIT", "1") == "0":
             return
         H = self._hidden_dim
         reqs = []
@@ -250,9 +250,9 @@ class GNN:
             if not self._dense_f16x2(d_in, d_out):
                 continue
             if not backward:
-                reqs.append((w.value, "cols", lambda w=w: ops.sp_split_cols(w.value, defer=True)))
+                reqs.append((w.value, "cols", lambda w=w: ops.sp_split_cols_jobs(w.value)))
             elif ops.sp_tiles(d_in) and (i > 0 or need_input_grad):  # (the projection's input gradient: on request only)
-                reqs.append((w.value, "rows", lambda w=w: ops.sp_split_rows(w.value, defer=True)))
+                reqs.append((w.value, "rows", lambda w=w: ops.sp_split_rows_jobs(w.value)))
         for mp in self._mp_layers:
             reqs.extend(mp.weight_operand_requests(graph, V, H, backward))
         ops.presplit_weight_operands(reqs)
@@ -262,7 +262,7 @@ class GNN:
         the layer-input dropout that follows: applied in the product's epilogue where the split-operand kernel runs it.
         -> (output, pre-activation | None, dropout applied?)"""
         if x.shape[0] > 0 and self._dense_f16x2(w.value.shape[0], w.value.shape[1]):
-            wt = ops.sp_weight_operand(w.value, "cols", lambda: ops.sp_split_cols(w.value, defer=True))
+            wt = ops.sp_weight_operand(w.value, "cols", lambda: ops.sp_split_cols_jobs(w.value))
             if act_name == "gelu":
                 pre = ops.sp_gemm_nt(ops.sp_rows_of(x), wt)
                 return ops.activation_forward("gelu", pre), pre, False
@@ -287,7 +287,7 @@ class GNN:
             if not need_input_grad:
                 return None
             if ops.sp_tiles(d_in):
-                wr = ops.sp_weight_operand(w.value, "rows", lambda: ops.sp_split_rows(w.value, defer=True))
+                wr = ops.sp_weight_operand(w.value, "rows", lambda: ops.sp_split_rows_jobs(w.value))
                 return ops.sp_gemm_nt(g_sp, wr, act_grad=act_grad)
             return ops.gemm_grad(gpre, w.value, trans_b=True, act_grad=act_grad)
         w.grad = ops.gemm(x, gpre, trans_a=True)
@@ -469,57 +469,54 @@ class GNN:
             g = torch.zeros_like(ctx["steps"][-1].get("dense_out", ctx["h0"])) if self._num_layers else None
         g_is_pre = False  # g already carries the activation derivative of the op differentiated next
         g_last = None
-        try:
-            was_f16x2 = ops.get_gemm_mode() == ops.GEMM_F16X2
-            self._backward_passes += 1
-            periodic = self.guard_check_every > 0 and self._backward_passes % self.guard_check_every == 0
-            if ops.capturing():  # a step being captured into a hipGraph cannot wait for the device: never a checked pass
-                if was_f16x2 and self._guard_sync_passes > 0:
-                    raise RuntimeError("tf2_gnn_amd: this GNN's first backward passes are checked synchronously "
-                                       f"(TFGNN_GUARD_SYNC_PASSES, {self._guard_sync_passes} left); run them eagerly before "
-                                       "capturing the step (capture.CapturedStep warmup)")
-                periodic = False
-            if not (was_f16x2 and (self._guard_sync_passes > 0 or periodic)):
-                self.guard_tripped_last_backward = bool(was_f16x2 and ops.f16x2_guard_flag_async())
-                if was_f16x2:
-                    self._unchecked_split_passes += 1
-                    self._unchecked_epoch = ops.REARM_EPOCH[0]
-                return self._backward_walk(ctx, g, g_is_pre, g_last, extras, need_input_grad)
-            # The spread guard of the split weight-gradient products reports through a host-visible flag WITHOUT a stream
-            # synchronisation: a pass that trips it has produced its gradients by the time the host notices.  For the
-            # first passes of a model (TFGNN_GUARD_SYNC_PASSES, default 3: whether a model's gradient rows are spread
-            # that far shows at once - RGAT's attention-weighted rows trip it on the first step) wait for the pass and,
-            # if it tripped, run it again on sturdier kernels, one step per attempt (_demote_fragile_weight_gradients): this
-            # stack's Dense / projection weight gradients on the two-factor product, then its Dense products off the split
-            # operands (their operand rows - un-normalised sums, attention-weighted gradients - are the usual culprit; the
-            # message products keep their split operands), then the per-relation MLP weight gradients, then the whole mode.  Later
-            # trips demote the mode from the NEXT pass on and say so (ops.get_gemm_mode warns), but the tripping pass
-            # itself is not recomputed (README.md).  While this section runs, a set flag does not demote the mode on sight.
-            if self._guard_sync_passes > 0:
-                self._guard_sync_passes -= 1
-            self.guard_tripped_last_backward = False
-            self._unchecked_split_passes = 0
-            with ops.hold_spread_guard():
-                result = self._backward_walk(ctx, g, g_is_pre, g_last, extras, need_input_grad)
-                for attempt in range(4):
-                    if not ops.f16x2_guard_tripped_sync():
-                        break
-                    self.guard_tripped_last_backward = True
-                    what = self._demote_fragile_weight_gradients() if attempt < 3 else None
-                    if what:
-                        ops.rearm_spread_guard()
-                        import warnings
+        was_f16x2 = ops.get_gemm_mode() == ops.GEMM_F16X2
+        self._backward_passes += 1
+        periodic = self.guard_check_every > 0 and self._backward_passes % self.guard_check_every == 0
+        if ops.capturing():  # a step being captured into a hipGraph cannot wait for the device: never a checked pass
+            if was_f16x2 and self._guard_sync_passes > 0:
+                raise RuntimeError("tf2_gnn_amd: this GNN's first backward passes are checked synchronously "
+                                   f"(TFGNN_GUARD_SYNC_PASSES, {self._guard_sync_passes} left); run them eagerly before "
+                                   "capturing the step (capture.CapturedStep warmup)")
+            periodic = False
+        if not (was_f16x2 and (self._guard_sync_passes > 0 or periodic)):
+            self.guard_tripped_last_backward = bool(was_f16x2 and ops.f16x2_guard_flag_async())
+            if was_f16x2:
+                self._unchecked_split_passes += 1
+                self._unchecked_epoch = ops.REARM_EPOCH[0]
+            return self._backward_walk(ctx, g, g_is_pre, g_last, extras, need_input_grad)
+        # The spread guard of the split weight-gradient products reports through a host-visible flag WITHOUT a stream
+        # synchronisation: a pass that trips it has produced its gradients by the time the host notices.  For the
+        # first passes of a model (TFGNN_GUARD_SYNC_PASSES, default 3: whether a model's gradient rows are spread
+        # that far shows at once - RGAT's attention-weighted rows trip it on the first step) wait for the pass and,
+        # if it tripped, run it again on sturdier kernels, one step per attempt (_demote_fragile_weight_gradients): this
+        # stack's Dense / projection weight gradients on the two-factor product, then its Dense products off the split
+        # operands (their operand rows - un-normalised sums, attention-weighted gradients - are the usual culprit; the
+        # message products keep their split operands), then the per-relation MLP weight gradients, then the whole mode.  Later
+        # trips demote the mode from the NEXT pass on and say so (ops.get_gemm_mode warns), but the tripping pass
+        # itself is not recomputed (README.md).  While this section runs, a set flag does not demote the mode on sight.
+        if self._guard_sync_passes > 0:
+            self._guard_sync_passes -= 1
+        self.guard_tripped_last_backward = False
+        self._unchecked_split_passes = 0
+        with ops.hold_spread_guard():
+            result = self._backward_walk(ctx, g, g_is_pre, g_last, extras, need_input_grad)
+            for attempt in range(4):
+                if not ops.f16x2_guard_tripped_sync():
+                    break
+                self.guard_tripped_last_backward = True
+                what = self._demote_fragile_weight_gradients() if attempt < 3 else None
+                if what:
+                    ops.rearm_spread_guard()
+                    import warnings
 
-                        warnings.warn(f"tf2_gnn_amd: operand rows of a weight-gradient product of this GNN are spread beyond the range "
-                                      f"of the split-operand product that ran: {what}; the pass was recomputed")
-                    else:
-                        ops.demote_gemm_mode()  # the whole mode (sticky), with a warning
-                    for v in self.trainable_variables:
-                        v.grad = None
-                    result = self._backward_walk(ctx, g, False, None, extras, need_input_grad)
-            return result
-        finally:
-            ops.aux_flush()  # nothing the pass deferred is left for a later call
+                    warnings.warn(f"tf2_gnn_amd: operand rows of a weight-gradient product of this GNN are spread beyond the range "
+                                  f"of the split-operand product that ran: {what}; the pass was recomputed")
+                else:
+                    ops.demote_gemm_mode()  # the whole mode (sticky), with a warning
+                for v in self.trainable_variables:
+                    v.grad = None
+                result = self._backward_walk(ctx, g, False, None, extras, need_input_grad)
+        return result
 
     def guard_state(self) -> Dict[str, Any]:
         """What the spread-guard policy has done to this stack so far: ``tripped`` (the last backward pass, see

@@ -433,10 +433,10 @@ class GNN_Edge_MLP(MessagePassing):
         if L != graph.num_edge_types or Din != in_dim or not self._f16x2_eligible(num_nodes, in_dim, L, H):
             return []
         if backward:
-            return [(W, "rows", lambda: ops.sp_split_rows(W[0], segments=(H, Din * H, L * H), defer=True))]
+            return [(W, "rows", lambda: ops.sp_split_rows_jobs(W[0], segments=(H, Din * H, L * H)))]
         if messages_per_edge(self, graph, in_dim, H):  # (one product per edge type on rows of X: no stacked operand)
             return []
-        return [(W, "cols", lambda: ops.sp_split_cols(W.view(L * Din, H), defer=True))]
+        return [(W, "cols", lambda: ops.sp_split_cols_jobs(W.view(L * Din, H)))]
 
     def _forward_A(self, X, g, fuse_act, want_split=False, drop=None):
         if self._use_compact_buckets(g):
@@ -486,8 +486,8 @@ class GNN_Edge_MLP(MessagePassing):
                 pre, _ = ops.mp_forward(g, view, X, W, row_scale=row_scale, act=None if gelu_split else fuse_act,
                                         dropout=drop if fuse_drop else None, tile_kmask=kmask, row_map=rmap, want_split=split_out)
             else:
-                A_sp = ops.graph_gather_sp(g, view, X, row_scale=row_scale, rows_per_operand_row=L, defer_combine=True)
-                Wt_sp = ops.sp_weight_operand(W, "cols", lambda: ops.sp_split_cols(W.view(L * Din, H), defer=True))
+                A_sp = ops.graph_gather_sp(g, view, X, row_scale=row_scale, rows_per_operand_row=L)
+                Wt_sp = ops.sp_weight_operand(W, "cols", lambda: ops.sp_split_cols_jobs(W.view(L * Din, H)))
                 if split_out:  # (never with a split gelu)
                     pre, _ = ops.sp_gemm_nt_split(A_sp, Wt_sp, act=fuse_act, dropout=drop if fuse_drop else None, tile_kmask=kmask,
                                                   row_map=rmap)
@@ -558,9 +558,8 @@ class GNN_Edge_MLP(MessagePassing):
             X_sp = ops.sp_rows_of(X)  # written by the dropout kernel when X came out of one
             dX, _, dW = ops.mp_backward(g, d_agg.contiguous(), W, X_sp, edge_weight=ew_s, skip=skip, want_split=split, **kw)
         else:
-            G_sp = ops.graph_gather_sp(g, ops.VIEW_BY_SRC_TYPED, d_agg.contiguous(), edge_weight=ew_s, rows_per_operand_row=L,
-                                       defer_combine=True)
-            Wh_sp = ops.sp_weight_operand(W, "rows", lambda: ops.sp_split_rows(W[0], segments=(H, D * H, L * H), defer=True))
+            G_sp = ops.graph_gather_sp(g, ops.VIEW_BY_SRC_TYPED, d_agg.contiguous(), edge_weight=ew_s, rows_per_operand_row=L)
+            Wh_sp = ops.sp_weight_operand(W, "rows", lambda: ops.sp_split_rows_jobs(W[0], segments=(H, D * H, L * H)))
             if split:
                 dX, _ = ops.sp_gemm_nt_split(G_sp, Wh_sp, **kw, **skip)
             else:
@@ -661,10 +660,10 @@ class GNN_Edge_MLP(MessagePassing):
 
     @staticmethod
     def _stacked_transposed_operand(W):
-        """[L, in, out] kernels -> SP16 [out, L * in]: column block l is W_l^T, relation l's [N, K] operand of the forward product
-        (ONE split launch for the whole stack; a row's scale is shared by the relations)"""
+        """[L, in, out] kernels -> SP16 [out, L * in]: column block l is W_l^T, relation l's [N, K] operand of the forward product,
+        as split jobs (ONE split for the whole stack; a row's scale is shared by the relations)"""
         L, K, N = W.shape
-        return ops.sp_split_cols(W.view(L * K, N), defer=True)
+        return ops.sp_split_cols_jobs(W.view(L * K, N))
 
     def _forward_B_compact_split(self, X, g, fuse_act):
         mlps = self._edge_type_mlps
@@ -983,9 +982,9 @@ class GNN_Edge_MLP(MessagePassing):
         dX = None
         halves = ((ops.VIEW_BY_SRC_TYPED, ops.G_EID_BY_SRC, True, 0), (ops.VIEW_BY_DST_TYPED, ops.G_EID_BY_DST, False, D))
         for view, eid, by_src, d0 in halves:
-            G_sp = ops.graph_gather_sp(g, view, dcur, col=g.array(eid), rows_per_operand_row=L, defer_combine=True)
-            Wh_sp = ops.sp_weight_operand(W0, f"rows_half{d0}", lambda d0=d0: ops.sp_split_rows(
-                W0[0, d0:d0 + D], segments=(H0, 2 * D * H0, L * H0), defer=True))  # row d = [W_0[d0 + d, :] | W_1[d0 + d, :] | ..]
+            G_sp = ops.graph_gather_sp(g, view, dcur, col=g.array(eid), rows_per_operand_row=L)
+            Wh_sp = ops.sp_weight_operand(W0, f"rows_half{d0}", lambda d0=d0: ops.sp_split_rows_jobs(
+                W0[0, d0:d0 + D], segments=(H0, 2 * D * H0, L * H0)))  # row d = [W_0[d0 + d, :] | W_1[d0 + d, :] | ..]
             skip = self._skip_args(g, L, H0, by_src)
             if dX is None:
                 dX = ops.sp_gemm_nt(G_sp, Wh_sp, **kw, **skip)

@@ -98,7 +98,7 @@ class RGAT(MessagePassing):
         f16 = self._f16x2_eligible(V, X.shape[1], L, H)
         if f16:
             # f16x2: Y = X [W_0 | ... | W_{L-1}] on split operands (X's split form comes from the dropout kernel in a GNN stack)
-            Wn = ops.sp_weight_operand(self._kernels, "cols", lambda: ops.sp_split_cols(self._kernels, defer=True))
+            Wn = ops.sp_weight_operand(self._kernels, "cols", lambda: ops.sp_split_cols_jobs(self._kernels))
             Y = ops.sp_gemm_nt(ops.sp_rows_of(X), Wn)
         else:
             Y = ops.gemm(X, self._kernels)  # [V, L*H] == rows (v, l) of width H
@@ -254,7 +254,7 @@ class RGAT(MessagePassing):
                                                        ops._ptr(dY_sp.data), ops._ptr(dY_sp.inv_scale), ops._stream())
             if rc == 0:
                 d_kernels = ops.gemm(X, dY.view(V, L * H), trans_a=True)  # X^T dY  [D, L*H]
-                Wr = ops.sp_weight_operand(self._kernels, "rows", lambda: ops.sp_split_rows(self._kernels, defer=True))
+                Wr = ops.sp_weight_operand(self._kernels, "rows", lambda: ops.sp_split_rows_jobs(self._kernels))
                 if want_split_input_grad and ops.sp_one_tile(D):
                     dX, _ = ops.sp_gemm_nt_split(dY_sp, Wr, out_mul=out_mul, act_grad=out_act_grad)
                 else:

@@ -6,7 +6,6 @@ current HIP stream, every FLOP and byte of the hot path runs in libtfgnn.so.
 from __future__ import annotations
 
 import ctypes
-import threading
 import weakref
 import os
 from typing import Optional, Sequence
@@ -81,66 +80,41 @@ _get_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 _get_device = getattr(torch._C, "_cuda_getDevice", None)
 
 
-def _raw_stream() -> int:
-    """hipStream_t of torch's current stream on the current device.  torch.cuda.current_stream() builds a Stream object per
-    call (~4 us: 74 calls = 0.3 ms of the 1.5 ms a PPI-sized step spends on the host, profiles/r06_ppi_host_profile_before.txt);
-    the two private accessors it is made of cost ~0.3 us."""
+def _stream() -> int:
+    """hipStream_t of torch's current stream on the current device: the launch stream of a library call.
+    torch.cuda.current_stream() builds a Stream object per call (~4 us: 74 calls = 0.3 ms of the 1.5 ms a PPI-sized step
+    spends on the host, profiles/r06_ppi_host_profile_before.txt); the two private accessors it is made of cost ~0.3 us."""
     if _get_raw_stream is not None and _get_device is not None:
         return _get_raw_stream(_get_device())
     return torch.cuda.current_stream().cuda_stream
 
 
-def _stream() -> int:
-    """The launch stream of a library call.  Every wrapper evaluates this right before its C call, which makes it the one
-    place where deferred small passes (``aux_defer``) that the coming kernel may depend on are launched first."""
-    if _AUX_PENDING:
-        aux_flush()
-    return _raw_stream()
-
-
 # ---- small passes that share a launch (include/tfgnn.h tfgnn_aux_launch) ---------------------------------------------------------
-# A deferred job runs in the next library launch: ``_stream()`` flushes the queue before every library call.  A flush launches
-# the stage-0 jobs, then the stage-1 jobs (which read what a stage-0 job wrote: the split behind the column maxima of a
-# two-pass weight split), both on the stream the jobs were deferred for.  Deferring only ever moves a pass LATER, and nothing
-# is launched between a deferral and the flush that runs it, so every input of a job is complete and none is overwritten in
-# between.  Jobs pending for one stream are flushed before a job for another stream is queued.
-# INTERNAL: ``defer=`` / ``defer_combine=`` arguments of the wrappers are for the layer code of this package, which always issues
-# the consumer of a deferred result as a library call right behind it.  A caller outside the library that reads a deferred
-# result with torch (or synchronises and expects it to exist) must call ``aux_flush()`` first; ``SplitOperand.synced()`` does.
-# The queue is guarded by a lock: autograd runs ``GNN.backward`` on its own thread (ADVICE r4).
-_AUX_PENDING = []  # [(stage, AuxJob, keep-alive tuple)]
-_AUX_STREAM = [None]
-_AUX_LOCK = threading.RLock()
+# The weight splits of a pass are built as jobs (``sp_split_rows_jobs`` / ``sp_split_cols_jobs``: allocate the operand, fill the
+# job, launch nothing) and launched by whoever built them, at once: ``sp_weight_operand`` launches the one split it needs,
+# ``presplit_weight_operands`` all stale operands of a pass together.  Nothing is queued between calls.
+class SplitJobs:
+    """A split operand that is still to be written: ``operand`` (allocated, empty), the jobs that write it - ``stage0``, then
+    ``stage1`` in a launch after it (the conversion behind the column maxima of a two-pass weight split) - and ``keep``, the
+    tensors the jobs read or write, to be held until ``aux_flush`` has launched them."""
+
+    __slots__ = ("operand", "stage0", "stage1", "keep")
+
+    def __init__(self, operand, stage0=(), stage1=(), keep=()):
+        self.operand, self.stage0, self.stage1, self.keep = operand, stage0, stage1, keep
 
 
-def aux_enabled() -> bool:
-    return env("TFGNN_AUX_MERGE", "1") != "0"
-
-
-def aux_defer(job, keep=(), stage: int = 0) -> None:
-    """Queue a tfgnn_aux_job (``_lib.AuxJob``; kind 0 = nothing) for the next flush, in its stage-0 launch or (stage 1) in
-    the launch after it.  ``keep``: tensors the job reads or writes, held until it has been launched."""
-    if job.kind == 0 or job.num_blocks == 0:
-        return
-    st = _raw_stream()
-    with _AUX_LOCK:
-        if _AUX_PENDING and _AUX_STREAM[0] != st:
-            aux_flush()
-        _AUX_STREAM[0] = st
-        _AUX_PENDING.append((stage, job, keep))
-
-
-def aux_flush() -> None:
-    """Launch what has been deferred (one launch per 8 jobs): the stage-0 jobs, then the stage-1 jobs, on the stream they
-    were deferred for."""
-    with _AUX_LOCK:
-        batch = list(_AUX_PENDING)
-        del _AUX_PENDING[:]
-        for stage in (0, 1):
-            live = [j for s, j, _ in batch if s == stage]
-            if live:
-                jobs = (_lib.AuxJob * len(live))(*live)
-                _lib.check(_lib.load().tfgnn_aux_launch(jobs, len(jobs), _AUX_STREAM[0]))
+def aux_flush(batch) -> None:
+    """Launch a sequence of ``SplitJobs`` on the current stream: the stage-0 jobs of all of them in one tfgnn_aux_launch, then
+    the stage-1 jobs in a second one; empty jobs (kind 0, or no blocks) are skipped.  Returns when both launches have been
+    issued.  (The module-level name is part of what bench.py measures: its step breakdown looks ``aux_flush`` up to attribute
+    the launches at the start of a pass.)"""
+    stream = _stream()
+    for stage in ("stage0", "stage1"):
+        live = [j for sj in batch for j in getattr(sj, stage) if j.kind != 0 and j.num_blocks != 0]
+        if live:
+            jobs = (_lib.AuxJob * len(live))(*live)
+            _lib.check(_lib.load().tfgnn_aux_launch(jobs, len(jobs), stream))
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -357,7 +331,7 @@ _workspaces = {}
 
 
 def _workspace(device, nbytes: int) -> torch.Tensor:
-    key = (device.type, device.index, _raw_stream())
+    key = (device.type, device.index, _stream())
     ws = _workspaces.get(key)
     if ws is None or ws.numel() < nbytes:
         ws = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
@@ -622,7 +596,6 @@ def _f16x2_on() -> bool:
         try:
             handled = [w for w in (fn() for fn in list(_LATE_TRIP_POLICIES.values())) if w]
             if handled:
-                aux_flush()
                 _lib.check(lib.tfgnn_gemm_set_mode(GEMM_F16X2))
                 on = True
                 import warnings
@@ -652,7 +625,6 @@ def set_gemm_mode(mode) -> int:
     lib = _lib.load()
     prev = get_gemm_mode()
     mode = _GEMM_MODE_NAMES.get(mode, mode)
-    aux_flush()
     _lib.check(lib.tfgnn_gemm_set_mode(mode))
     _f16x2[0] = mode == GEMM_F16X2
     if mode == GEMM_F16X2:
@@ -719,7 +691,6 @@ class hold_spread_guard:
 def rearm_spread_guard() -> None:
     """Clear the spread flag WITHOUT demoting the mode (the caller has dealt with the product that tripped it).  Waits for the
     stream first: a factor computation still in flight must not set it again."""
-    aux_flush()
     torch.cuda.current_stream().synchronize()
     _lib.load().tfgnn_sp_spread_flag(1)
 
@@ -745,7 +716,6 @@ def f16x2_guard_tripped_sync() -> bool:
     """Wait for the current stream, then read the spread guard: True if a split weight-gradient product enqueued so far met
     operand rows spread over more than 2^20 (its result may have lost low-order rows).  The synchronous form of the guard:
     ``GNN.backward`` uses it for the first backward passes of a model and recomputes a tripped pass on the exact kernels."""
-    aux_flush()
     torch.cuda.current_stream().synchronize()
     return bool(_lib.load().tfgnn_sp_spread_flag(0))
 
@@ -1083,8 +1053,7 @@ def dropout_epoch() -> int:
     """The dropout epoch (include/tfgnn.h: masks are a function of (seed, element, epoch); 0 unless something advanced it).
     Waits for the current stream."""
     v = ctypes.c_uint32()
-    aux_flush()
-    _lib.check(_lib.load().tfgnn_dropout_epoch_get(ctypes.byref(v), _raw_stream()))
+    _lib.check(_lib.load().tfgnn_dropout_epoch_get(ctypes.byref(v), _stream()))
     return int(v.value)
 
 
@@ -1435,20 +1404,9 @@ class SplitOperand:
     def __init__(self, data, inv_scale, rows, cols, scale_block):
         self.data, self.inv_scale, self.rows, self.cols, self.scale_block = data, inv_scale, rows, cols, scale_block
 
-    def synced(self) -> "SplitOperand":
-        """self, after every deferred small pass has been launched: an operand made with ``defer=True`` is written by the
-        next merged launch, which only a following LIBRARY call triggers - read ``data`` / ``inv_scale`` with torch (or hand
-        them to another library) through this."""
-        aux_flush()
-        return self
 
-
-def sp_split_rows(x: torch.Tensor, *, scale_block: int = 0, segments=None, fixed_inv_scale: Optional[torch.Tensor] = None,
-                  out: Optional[SplitOperand] = None, defer: bool = False) -> SplitOperand:
-    """SP16 form of the rows of ``x`` [R, C] (unit inner stride).  ``segments = (seg_len, seg_stride, cols)``: row r is
-    assembled from cols / seg_len pieces x.data[r * ld + j * seg_stride : ... + seg_len] (e.g. row d of
-    [W_0[d, :] | W_1[d, :] | ...] from stacked kernels [L, D, H]: x = W[0], segments = (H, D * H, L * H))."""
-    lib = _lib.load()
+def _split_rows_args(x, scale_block, segments, fixed_inv_scale, out):
+    """-> (out, the arguments tfgnn_sp_split_rows and tfgnn_sp_split_rows_job share, the tensors they point into)"""
     _require_dev(x, torch.float32, "x")
     x, ld = _rowmajor(x, "x")
     rows = x.shape[0]
@@ -1463,17 +1421,31 @@ def sp_split_rows(x: torch.Tensor, *, scale_block: int = 0, segments=None, fixed
             out = SplitOperand(data, fixed_inv_scale, rows, cols, 0)  # one scale for the whole tensor
         else:
             out = SplitOperand(data, torch.empty((rows, cols // sb), dtype=torch.float32, device=x.device), rows, cols, sb)
-    if defer and rows > 0 and aux_enabled():  # a job of the next merged small-pass launch (weights: nothing but launch latency)
-        job = _lib.AuxJob()
-        _lib.check(lib.tfgnn_sp_split_rows_job(_ptr(x), ld, seg_len, seg_stride, rows, cols, sb, _ptr(out.data), out.data.stride(0),
-                                               None if fixed_inv_scale is not None else _ptr(out.inv_scale), _ptr(fixed_inv_scale),
-                                               ctypes.byref(job)))
-        aux_defer(job, keep=(x, out.data, out.inv_scale, fixed_inv_scale))
-        return out
-    _lib.check(lib.tfgnn_sp_split_rows(_ptr(x), ld, seg_len, seg_stride, rows, cols, sb, _ptr(out.data), out.data.stride(0),
-                                       None if fixed_inv_scale is not None else _ptr(out.inv_scale), _ptr(fixed_inv_scale),
-                                       _stream()))
+    args = (_ptr(x), ld, seg_len, seg_stride, rows, cols, sb, _ptr(out.data), out.data.stride(0),
+            None if fixed_inv_scale is not None else _ptr(out.inv_scale), _ptr(fixed_inv_scale))
+    return out, args, (x, out.data, out.inv_scale, fixed_inv_scale)
+
+
+def sp_split_rows(x: torch.Tensor, *, scale_block: int = 0, segments=None, fixed_inv_scale: Optional[torch.Tensor] = None,
+                  out: Optional[SplitOperand] = None) -> SplitOperand:
+    """SP16 form of the rows of ``x`` [R, C] (unit inner stride).  ``segments = (seg_len, seg_stride, cols)``: row r is
+    assembled from cols / seg_len pieces x.data[r * ld + j * seg_stride : ... + seg_len] (e.g. row d of
+    [W_0[d, :] | W_1[d, :] | ...] from stacked kernels [L, D, H]: x = W[0], segments = (H, D * H, L * H))."""
+    out, args, _ = _split_rows_args(x, scale_block, segments, fixed_inv_scale, out)
+    _lib.check(_lib.load().tfgnn_sp_split_rows(*args, _stream()))
     return out
+
+
+def sp_split_rows_jobs(x: torch.Tensor, *, scale_block: int = 0, segments=None, fixed_inv_scale: Optional[torch.Tensor] = None,
+                       out: Optional[SplitOperand] = None) -> SplitJobs:
+    """``sp_split_rows`` as a job of a shared small-pass launch (weights: nothing but launch latency): allocates the operand and
+    fills the job, launches nothing - ``aux_flush`` does."""
+    out, args, keep = _split_rows_args(x, scale_block, segments, fixed_inv_scale, out)
+    if out.rows <= 0:
+        return SplitJobs(out)
+    job = _lib.AuxJob()
+    _lib.check(_lib.load().tfgnn_sp_split_rows_job(*args, ctypes.byref(job)))
+    return SplitJobs(out, (job,), (), keep)
 
 
 _sp_rows_memo = {}  # id(tensor) -> (weakref, version, SplitOperand): split forms written by the kernel that produced the tensor
@@ -1498,40 +1470,44 @@ def sp_rows_of(x: torch.Tensor) -> SplitOperand:
     return op
 
 
-def sp_split_cols(w: torch.Tensor, defer: bool = False, out: Optional[SplitOperand] = None) -> SplitOperand:
-    """SP16 form of w^T for a row-major [K, N] matrix (a Keras kernel): rows = N, cols = K, one scale per row.
-    defer: as a job of the next merged small-pass launch (``aux_defer``).  out: write into this operand (N rows of K columns:
-    a slice of a stack of per-group operands)."""
-    lib = _lib.load()
+def _split_cols_operand(w, out):
+    """-> (w, its leading dimension, K, N, data, inv_scale) of the SP16 form of w^T"""
     _require_dev(w, torch.float32, "w")
     w, ld = _rowmajor(w, "w")
     K, N = w.shape
     if out is not None:
         if out.rows != N or out.cols != K:
             raise ValueError("sp_split_cols: out must hold N rows of K columns")
-        data, inv = out.data, out.inv_scale
-    else:
-        data = torch.empty((N, K * 4), dtype=torch.uint8, device=w.device)
-        inv = torch.empty((N, 1), dtype=torch.float32, device=w.device)
-    if defer and aux_enabled():
-        two_pass = lib.tfgnn_sp_split_cols_two_pass_bytes(K, N)
-        if two_pass:
-            # long K (the stacked kernels of many relations): the column maxima as a pass of their own in THIS merged launch, the
-            # conversion - which then reads every byte once instead of once per K slice - in the next one (stage 1 of the
-            # same flush: before the consumer's kernel)
-            cm = torch.empty(two_pass, dtype=torch.uint8, device=w.device)
-            mjob, sjob = _lib.AuxJob(), _lib.AuxJob()
-            _lib.check(lib.tfgnn_sp_split_cols_jobs(_ptr(w), ld, K, N, _ptr(data), data.stride(0), _ptr(inv), _ptr(cm), two_pass,
-                                                    ctypes.byref(mjob), ctypes.byref(sjob)))
-            aux_defer(mjob, keep=(w, cm))
-            aux_defer(sjob, keep=(w, data, inv, cm), stage=1)
-            return SplitOperand(data, inv, N, K, K)
-        job = _lib.AuxJob()
-        _lib.check(lib.tfgnn_sp_split_cols_job(_ptr(w), ld, K, N, _ptr(data), data.stride(0), _ptr(inv), ctypes.byref(job)))
-        aux_defer(job, keep=(w, data, inv))
-    else:
-        _lib.check(lib.tfgnn_sp_split_cols(_ptr(w), ld, K, N, _ptr(data), data.stride(0), _ptr(inv), _stream()))
+        return w, ld, K, N, out.data, out.inv_scale
+    return (w, ld, K, N, torch.empty((N, K * 4), dtype=torch.uint8, device=w.device),
+            torch.empty((N, 1), dtype=torch.float32, device=w.device))
+
+
+def sp_split_cols(w: torch.Tensor, out: Optional[SplitOperand] = None) -> SplitOperand:
+    """SP16 form of w^T for a row-major [K, N] matrix (a Keras kernel): rows = N, cols = K, one scale per row.
+    out: write into this operand (N rows of K columns: a slice of a stack of per-group operands)."""
+    w, ld, K, N, data, inv = _split_cols_operand(w, out)
+    _lib.check(_lib.load().tfgnn_sp_split_cols(_ptr(w), ld, K, N, _ptr(data), data.stride(0), _ptr(inv), _stream()))
     return SplitOperand(data, inv, N, K, K)
+
+
+def sp_split_cols_jobs(w: torch.Tensor, out: Optional[SplitOperand] = None) -> SplitJobs:
+    """``sp_split_cols`` as jobs of shared small-pass launches: allocates the operand and fills the jobs, launches nothing -
+    ``aux_flush`` does.  Long K (the stacked kernels of many relations, tfgnn_sp_split_cols_two_pass_bytes > 0): the column
+    maxima as a stage-0 job, the conversion - which then reads every byte once instead of once per K slice - as a stage-1 job."""
+    lib = _lib.load()
+    w, ld, K, N, data, inv = _split_cols_operand(w, out)
+    op = SplitOperand(data, inv, N, K, K)
+    two_pass = lib.tfgnn_sp_split_cols_two_pass_bytes(K, N)
+    if two_pass:
+        cm = torch.empty(two_pass, dtype=torch.uint8, device=w.device)
+        mjob, sjob = _lib.AuxJob(), _lib.AuxJob()
+        _lib.check(lib.tfgnn_sp_split_cols_jobs(_ptr(w), ld, K, N, _ptr(data), data.stride(0), _ptr(inv), _ptr(cm), two_pass,
+                                                ctypes.byref(mjob), ctypes.byref(sjob)))
+        return SplitJobs(op, (mjob,), (sjob,), (w, data, inv, cm))
+    job = _lib.AuxJob()
+    _lib.check(lib.tfgnn_sp_split_cols_job(_ptr(w), ld, K, N, _ptr(data), data.stride(0), _ptr(inv), ctypes.byref(job)))
+    return SplitJobs(op, (job,), (), (w, data, inv))
 
 
 def _tile_kmask(t, M):
@@ -1560,7 +1536,6 @@ def _ensure_splitk_workspace(device, rows: int) -> None:
     if env("TFGNN_NT_SPLITK", "1") == "0":
         return
     ws = torch.empty(_SPLITK_BYTES, dtype=torch.uint8, device=device)
-    aux_flush()
     _lib.check(_lib.load().tfgnn_sp_gemm_nt_set_splitk_workspace(_ptr(ws), _SPLITK_BYTES))
     _SPLITK_WS["ws"] = ws
 
@@ -1817,8 +1792,7 @@ def split_rows_remembered(x: torch.Tensor) -> SplitOperand:
 
 
 def graph_gather_sp(graph: "Graph", view: int, inp: torch.Tensor, *, col=None, edge_weight=None, row_scale=None,
-                    fixed_inv_scale: Optional[torch.Tensor] = None, rows_per_operand_row: int = 1,
-                    defer_combine: bool = False) -> SplitOperand:
+                    fixed_inv_scale: Optional[torch.Tensor] = None, rows_per_operand_row: int = 1) -> SplitOperand:
     """graph_gather (plain sums) with the result written as an SP16 operand (tfgnn_graph_gather_reduce_sp).
     ``rows_per_operand_row`` = L folds the rows (v, l) of a typed view into the [V, L * width] operand with one scale
     block per edge type.  Compact views: one operand row (and scale) per non-empty bucket."""
@@ -1845,24 +1819,12 @@ def graph_gather_sp(graph: "Graph", view: int, inp: torch.Tensor, *, col=None, e
     graph.ensure(_VIEW_PARTS[view])
     ws_bytes = lib.tfgnn_graph_gather_workspace_bytes(graph._h, view, width)
     ws = _workspace(inp.device, ws_bytes) if ws_bytes else None
-    if defer_combine and aux_enabled():
-        # (the form that used to get the combine pass of the long buckets back as a job of the next merged launch: the gather
-        # combines them inside its own launch now, the job comes back empty and nothing is queued)
-        job = _lib.AuxJob()
-        _lib.check(
-            lib.tfgnn_graph_gather_reduce_sp_deferred(
-                graph._h, view, _ptr(col), _ptr(edge_weight), _ptr(row_scale), _ptr(inp), ld_in, width, _ptr(data), width * 4,
-                _ptr(inv), _ptr(fixed_inv_scale), _ptr(ws), ws.numel() if ws is not None else 0, ctypes.byref(job), _stream(),
-            )
+    _lib.check(
+        lib.tfgnn_graph_gather_reduce_sp(
+            graph._h, view, _ptr(col), _ptr(edge_weight), _ptr(row_scale), _ptr(inp), ld_in, width, _ptr(data), width * 4,
+            _ptr(inv), _ptr(fixed_inv_scale), _ptr(ws), ws.numel() if ws is not None else 0, _stream(),
         )
-        aux_defer(job, keep=(graph, row_scale, ws, data, inv, fixed_inv_scale))
-    else:
-        _lib.check(
-            lib.tfgnn_graph_gather_reduce_sp(
-                graph._h, view, _ptr(col), _ptr(edge_weight), _ptr(row_scale), _ptr(inp), ld_in, width, _ptr(data), width * 4,
-                _ptr(inv), _ptr(fixed_inv_scale), _ptr(ws), ws.numel() if ws is not None else 0, _stream(),
-            )
-        )
+    )
     if fixed_inv_scale is not None:
         return SplitOperand(data, fixed_inv_scale, num_rows // R, R * width, 0)  # scale_block 0: one scale for the tensor
     return SplitOperand(data, inv, num_rows // R, R * width, width)
@@ -1908,7 +1870,7 @@ def mp_forward(graph: "Graph", view: int, x: torch.Tensor, W: torch.Tensor, *, r
     ws = _workspace(dev, ws_bytes) if ws_bytes else None
     rate, seed = dropout if dropout is not None else (0.0, 0)
     _ensure_splitk_workspace(dev, V)
-    stream = _stream()  # (launches what was deferred before this layer: its inputs may depend on it)
+    stream = _stream()
     a = _lib.MpForwardArgs()
     a.struct_size = ctypes.sizeof(_lib.MpForwardArgs)
     a.kind = 0
@@ -2099,7 +2061,6 @@ def notify_weights_changed(tensor: Optional[torch.Tensor] = None) -> None:
     through ``tensor.data``, a raw-pointer optimizer kernel, another framework writing into the buffer.  Every derived form
     of ``tensor`` (or of all weights) is dropped and rebuilt at its next use.  ``Variable.assign`` / ``Variable.mark_updated``
     call this; in-place torch arithmetic on ``Variable.value`` itself is seen through the version counter as well."""
-    aux_flush()  # a deferred split job reads its source weight when it is LAUNCHED: run it on the old values, then drop it
     if tensor is None:
         _sp_weight_cache.clear()
         return
@@ -2137,17 +2098,20 @@ def sp_weight_operand(w: torch.Tensor, kind: str, build):
     op = _cached_weight_operand(w, kind)
     if op is None:
         op = build()
+        if isinstance(op, SplitJobs):
+            aux_flush([op])
+            op = op.operand
         _cache_weight_operand(w, kind, op)
     return op
 
 
 def presplit_weight_operands(requests) -> int:
-    """Build every STALE derived form among ``requests`` = [(w, kind, build)] now, in one merged small-pass launch (one per
-    eight jobs): the start of a stack's forward or backward pass, where all the operands of the pass can be split at once -
-    the weights do not change between the optimizer update and the end of the backward pass - instead of one launch in
-    front of every layer's product.  ``build()`` is what the consumer would hand to ``sp_weight_operand`` (it defers its job);
-    the same jobs, launched earlier: bit-identical operands.  An operand enters the cache only after its job has been
-    launched, so a failure on the way leaves no entry behind that a later call could mistake for a built operand.
+    """Build every STALE derived form among ``requests`` = [(w, kind, build)] now, the split jobs among them in one shared
+    small-pass launch (``aux_flush``): the start of a stack's forward or backward pass, where all the operands of the pass can be
+    split at once - the weights do not change between the optimizer update and the end of the backward pass - instead of one
+    launch in front of every layer's product.  ``build()`` is what the consumer would hand to ``sp_weight_operand``; the same
+    jobs, launched earlier: bit-identical operands.  An operand enters the cache only after its job has been launched, so a
+    failure on the way leaves no entry behind that a later call could mistake for a built operand.
     -> number of operands built."""
     made, seen = [], set()
     for w, kind, build in requests:
@@ -2157,9 +2121,9 @@ def presplit_weight_operands(requests) -> int:
         seen.add(key)
         made.append((w, kind, build()))
     if made:
-        aux_flush()
+        aux_flush([op for _, _, op in made if isinstance(op, SplitJobs)])
         for w, kind, op in made:
-            _cache_weight_operand(w, kind, op)
+            _cache_weight_operand(w, kind, op.operand if isinstance(op, SplitJobs) else op)
     return len(made)
 
 
@@ -2171,8 +2135,6 @@ def _cached_weight_operand(w: torch.Tensor, kind: str):
             raise RuntimeError("a weight tensor changed without a version bump (update through .data or a raw pointer?): "
                                "call Variable.mark_updated() / ops.notify_weights_changed() after such an update")
         return hit[1]
-    if hit is not None:
-        aux_flush()  # the stale form may still have its (deferred) conversion pending: launch it before the new one is queued
     return None
 
 

@@ -156,7 +156,6 @@ class Optimizer:
                 live.append((var, grad))
         if not live:
             raise ValueError("No gradients provided for any variable.")
-        ops.aux_flush()  # deferred weight splits read the weights when they are launched: before the update writes them
         dev = live[0][0].value.device
         state = self._ensure_state(dev)
         rows = np.empty((len(live), 8), dtype=np.int64)
