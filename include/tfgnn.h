@@ -855,6 +855,24 @@ size_t tfgnn_sp_gemm_tn_workspace_bytes(int64_t M, int64_t N, int64_t K, int64_t
  * (0 / 1), clears it when reset != 0.  The host mirror (tf2_gnn_amd.ops) routes the split-operand layer paths to the
  * exact bf16x3 kernels from the next call on once the flag is seen. */
 int tfgnn_sp_spread_flag(int reset);
+/* In-stream repair of a tripped product (opt-in; off unless the environment sets TFGNN_GUARD_REPAIR to a non-zero number).
+ * While armed, every tfgnn_sp_gemm_tn / tfgnn_sp_gemm_tn_wide - also the one inside tfgnn_mp_backward - enqueues on the
+ * caller's stream: a memset node that zeroes a trip word in a 256-byte tail of the call's own workspace (the two
+ * *_workspace_bytes functions return 256 bytes more while armed, exactly the unarmed value otherwise), the unchanged product
+ * kernels with their guard pointed at that word INSTEAD of the library-wide flag, a repair kernel, and the unchanged reduce
+ * pass.  The repair kernel returns at once while the word is 0.  Otherwise it recomputes every split-K slab of the WHOLE
+ * product in fp32 (FMA, ascending k: a fixed order) straight from the SP16 operands, element = (h + l) * inv_scale, skipping
+ * (k, block) pairs with the all-zero marker scale as the product does, and sets the reference scales the reduce pass
+ * multiplies back to 1 - the result lands through the same accumulate / scatter / column-range path as any other, and is
+ * right in the very pass that tripped.  No host synchronisation and no allocation at launch time: the sequence can be captured
+ * into a hipGraph and every replay repairs itself.  A covered product no longer raises tfgnn_sp_spread_flag, so nothing
+ * demotes the mode.  NOT covered: tfgnn_sp_gemm_tn_grouped, which keeps reporting through the host-visible flag.
+ * tfgnn_sp_guard_repair: on = 1 arms, 0 disarms, -1 only queries; returns the previous state (0 / 1) or a negative error
+ * code.  Arming allocates a device counter: not legal while a stream is capturing (arm before the capture).
+ * tfgnn_sp_repair_stats: out2[0] = products enqueued with repair armed (host counter), out2[1] = products repaired (device
+ * counter of the current device); reset != 0 clears both.  Waits for the device: not legal while a stream is capturing. */
+int tfgnn_sp_guard_repair(int on);
+int tfgnn_sp_repair_stats(int64_t* out2, int reset);
 int tfgnn_sp_gemm_tn(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, int64_t a_first_col,
                      const float* d_a_inv_scale, int64_t a_total_cols, int a_scale_block, const void* d_B_sp,
                      int64_t ldb_bytes, int64_t b_first_col, const float* d_b_inv_scale, float* d_C, int64_t group_rows,

@@ -20,6 +20,8 @@ _SIGNATURES = [
     ("tfgnn_gemm_gathered_supported", c_int, [c_int64, c_int64, c_int64, c_int64, c_int64]),
     ("tfgnn_launch_counts", c_int, [POINTER(c_int64), c_int]),
     ("tfgnn_sp_spread_flag", c_int, [c_int]),
+    ("tfgnn_sp_guard_repair", c_int, [c_int]),
+    ("tfgnn_sp_repair_stats", c_int, [POINTER(c_int64), c_int]),
     (
         "tfgnn_graph_create",
         c_int,

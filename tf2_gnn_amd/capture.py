@@ -22,8 +22,11 @@ What a replay does NOT freeze.
     device memory (``tfgnn_dropout_epoch_advance``), so every replay draws fresh masks and the forward and backward
     kernels of one replay the same ones (include/tfgnn.h "dropout EPOCH").
   * The spread guard of the f16x2 mode: its flag is host-mapped memory and keeps working; a replay cannot re-route itself
-    to other kernels, so ``replay()`` reports a trip (``guard_tripped``) instead of demoting anything - capture in
-    ``bf16x3`` for a model whose gradients trip it.
+    to other kernels, so ``replay()`` reports a trip (``guard_tripped``) instead of demoting anything.  For a model whose
+    gradients trip it, either capture in ``bf16x3`` or arm the in-stream repair BEFORE building the step
+    (``ops.set_guard_repair(True)``): the weight-gradient products then repair themselves on the device in every replay
+    (a memset node, the product, a repair kernel that returns at once unless the product tripped, the reduce pass - all nodes
+    of the graph), the flag stays down and the replayed gradients are the repaired ones.
 
 PyTorch supplies the capture machinery (``torch.cuda.CUDAGraph`` is hipGraph on ROCm: stream capture, a private memory
 pool for what the step allocates); nothing of the step's arithmetic runs in torch.
@@ -78,7 +81,7 @@ class CapturedStep:
         torch.cuda.synchronize()
         if ops.get_gemm_mode() == ops.GEMM_F16X2 and ops.f16x2_guard_flag_async():
             raise RuntimeError("the spread guard of the f16x2 mode tripped during the warm-up steps; capture this step in "
-                               "ops.set_gemm_mode('bf16x3')")
+                               "ops.set_gemm_mode('bf16x3'), or arm ops.set_guard_repair(True) before building it")
         # every derived form of the weights is rebuilt INSIDE the capture: replays follow in-place weight updates
         ops.clear_weight_operand_cache()
         graph = torch.cuda.CUDAGraph()

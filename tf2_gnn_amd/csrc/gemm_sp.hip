@@ -34,6 +34,7 @@
 #include "aux_jobs.hpp"
 #include "common.hpp"
 #include "sp16.hpp"
+#include "tn_repair.hpp"
 
 namespace tfgnn {
 
@@ -1886,13 +1887,18 @@ static size_t sp_gemm_tn_ws_bytes(int64_t M, int64_t N, int64_t K, int64_t a_tot
   if (wide) splits = std::max<int64_t>(splits, ceil_div(K, SP_TN_BSC_MAX_CHUNK));
   return factors + (size_t)splits * (size_t)Mp * (size_t)N * 4;
 }
+// what a call needs NOW: with repair armed (tn_repair.hpp) the trip word's tail follows the slabs
+static size_t sp_gemm_tn_ws_need(int64_t M, int64_t N, int64_t K, int64_t a_total_cols, int a_scale_block, bool wide, bool repair) {
+  const size_t base = sp_gemm_tn_ws_bytes(M, N, K, a_total_cols, a_scale_block, wide);
+  return base && repair ? base + kTnRepairTailBytes : base;
+}
 
 size_t tfgnn_sp_gemm_tn_workspace_bytes(int64_t M, int64_t N, int64_t K, int64_t a_total_cols, int a_scale_block) {
-  return sp_gemm_tn_ws_bytes(M, N, K, a_total_cols, a_scale_block, false);
+  return sp_gemm_tn_ws_need(M, N, K, a_total_cols, a_scale_block, false, tn_repair_armed());
 }
 
 size_t tfgnn_sp_gemm_tn_wide_workspace_bytes(int64_t M, int64_t N, int64_t K, int64_t a_total_cols, int a_scale_block) {
-  return sp_gemm_tn_ws_bytes(M, N, K, a_total_cols, a_scale_block, true);
+  return sp_gemm_tn_ws_need(M, N, K, a_total_cols, a_scale_block, true, tn_repair_armed());
 }
 
 static int sp_gemm_tn_impl(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, int64_t a_first_col,
@@ -1927,10 +1933,19 @@ static int sp_gemm_tn_impl(int64_t M, int64_t N, int64_t K, const void* d_A_sp, 
   }
   const int64_t nblk = a_total_cols / a_scale_block, kpad = (K + 15) & ~15ll;
   const size_t f_bytes = ((size_t)nblk * kpad * 2 + 255) & ~(size_t)255, r_bytes = ((size_t)nblk * (1 + SP_TN_MAXCHUNKS + 512) * 4 + 255) & ~(size_t)255;
-  const size_t need = f_bytes + r_bytes + (size_t)splits * (size_t)Mp * (size_t)N * 4;
-  TFGNN_REQUIRE(d_workspace && workspace_bytes >= need && (uintptr_t)d_workspace % 256 == 0,
+  // repair armed (tfgnn_sp_guard_repair): the guard reports into a word of this call's own workspace - zeroed by a memset node
+  // in front of the product - and sp_tn_repair_kernel, between the product and the reduce pass, acts on it in stream order
+  const bool repair = tn_repair_armed();
+  const size_t slabs_end = f_bytes + r_bytes + (size_t)splits * (size_t)Mp * (size_t)N * 4;  // a multiple of 256
+  const size_t need = sp_gemm_tn_ws_need(M, N, K, a_total_cols, a_scale_block, wide, repair);
+  TFGNN_REQUIRE(d_workspace && need >= slabs_end && workspace_bytes >= need && (uintptr_t)d_workspace % 256 == 0,
                 "tfgnn_sp_gemm_tn: workspace too small or unaligned (need %zu bytes)", need);
   hipStream_t s = (hipStream_t)stream;
+  int* guard_word = sp_spread_flag_device();
+  if (repair) {
+    guard_word = (int*)((uint8_t*)d_workspace + slabs_end);
+    if (int rc = tn_repair_begin(guard_word, s)) return rc;
+  }
   _Float16* F = (_Float16*)d_workspace;
   float* ref = (float*)((uint8_t*)d_workspace + f_bytes);
   // factors in the kernel (FIK): every workgroup normalises its own K range - no factor pass at all
@@ -1949,7 +1964,7 @@ static int sp_gemm_tn_impl(int64_t M, int64_t N, int64_t K, const void* d_A_sp, 
                          slice_max, fch);
     }
     hipLaunchKernelGGL(sp_tn_factors_kernel, dim3((unsigned)nblk * fch), dim3(1024), 0, s, d_a_inv_scale, nblk, d_b_inv_scale, (int64_t)1, K, F,
-                       kpad, ref, sp_spread_flag_device(), fch, (const float*)slice_max);
+                       kpad, ref, guard_word, fch, (const float*)slice_max);
     TFGNN_LAUNCH_CHECK();
   }
   SpTnArgs g{};
@@ -1957,7 +1972,7 @@ static int sp_gemm_tn_impl(int64_t M, int64_t N, int64_t K, const void* d_A_sp, 
   g.A = (const uint8_t*)d_A_sp + a_first_col * 4; g.lda = lda_bytes;
   g.B = (const uint8_t*)d_B_sp + b_first_col * 4; g.ldb = ldb_bytes;
   g.F = F; g.f_ld = kpad; g.a_sb = a_scale_block; g.a_col0 = a_first_col; g.a_nblk = (int)nblk;
-  g.inv_a = d_a_inv_scale; g.inv_b = d_b_inv_scale; g.ref_split = ref_split; g.spread_flag = sp_spread_flag_device();
+  g.inv_a = d_a_inv_scale; g.inv_b = d_b_inv_scale; g.ref_split = ref_split; g.spread_flag = guard_word;
   g.partial = (float*)((uint8_t*)d_workspace + f_bytes + r_bytes);
   const int64_t steps = (K + 15) / 16;
   g.k_chunk = ((steps + splits - 1) / splits) * 16;
@@ -1996,6 +2011,14 @@ static int sp_gemm_tn_impl(int64_t M, int64_t N, int64_t K, const void* d_A_sp, 
   }
   TFGNN_LAUNCH_CHECK();
 #undef SP_LAUNCH_TN
+  if (repair) {
+    TnRepairArgs rp{};
+    rp.M = M; rp.N = N; rp.K = K; rp.A = g.A; rp.lda = lda_bytes; rp.B = g.B; rp.ldb = ldb_bytes;
+    rp.inv_a = d_a_inv_scale; rp.inv_b = d_b_inv_scale; rp.a_sb = a_scale_block; rp.a_col0 = a_first_col; rp.a_nblk = (int)nblk;
+    rp.partial = g.partial; rp.slab = Mp * N; rp.k_chunk = g.k_chunk; rp.splits = splits_used;
+    rp.ref = fik ? ref_split : ref; rp.ref_per_split = fik ? 1 : 0; rp.trip = guard_word;
+    if (int rc = tn_repair_enqueue(rp, s)) return rc;
+  }
   const int64_t total = M * N;
   TnReduceArgs ra{};
   ra.partial = g.partial; ra.splits = splits_used; ra.M = M; ra.N = N; ra.ref = fik ? ref_split : ref; ra.a_col0 = a_first_col; ra.a_sb = a_scale_block;

@@ -706,6 +706,34 @@ def launch_counts() -> dict:
     return dict(zip(KERNEL_FAMILIES, (int(v) for v in buf)))
 
 
+def set_guard_repair(on: bool) -> bool:
+    """Arm (True) or disarm the in-stream repair of tripped split-operand weight-gradient products (include/tfgnn.h,
+    tfgnn_sp_guard_repair) -> the previous state.  While armed, ``sp_gemm_tn`` (both forms) and the product inside
+    ``mp_backward`` recompute a product whose spread guard trips in fp32 from the SP16 operands, on the stream and before
+    their reduce pass: the pass's own gradients are right, the host flag stays down, the mode stays ``f16x2`` - also in a
+    replayed ``capture.CapturedStep`` (arm before building it; arming allocates, so not while capturing).  Off by default
+    (environment TFGNN_GUARD_REPAIR=1 arms at start).  ``sp_gemm_tn_grouped`` is not covered."""
+    if capturing():
+        raise RuntimeError("tf2_gnn_amd: set_guard_repair is not legal while the stream is capturing (arm before the capture)")
+    rc = _lib.load().tfgnn_sp_guard_repair(1 if on else 0)
+    if rc < 0:
+        _lib.check(rc)
+    return bool(rc)
+
+
+def guard_repair() -> bool:
+    """Is the in-stream repair of tripped weight-gradient products armed (``set_guard_repair``)?"""
+    return bool(_lib.load().tfgnn_sp_guard_repair(-1))
+
+
+def repair_stats(reset: bool = False) -> dict:
+    """{"armed_products": products enqueued with repair armed (host counter), "repaired_products": products the device
+    repaired}; waits for the device (not legal while capturing).  ``reset`` clears both."""
+    buf = (ctypes.c_int64 * 2)()
+    _lib.check(_lib.load().tfgnn_sp_repair_stats(buf, int(bool(reset))))
+    return {"armed_products": int(buf[0]), "repaired_products": int(buf[1])}
+
+
 def f16x2_guard_flag_async() -> bool:
     """The spread flag as the host sees it NOW, without waiting for the device (what products enqueued earlier have reported
     so far)."""
