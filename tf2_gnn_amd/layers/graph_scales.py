@@ -3,6 +3,7 @@ tfgnn_graph_scales once per (graph, normalize, aggregation) and cached on the Gr
 from __future__ import annotations
 
 import ctypes
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -11,18 +12,24 @@ from .. import _lib, ops
 _AGG_MODE = {"sum": 0, "max": 0, "mean": 1, "sqrt_n": 2}
 
 
-def graph_scales(g: "ops.Graph", normalize: bool, aggregation: str):
-    """-> (row_scale [V*L] | None, edge_weight_by_dst [E] | None, edge_weight_by_src [E] | None,
-           node_scale [V] | None); None means "all ones" (lets the kernels skip the load)."""
+class GraphScales(NamedTuple):
+    """None means "all ones" (lets the kernels skip the load)."""
+    row_scale: Optional[torch.Tensor]           # [V*L], over the (node, type) rows
+    edge_weight_by_dst: Optional[torch.Tensor]  # [E]
+    edge_weight_by_src: Optional[torch.Tensor]  # [E]
+    node_scale: Optional[torch.Tensor]          # [V]
+
+
+def graph_scales(g: "ops.Graph", normalize: bool, aggregation: str) -> GraphScales:
     mode = _AGG_MODE[aggregation]
     key = ("scales", bool(normalize), mode)
     cached = g._cache.get(key)
     if cached is not None:
         return cached
     if not normalize and mode == 0:
-        res = (None, None, None, None)
+        res = GraphScales(None, None, None, None)
     elif normalize and mode == 0:
-        res = (
+        res = GraphScales(
             g.array(ops.G_INVDEG_BY_DST),
             g.array(ops.G_INVDEG_EDGE_BY_DST),
             g.array(ops.G_INVDEG_EDGE_BY_SRC),
@@ -41,7 +48,7 @@ def graph_scales(g: "ops.Graph", normalize: bool, aggregation: str):
                 ops._ptr(ew_d), ops._stream(),
             )
         )
-        res = (row_scale, ew_d if normalize else None, ew_s, node_scale)
+        res = GraphScales(row_scale, ew_d if normalize else None, ew_s, node_scale)
     g._cache[key] = res
     return res
 

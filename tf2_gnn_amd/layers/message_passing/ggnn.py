@@ -68,7 +68,7 @@ class GGNN(GNN_Edge_MLP):
     def _finish(self, agg, X, ctx, training):
         ru = self._recurrent_unit
         b = ru["bias"].value
-        # round 6 (QM9-sized batches, mode f16x2): both products of the cell inside the gate kernel - mh = h U + b_1 is neither
+        # (QM9-sized batches, mode f16x2) both products of the cell inside the gate kernel - mh = h U + b_1 is neither
         # written by a product of its own nor read back; of it the backward pass needs the candidate third only
         both = ops.gemm_gru2(agg, ru["kernel"].value, b[0], X, ru["recurrent_kernel"].value, b[1])
         if both is not None:
@@ -107,8 +107,8 @@ class GGNN(GNN_Edge_MLP):
     def recomputes_input_dropout(self, num_nodes: int, in_dim: int, num_edge_types: int) -> bool:
         """the three terms of d(node_embeddings) each take the recomputed mask in their epilogue (_backward_f16x2)"""
         H = self._hidden_dim
-        return (type(self).backward is GGNN.backward and H % 64 == 0 and H <= 512 and in_dim == H and not self._user_message_function()
-                and self._path() == "A" and self._f16x2_eligible(num_nodes, in_dim, num_edge_types, H))
+        return (type(self).backward is GGNN.backward and H % 64 == 0 and H <= 512 and in_dim == H
+                and self._route(num_nodes, in_dim, num_edge_types).split_eligible)
 
     def backward_with_epilogue(self, grad_output, grad_is_pre_activation=False, out_mul=None, out_act_grad=None,
                                want_split_input_grad=False):
@@ -126,7 +126,7 @@ class GGNN(GNN_Edge_MLP):
         return apply_gradient_epilogue(dX, None, out_act_grad) if out_act_grad is not None else dX
 
     def _backward_f16x2(self, grad_output, ctx, X, out_mul=None):
-        """The GRU part of the backward pass on split operands (round 3): the gate-gradient kernel writes dmx / dmh only as
+        """The GRU part of the backward pass on split operands: the gate-gradient kernel writes dmx / dmh only as
         SP16 operands (with the bias gradients folded in), the two kernel gradients are tfgnn_sp_gemm_tn products (K = V
         rows), the two input gradients tfgnn_sp_gemm_nt products - no fp32 [V, 3H] tensor is written or re-read, and the
         products run 3 piece products instead of 6.  The three terms of d(node_embeddings) - dh_new * z, dmh recurrent^T and the

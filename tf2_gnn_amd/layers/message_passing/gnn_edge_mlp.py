@@ -19,7 +19,7 @@ Here the same function is evaluated with the per-edge matmul moved to the node s
 """
 from __future__ import annotations
 
-from typing import Any, Dict, List, Optional
+from typing import Any, Dict, List, NamedTuple, Optional
 
 import torch
 
@@ -54,18 +54,18 @@ def _skip_empty_blocks(L: int, Din: int) -> bool:
     return 2 <= L <= 8 and Din % 16 == 0 and Din <= 1024 and ops.env("TFGNN_NT_SKIP_EMPTY", "1") == "1"
 
 
-def per_edge_products_supported(g, D, N) -> bool:
+def per_edge_products_supported(V, edges_per_type, D, N) -> bool:
     """one product row per EDGE (rows of X [V, D] read through an index, N output columns) rather than per (node, type) bucket?
     Pays when edges are fewer than buckets and the fused gathered product (tfgnn_gemm_gathered) takes every edge type's
     product - the library is asked (tfgnn_gemm_gathered_supported), the shape conditions are not restated here."""
     if ops.get_gemm_mode() == ops.GEMM_FP32:
         return False
-    L, E, V = g.num_edge_types, g.num_edges, g.num_nodes
-    if E == 0 or E >= V * L:
+    E = sum(edges_per_type)
+    if E == 0 or E >= V * len(edges_per_type):
         return False
     lib = _lib.load()
     forced = PER_EDGE_MIN_ROWS < 65536  # the layer-logic tests run the formulation on small graphs (separate gather + product)
-    for c in g.edges_per_type:
+    for c in edges_per_type:
         if c == 0:
             continue
         if forced:
@@ -76,9 +76,20 @@ def per_edge_products_supported(g, D, N) -> bool:
     return True
 
 
-def messages_per_edge(layer, g, D, H) -> bool:
-    """path A with one message per edge?  (sum-like aggregation of plain messages only)"""
-    return layer._aggregation_name != "max" and not layer._pre_activation() and per_edge_products_supported(g, D, H)
+class Route(NamedTuple):
+    """How the layer evaluates one pass on one batch shape: ``GNN_Edge_MLP._route`` decides, everything else reads it."""
+    # (the forms are the suffixes of the ``_forward_*`` / ``_backward_*`` methods; "generic" - a user's message function, which runs
+    #  on MessagePassing's generic path - is an answer to the stack only and is never dispatched)
+    forward: str                        # generic, A_split, A_dense, A_per_edge, A_compact, B_dense, B_compact, B_compact_split, C
+    backward: str                       # generic, A_split, A_dense, A_target, A_compact, B_dense, B_compact, B_compact_split, C
+    parts: int                          # the Graph parts (ops.G_PART_*) the two passes read: what the stack builds with the batch
+    settled: bool = True                # False: asked without the edge counts or the graph's non-empty bucket counts, which may still turn
+    #                                     the forms into the per-edge or a compact one; ``parts`` and ``split_eligible`` hold either way
+    split_eligible: bool = False        # path A without target states in mode f16x2 on shapes the split-operand kernels tile
+    pattern_forward: int = 0            # width of the type blocks that the forward product skips where a row tile has none, its rows in
+    pattern_backward: int = 0           # the order of the nodes' emptiness patterns (input-gradient products alike); 0: node order
+    per_edge_first_layer: bool = False  # path C: the first layer runs once per edge on gathered rows
+    first_layer_split: bool = False     # path C: the gradients of the first layer on split operands
 
 
 def _type_slices(off):
@@ -201,28 +212,7 @@ class GNN_Edge_MLP(MessagePassing):
     def graph_parts(self, num_nodes: int, edges_per_type, in_dim: int) -> int:
         """path A without target states reads the typed views only (forward: buckets by target, backward: by source); with
         one message per edge (molecule-sized batches) the node view as well.  Everything else: all parts."""
-        from types import SimpleNamespace
-
-        if not self._user_message_function() and self._path() == "C":
-            # the first-layer gradients on split operands walk the nodes in the order of their emptiness patterns
-            L, H0 = len(edges_per_type), int(self._edge_type_mlps.kernels[0].shape[2])
-            if self._first_layer_grads_split_ok(int(num_nodes), int(in_dim), L, H0) and _skip_empty_blocks(L, H0):
-                return ops.G_PARTS_DEFAULT | ops.G_PART_DST_PATTERN
-        if self._user_message_function() or self._path() != "A" or self._use_target_state_as_input or self._compact_opt_in:
-            return ops.G_PARTS_DEFAULT
-        shape = SimpleNamespace(num_edge_types=len(edges_per_type), num_edges=int(sum(edges_per_type)), num_nodes=int(num_nodes),
-                                edges_per_type=tuple(int(c) for c in edges_per_type))
-        if messages_per_edge(self, shape, in_dim, self._hidden_dim):
-            parts = ops.G_PART_PLAN_TYPED | ops.G_PART_PLAN_NODE | ops.G_PART_EDGE_IDS
-            # the backward pass keeps the bucket formulation; on split operands its input-gradient product walks the nodes in the
-            # order of their by-source emptiness patterns (built with the batch, not in the middle of the step)
-            if (self._f16x2_eligible(shape.num_nodes, in_dim, shape.num_edge_types, self._hidden_dim)
-                    and _skip_empty_blocks(shape.num_edge_types, self._hidden_dim)):
-                parts |= ops.G_PART_DST_PATTERN
-            return parts
-        if _skip_empty_blocks(shape.num_edge_types, in_dim):
-            return ops.G_PART_PLAN_TYPED | ops.G_PART_DST_PATTERN
-        return ops.G_PART_PLAN_TYPED
+        return self._route(int(num_nodes), int(in_dim), len(edges_per_type), tuple(int(c) for c in edges_per_type)).parts
 
     # ---- which formulation ------------------------------------------------------------------
     def _path(self) -> str:
@@ -233,6 +223,64 @@ class GNN_Edge_MLP(MessagePassing):
         if not self._use_target_state_as_input:
             return "B"
         return "C"
+
+    def _route(self, V: int, D: int, L: int, edges_per_type=None, nonempty_offsets=None) -> Route:
+        """The one place that chooses the formulation, for V nodes of width D and L edge types in the GEMM mode of the moment."""
+        # ``edges_per_type``: host counts (None: not known yet); ``nonempty_offsets``: the graph's ``Graph.nonempty_offsets``
+        # (None: no graph yet), asked only where a compact form is possible.  Mode demotion, the thresholds that tests lower, the
+        # environment switches and ``_grouped_tn_split_ok`` change between passes: nothing here is cached.
+        if self._user_message_function():
+            return Route("generic", "generic", ops.G_PARTS_DEFAULT)
+        H, kernels = self._hidden_dim, self._edge_type_mlps.kernels
+        E = None if edges_per_type is None else sum(edges_per_type)
+        path = self._path()
+        if path == "C":
+            return self._route_C(V, D, L, edges_per_type)
+        if path == "B":
+            if nonempty_offsets is None or L == 0 or E == 0 or nonempty_offsets(True)[-1] >= self.SPARSE_SOURCE_THRESHOLD * V * L:
+                return Route("B_dense", "B_dense", ops.G_PARTS_DEFAULT, settled=nonempty_offsets is not None)
+            # grouped products on split operands: every width a column tile of the split-operand product and a multiple of its
+            # scale blocks; rows x bytes below 4 GB
+            dims = [D] + [int(W.shape[2]) for W in kernels]
+            split = (ops.get_gemm_mode() == ops.GEMM_F16X2 and all(d % 128 == 0 and d <= 1024 for d in dims) and V * D * 4 < (1 << 32) - 65536
+                     and nonempty_offsets(True)[-1] >= self.GROUPED_SPLIT_MIN_ROWS)
+            form = "B_compact_split" if split else "B_compact"
+            return Route(form, form, ops.G_PARTS_DEFAULT)
+        if self._use_target_state_as_input:
+            return Route("A_dense", "A_target", ops.G_PARTS_DEFAULT)
+        eligible, opt_in = self._f16x2_eligible(V, D, L, H), self._compact_opt_in
+        if (opt_in and nonempty_offsets is not None and L > 0 and E  # (E: None without the edge counts - nothing to decide on)
+                and nonempty_offsets(False)[-1] < self.SPARSE_BUCKET_THRESHOLD * V * L):
+            return Route("A_compact", "A_compact", ops.G_PARTS_DEFAULT, split_eligible=eligible)
+        # the backward pass keeps the bucket formulation whatever the forward pass does; on split operands its input-gradient
+        # product walks the nodes in the order of their by-source emptiness patterns (built with the batch)
+        backward = "A_split" if eligible else "A_dense"
+        skip_backward = H if eligible and _skip_empty_blocks(L, H) else 0
+        if edges_per_type is not None and per_edge_products_supported(V, edges_per_type, D, H):
+            forward = "A_per_edge"
+            parts = ops.G_PART_PLAN_TYPED | ops.G_PART_PLAN_NODE | ops.G_PART_EDGE_IDS | (ops.G_PART_DST_PATTERN if skip_backward else 0)
+        else:  # (the pattern order is asked for in every mode and on every width that has blocks to skip)
+            forward = backward
+            parts = ops.G_PART_PLAN_TYPED | (ops.G_PART_DST_PATTERN if _skip_empty_blocks(L, D) else 0)
+        return Route(forward, backward, ops.G_PARTS_DEFAULT if opt_in else parts, split_eligible=eligible,
+                     settled=edges_per_type is not None and (not opt_in or nonempty_offsets is not None),
+                     pattern_forward=D if forward == "A_split" and _skip_empty_blocks(L, D) else 0, pattern_backward=skip_backward)
+
+    def _route_C(self, V: int, D: int, L: int, edges_per_type=None) -> Route:
+        """path C's part of ``_route``"""
+        # (GNN_FiLM's per-edge form borrows path C's machinery - ``_edge_messages_C``, ``_backward_C`` - whatever ``_path()``
+        #  says of its edge MLPs: those two ask here where no route is handed to them)
+        # the first layer's gradients on split operands: widths the split-operand kernels tile, unless the stack's guard
+        # policy handed these weight gradients back to the exact kernels (GNN._demote_fragile_weight_gradients); their
+        # input-gradient products walk the nodes in the order of their emptiness patterns
+        H0 = int(self._edge_type_mlps.kernels[0].shape[2])
+        split = bool(ops.get_gemm_mode() == ops.GEMM_F16X2 and ops.env("TFGNN_EDGE_FIRST_LAYER_F16X2", "1") == "1"
+                     and self._grouped_tn_split_ok and V > 0 and L > 0 and H0 % 16 == 0 and H0 <= 512 and 32 <= D <= 512
+                     and ops.sp_tiles(D) and ops.sp_tiles(H0))
+        skip = H0 if split and _skip_empty_blocks(L, H0) else 0
+        return Route("C", "C", ops.G_PARTS_DEFAULT | (ops.G_PART_DST_PATTERN if skip else 0),
+                     settled=edges_per_type is not None, pattern_backward=skip, first_layer_split=split,
+                     per_edge_first_layer=edges_per_type is not None and per_edge_products_supported(V, edges_per_type, D, H0))
 
     def _pre_activation(self) -> bool:
         """activation applied per message before aggregation? (base class only, message_passing.py:169)"""
@@ -247,8 +295,7 @@ class GNN_Edge_MLP(MessagePassing):
 
     # ---- scale helpers ----------------------------------------------------------------------
     def _scales(self, g: "ops.Graph"):
-        """(row_scale over rows (v,l) | None, edge weights by-dst | None, edge weights by-src | None,
-        node scale [V] | None) for the configured normalisation / aggregation."""
+        """the ``GraphScales`` of the configured normalisation / aggregation"""
         from ..graph_scales import graph_scales
 
         return graph_scales(g, bool(self._normalize_by_num_incoming), self._aggregation_name)
@@ -285,9 +332,14 @@ class GNN_Edge_MLP(MessagePassing):
             raise ValueError(
                 f"layer was built for {self._num_edge_types} edge types, got {g.num_edge_types}"
             )
-        agg, ctx, dropped = self._aggregate_messages(X, g, self._post_activation_name(), want_split, drop)
-        ctx["graph"] = g
-        ctx["X"] = X
+        route = self._route(V, X.shape[1], g.num_edge_types, g.edges_per_type, g.nonempty_offsets)
+        assert route.forward != "generic"  # (a user's message function returned above)
+        forward = getattr(self, "_forward_" + route.forward)
+        if route.forward == "A_split":  # the one form whose product takes the stack's requests in its epilogue
+            agg, ctx, dropped = forward(X, g, self._post_activation_name(), route, want_split, drop)
+        else:
+            (agg, ctx), dropped = forward(X, g, self._post_activation_name(), route), False
+        ctx.update(graph=g, X=X, route=route)
         self._ctx = ctx
         return self._finish(agg, X, ctx, training), dropped
 
@@ -295,14 +347,6 @@ class GNN_Edge_MLP(MessagePassing):
         """base class: the activation was fused into the aggregation step."""
         ctx["out"] = agg
         return agg
-
-    def _aggregate_messages(self, X, g, fuse_act, want_split=False, drop=None):
-        """-> (act?(aggregated messages) [V, H], ctx, ``drop`` applied?).  ``want_split``: write the result as a split operand
-        as well; ``drop`` = (rate, seed): the dropout the result is only ever read through (call_with_epilogue)."""
-        path = self._path()
-        if path == "A":
-            return self._forward_A(X, g, fuse_act, want_split, drop)
-        return (self._forward_B if path == "B" else self._forward_C)(X, g, fuse_act)
 
     # ---- general aggregation (max / activation before aggregation) ----------------------------------
     def _agg_general(self) -> bool:
@@ -375,46 +419,30 @@ class GNN_Edge_MLP(MessagePassing):
     # is unchanged.  Kept opt-in (hyper-parameter "use_compact_buckets").
     SPARSE_BUCKET_THRESHOLD = 0.85
 
-    def _use_compact_buckets(self, g) -> bool:
-        if not self._compact_opt_in:
-            return False
-        if self._use_target_state_as_input or g.num_edge_types == 0 or g.num_edges == 0:
-            return False
-        nz = g.nonempty_offsets(False)[-1]
-        return nz < self.SPARSE_BUCKET_THRESHOLD * g.num_nodes * g.num_edge_types
-
-    def _forward_A_compact(self, X, g, fuse_act):
+    def _forward_A_compact(self, X, g, fuse_act, route):
         """path A over the non-empty buckets only (type-major compact rows):
              A_c[c]  = scale * sum of source rows of bucket c          gather, compact output
              Y_c     = A_c[rows of type l] @ W_l  for every l          grouped MFMA GEMM
              out[v]  = act( sum over the non-empty buckets of v )       <= L rows per node"""
-        row_scale, _, _, _ = self._scales(g)
         W = self._edge_type_mlps.kernels[0]  # [L, D, H]
         off_h = g.nonempty_offsets(False)
-        Ac = ops.graph_gather(g, ops.VIEW_BY_DST_TYPED_COMPACT, X, row_scale=row_scale)
+        Ac = ops.graph_gather(g, ops.VIEW_BY_DST_TYPED_COMPACT, X, row_scale=self._scales(g).row_scale)
         Yc = ops.gemm_grouped_rows(Ac, g.array(ops.G_NZ_OFF_BY_DST), off_h, W)
-        gelu_split = fuse_act == "gelu"
-        pre = ops.gather_reduce(
-            g.array(ops.G_NZ_NODEPTR_BY_DST), g.array(ops.G_NZ_COL_BY_DST), Yc, post_act=None if gelu_split else fuse_act
-        )
+        pre = ops.gather_reduce(g.array(ops.G_NZ_NODEPTR_BY_DST), g.array(ops.G_NZ_COL_BY_DST), Yc,
+                                post_act=None if fuse_act == "gelu" else fuse_act)
         ctx = {"path": "Ac", "fused_act": fuse_act}
-        return self._split_gelu(pre, fuse_act, ctx), ctx, False
+        return self._split_gelu(pre, fuse_act, ctx), ctx
 
     def _backward_A_compact(self, d_agg, ctx):
-        g, X = ctx["graph"], ctx["X"]
-        mlps = self._edge_type_mlps
+        g, X, mlps = ctx["graph"], ctx["X"], self._edge_type_mlps
         W = mlps.kernels[0]  # [L, D, H]
-        L = g.num_edge_types
-        _, _, ew_s, _ = self._scales(g)
-        off_h = g.nonempty_offsets(True)
-        nz = off_h[-1]
-        off_d = g.array(ops.G_NZ_OFF_BY_SRC)
+        off_h, off_d = g.nonempty_offsets(True), g.array(ops.G_NZ_OFF_BY_SRC)
         # G_c[c] = sum over the out-edges of bucket c = (u, l) of w_e * d_agg[target]
-        Gc = ops.graph_gather(g, ops.VIEW_BY_SRC_TYPED_COMPACT, d_agg, edge_weight=ew_s)  # [nz, H]
+        Gc = ops.graph_gather(g, ops.VIEW_BY_SRC_TYPED_COMPACT, d_agg, edge_weight=self._scales(g).edge_weight_by_src)  # [nz, H]
         Zc = ops.gemm_grouped_rows(Gc, off_d, off_h, W, trans_b=True)  # [nz, D] = G_c,l @ W_l^T
         dX = ops.gather_reduce(g.array(ops.G_NZ_NODEPTR_BY_SRC), g.array(ops.G_NZ_COL_BY_SRC), Zc)
-        Xc = ops.gather_reduce(self._ident_nz(g, nz), g.array(ops.G_NZ_NODE_BY_SRC), X)  # source states of the compact rows
-        mlps.set_grads([ops.gemm_grouped_k(Xc, Gc, off_d, off_h, L)])  # dW_l = X_c,l^T @ G_c,l
+        Xc = ops.gather_reduce(self._ident_nz(g, off_h[-1]), g.array(ops.G_NZ_NODE_BY_SRC), X)  # source states of the compact rows
+        mlps.set_grads([ops.gemm_grouped_k(Xc, Gc, off_d, off_h, g.num_edge_types)])  # dW_l = X_c,l^T @ G_c,l
         return dX
 
     def _f16x2_eligible(self, V, D, L, H) -> bool:
@@ -422,85 +450,97 @@ class GNN_Edge_MLP(MessagePassing):
         return (ops.get_gemm_mode() == ops.GEMM_F16X2 and not self._use_target_state_as_input and L > 0 and V > 0
                 and D % 16 == 0 and D <= 512 and 32 <= H <= 512 and ops.sp_tiles(H) and ops.sp_tiles(D))
 
-    def weight_operand_requests(self, graph, num_nodes: int, in_dim: int, backward: bool):
-        """path A on split operands: W^T as the [H, L * D] operand of the forward product, the rows [W_0[d] | W_1[d] | ..] of
-        the input-gradient product (the keys and builders of ``_forward_A`` / ``_backward_A_f16x2``)"""
-        if (not getattr(self, "built", False) or self._user_message_function() or self._path() != "A"
-                or self._use_target_state_as_input or self._compact_opt_in):
-            return []
-        W = self._edge_type_mlps.kernels[0]  # [L, Din, H]
-        L, Din, H = (int(v) for v in W.shape)
-        if L != graph.num_edge_types or Din != in_dim or not self._f16x2_eligible(num_nodes, in_dim, L, H):
-            return []
-        if backward:
-            return [(W, "rows", lambda: ops.sp_split_rows_jobs(W[0], segments=(H, Din * H, L * H)))]
-        if messages_per_edge(self, graph, in_dim, H):  # (one product per edge type on rows of X: no stacked operand)
-            return []
-        return [(W, "cols", lambda: ops.sp_split_cols_jobs(W.view(L * Din, H)))]
+    # ---- the split forms of the kernels, each written once: the stack's request and the pass that reads it share the builder
+    @staticmethod
+    def _cols_operand(W):
+        """[L, in, out] kernels -> SP16 [out, L * in]: column block l is W_l^T, relation l's [N, K] operand of a forward product,
+        as split jobs (ONE split for the whole stack; a row's scale is shared by the relations)"""
+        return ops.sp_split_cols_jobs(W.view(-1, W.shape[2]))
 
-    def _forward_A(self, X, g, fuse_act, want_split=False, drop=None):
-        if self._use_compact_buckets(g):
-            return self._forward_A_compact(X, g, fuse_act)
-        V, D = X.shape
+    @staticmethod
+    def _rows_operand(W, d0=0, D=None):
+        """[L, in, out] kernels -> SP16 [D, L * out]: row d = [W_0[d0 + d] | W_1[d0 + d] | ..], as split jobs"""
+        # (the operand of an input-gradient product over the input rows d0 .. d0 + D; default: all of them)
+        L, Din, H = W.shape
+        return ops.sp_split_rows_jobs(W[0, d0:d0 + (Din if D is None else D)], segments=(H, Din * H, L * H))
+
+    def _stacked_operand(self, kind):
+        # -> (kernels, kind, builder) of path A's stacked kernels: "cols" for the forward product, "rows" for dX = G W^T
+        W = self._edge_type_mlps.kernels[0]
+        return W, kind, lambda: (self._cols_operand if kind == "cols" else self._rows_operand)(W)
+
+    def weight_operand_requests(self, graph, num_nodes: int, in_dim: int, backward: bool):
+        """path A on split operands: what ``_forward_A_split`` / ``_backward_A_split`` read of the kernels"""
+        if not getattr(self, "built", False) or tuple(self._edge_type_mlps.kernels[0].shape[:2]) != (graph.num_edge_types, in_dim):
+            return []
+        route = self._route(num_nodes, in_dim, graph.num_edge_types, graph.edges_per_type)
+        if not route.settled or (route.backward if backward else route.forward) != "A_split":
+            return []  # (one product per edge type on rows of X, a compact form, the exact kernels: no stacked operand)
+        return [self._stacked_operand("rows" if backward else "cols")]
+
+    def _forward_A_per_edge(self, X, g, fuse_act, route):
+        # molecule-sized graphs have fewer edges than (node, type) buckets (QM9: 3.4 M vs 5.8 M): the bucket matrix
+        # [V, L D] would be mostly zeros.  One message per EDGE instead - x_u W_l on rows of X read through the edge's
+        # source index - summed per target by the node-view gather (the machinery of path C)
+        scales, W = self._scales(g), self._edge_type_mlps.kernels[0]  # W: [L, D, H]
+        src_l, _, _, _, off, _ = self._original_order(g, scales.edge_weight_by_dst)
+        src_node = self._orig_src_node(g, src_l)
+        msgs = torch.empty((g.num_edges, self._hidden_dim), dtype=torch.float32, device=X.device)
+        for l, sl in _type_slices(off):
+            ops.gemm_gathered(X, src_node[sl], W[l], out=msgs[sl])
+        ctx = {"path": "A", "A": None, "fused_act": fuse_act, "f16x2": route.split_eligible}
+        return self._gather_messages(g, msgs, g.array(ops.G_EID_BY_DST), scales.edge_weight_by_dst, scales.node_scale, fuse_act, ctx), ctx
+
+    def _forward_A_split(self, X, g, fuse_act, route, want_split=False, drop=None):
+        """-> (output, ctx, ``drop`` applied?)"""
+        # f16x2: the gather writes [A_0 | ... | A_{L-1}] directly as the split operand (one scale per (node, type) bucket), the
+        # kernels are split once per value, the product only moves data and multiplies.  Most nodes of a typed graph receive
+        # edges of only some types: with the nodes in the order of their emptiness pattern (Graph part DST_PATTERN) whole
+        # 128-row tiles of A have all-zero type blocks, which the product skips.  The product's epilogue writes its rows back
+        # in node order, so nothing downstream sees the order.
         L, H = g.num_edge_types, self._hidden_dim
-        T = self._use_target_state_as_input
-        row_scale, _, _, _ = self._scales(g)
         W = self._edge_type_mlps.kernels[0]  # [L, Din, H]
-        Din = W.shape[1]
-        if not T and messages_per_edge(self, g, D, H):
-            # molecule-sized graphs have fewer edges than (node, type) buckets (QM9: 3.4 M vs 5.8 M): the bucket matrix
-            # [V, L D] would be mostly zeros.  One message per EDGE instead - x_u W_l on rows of X read through the edge's
-            # source index - summed per target by the node-view gather (the machinery of path C)
-            _, ew_d, _, node_scale = self._scales(g)
-            src_l, _, _, _, off, _ = self._original_order(g, ew_d)
-            src_node = self._orig_src_node(g, src_l)
-            msgs = torch.empty((g.num_edges, H), dtype=torch.float32, device=X.device)
-            for l, sl in _type_slices(off):
-                ops.gemm_gathered(X, src_node[sl], W[l], out=msgs[sl])
-            ctx = {"path": "A", "A": None, "fused_act": fuse_act, "f16x2": self._f16x2_eligible(V, D, L, H)}
-            return self._gather_messages(g, msgs, g.array(ops.G_EID_BY_DST), ew_d, node_scale, fuse_act, ctx), ctx, False
-        if self._f16x2_eligible(V, D, L, H):
-            # f16x2: the gather writes [A_0 | ... | A_{L-1}] directly as the split operand (one scale per (node, type)
-            # bucket), the kernels are split once per value, the product only moves data and multiplies
-            # most nodes of a typed graph receive edges of only some types: with the nodes in the order of their emptiness
-            # pattern (Graph part DST_PATTERN) whole 128-row tiles of A have all-zero type blocks, which the product skips.
-            # The product's epilogue writes its rows back in node order, so nothing downstream sees the order.
-            skip = _skip_empty_blocks(L, Din)
-            kmask = g.array(ops.G_PATTERN_TILEMASK_BY_DST) if skip else None
-            rmap = g.array(ops.G_PATTERN_NODE_BY_DST) if skip else None
-            # (a gather that leaves the zero rows of skipped blocks unwritten - 38 % of the operand's 154 MB at the benchmark
-            #  batch - measured no gain in round 5, 2.370 vs 2.368 ms per step: the gather's time is its reads.  Removed.)
-            view = ops.VIEW_BY_DST_TYPED_PATTERN if skip else ops.VIEW_BY_DST_TYPED
-            gelu_split = fuse_act == "gelu"
-            want_split = want_split or self._always_split_output
-            out_scale = 1.0
-            # ``drop``: (rate, seed) of the NEXT layer's input dropout (GNN stack).  This layer's output is only ever read through
-            # it: apply the mask in the product's epilogue and write the dropped result in both forms (fp32 for the next gather,
-            # SP16 for its weight-gradient product)
-            fuse_drop = drop is not None and not gelu_split and ops.sp_one_tile(H) and type(self)._finish is GNN_Edge_MLP._finish
-            # (a split result: the consumer finds it with sp_rows_of)
-            split_out = fuse_drop or (want_split and not gelu_split and ops.sp_one_tile(H))
-            if ops.mp_entry_enabled() and Din == D:
-                # round 6: gather + weight split + merged small passes + product in ONE library call (tfgnn_mp_forward) - the
-                # kernels and arguments of the op-level route below, without Python between the launches
-                pre, _ = ops.mp_forward(g, view, X, W, row_scale=row_scale, act=None if gelu_split else fuse_act,
-                                        dropout=drop if fuse_drop else None, tile_kmask=kmask, row_map=rmap, want_split=split_out)
+        row_scale = self._scales(g).row_scale
+        skip = route.pattern_forward != 0
+        kmask, rmap = (g.array(ops.G_PATTERN_TILEMASK_BY_DST), g.array(ops.G_PATTERN_NODE_BY_DST)) if skip else (None, None)
+        # (a gather that leaves the zero rows of skipped blocks unwritten - 38 % of the operand's 154 MB at the benchmark
+        #  batch - measured no gain, 2.370 vs 2.368 ms per step: the gather's time is its reads.  Removed.)
+        view = ops.VIEW_BY_DST_TYPED_PATTERN if skip else ops.VIEW_BY_DST_TYPED
+        gelu_split = fuse_act == "gelu"
+        want_split = want_split or self._always_split_output
+        # ``drop``: (rate, seed) of the NEXT layer's input dropout (GNN stack).  This layer's output is only ever read through
+        # it: apply the mask in the product's epilogue and write the dropped result in both forms (fp32 for the next gather,
+        # SP16 for its weight-gradient product)
+        fuse_drop = drop is not None and not gelu_split and ops.sp_one_tile(H) and type(self)._finish is GNN_Edge_MLP._finish
+        # (a split result: the consumer finds it with sp_rows_of)
+        split_out = fuse_drop or (want_split and not gelu_split and ops.sp_one_tile(H))
+        if ops.mp_entry_enabled() and W.shape[1] == X.shape[1]:
+            # gather + weight split + merged small passes + product in ONE library call (tfgnn_mp_forward) - the kernels and
+            # arguments of the op-level route below, without Python between the launches
+            pre, _ = ops.mp_forward(g, view, X, W, row_scale=row_scale, act=None if gelu_split else fuse_act,
+                                    dropout=drop if fuse_drop else None, tile_kmask=kmask, row_map=rmap, want_split=split_out)
+        else:
+            A_sp = ops.graph_gather_sp(g, view, X, row_scale=row_scale, rows_per_operand_row=L)
+            Wt_sp = ops.sp_weight_operand(*self._stacked_operand("cols"))
+            if split_out:  # (never with a split gelu)
+                pre, _ = ops.sp_gemm_nt_split(A_sp, Wt_sp, act=fuse_act, dropout=drop if fuse_drop else None, tile_kmask=kmask,
+                                              row_map=rmap)
             else:
-                A_sp = ops.graph_gather_sp(g, view, X, row_scale=row_scale, rows_per_operand_row=L)
-                Wt_sp = ops.sp_weight_operand(W, "cols", lambda: ops.sp_split_cols_jobs(W.view(L * Din, H)))
-                if split_out:  # (never with a split gelu)
-                    pre, _ = ops.sp_gemm_nt_split(A_sp, Wt_sp, act=fuse_act, dropout=drop if fuse_drop else None, tile_kmask=kmask,
-                                                  row_map=rmap)
-                else:
-                    pre = ops.sp_gemm_nt(A_sp, Wt_sp, act=None if gelu_split else fuse_act, tile_kmask=kmask, row_map=rmap)
-            if fuse_drop:
-                out_scale = 1.0 - float(drop[0])
-            ctx = {"path": "A", "A": None, "fused_act": fuse_act, "f16x2": True, "out_scale": out_scale}
-            return self._split_gelu(pre, fuse_act, ctx), ctx, fuse_drop  # (fuse_drop: never with a split gelu)
+                pre = ops.sp_gemm_nt(A_sp, Wt_sp, act=None if gelu_split else fuse_act, tile_kmask=kmask, row_map=rmap)
+        ctx = {"path": "A", "A": None, "fused_act": fuse_act, "f16x2": True, "out_scale": 1.0 - float(drop[0]) if fuse_drop else 1.0}
+        return self._split_gelu(pre, fuse_act, ctx), ctx, fuse_drop  # (fuse_drop: never with a split gelu)
+
+    def _forward_A_dense(self, X, g, fuse_act, route):
+        # the bucket matrix [V, L * Din] in fp32 and one product with the vertical stack of the kernels; with target states
+        # (backward form A_target) the second half of every bucket row holds the target's own state times its multiplier
+        (V, D), L = X.shape, g.num_edge_types
+        row_scale = self._scales(g).row_scale
+        W = self._edge_type_mlps.kernels[0]  # [L, Din, H]
+        Din, H = W.shape[1:]
         A = torch.empty((V, L * Din), dtype=torch.float32, device=X.device)
         Arows = A.view(V * L, Din)
         ops.graph_gather(g, ops.VIEW_BY_DST_TYPED, X, row_scale=row_scale, out=Arows[:, :D])
-        if T:
+        if route.backward == "A_target":
             # sum_e s_e [x_u | x_v] W = (sum_e s_e x_u) W_s + (c * s) x_v W_t
             from ..graph_scales import target_multiplier
 
@@ -514,33 +554,33 @@ class GNN_Edge_MLP(MessagePassing):
         else:
             pre = ops.gemm(A, W.view(L * Din, H), act=act)
         ctx = {"path": "A", "A": A, "fused_act": fuse_act}
-        return self._split_gelu(pre, fuse_act, ctx), ctx, False
+        return self._split_gelu(pre, fuse_act, ctx), ctx
 
     @staticmethod
-    def _skip_args(g, L, width, by_src):
+    def _skip_args(g, width, by_src):
         """the arguments that let a split-operand NT product over [V, L * width] bucket rows skip the all-zero type blocks of a
         row tile: it reads its rows in the order of the nodes' emptiness patterns (a_rows) and writes node order again (row_map;
-        mask, saved activation and dropout index follow it).  {} where nothing is skipped (``_skip_empty_blocks``)."""
-        if not _skip_empty_blocks(L, width):
+        mask, saved activation and dropout index follow it).  {} where nothing is skipped (``width`` = 0: Route.pattern_*)."""
+        if not width:
             return {}
         node_at = g.array(ops.G_PATTERN_NODE_BY_SRC if by_src else ops.G_PATTERN_NODE_BY_DST)
         kmask = g.array(ops.G_PATTERN_TILEMASK_BY_SRC if by_src else ops.G_PATTERN_TILEMASK_BY_DST)
         return dict(tile_kmask=kmask, a_rows=node_at, row_map=node_at)
 
-    def _backward_A_f16x2(self, d_agg, ctx, g, X, ew_s, epilogue=None, want_split=False, accumulate=None):
+    def _backward_A_split(self, d_agg, ctx, epilogue=None, want_split=False, accumulate=None):
         """path A backward on split operands: the transposed gather writes G = [G_0 | ... | G_{L-1}] as an SP16 operand
         (one scale per (source, type) bucket) that serves both dX = G @ [W_0 | ... | W_{L-1}]^T (NT) and
         dW_l = X^T G_l (TN, where the per-row scales become per-k factors: tfgnn_sp_gemm_tn).  The requests of
         ``_backward_messages`` ride in the epilogue of the dX product.  -> (dX, a request was given: it was applied)"""
-        V, D = X.shape
-        L, H = g.num_edge_types, self._hidden_dim
-        mlps = self._edge_type_mlps
+        g, X, mlps = ctx["graph"], ctx["X"], self._edge_type_mlps
+        D, L, H = X.shape[1], g.num_edge_types, self._hidden_dim
         W = mlps.kernels[0]  # [L, D, H]
-        # Round 5: the by-source buckets are as sparse as the by-target ones (45 % empty on the R-MAT batch).  G stays in node
-        # order - the weight-gradient product below pairs its rows with X's -, the input-gradient product reads its rows in the
-        # order of the by-source emptiness patterns and skips the all-zero type blocks of a row tile.  Skipped terms are exact
+        ew_s = self._scales(g).edge_weight_by_src
+        # The by-source buckets are as sparse as the by-target ones (45 % empty on the R-MAT batch).  G stays in node order -
+        # the weight-gradient product below pairs its rows with X's -, the input-gradient product reads its rows in the order
+        # of the by-source emptiness patterns and skips the all-zero type blocks of a row tile.  Skipped terms are exact
         # zeros: bit-equal.
-        skip = self._skip_args(g, L, H, True) if V > 0 else {}
+        skip = self._skip_args(g, ctx["route"].pattern_backward, True)
         # the request, decoded once for both routes below
         applied = accumulate is not None or epilogue is not None
         split = False
@@ -553,13 +593,13 @@ class GNN_Edge_MLP(MessagePassing):
         else:
             kw = {}
         if ops.mp_entry_enabled():
-            # round 6: the whole pass in ONE library call (tfgnn_mp_backward): gather over the by-source buckets, the rows form of
-            # the kernels when stale, the merged small passes, dX = G W^T with its epilogue, dW = X^T G - the op-level sequence below
+            # the whole pass in ONE library call (tfgnn_mp_backward): gather over the by-source buckets, the rows form of the
+            # kernels when stale, the merged small passes, dX = G W^T with its epilogue, dW = X^T G - the op-level sequence below
             X_sp = ops.sp_rows_of(X)  # written by the dropout kernel when X came out of one
             dX, _, dW = ops.mp_backward(g, d_agg.contiguous(), W, X_sp, edge_weight=ew_s, skip=skip, want_split=split, **kw)
         else:
             G_sp = ops.graph_gather_sp(g, ops.VIEW_BY_SRC_TYPED, d_agg.contiguous(), edge_weight=ew_s, rows_per_operand_row=L)
-            Wh_sp = ops.sp_weight_operand(W, "rows", lambda: ops.sp_split_rows_jobs(W[0], segments=(H, D * H, L * H)))
+            Wh_sp = ops.sp_weight_operand(*self._stacked_operand("rows"))
             if split:
                 dX, _ = ops.sp_gemm_nt_split(G_sp, Wh_sp, **kw, **skip)
             else:
@@ -620,21 +660,13 @@ class GNN_Edge_MLP(MessagePassing):
     # grouped GEMMs over the compact rows only.
     SPARSE_SOURCE_THRESHOLD = 0.6
 
-    # ---- path Bc on split operands (round 5; BASELINE configs[4]) ------------------------------------------------------------
+    # ---- path Bc on split operands (BASELINE configs[4]) ---------------------------------------------------------------------
     # The per-relation MLPs over the non-empty (source, type) rows as grouped products on SP16 operands (3 piece products per
     # fp32 product; the bf16x3 grouped kernels spend 6): the first layer reads the node states through the row -> node index
     # (no expanded copy of X for the forward pass), a hidden layer's product writes its relu output ALSO as the operand of the
     # next product, the input-gradient products carry relu' of the saved activations and write the operand of the next
     # gradient product; the weight gradients are one split-operand TN product per relation over that relation's row range.
     GROUPED_SPLIT_MIN_ROWS = 4096  # (tests lower it: below this the grouped bf16x3 kernels are as good)
-
-    def _grouped_split_ok(self, X, g) -> bool:
-        if ops.get_gemm_mode() != ops.GEMM_F16X2:
-            return False
-        dims = [X.shape[1]] + [int(W.shape[2]) for W in self._edge_type_mlps.kernels]
-        # every width a column tile of the split-operand product and a multiple of its scale blocks; rows x bytes below 4 GB
-        return (all(d % 128 == 0 and d <= 1024 for d in dims) and X.shape[0] * X.shape[1] * 4 < (1 << 32) - 65536
-                and g.nonempty_offsets(True)[-1] >= self.GROUPED_SPLIT_MIN_ROWS)
 
     @staticmethod
     def _row_groups(g):
@@ -658,32 +690,36 @@ class GNN_Edge_MLP(MessagePassing):
         handed them back (``_grouped_tn_split_ok``), and not for more K ranges than one launch takes (~10^6 compact rows)."""
         return bool(self._grouped_tn_split_ok) and self._row_groups(g).tn_tables()[2] <= ops.TN_GROUPED_MAX_RANGES
 
-    @staticmethod
-    def _stacked_transposed_operand(W):
-        """[L, in, out] kernels -> SP16 [out, L * in]: column block l is W_l^T, relation l's [N, K] operand of the forward product,
-        as split jobs (ONE split for the whole stack; a row's scale is shared by the relations)"""
-        L, K, N = W.shape
-        return ops.sp_split_cols_jobs(W.view(L * K, N))
-
-    def _forward_B_compact_split(self, X, g, fuse_act):
-        mlps = self._edge_type_mlps
-        _, ew_d, _, node_scale = self._scales(g)
+    def _forward_B_compact_split(self, X, g, fuse_act, route):
+        mlps, scales = self._edge_type_mlps, self._scales(g)
         groups = self._row_groups(g)
         node_of = g.array(ops.G_NZ_NODE_BY_SRC)
         x_sp = ops.sp_rows_of(X)
         acts, cur_sp, cur32 = [], x_sp, None
         for j, W in enumerate(mlps.kernels):
             last = j == mlps.num_layers - 1
-            wt = ops.sp_weight_operand(W, "grouped_cols", lambda W=W: self._stacked_transposed_operand(W))
+            wt = ops.sp_weight_operand(W, "grouped_cols", lambda W=W: self._cols_operand(W))
             cur32, nxt_sp = ops.sp_gemm_nt_grouped(cur_sp, wt, groups, a_rows=node_of if j == 0 else None,
                                                    act=None if last else "relu", want_split=not last, b_column_blocks=True)
             acts.append(cur32)
             cur_sp = nxt_sp
         colc = self._compact_src_col(g)
-        ctx = {"path": "Bc", "fused_act": fuse_act, "Xc": None, "x_sp": x_sp, "mlp_acts": acts, "colc": colc, "grouped_split": True}
-        return self._gather_messages(g, cur32, colc, ew_d, node_scale, fuse_act, ctx), ctx, False
+        ctx = {"path": "Bc", "fused_act": fuse_act, "Xc": None, "x_sp": x_sp, "mlp_acts": acts, "colc": colc}
+        return self._gather_messages(g, cur32, colc, scales.edge_weight_by_dst, scales.node_scale, fuse_act, ctx), ctx
 
-    def _backward_B_compact_split(self, dcur, ctx, g):
+    def _backward_B_compact_split(self, d_agg, ctx):
+        g = ctx["graph"]
+        if self._agg_general():
+            dcur = self._general_bucket_grads(d_agg, ctx, ctx["mlp_acts"][-1], ctx["colc"], ops.VIEW_BY_SRC_TYPED_COMPACT)
+        elif self._grouped_tn_route(g) and d_agg.shape[1] % 16 == 0:
+            # every consumer of d(MLP outputs) takes the split form: the gather writes it (no fp32 [nz, H], no split pass)
+            dcur = ops.graph_gather_sp(g, ops.VIEW_BY_SRC_TYPED_COMPACT, d_agg.contiguous(), edge_weight=self._scales(g).edge_weight_by_src)
+        else:
+            dcur = ops.graph_gather(g, ops.VIEW_BY_SRC_TYPED_COMPACT, d_agg, edge_weight=self._scales(g).edge_weight_by_src)
+        dxc = self._compact_split_mlp_grads(dcur, ctx, g)
+        return ops.gather_reduce(g.array(ops.G_NZ_NODEPTR_BY_SRC), g.array(ops.G_NZ_COL_BY_SRC), dxc)
+
+    def _compact_split_mlp_grads(self, dcur, ctx, g):
         """d(MLP outputs) [nz, H] -> d(compact inputs) [nz, D]; fills the kernel gradients (see _forward_B_compact_split).
         The kernel gradients dW_l = inp_l^T d_l are split-operand TN products while ``_grouped_tn_split_ok``: that product
         applies one combined fp16 factor per operand row pair, and its spread guard trips when a relation's rows are spread over
@@ -740,16 +776,10 @@ class GNN_Edge_MLP(MessagePassing):
         mlps.set_grads(grads)
         return dcur32
 
-    def _forward_B_compact(self, X, g, fuse_act):
-        if self._grouped_split_ok(X, g):
-            return self._forward_B_compact_split(X, g, fuse_act)
-        L, H = g.num_edge_types, self._hidden_dim
-        mlps = self._edge_type_mlps
-        _, ew_d, _, node_scale = self._scales(g)
-        off_h = g.nonempty_offsets(True)
-        nz = off_h[-1]
-        off_dev = g.array(ops.G_NZ_OFF_BY_SRC)
-        Xc = ops.gather_reduce(self._ident_nz(g, nz), g.array(ops.G_NZ_NODE_BY_SRC), X)  # states of the non-empty (source, type) pairs
+    def _forward_B_compact(self, X, g, fuse_act, route):
+        mlps, scales = self._edge_type_mlps, self._scales(g)
+        off_h, off_dev = g.nonempty_offsets(True), g.array(ops.G_NZ_OFF_BY_SRC)
+        Xc = ops.gather_reduce(self._ident_nz(g, off_h[-1]), g.array(ops.G_NZ_NODE_BY_SRC), X)  # states of the non-empty (source, type) pairs
         acts, cur = [], Xc
         for j, W in enumerate(mlps.kernels):
             last = j == mlps.num_layers - 1
@@ -757,33 +787,29 @@ class GNN_Edge_MLP(MessagePassing):
             acts.append(cur)
         colc = self._compact_src_col(g)
         ctx = {"path": "Bc", "fused_act": fuse_act, "Xc": Xc, "mlp_acts": acts, "colc": colc}
-        return self._gather_messages(g, cur, colc, ew_d, node_scale, fuse_act, ctx), ctx, False
+        return self._gather_messages(g, cur, colc, scales.edge_weight_by_dst, scales.node_scale, fuse_act, ctx), ctx
+
+    def _general_bucket_grads(self, d_agg, ctx, msgs, msg_row, view):
+        # max / activation before aggregation on path B: per-edge gradients first (``msgs`` rows ``msg_row`` are the messages in
+        # by-dst order), then their sum over every (source, type) bucket of ``view``
+        g = ctx["graph"]
+        scales = self._scales(g)
+        dM = self._message_grads(g, d_agg, ctx, msgs, msg_row, g.array(ops.G_TARGET_BY_DST), scales.edge_weight_by_dst,
+                                 scales.node_scale, _edge_identity(g)[: g.num_edges])
+        return ops.graph_gather(g, view, dM, col=g.array(ops.G_SRC2DST_POS))
 
     def _backward_B_compact(self, d_agg, ctx):
-        g = ctx["graph"]
-        L = g.num_edge_types
-        mlps = self._edge_type_mlps
-        _, _, ew_s, _ = self._scales(g)
-        off_h = g.nonempty_offsets(True)
-        off_dev = g.array(ops.G_NZ_OFF_BY_SRC)
+        g, mlps = ctx["graph"], self._edge_type_mlps
+        off_h, off_dev = g.nonempty_offsets(True), g.array(ops.G_NZ_OFF_BY_SRC)
         acts = ctx["mlp_acts"]
         if self._agg_general():
-            _, ew_d, _, node_scale = self._scales(g)
-            dM = self._message_grads(g, d_agg, ctx, acts[-1], ctx["colc"], g.array(ops.G_TARGET_BY_DST), ew_d, node_scale,
-                                     _edge_identity(g)[: g.num_edges])
-            dcur = ops.graph_gather(g, ops.VIEW_BY_SRC_TYPED_COMPACT, dM, col=g.array(ops.G_SRC2DST_POS))
-        elif ctx.get("grouped_split") and self._grouped_tn_route(g) and d_agg.shape[1] % 16 == 0:
-            # every consumer of d(MLP outputs) takes the split form: the gather writes it (no fp32 [nz, H], no split pass)
-            dcur = ops.graph_gather_sp(g, ops.VIEW_BY_SRC_TYPED_COMPACT, d_agg.contiguous(), edge_weight=ew_s)
-        else:
-            dcur = ops.graph_gather(g, ops.VIEW_BY_SRC_TYPED_COMPACT, d_agg, edge_weight=ew_s)  # d(MLP outputs) [nz, H]
-        if ctx.get("grouped_split"):
-            dxc = self._backward_B_compact_split(dcur, ctx, g)
-            return ops.gather_reduce(g.array(ops.G_NZ_NODEPTR_BY_SRC), g.array(ops.G_NZ_COL_BY_SRC), dxc)
+            dcur = self._general_bucket_grads(d_agg, ctx, acts[-1], ctx["colc"], ops.VIEW_BY_SRC_TYPED_COMPACT)
+        else:  # d(MLP outputs) [nz, H]
+            dcur = ops.graph_gather(g, ops.VIEW_BY_SRC_TYPED_COMPACT, d_agg, edge_weight=self._scales(g).edge_weight_by_src)
         grads = [None] * mlps.num_layers
         for j in range(mlps.num_layers - 1, -1, -1):
             inp = ctx["Xc"] if j == 0 else acts[j - 1]
-            grads[j] = ops.gemm_grouped_k(inp, dcur, off_dev, off_h, L)
+            grads[j] = ops.gemm_grouped_k(inp, dcur, off_dev, off_h, g.num_edge_types)
             # (hidden layers: relu' of the layer below rides in the product's epilogue)
             dcur = ops.gemm_grouped_rows(dcur, off_dev, off_h, mlps.kernels[j], trans_b=True,
                                          act_grad=("relu", inp) if j > 0 else None)
@@ -791,15 +817,25 @@ class GNN_Edge_MLP(MessagePassing):
         # dX[u] = sum over the non-empty (u, l) pairs
         return ops.gather_reduce(g.array(ops.G_NZ_NODEPTR_BY_SRC), g.array(ops.G_NZ_COL_BY_SRC), dcur)
 
-    def _forward_B(self, X, g, fuse_act):
-        V = X.shape[0]
-        L, H = g.num_edge_types, self._hidden_dim
-        if L > 0 and g.num_edges > 0 and g.nonempty_offsets(True)[-1] < self.SPARSE_SOURCE_THRESHOLD * V * L:
-            return self._forward_B_compact(X, g, fuse_act)
-        _, ew_d, _, node_scale = self._scales(g)
+    def _forward_B_dense(self, X, g, fuse_act, route):
+        V, L, H = X.shape[0], g.num_edge_types, self._hidden_dim
+        scales = self._scales(g)
         ctx = {"path": "B", "fused_act": fuse_act}
         Y = self._mlp_all_types(X, L, ctx)
-        return self._gather_messages(g, Y.view(V * L, H), None, ew_d, node_scale, fuse_act, ctx), ctx, False
+        return self._gather_messages(g, Y.view(V * L, H), None, scales.edge_weight_by_dst, scales.node_scale, fuse_act, ctx), ctx
+
+    def _backward_B_dense(self, d_agg, ctx):
+        g, X, mlps = ctx["graph"], ctx["X"], self._edge_type_mlps
+        V, L, H = X.shape[0], g.num_edge_types, self._hidden_dim
+        if self._agg_general():
+            Y = ctx["mlp_acts"][-1].view(V * L, H)
+            G = self._general_bucket_grads(d_agg, ctx, Y, g.array(ops.G_COLL_BY_DST), ops.VIEW_BY_SRC_TYPED)
+        else:  # G[u, l, :] = sum over edges (u -> v) of type l of w_e * d_agg[v, :]
+            G = ops.graph_gather(g, ops.VIEW_BY_SRC_TYPED, d_agg, edge_weight=self._scales(g).edge_weight_by_src)
+        dX = torch.empty_like(X)
+        self._mlp_all_types_backward(mlps, X, ctx["mlp_acts"], G.view(V, L, H), dX, accumulate=False)
+        mlps.publish_grads()
+        return dX
 
     def _original_order(self, g, ew_d):
         """index arrays in concatenated-adjacency-list order (type-contiguous), cached on the Graph."""
@@ -825,15 +861,16 @@ class GNN_Edge_MLP(MessagePassing):
             g._cache[key] = cached
         return cached
 
-    def _edge_messages_C(self, X, g, ew_d):
+    def _edge_messages_C(self, X, g, ew_d, route=None):
         """per-edge MLP outputs [E, H] in edge-list order (target states + hidden layers); see csrc/edge.hip."""
+        # (``route``: the pass's, where the caller has one - GNN_FiLM's per-edge form has not)
         V, D = X.shape
         L, E = g.num_edge_types, g.num_edges
         mlps = self._edge_type_mlps
         src_l, tgt_l, tgt_node, _, off, _ = self._original_order(g, ew_d)
         H0 = mlps.kernels[0].shape[2]
         first_act = "relu" if mlps.num_layers > 1 else None
-        if per_edge_products_supported(g, D, H0):
+        if (route or self._route_C(V, D, L, g.edges_per_type)).per_edge_first_layer:
             # few edges per (node, type) pair (molecules: E < V L): the first layer runs once per EDGE on rows of X read
             # through the edge's source / target index - x_u W_s, then act(. + x_v W_t) - instead of once per (node, type)
             # pair followed by a pass that adds the two gathered rows
@@ -882,15 +919,15 @@ class GNN_Edge_MLP(MessagePassing):
             out = ops.activation_forward(fuse_act, out)
         return self._split_gelu(out, fuse_act, ctx)
 
-    def _forward_C(self, X, g, fuse_act):
+    def _forward_C(self, X, g, fuse_act, route):
         V = X.shape[0]
-        _, ew_d, _, node_scale = self._scales(g)
-        cur, acts = self._edge_messages_C(X, g, ew_d)
+        scales = self._scales(g)
+        cur, acts = self._edge_messages_C(X, g, scales.edge_weight_by_dst, route)
         H0 = self._edge_type_mlps.kernels[0].shape[2]
         ctx = {"path": "C", "fused_act": fuse_act, "edge_acts": acts, "P_shape": (V, g.num_edge_types * H0)}
         if g.num_edges == 0:
-            return self._aggregate_nothing(V, X, fuse_act, ctx), ctx, False
-        return self._gather_messages(g, cur, g.array(ops.G_EID_BY_DST), ew_d, node_scale, fuse_act, ctx), ctx, False
+            return self._aggregate_nothing(V, X, fuse_act, ctx), ctx
+        return self._gather_messages(g, cur, g.array(ops.G_EID_BY_DST), scales.edge_weight_by_dst, scales.node_scale, fuse_act, ctx), ctx
 
     def _backward_C(self, d_agg, ctx, dcur=None, epilogue=None):
         """``dcur``: d(per-edge MLP outputs) [E, H] in edge-list order when the caller already has it (GNN_FiLM).
@@ -902,7 +939,8 @@ class GNN_Edge_MLP(MessagePassing):
         if E == 0:
             mlps.set_grads([torch.zeros_like(W) for W in mlps.kernels])
             return torch.zeros_like(X), False
-        _, ew_d, _, node_scale = self._scales(g)
+        scales = self._scales(g)
+        ew_d, node_scale = scales.edge_weight_by_dst, scales.node_scale
         general = self._agg_general()
         acts = ctx["edge_acts"]
         if dcur is not None:
@@ -934,8 +972,11 @@ class GNN_Edge_MLP(MessagePassing):
             dcur = dprev
         # first layer: z0[e] = relu(P[(src,l)] + Q[(tgt,l)]); dcur is d(P+Q) per edge
         H0 = mlps.kernels[0].shape[2]
-        if self._first_layer_grads_split_ok(V, D, L, H0):
-            grads[0], dX = self._backward_C_first_layer_split(dcur, g, X, L, H0, epilogue)
+        # (decided NOW, not with the forward pass: the stack's guard policy hands these gradients back to the exact kernels
+        #  between a backward pass that tripped the spread guard and its repeat on the same context)
+        route = self._route_C(V, D, L)
+        if route.first_layer_split:
+            grads[0], dX = self._backward_C_first_layer_split(dcur, g, X, L, H0, route.pattern_backward, epilogue)
             mlps.set_grads(grads)
             return dX, epilogue is not None
         dP = ops.graph_gather(g, ops.VIEW_BY_SRC_TYPED, dcur, col=g.array(ops.G_EID_BY_SRC)).view(V, L * H0)
@@ -957,16 +998,9 @@ class GNN_Edge_MLP(MessagePassing):
         mlps.set_grads(grads)
         return dX, epilogue is not None
 
-    def _first_layer_grads_split_ok(self, V, D, L, H0) -> bool:
-        """path C, gradients of the first MLP layer on split operands?  (widths the split-operand kernels tile; the stack's guard
-        policy may have handed these weight gradients back to the exact kernels: GNN._demote_fragile_weight_gradients)"""
-        return (ops.get_gemm_mode() == ops.GEMM_F16X2 and ops.env("TFGNN_EDGE_FIRST_LAYER_F16X2", "1") == "1"
-                and self._grouped_tn_split_ok and V > 0 and L > 0 and H0 % 16 == 0 and H0 <= 512
-                and 32 <= D <= 512 and ops.sp_tiles(D) and ops.sp_tiles(H0))
-
-    def _backward_C_first_layer_split(self, dcur, g, X, L, H0, epilogue=None):
+    def _backward_C_first_layer_split(self, dcur, g, X, L, H0, skip_width, epilogue=None):
         """d(first-layer pre-activations) per edge [E, H0] -> (d kernels[0] [L, 2D, H0], dX [V, D]) on split operands (f16x2), the
-        two halves of the layer - source states, target states - alike (as _backward_A_f16x2 does for linear messages):
+        two halves of the layer - source states, target states - alike (as _backward_A_split does for linear messages):
           G = [G_0 | .. | G_{L-1}], G_l[u] = sum of dcur over the edges of type l that leave (enter) u: the typed gather writes
               it as an SP16 operand, one scale per (node, type) bucket;
           dX += G @ [W_0 | .. | W_{L-1}]^T   split-operand NT product over the nodes in the order of their emptiness patterns
@@ -983,9 +1017,8 @@ class GNN_Edge_MLP(MessagePassing):
         halves = ((ops.VIEW_BY_SRC_TYPED, ops.G_EID_BY_SRC, True, 0), (ops.VIEW_BY_DST_TYPED, ops.G_EID_BY_DST, False, D))
         for view, eid, by_src, d0 in halves:
             G_sp = ops.graph_gather_sp(g, view, dcur, col=g.array(eid), rows_per_operand_row=L)
-            Wh_sp = ops.sp_weight_operand(W0, f"rows_half{d0}", lambda d0=d0: ops.sp_split_rows_jobs(
-                W0[0, d0:d0 + D], segments=(H0, 2 * D * H0, L * H0)))  # row d = [W_0[d0 + d, :] | W_1[d0 + d, :] | ..]
-            skip = self._skip_args(g, L, H0, by_src)
+            Wh_sp = ops.sp_weight_operand(W0, f"rows_half{d0}", lambda d0=d0: self._rows_operand(W0, d0, D))
+            skip = self._skip_args(g, skip_width, by_src)
             if dX is None:
                 dX = ops.sp_gemm_nt(G_sp, Wh_sp, **kw, **skip)
             else:  # the factors distribute over the two terms: the second product adds into the first's result
@@ -1020,10 +1053,7 @@ class GNN_Edge_MLP(MessagePassing):
 
     def recomputes_input_dropout(self, num_nodes: int, in_dim: int, num_edge_types: int) -> bool:
         """path A on split operands: the mask rides in the epilogue of dX = G W^T (tfgnn_sp_gemm_nt_dropout recomputes it)"""
-        if (not self._plain_base_backward() or self._user_message_function() or self._path() != "A" or self._use_target_state_as_input
-                or not self._f16x2_eligible(num_nodes, in_dim, num_edge_types, self._hidden_dim)):
-            return False
-        return True
+        return self._plain_base_backward() and self._route(num_nodes, in_dim, num_edge_types).split_eligible
 
     def backward_with_epilogue(self, grad_output, grad_is_pre_activation=False, out_mul=None, out_act_grad=None,
                                want_split_input_grad=False):
@@ -1055,64 +1085,60 @@ class GNN_Edge_MLP(MessagePassing):
           ``accumulate`` = (buffer, out_mul): buffer += dX * out_mul, the buffer returned (GGNN's other terms of dX).
         -> (dX, request applied?): a route without such a product returns the plain dX and False, and the caller does it."""
         assert epilogue is None or accumulate is None
-        if ctx["path"] == "C":
+        form = ctx["route"].backward
+        if form == "A_split" and ops.get_gemm_mode() == ops.GEMM_F16X2:
+            return self._backward_A_split(d_agg, ctx, epilogue, want_split, accumulate)
+        if form in ("A_split", "A_dense"):  # (A_split: the spread guard demoted the mode after the forward pass)
+            return self._backward_A_dense(d_agg, ctx, epilogue)
+        if form == "C":
             return self._backward_C(d_agg, ctx, epilogue=epilogue)
-        if ctx["path"] == "Bc":
-            return self._backward_B_compact(d_agg, ctx), False
-        if ctx["path"] == "Ac":
-            return self._backward_A_compact(d_agg, ctx), False
-        g = ctx["graph"]
-        X = ctx["X"]
-        V, D = X.shape
-        L, H = g.num_edge_types, self._hidden_dim
-        mlps = self._edge_type_mlps
-        row_scale, ew_d, ew_s, node_scale = self._scales(g)
-        if ctx["path"] == "B" and self._agg_general():
-            # max / activation before aggregation: per-edge gradients first, then the sum over every (source, type) bucket
-            Y = ctx["mlp_acts"][-1].view(V * L, H)
-            dM = self._message_grads(g, d_agg, ctx, Y, g.array(ops.G_COLL_BY_DST), g.array(ops.G_TARGET_BY_DST), ew_d,
-                                     node_scale, _edge_identity(g)[: g.num_edges])
-            G = ops.graph_gather(g, ops.VIEW_BY_SRC_TYPED, dM, col=g.array(ops.G_SRC2DST_POS)).view(V, L, H)
-        elif ctx.get("f16x2") and ops.get_gemm_mode() == ops.GEMM_F16X2:  # (not after the spread guard demoted the mode)
-            return self._backward_A_f16x2(d_agg, ctx, g, X, ew_s, epilogue, want_split, accumulate)
-        else:
-            # G[u, l, :] = sum over edges (u -> v) of type l of w_e * d_agg[v, :]
-            G = ops.graph_gather(g, ops.VIEW_BY_SRC_TYPED, d_agg, edge_weight=ew_s).view(V, L, H)
-        dX = torch.empty_like(X)
-        if ctx["path"] == "A":
-            W = mlps.kernels[0]  # [L, Din, H]
-            Din = W.shape[1]
-            # horizontal stack [Din, L*H] of the L kernels: the backward pass becomes two large GEMMs
-            #   dX = [G_0|...|G_{L-1}] @ [W_0|...|W_{L-1}]^T      dW_h = X^T @ [G_0|...|G_{L-1}]
-            Wh = ops.sp_weight_operand(W, "stacked_rows", lambda: ops.permute_021(W))  # [Din, L, H], once per weight value
-            G2 = G.view(V, L * H)
-            if L > 0 and not self._use_target_state_as_input:
-                # dW^T = G^T X [L*H, D]: ten full 128-row output tiles instead of the 2.5 x 4 ragged ones of X^T G
-                if epilogue is not None:
-                    dX = ops.gemm_grad(G2, Wh.view(D, L * H), trans_b=True, out=dX, out_mul=epilogue[0], act_grad=epilogue[1])
-                else:
-                    ops.gemm(G2, Wh.view(D, L * H), trans_b=True, out=dX)
-                mlps.set_grads([ops.transpose_batched(ops.gemm(G2, X, trans_a=True).view(L, H, D))])
-                return dX, epilogue is not None
-            dWh = torch.empty((Din, L, H), dtype=torch.float32, device=X.device)
-            if L == 0:
-                dX.zero_()
-            else:
-                ops.gemm(G2, Wh[:D].view(D, L * H), trans_b=True, out=dX)
-                ops.gemm(X, G2, trans_a=True, out=dWh[:D].view(D, L * H))
-            if self._use_target_state_as_input and L > 0:
-                # target part: pre += (k_{l,v} x_v) W_t  ->  dW_t = (k x)^T d_agg ; dX_v += k d_agg W_t^T
-                from ..graph_scales import target_multiplier
+        return getattr(self, "_backward_" + form)(d_agg, ctx), False
 
-                k, ident_ptr, node_of_row = target_multiplier(g, row_scale)
-                A = ctx["A"].view(V, L, 2 * D)
-                for l in range(L):
-                    ops.gemm(A[:, l, D:], d_agg, trans_a=True, out=dWh[D:, l, :])
-                # dX_v += sum_l k_{l,v} * (d_agg[v] @ W_t[l]^T)
-                kd = ops.gather_reduce(ident_ptr, node_of_row, d_agg, edge_weight=k).view(V, L * H)
-                ops.gemm(kd, Wh[D:].view(D, L * H), trans_b=True, out=dX, accumulate=True)
-            mlps.set_grads([ops.permute_021(dWh)])
+    def _stacked_rows(self, W):
+        # horizontal stack [Din, L, H] of the L kernels, once per weight value: the backward pass becomes two large GEMMs
+        #   dX = [G_0|...|G_{L-1}] @ [W_0|...|W_{L-1}]^T      dW_h = X^T @ [G_0|...|G_{L-1}]
+        return ops.sp_weight_operand(W, "stacked_rows", lambda: ops.permute_021(W))
+
+    def _backward_A_dense(self, d_agg, ctx, epilogue=None):
+        """-> (dX, ``epilogue`` applied?): the factors ride in the epilogue of the input-gradient product"""
+        g, X, mlps = ctx["graph"], ctx["X"], self._edge_type_mlps
+        (V, D), L, H = X.shape, g.num_edge_types, self._hidden_dim
+        if L == 0:  # (nothing to multiply: the general body zeroes dX)
+            return self._backward_A_target(d_agg, ctx), False
+        # G[u, l, :] = sum over edges (u -> v) of type l of w_e * d_agg[v, :]
+        G2 = ops.graph_gather(g, ops.VIEW_BY_SRC_TYPED, d_agg, edge_weight=self._scales(g).edge_weight_by_src).view(V, L * H)
+        dX = torch.empty_like(X)
+        Wh = self._stacked_rows(mlps.kernels[0])
+        # dW^T = G^T X [L*H, D]: ten full 128-row output tiles instead of the 2.5 x 4 ragged ones of X^T G
+        if epilogue is not None:
+            dX = ops.gemm_grad(G2, Wh.view(D, L * H), trans_b=True, out=dX, out_mul=epilogue[0], act_grad=epilogue[1])
         else:
-            self._mlp_all_types_backward(mlps, X, ctx["mlp_acts"], G, dX, accumulate=False)
-            mlps.publish_grads()
-        return dX, False
+            ops.gemm(G2, Wh.view(D, L * H), trans_b=True, out=dX)
+        mlps.set_grads([ops.transpose_batched(ops.gemm(G2, X, trans_a=True).view(L, H, D))])
+        return dX, epilogue is not None
+
+    def _backward_A_target(self, d_agg, ctx):
+        g, X, mlps = ctx["graph"], ctx["X"], self._edge_type_mlps
+        (V, D), L, H = X.shape, g.num_edge_types, self._hidden_dim
+        scales = self._scales(g)
+        G2 = ops.graph_gather(g, ops.VIEW_BY_SRC_TYPED, d_agg, edge_weight=scales.edge_weight_by_src).view(V, L * H)
+        dX = torch.empty_like(X)
+        Wh = self._stacked_rows(mlps.kernels[0])  # [2D, L, H]
+        dWh = torch.empty_like(Wh)
+        if L == 0:
+            dX.zero_()
+        else:
+            from ..graph_scales import target_multiplier
+
+            ops.gemm(G2, Wh[:D].view(D, L * H), trans_b=True, out=dX)
+            ops.gemm(X, G2, trans_a=True, out=dWh[:D].view(D, L * H))
+            # target part: pre += (k_{l,v} x_v) W_t  ->  dW_t = (k x)^T d_agg ; dX_v += k d_agg W_t^T
+            k, ident_ptr, node_of_row = target_multiplier(g, scales.row_scale)
+            A = ctx["A"].view(V, L, 2 * D)
+            for l in range(L):
+                ops.gemm(A[:, l, D:], d_agg, trans_a=True, out=dWh[D:, l, :])
+            # dX_v += sum_l k_{l,v} * (d_agg[v] @ W_t[l]^T)
+            kd = ops.gather_reduce(ident_ptr, node_of_row, d_agg, edge_weight=k).view(V, L * H)
+            ops.gemm(kd, Wh[D:].view(D, L * H), trans_b=True, out=dX, accumulate=True)
+        mlps.set_grads([ops.permute_021(dWh)])
+        return dX

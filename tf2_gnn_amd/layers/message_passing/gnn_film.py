@@ -82,16 +82,17 @@ class GNN_FiLM(GNN_Edge_MLP):
         unlike the other layers the two factors cannot be merged - beta is added between them."""
         from ..graph_scales import graph_scales
 
-        row_scale, _, ew_s, _ = graph_scales(g, bool(self._normalize_by_num_incoming), "sum")
-        node_scale = graph_scales(g, bool(self._normalize_by_num_incoming), self._aggregation_name)[3]
-        return row_scale, ew_s, node_scale
+        per_bucket = graph_scales(g, bool(self._normalize_by_num_incoming), "sum")
+        node_scale = graph_scales(g, bool(self._normalize_by_num_incoming), self._aggregation_name).node_scale
+        return per_bucket.row_scale, per_bucket.edge_weight_by_src, node_scale
 
     # ---- per-edge form: gamma_{l,v} * (w_e * MLP_l([x_u | x_v])) + beta_{l,v} per edge, then any aggregation --------------
     def _call_per_edge(self, X, g):
         V, D = X.shape
         L, H, E = g.num_edge_types, self._hidden_dim, g.num_edges
         lib = _lib.load()
-        _, ew_d, _, node_scale = self._scales(g)
+        scales = self._scales(g)
+        ew_d, node_scale = scales.edge_weight_by_dst, scales.node_scale
         fuse_act = self._post_activation_name()
         ctx = {"graph": g, "X": X, "per_edge": True, "fused_act": fuse_act}
         film = self._mlp_all_types(X, L, ctx, mlps=self._film_mlps, key="film_acts")  # [V, L, 2H]
@@ -129,7 +130,8 @@ class GNN_FiLM(GNN_Edge_MLP):
             mlps.set_grads([torch.zeros_like(W) for W in mlps.kernels])
             return dX
         d_agg = self._backward_finish(grad_output, ctx)
-        _, ew_d, _, node_scale = self._scales(g)
+        scales = self._scales(g)
+        ew_d, node_scale = scales.edge_weight_by_dst, scales.node_scale
         src_l, tgt_l, tgt_node, w_orig, off, _ = self._original_order(g, ew_d)
         eid_d = g.array(ops.G_EID_BY_DST)
         dM = self._message_grads(g, d_agg, ctx, ctx["M"], None, tgt_node, None, node_scale, eid_d)  # [E, H], edge-list order

@@ -386,7 +386,7 @@ class MessagePassing:
         act = self._activation_name
         pre = act if self._message_activation_before_aggregation else None
         is_max = self._aggregation_name == "max"
-        node_scale = graph_scales(g, False, self._aggregation_name)[3]
+        node_scale = graph_scales(g, False, self._aggregation_name).node_scale
         eid_d = g.array(ops.G_EID_BY_DST)
         messages = torch.cat([m.detach() for m in messages_per_type], dim=0).contiguous()  # edge-list order
         target = torch.cat([a[:, 1] for a in adjacency_lists], dim=0).to(torch.int32).contiguous()
