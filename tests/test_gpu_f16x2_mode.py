@@ -232,7 +232,7 @@ def test_a_tripped_guard_recomputes_the_first_backward_passes_of_a_stack_on_the_
     and runs a tripped pass again on the exact kernels: the gradients a caller reads come from the bf16x3 kernels."""
     import warnings
 
-    from tf2_gnn_amd import _lib, ops
+    from tf2_gnn_amd import _lib, guard, ops
     from tf2_gnn_amd.data import make_synthetic_batch
     from tf2_gnn_amd.layers import GNN, GNNInput
     from tf2_gnn_amd.layers.message_passing import set_seed
@@ -258,13 +258,13 @@ def test_a_tripped_guard_recomputes_the_first_backward_passes_of_a_stack_on_the_
         return gnn, [v.grad.clone() for v in gnn.trainable_variables]
 
     _, exact = grads("bf16x3")
-    ops._spread_warned[0] = False  # (the warning is issued once per process)
+    guard.reset_warned()  # (the warning is issued once per process)
     with warnings.catch_warnings(record=True) as w:
         warnings.simplefilter("always")
         gnn, got = grads("f16x2")
     assert _lib.load().tfgnn_sp_spread_flag(0) == 1 and ops.get_gemm_mode() == ops.GEMM_BF16X3
     assert any("spread" in str(x.message) for x in w)
-    assert gnn._guard_sync_passes == 2
+    assert gnn.guard.sync_passes_left == 2
     # (the forward pass ran in f16x2 - its saved activations differ from the bf16x3 run's in the last bits - so the recomputed
     #  gradients agree with the exact run to fp32 rounding, and every weight gradient is finite and complete)
     for v, a, b in zip(gnn.trainable_variables, got, exact):
@@ -272,17 +272,17 @@ def test_a_tripped_guard_recomputes_the_first_backward_passes_of_a_stack_on_the_
         assert float((a - b).abs().max()) / scale <= 1e-5, v.name
     # the policy is visible to the caller and re-armable.  The pass reported the trip; the stack's own demotion of
     # its Dense products lasts until the mode is armed again, and the re-armed stack is checked synchronously again.
-    assert gnn.guard_tripped_last_backward is True and not gnn._dense_split_ok
+    assert gnn.guard_tripped_last_backward is True and gnn.guard.dense == "exact"
     ops.set_gemm_mode("f16x2")
-    assert gnn._dense_f16x2(H, H) and gnn._dense_split_ok and gnn._guard_sync_passes >= 3
+    assert gnn._dense_f16x2(H, H) and gnn.guard.dense != "exact" and gnn.guard.sync_passes_left >= 3
     # a well-conditioned pass on the re-armed stack: checked, not tripped, mode kept
     gnn(inp, training=True)
     gnn.backward(torch.randn((V, H), generator=gen).to(dev))
     assert gnn.guard_tripped_last_backward is False and ops.get_gemm_mode() == ops.GEMM_F16X2
     # after the warm-up passes a trip is only REPORTED, one pass late.  Round 6: the next query of the mode then walks the
-    # stack's staged policy one step (ops._f16x2_on -> GNN._on_late_guard_trip) instead of taking the whole mode off the split
+    # stack's staged policy one step (guard.get_gemm_mode -> GuardPolicy.on_late_trip) instead of taking the whole mode off the split
     # operands, re-arms the guard and has the stack's next passes checked synchronously again
-    gnn._guard_sync_passes = 0
+    gnn.guard.sync_passes_left = 0
     with warnings.catch_warnings(record=True) as w2:
         warnings.simplefilter("always")
         gnn(inp, training=True)
@@ -290,7 +290,7 @@ def test_a_tripped_guard_recomputes_the_first_backward_passes_of_a_stack_on_the_
         torch.cuda.synchronize()
         assert ops.get_gemm_mode() == ops.GEMM_F16X2
     assert any("not checked synchronously" in str(x.message) for x in w2)
-    assert _lib.load().tfgnn_sp_spread_flag(0) == 0 and gnn._guard_sync_passes == 3 and gnn.guard_state()["stage"] == "1a"
+    assert _lib.load().tfgnn_sp_spread_flag(0) == 0 and gnn.guard.sync_passes_left == 3 and gnn.guard_state()["stage"] == "1a"
     gnn(inp, training=True)
     gnn.backward(dOut)  # checked again: recomputed stage by stage until nothing trips
     assert gnn.guard_tripped_last_backward is True
@@ -301,10 +301,10 @@ def test_a_tripped_guard_recomputes_the_first_backward_passes_of_a_stack_on_the_
     ops.set_gemm_mode("f16x2")
     gnn(inp, training=True)
     gnn.backward(torch.randn((V, H), generator=gen).to(dev))  # (a quiet, checked pass: the re-armed stack's policy starts over)
-    gnn._guard_sync_passes = 0
+    gnn.guard.sync_passes_left = 0
     gnn.guard_check_every = 2
-    gnn._backward_passes = 0
-    ops._LATE_TRIP_POLICIES.clear()  # (the periodic check alone: without a staged policy a late trip demotes the mode on sight)
+    gnn.guard.backward_passes = 0
+    guard.forget_policies()  # (the periodic check alone: without a staged policy a late trip demotes the mode on sight)
     for i in range(2):
         gnn(inp, training=True)
         gnn.backward(dOut)
@@ -313,7 +313,7 @@ def test_a_tripped_guard_recomputes_the_first_backward_passes_of_a_stack_on_the_
             torch.cuda.synchronize()
             assert _lib.load().tfgnn_sp_spread_flag(0) == 1
             ops.set_gemm_mode("f16x2")  # (the host may or may not have demoted the mode on sight: arm it for the checked pass)
-            assert gnn._guard_sync_passes == 0
+            assert gnn.guard.sync_passes_left == 0
     assert gnn.guard_tripped_last_backward is True
     for v, b in zip(gnn.trainable_variables, exact):
         scale = max(float(b.abs().max()), 1e-30)
@@ -375,17 +375,18 @@ def test_rearming_the_mode_restores_both_demotion_stages_of_a_stack(dev, monkeyp
     assert any(mp._grouped_tn_used for mp in gnn._mp_layers)
     stages = []
     while True:
-        what = gnn._demote_fragile_weight_gradients()
+        what = gnn._advance_guard()
         if what is None:
             break
         stages.append(what)
     assert stages[-1].startswith("the per-relation MLP weight gradients") and len(stages) <= 3
-    assert not gnn._dense_split_ok or not gnn._dense_f16x2(128, 128)
+    assert gnn.guard.dense == "exact" or not gnn._dense_f16x2(128, 128)
     assert all(mp._grouped_tn_split_ok is False for mp in gnn._mp_layers if mp._grouped_tn_used)
-    gnn._guard_sync_passes = 0
+    gnn.guard.sync_passes_left = 0
     ops.set_gemm_mode("f16x2")  # re-arm
     gnn(inp, training=True)
-    assert gnn._tn_demoted_epoch is None and gnn._guard_sync_passes == gnn._guard_sync_passes_init and not gnn._dense_tn_wide
+    assert gnn.guard.grouped_tn == "split" and gnn.guard.sync_passes_left == gnn.guard.sync_passes_init
+    assert gnn.guard.dense == "split"
     assert all(mp._grouped_tn_split_ok for mp in gnn._mp_layers)
     gnn.backward(dOut)
     _assert_mode_kept()
@@ -468,7 +469,7 @@ def test_gnn_stack_gradients_are_linear_in_the_loss_gradient_magnitude(dev, mp_s
     relu decisions: no kink noise - a first version compared each run with the fp64 oracle and tripped over relu units of the
     640 x 128 states flipping between fp32 and fp64, at every scale alike) to 1e-5 of each gradient's largest entry - the
     scale-1 gradients themselves are pinned to fp64 by tests/test_gpu_layers.py::test_gnn_stack_forward_backward_parity and the
-    per-layer tests above.  Nothing may demote: neither the stack's Dense products (`_dense_split_ok`) nor the mode."""
+    per-layer tests above.  Nothing may demote: neither the stack's Dense products (`guard.dense`) nor the mode."""
     from tests.helpers import random_graph, to_dev
     from tf2_gnn_amd.layers import GNN, GNNInput
     from tf2_gnn_amd.layers.message_passing import set_seed
@@ -488,7 +489,7 @@ def test_gnn_stack_gradients_are_linear_in_the_loss_gradient_magnitude(dev, mp_s
         gnn(inp, training=False)
         dX = gnn.backward(dOut * scale, need_input_grad=True)
         torch.cuda.synchronize()
-        assert gnn.guard_tripped_last_backward in (False, None) and gnn._dense_split_ok
+        assert gnn.guard_tripped_last_backward in (False, None) and gnn.guard.dense != "exact"
         _assert_mode_kept()
         return [dX / scale] + [v.grad / scale for v in gnn.trainable_variables]
 

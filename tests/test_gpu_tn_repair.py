@@ -323,6 +323,8 @@ def _new_gnn(params):
 def test_an_unchecked_pass_of_a_stack_hands_out_repaired_gradients(dev):
     """2-layer RGCN stack, dOut rows spread over 2^60, no synchronous guard passes: the pass that would have tripped the guard
     repairs its own products - no warning, host flag down, no policy stage taken, gradients those of the exact kernels."""
+    from tf2_gnn_amd import guard
+
     params, inp, dOut = _stack(dev)
     with armed() as ops:
         ops.set_gemm_mode("bf16x3")
@@ -333,13 +335,13 @@ def test_an_unchecked_pass_of_a_stack_hands_out_repaired_gradients(dev):
         exact = [v.grad.clone() for v in twin.trainable_variables]
         ops.set_gemm_mode("f16x2")
         ops.repair_stats(reset=True)
-        ops._spread_warned[0] = False  # (the warning is issued once per process)
+        guard.reset_warned()  # (the warning is issued once per process)
         with warnings.catch_warnings(record=True) as w:
             warnings.simplefilter("always")
             gnn = _new_gnn(params)
-            gnn._guard_sync_passes = 0
+            gnn.guard.sync_passes_left = 0
             gnn(inp, training=True)
-            gnn._guard_sync_passes = 0
+            gnn.guard.sync_passes_left = 0
             gnn.backward(dOut)
             torch.cuda.synchronize()
             assert ops.get_gemm_mode() == ops.GEMM_F16X2

@@ -21,8 +21,8 @@ What a replay does NOT freeze.
   * Dropout: masks are a function of (seed, element, EPOCH); the first node of the captured step advances the epoch word in
     device memory (``tfgnn_dropout_epoch_advance``), so every replay draws fresh masks and the forward and backward
     kernels of one replay the same ones (include/tfgnn.h "dropout EPOCH").
-  * The spread guard of the f16x2 mode: its flag is host-mapped memory and keeps working; a replay cannot re-route itself
-    to other kernels, so ``replay()`` reports a trip (``guard_tripped``) instead of demoting anything.  For a model whose
+  * The spread guard of the f16x2 mode (guard.py): its flag is host-mapped memory and keeps working; a replay cannot re-route
+    itself to other kernels (``GuardPolicy.begin_backward`` never checks a pass that is being captured), so ``replay()`` reports a trip (``guard_tripped``) instead of demoting anything.  For a model whose
     gradients trip it, either capture in ``bf16x3`` or arm the in-stream repair BEFORE building the step
     (``ops.set_guard_repair(True)``): the weight-gradient products then repair themselves on the device in every replay
     (a memset node, the product, a repair kernel that returns at once unless the product tripped, the reduce pass - all nodes
@@ -51,7 +51,7 @@ class CapturedStep:
     and are re-bound by any later eager call.  ``fn`` must not synchronise with the device (no ``.item()``,
     no new adjacency: ``ops.Graph`` construction reads sizes back) - run it eagerly first (``warmup``) so that every
     lazily built piece exists: weights, the batch's bucketed ``Graph`` (cached on the adjacency tensors), workspaces, the
-    synchronous guard passes of a new ``GNN`` (``TFGNN_GUARD_SYNC_PASSES``)."""
+    synchronous guard passes of a new ``GNN`` (``TFGNN_GUARD_SYNC_PASSES``, ``gnn.guard.sync_passes_left``)."""
 
     def __init__(self, fn: Callable[[], Any], warmup: int = 4, advance_dropout_epoch: bool = True):
         self._fn = fn

@@ -15,7 +15,7 @@ from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
-from .. import ops
+from .. import guard, ops
 from ..utils.param_helpers import get_activation_function
 from .graph_global_exchange import (
     GraphGlobalExchange,
@@ -99,27 +99,13 @@ class GNN:
         self._ctx = None
         self._dropout_calls = 0
         self.dropout_seed = 0
-        # Spread-guard policy of the f16x2 mode (backward()): the first `_guard_sync_passes` backward passes are checked
-        # synchronously and recomputed on exact kernels when they trip; after that every `guard_check_every`-th pass is
-        # (TFGNN_GUARD_CHECK_EVERY, 0 = never: a later trip only demotes the NEXT pass).  `guard_tripped_last_backward`
-        # tells the caller what the last pass saw: False / True after a checked pass (True: recomputed on exact kernels),
-        # for an unchecked pass the asynchronous flag as it stood when the pass was enqueued (a trip of that very pass shows
-        # one pass later, together with the demotion warning) - a training loop that must not consume such gradients tests it.
-        self._guard_sync_passes_init = int(ops.env("TFGNN_GUARD_SYNC_PASSES", "3"))
-        self._guard_sync_passes = self._guard_sync_passes_init
-        self.guard_check_every = int(ops.env("TFGNN_GUARD_CHECK_EVERY", "0"))
-        self.guard_tripped_last_backward: Optional[bool] = None
-        self._backward_passes = 0
-        self._unchecked_split_passes = 0  # backward passes in mode f16x2 since the last synchronous check (late trips: below)
-        self._unchecked_epoch = -1        # ops.REARM_EPOCH at the last of them
-        self._late_trip_pass = -1         # the backward pass whose late trip moved the policy (one step per pass)
-        self._late_trip_hook = ops.register_late_trip_policy(self)
-        self._dense_split_ok = True  # cleared when the spread guard trips on this stack's Dense products (backward())
-        self._dense_demoted_epoch = -1  # ops.REARM_EPOCH at that moment: set_gemm_mode("f16x2") re-arms this stack as well
-        self._tn_demoted_epoch = None   # the same for stage 2 (per-relation weight gradients of the message-passing layers)
-        # stage 1a: the Dense / projection weight gradients on the TWO-FACTOR product (each operand's rows guarded on their own,
-        # 2^22) before they leave the split operands altogether (stage 1b)
-        self._dense_tn_wide = False
+        # the spread-guard policy of the f16x2 mode (guard.py): which passes backward() checks, what a trip demotes
+        self.guard = guard.GuardPolicy(self._advance_guard, sync_passes=int(ops.env("TFGNN_GUARD_SYNC_PASSES", "3")),
+                                       check_every=int(ops.env("TFGNN_GUARD_CHECK_EVERY", "0")))
+
+    guard_tripped_last_backward = property(lambda self: self.guard.tripped_last_backward,
+                                           lambda self, v: setattr(self.guard, "tripped_last_backward", v))
+    guard_check_every = property(lambda self: self.guard.check_every, lambda self, v: setattr(self.guard, "check_every", v))
 
     # ---- Keras-like plumbing ----------------------------------------------------------------
     @property
@@ -222,14 +208,8 @@ class GNN:
         # factor and reduce passes of two more weight-gradient products took it back.  With the weight splits riding in the
         # merged small-pass launches, the factors computed inside the weight-gradient kernel and the layer-input dropout in
         # these products' epilogues (all four dropout passes of the benchmark stack gone) it is worth 2.48 vs 2.51 ms.
-        if (not self._dense_split_ok or self._dense_tn_wide) and ops.REARM_EPOCH[0] != self._dense_demoted_epoch:
-            # the mode was re-armed (ops.set_gemm_mode("f16x2")) after this stack moved its Dense weight gradients to the
-            # two-factor product or its Dense products off the split operands: try again, with the synchronous check of the
-            # first passes
-            self._dense_split_ok = True
-            self._dense_tn_wide = False
-            self._guard_sync_passes = max(self._guard_sync_passes, self._guard_sync_passes_init)
-        if ops.env("TFGNN_DENSE_F16X2", "1") == "0" or not self._dense_split_ok:
+        self.guard.sync_with_rearm_epoch()
+        if ops.env("TFGNN_DENSE_F16X2", "1") == "0" or self.guard.dense == "exact":
             return False
         return ops.get_gemm_mode() == ops.GEMM_F16X2 and in_dim % 16 == 0 and in_dim >= 32 and ops.sp_tiles(out_dim)
 
@@ -280,7 +260,7 @@ class GNN:
         d_in, d_out = w.value.shape
         if x.shape[0] > 0 and self._dense_f16x2(d_in, d_out):
             g_sp = ops.sp_rows_of(gpre)  # written by the epilogue of the product above when that is a split-operand product
-            if self._dense_tn_wide:  # (guard policy stage 1a: both operands' rows are un-normalised sums)
+            if self.guard.dense == "wide":  # (guard policy stage 1a: both operands' rows are un-normalised sums)
                 w.grad = ops.sp_gemm_tn(ops.sp_rows_of(x), g_sp, out=torch.empty_like(w.value), wide=True)
             else:
                 w.grad = ops.sp_gemm_tn(ops.sp_rows_of(x), g_sp)  # [in, out] = x^T gpre
@@ -324,14 +304,7 @@ class GNN:
         X = inputs.node_features
         V = X.shape[0]
         adj = inputs.adjacency_lists
-        if self._tn_demoted_epoch is not None and ops.REARM_EPOCH[0] != self._tn_demoted_epoch:
-            # the mode was re-armed (ops.set_gemm_mode("f16x2")) after stage 2 of the guard policy took the per-relation weight
-            # gradients of this stack's layers off the split operands: they try again, under the synchronous check
-            for mp in self._mp_layers:
-                if mp._grouped_tn_split_ok is False:
-                    mp._grouped_tn_split_ok = True
-            self._tn_demoted_epoch = None
-            self._guard_sync_passes = max(self._guard_sync_passes, self._guard_sync_passes_init)
+        self.guard.sync_with_rearm_epoch(self._mp_layers)
         graph = adj if isinstance(adj, ops.Graph) else get_graph(
             adj, V, parts=self.graph_parts(V, [int(a.shape[0]) if a.numel() else 0 for a in adj]))
         graph = get_graph(graph, V)
@@ -469,48 +442,19 @@ class GNN:
             g = torch.zeros_like(ctx["steps"][-1].get("dense_out", ctx["h0"])) if self._num_layers else None
         g_is_pre = False  # g already carries the activation derivative of the op differentiated next
         g_last = None
-        was_f16x2 = ops.get_gemm_mode() == ops.GEMM_F16X2
-        self._backward_passes += 1
-        periodic = self.guard_check_every > 0 and self._backward_passes % self.guard_check_every == 0
-        if ops.capturing():  # a step being captured into a hipGraph cannot wait for the device: never a checked pass
-            if was_f16x2 and self._guard_sync_passes > 0:
-                raise RuntimeError("tf2_gnn_amd: this GNN's first backward passes are checked synchronously "
-                                   f"(TFGNN_GUARD_SYNC_PASSES, {self._guard_sync_passes} left); run them eagerly before "
-                                   "capturing the step (capture.CapturedStep warmup)")
-            periodic = False
-        if not (was_f16x2 and (self._guard_sync_passes > 0 or periodic)):
-            self.guard_tripped_last_backward = bool(was_f16x2 and ops.f16x2_guard_flag_async())
-            if was_f16x2:
-                self._unchecked_split_passes += 1
-                self._unchecked_epoch = ops.REARM_EPOCH[0]
+        if not self.guard.begin_backward(ops.get_gemm_mode() == ops.GEMM_F16X2, ops.capturing()):
             return self._backward_walk(ctx, g, g_is_pre, g_last, extras, need_input_grad)
-        # The spread guard of the split weight-gradient products reports through a host-visible flag WITHOUT a stream
-        # synchronisation: a pass that trips it has produced its gradients by the time the host notices.  For the
-        # first passes of a model (TFGNN_GUARD_SYNC_PASSES, default 3: whether a model's gradient rows are spread
-        # that far shows at once - RGAT's attention-weighted rows trip it on the first step) wait for the pass and,
-        # if it tripped, run it again on sturdier kernels, one step per attempt (_demote_fragile_weight_gradients): this
-        # stack's Dense / projection weight gradients on the two-factor product, then its Dense products off the split
-        # operands (their operand rows - un-normalised sums, attention-weighted gradients - are the usual culprit; the
-        # message products keep their split operands), then the per-relation MLP weight gradients, then the whole mode.  Later
-        # trips demote the mode from the NEXT pass on and say so (ops.get_gemm_mode warns), but the tripping pass
-        # itself is not recomputed (README.md).  While this section runs, a set flag does not demote the mode on sight.
-        if self._guard_sync_passes > 0:
-            self._guard_sync_passes -= 1
-        self.guard_tripped_last_backward = False
-        self._unchecked_split_passes = 0
+        # a checked pass: wait for it and, while it trips, run it again one stage of the policy further, at last on the demoted mode
         with ops.hold_spread_guard():
             result = self._backward_walk(ctx, g, g_is_pre, g_last, extras, need_input_grad)
             for attempt in range(4):
                 if not ops.f16x2_guard_tripped_sync():
                     break
-                self.guard_tripped_last_backward = True
-                what = self._demote_fragile_weight_gradients() if attempt < 3 else None
+                self.guard.tripped_last_backward = True
+                what = self._advance_guard() if attempt < 3 else None
                 if what:
                     ops.rearm_spread_guard()
-                    import warnings
-
-                    warnings.warn(f"tf2_gnn_amd: operand rows of a weight-gradient product of this GNN are spread beyond the range "
-                                  f"of the split-operand product that ran: {what}; the pass was recomputed")
+                    guard.warn_recomputed(what)
                 else:
                     ops.demote_gemm_mode()  # the whole mode (sticky), with a warning
                 for v in self.trainable_variables:
@@ -519,59 +463,14 @@ class GNN:
         return result
 
     def guard_state(self) -> Dict[str, Any]:
-        """What the spread-guard policy has done to this stack so far: ``tripped`` (the last backward pass, see
-        ``guard_tripped_last_backward``) and ``stage`` - "none", "1a" (Dense / projection weight gradients on the two-factor
-        product), "1b" (Dense products off the split operands), "2" (per-relation weight gradients on the exact kernels),
-        "3" (the whole mode demoted to bf16x3).  bench.py prints it with every line."""
-        stage = "none"
-        if self._dense_tn_wide:
-            stage = "1a"
-        if not self._dense_split_ok:
-            stage = "1b"
-        if self._tn_demoted_epoch is not None:
-            stage = "2"
-        if self._backward_passes and ops.get_gemm_mode() != ops.GEMM_F16X2:
-            stage = "3" if stage != "none" or ops.f16x2_guard_flag_async() else stage
-        return {"tripped": self.guard_tripped_last_backward, "stage": stage, "checked_passes_left": self._guard_sync_passes}
+        """What the spread-guard policy (``guard.GuardPolicy``) has done to this stack so far: ``tripped`` (the last backward
+        pass), ``stage`` ("none", "1a", "1b", "2", "3": the whole mode demoted) and ``checked_passes_left``.  bench.py prints it."""
+        return self.guard.state()
 
-    def _on_late_guard_trip(self) -> Optional[str]:
-        """A backward pass that was NOT checked synchronously tripped the spread guard (ops._f16x2_on sees the flag some time
-        later - possibly while that pass is still being enqueued).  Instead of losing the whole mode, a stack that ran such
-        passes walks its staged policy one step - one step per pass, however many of its products report - and has its next
-        passes checked (and recomputed when they trip) again.  -> what changed kernels, None: nothing left / not involved."""
-        if self._unchecked_split_passes == 0 or self._unchecked_epoch != ops.REARM_EPOCH[0]:
-            return None  # (no unchecked pass of this stack since the mode was last armed: somebody else's products)
-        if self._late_trip_pass == self._backward_passes:
-            return "(this stack's policy has moved a step for that pass already)"
-        what = self._demote_fragile_weight_gradients()
-        if what:
-            self._late_trip_pass = self._backward_passes
-            self._guard_sync_passes = max(self._guard_sync_passes, self._guard_sync_passes_init)
-            self.guard_tripped_last_backward = True
-        return what
-
-    def _demote_fragile_weight_gradients(self) -> Optional[str]:
-        """The stages of the spread guard's policy before the whole mode is demoted: the weight-gradient products whose operand
-        ROWS are un-normalised sums change kernels, one step per call - first this stack's Dense / projection weight gradients
-        go from the combined-factor TN product (range 2^20) to the two-factor one (2^22 per operand), then these products leave
-        the split operands, then the per-relation TN products of the compact-row MLP path (RGIN, GNN_Edge_MLP: the two-factor
-        product) go to the exact kernels; the message products keep their split operands.
-        -> what was demoted, or None when nothing is left to demote."""
-        if self._dense_split_ok and self._dense_f16x2(self._hidden_dim, self._hidden_dim):
-            self._dense_demoted_epoch = ops.REARM_EPOCH[0]
-            if not self._dense_tn_wide:
-                self._dense_tn_wide = True
-                return "the Dense / projection weight gradients (now on the two-factor split-operand product)"
-            self._dense_split_ok = False
-            return "the Dense / projection products (now on the exact bf16x3 kernels)"
-        did = False
-        for mp in self._mp_layers:
-            if mp._grouped_tn_used and mp._grouped_tn_split_ok:
-                mp._grouped_tn_split_ok = False
-                did = True
-        if did:
-            self._tn_demoted_epoch = ops.REARM_EPOCH[0]
-        return "the per-relation MLP weight gradients (now on the exact bf16x3 kernels)" if did else None
+    def _advance_guard(self) -> Optional[str]:
+        """One stage of the guard policy on this stack's layers -> what was demoted, None: nothing is left to demote."""
+        dense_possible = self.guard.dense != "exact" and self._dense_f16x2(self._hidden_dim, self._hidden_dim)
+        return self.guard.advance(self._mp_layers, dense_possible)
 
     @staticmethod
     def _activation_backward_scaled(act, g, saved, saved_scale):

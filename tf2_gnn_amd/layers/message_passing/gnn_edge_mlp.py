@@ -271,7 +271,7 @@ class GNN_Edge_MLP(MessagePassing):
         # (GNN_FiLM's per-edge form borrows path C's machinery - ``_edge_messages_C``, ``_backward_C`` - whatever ``_path()``
         #  says of its edge MLPs: those two ask here where no route is handed to them)
         # the first layer's gradients on split operands: widths the split-operand kernels tile, unless the stack's guard
-        # policy handed these weight gradients back to the exact kernels (GNN._demote_fragile_weight_gradients); their
+        # policy handed these weight gradients back to the exact kernels (guard.GuardPolicy.advance); their
         # input-gradient products walk the nodes in the order of their emptiness patterns
         H0 = int(self._edge_type_mlps.kernels[0].shape[2])
         split = bool(ops.get_gemm_mode() == ops.GEMM_F16X2 and ops.env("TFGNN_EDGE_FIRST_LAYER_F16X2", "1") == "1"

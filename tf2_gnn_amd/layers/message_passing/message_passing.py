@@ -179,7 +179,7 @@ class MessagePassing:
             "hidden_dim": 7,
         }
 
-    # Defaults of the per-layer state of the stack's spread-guard policy (GNN._demote_fragile_weight_gradients); __init__ copies
+    # Defaults of the per-layer state of the stack's spread-guard policy (guard.GuardPolicy.advance); __init__ copies
     # them into the instance, where they live across passes:
     _grouped_tn_split_ok = True  # the per-relation weight gradients may run on the split-operand TN products (stage 2 clears it)
     _grouped_tn_used = False     # a backward pass of this layer ran such a product (what stage 2 can demote)

@@ -6,13 +6,16 @@ current HIP stream, every FLOP and byte of the hot path runs in libtfgnn.so.
 from __future__ import annotations
 
 import ctypes
-import weakref
 import os
 from typing import Optional, Sequence
 
 import torch
 
 from . import _lib
+from .guard import (  # noqa: F401 - the GEMM mode, its spread guard and the in-stream repair: their public names are these
+    GEMM_BF16X3, GEMM_BF16X3_EXACT, GEMM_F16X2, GEMM_FP32, capturing, demote_gemm_mode, f16x2_guard_flag_async,
+    f16x2_guard_tripped_sync, get_gemm_mode, guard_repair, hold_spread_guard, rearm_spread_guard, repair_stats, set_gemm_mode,
+    set_guard_repair)
 
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_LEAKY_RELU, ACT_ELU, ACT_SELU, ACT_GELU, ACT_SIGMOID = range(8)
 REDUCE_SUM, REDUCE_MAX = 0, 1
@@ -572,129 +575,6 @@ def gemm_grad(a, b, *, trans_b=False, out=None, out_mul=None, act_grad=None, acc
     return res
 
 
-GEMM_FP32, GEMM_BF16X3, GEMM_BF16X3_EXACT, GEMM_F16X2 = 0, 6, 9, 3
-_GEMM_MODE_NAMES = {"fp32": GEMM_FP32, "bf16x3": GEMM_BF16X3, "bf16x3_9": GEMM_BF16X3_EXACT, "f16x2": GEMM_F16X2}
-_f16x2 = [None]  # None: not decided yet (environment TFGNN_GEMM_MODE; unset = f16x2, the default since round 3)
-_spread_warned = [False]
-
-
-def _f16x2_on() -> bool:
-    """Is the library in mode f16x2 (include/tfgnn.h TFGNN_GEMM_F16X2)?  The library itself holds the mode and demotes it when
-    the spread guard of the split weight-gradient product trips (tfgnn_gemm_get_mode); this mirror only warns once."""
-    if (_GUARD_HOLD[0] or _in_late_trip[0]) and _f16x2[0]:
-        return True  # a caller that checks the guard synchronously at the end of its pass decides what a trip demotes
-    lib = _lib.load()
-    on = lib.tfgnn_gemm_get_mode() == GEMM_F16X2  # (the library takes the mode off - sticky - when it finds the flag up)
-    if _f16x2[0] and not on and _LATE_TRIP_POLICIES and lib.tfgnn_sp_spread_flag(0) and not capturing():
-        # A pass that was not checked synchronously tripped the guard, and the library has just taken the whole mode off the split
-        # operands for it.  If the stacks that ran such passes still have a stage of their policy to give (GNN._on_late_guard_trip:
-        # only the weight-gradient products whose operand rows are spread change kernels, one stage per pass), the mode goes back
-        # on - tfgnn_gemm_set_mode waits for the device and clears the flag - and those stacks' next passes are checked
-        # synchronously again.  The tripping pass itself is not recomputed.  (ONE read of the flag decides - the library's: a
-        # look at the flag here followed by the library's own could straddle the moment the device raises it.)
-        _in_late_trip[0] = True
-        try:
-            handled = [w for w in (fn() for fn in list(_LATE_TRIP_POLICIES.values())) if w]
-            if handled:
-                _lib.check(lib.tfgnn_gemm_set_mode(GEMM_F16X2))
-                on = True
-                import warnings
-
-                warnings.warn("tf2_gnn_amd: operand rows of a weight-gradient product spread beyond the range of the split-operand "
-                              "product that ran, in a pass that was not checked synchronously (its gradients may have lost "
-                              "low-order rows): " + "; ".join(handled) + "; the next passes are checked again")
-        finally:
-            _in_late_trip[0] = False
-    if _f16x2[0] and not on and not _spread_warned[0] and lib.tfgnn_sp_spread_flag(0):
-        _spread_warned[0] = True
-        import warnings
-
-        warnings.warn("tf2_gnn_amd: operand rows of a weight-gradient product spread over more than 2^20 in magnitude; "
-                      "the f16x2 layer paths are switched to the exact bf16x3 kernels (ops.set_gemm_mode('f16x2') re-arms them)")
-    _f16x2[0] = on
-    return on
-
-
-def set_gemm_mode(mode) -> int:
-    """Select how the Dense products are evaluated: "fp32" (fp32 MFMA), "bf16x3" (exact 3-way bf16 split of both operands,
-    6 piece products), "bf16x3_9" (all 9) or "f16x2": the layers hand the hot products pre-split SP16 operands
-    (tfgnn_sp_gemm_*: 2-way fp16 split, 3 piece products, the gather writes the operand) and every other product runs as in
-    "bf16x3" - include/tfgnn.h, tfgnn_gemm_set_mode.  "f16x2" is the DEFAULT of the library (environment TFGNN_GEMM_MODE
-    overrides); its spread guard (tfgnn_sp_spread_flag) demotes it to "bf16x3" when an operand's row scales spread over more
-    than 2^20; setting "f16x2" again re-arms the guard (waits for the device).  Returns the previous mode id."""
-    lib = _lib.load()
-    prev = get_gemm_mode()
-    mode = _GEMM_MODE_NAMES.get(mode, mode)
-    _lib.check(lib.tfgnn_gemm_set_mode(mode))
-    _f16x2[0] = mode == GEMM_F16X2
-    if mode == GEMM_F16X2:
-        REARM_EPOCH[0] += 1  # stacks that demoted their own Dense products take the split kernels again (GNN._dense_f16x2)
-    return prev
-
-
-def get_gemm_mode() -> int:
-    if _f16x2_on():
-        return GEMM_F16X2
-    return _lib.load().tfgnn_gemm_get_mode()
-
-
-_GUARD_HOLD = [0]
-_in_late_trip = [False]
-_LATE_TRIP_POLICIES = weakref.WeakValueDictionary()  # id -> bound-method holder of the stacks with a staged guard policy
-
-
-class _LateTripHook:
-    """Keeps a stack's policy callable reachable through a weak dictionary: the hook lives as long as its owner does."""
-
-    def __init__(self, owner):
-        self._owner = weakref.ref(owner)
-
-    def __call__(self):
-        o = self._owner()
-        return o._on_late_guard_trip() if o is not None else None
-
-
-def register_late_trip_policy(owner) -> "_LateTripHook":
-    """``owner._on_late_guard_trip() -> Optional[str]`` is asked when an unchecked pass trips the spread guard (``_f16x2_on``).
-    The caller keeps the returned hook alive (an attribute of the owner)."""
-    hook = _LateTripHook(owner)
-    _LATE_TRIP_POLICIES[id(hook)] = hook
-    return hook
-
-
-REARM_EPOCH = [0]  # times the f16x2 mode was (re-)armed by set_gemm_mode("f16x2")
-
-
-def demote_gemm_mode() -> int:
-    """Let the library act on a set spread flag NOW, also inside ``hold_spread_guard`` -> the mode in force afterwards."""
-    held, _GUARD_HOLD[0] = _GUARD_HOLD[0], 0
-    try:
-        return get_gemm_mode()
-    finally:
-        _GUARD_HOLD[0] = held
-
-
-class hold_spread_guard:
-    """Inside this context a tripped spread flag does not demote the mode on sight: the caller reads the flag itself
-    (``f16x2_guard_tripped_sync``) when its pass is complete and decides what to demote (``GNN.backward``)."""
-
-    def __enter__(self):
-        _f16x2_on()
-        _GUARD_HOLD[0] += 1
-        return self
-
-    def __exit__(self, *exc):
-        _GUARD_HOLD[0] -= 1
-        return False
-
-
-def rearm_spread_guard() -> None:
-    """Clear the spread flag WITHOUT demoting the mode (the caller has dealt with the product that tripped it).  Waits for the
-    stream first: a factor computation still in flight must not set it again."""
-    torch.cuda.current_stream().synchronize()
-    _lib.load().tfgnn_sp_spread_flag(1)
-
-
 KERNEL_FAMILIES = ("gemm_fp32", "gemm_bf16x3", "sp_nt", "sp_tn", "gather_sp", "gather", "fused_nt", "gemm_stream", "stream_f16x2")
 
 
@@ -704,48 +584,6 @@ def launch_counts() -> dict:
     buf = (ctypes.c_int64 * len(KERNEL_FAMILIES))()
     _lib.check(_lib.load().tfgnn_launch_counts(buf, len(KERNEL_FAMILIES)))
     return dict(zip(KERNEL_FAMILIES, (int(v) for v in buf)))
-
-
-def set_guard_repair(on: bool) -> bool:
-    """Arm (True) or disarm the in-stream repair of tripped split-operand weight-gradient products (include/tfgnn.h,
-    tfgnn_sp_guard_repair) -> the previous state.  While armed, ``sp_gemm_tn`` (both forms) and the product inside
-    ``mp_backward`` recompute a product whose spread guard trips in fp32 from the SP16 operands, on the stream and before
-    their reduce pass: the pass's own gradients are right, the host flag stays down, the mode stays ``f16x2`` - also in a
-    replayed ``capture.CapturedStep`` (arm before building it; arming allocates, so not while capturing).  Off by default
-    (environment TFGNN_GUARD_REPAIR=1 arms at start).  ``sp_gemm_tn_grouped`` is not covered."""
-    if capturing():
-        raise RuntimeError("tf2_gnn_amd: set_guard_repair is not legal while the stream is capturing (arm before the capture)")
-    rc = _lib.load().tfgnn_sp_guard_repair(1 if on else 0)
-    if rc < 0:
-        _lib.check(rc)
-    return bool(rc)
-
-
-def guard_repair() -> bool:
-    """Is the in-stream repair of tripped weight-gradient products armed (``set_guard_repair``)?"""
-    return bool(_lib.load().tfgnn_sp_guard_repair(-1))
-
-
-def repair_stats(reset: bool = False) -> dict:
-    """{"armed_products": products enqueued with repair armed (host counter), "repaired_products": products the device
-    repaired}; waits for the device (not legal while capturing).  ``reset`` clears both."""
-    buf = (ctypes.c_int64 * 2)()
-    _lib.check(_lib.load().tfgnn_sp_repair_stats(buf, int(bool(reset))))
-    return {"armed_products": int(buf[0]), "repaired_products": int(buf[1])}
-
-
-def f16x2_guard_flag_async() -> bool:
-    """The spread flag as the host sees it NOW, without waiting for the device (what products enqueued earlier have reported
-    so far)."""
-    return bool(_lib.load().tfgnn_sp_spread_flag(0))
-
-
-def f16x2_guard_tripped_sync() -> bool:
-    """Wait for the current stream, then read the spread guard: True if a split weight-gradient product enqueued so far met
-    operand rows spread over more than 2^20 (its result may have lost low-order rows).  The synchronous form of the guard:
-    ``GNN.backward`` uses it for the first backward passes of a model and recomputes a tripped pass on the exact kernels."""
-    torch.cuda.current_stream().synchronize()
-    return bool(_lib.load().tfgnn_sp_spread_flag(0))
 
 
 @_writes_out
@@ -1063,7 +901,7 @@ def dropout_forward(x: torch.Tensor, rate: float, seed: int, want_mask: bool = T
     x = x.contiguous()
     y = torch.empty_like(x)
     mask = torch.empty_like(x) if want_mask else None
-    if _f16x2_on() and x.dim() == 2 and x.shape[1] % 16 == 0 and 32 <= x.shape[1] <= 512 and x.shape[0] > 0:
+    if get_gemm_mode() == GEMM_F16X2 and x.dim() == 2 and x.shape[1] % 16 == 0 and 32 <= x.shape[1] <= 512 and x.shape[0] > 0:
         rows, cols = x.shape
         op = SplitOperand(torch.empty((rows, cols * 4), dtype=torch.uint8, device=x.device),
                           torch.empty((rows, 1), dtype=torch.float32, device=x.device), rows, cols, cols)
@@ -1092,11 +930,6 @@ def dropout_epoch_advance() -> None:
 
 def dropout_epoch_set(value: int) -> None:
     _lib.check(_lib.load().tfgnn_dropout_epoch_set(int(value) & 0xFFFFFFFF, _stream()))
-
-
-def capturing() -> bool:
-    """Is the current stream being captured into a hipGraph (``capture.CapturedStep``)?  Host synchronisation is illegal then."""
-    return bool(torch.cuda.is_current_stream_capturing())
 
 
 def dropout_mask(shape, rate: float, seed: int, device=None) -> torch.Tensor:
