@@ -744,7 +744,10 @@ int tfgnn_sp_gemm_tn_wide(int64_t M, int64_t N, int64_t K, const void* d_A_sp, i
  * of the per-relation MLPs): d_split_table int32 [num_splits][2] = (first row, rows <= 2016) of every K range, ranges of a group
  * consecutive; d_group_split_offsets int32 [num_groups + 1] = first range of every group.  Output g at d_C + g *
  * c_group_stride, element (m, n) at m * stride_row + n * stride_col.  Workspace: 4 * 512 * (a_total_cols / a_scale_block)
- * rounded up to 256, + num_splits * roundup(M, 128) * N * 4 bytes.  num_splits <= 512. */
+ * rounded up to 256, + num_splits * roundup(M, 128) * N * 4 bytes.  num_splits <= 512.
+ * tfgnn_sp_gemm_tn_grouped_workspace_bytes returns that size - plus the tail of the trip words (2304 bytes) while the in-stream
+ * repair is armed (tfgnn_sp_guard_repair below); 0 for a shape the product rejects.  A call whose workspace is smaller fails. */
+size_t tfgnn_sp_gemm_tn_grouped_workspace_bytes(int64_t M, int64_t N, int64_t a_total_cols, int a_scale_block, int num_splits);
 int tfgnn_sp_gemm_tn_grouped(int64_t M, int64_t N, const void* d_A_sp, int64_t lda_bytes, const float* d_a_inv_scale,
                              int64_t a_total_cols, int a_scale_block, const void* d_B_sp, int64_t ldb_bytes, const float* d_b_inv_scale,
                              int num_groups, const int32_t* d_group_split_offsets, int num_splits, const int32_t* d_split_table,
@@ -866,7 +869,14 @@ int tfgnn_sp_spread_flag(int reset);
  * multiplies back to 1 - the result lands through the same accumulate / scatter / column-range path as any other, and is
  * right in the very pass that tripped.  No host synchronisation and no allocation at launch time: the sequence can be captured
  * into a hipGraph and every replay repairs itself.  A covered product no longer raises tfgnn_sp_spread_flag, so nothing
- * demotes the mode.  NOT covered: tfgnn_sp_gemm_tn_grouped, which keeps reporting through the host-visible flag.
+ * demotes the mode.
+ * tfgnn_sp_gemm_tn_grouped is covered too, range by range: its tail (tfgnn_sp_gemm_tn_grouped_workspace_bytes grows by it while
+ * armed) holds one trip word per K range of the split table plus one "counted" word, all zeroed by one small kernel in front
+ * of the product (a kernel node in a hipGraph, where the plain products have a 4-byte memset node); a range that sees a pair
+ * beyond the guard sets its own word, and the repair kernel rewrites the slab of that range alone (same
+ * arithmetic) and sets that range's reference scales to 1.  The other ranges of the group keep what the product wrote; the
+ * grouped reduce pass multiplies every slab by its own reference and adds them in range order, so the result depends only on
+ * the operands and the tables.  A grouped launch counts as ONE repaired product, however many of its ranges tripped.
  * tfgnn_sp_guard_repair: on = 1 arms, 0 disarms, -1 only queries; returns the previous state (0 / 1) or a negative error
  * code.  Arming allocates a device counter: not legal while a stream is capturing (arm before the capture).
  * tfgnn_sp_repair_stats: out2[0] = products enqueued with repair armed (host counter), out2[1] = products repaired (device

@@ -233,6 +233,7 @@ _SIGNATURES = [
          c_void_p, c_size_t, c_void_p],
     ),
     ("tfgnn_sp_gemm_tn_workspace_bytes", c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int]),
+    ("tfgnn_sp_gemm_tn_grouped_workspace_bytes", c_size_t, [c_int64, c_int64, c_int64, c_int, c_int]),
     (
         "tfgnn_sp_gemm_tn_grouped",
         c_int,

@@ -24,9 +24,10 @@ What a replay does NOT freeze.
   * The spread guard of the f16x2 mode (guard.py): its flag is host-mapped memory and keeps working; a replay cannot re-route
     itself to other kernels (``GuardPolicy.begin_backward`` never checks a pass that is being captured), so ``replay()`` reports a trip (``guard_tripped``) instead of demoting anything.  For a model whose
     gradients trip it, either capture in ``bf16x3`` or arm the in-stream repair BEFORE building the step
-    (``ops.set_guard_repair(True)``): the weight-gradient products then repair themselves on the device in every replay
-    (a memset node, the product, a repair kernel that returns at once unless the product tripped, the reduce pass - all nodes
-    of the graph), the flag stays down and the replayed gradients are the repaired ones.
+    (``ops.set_guard_repair(True)``): the weight-gradient products of all five layer kinds - the grouped per-relation
+    product of RGIN and the compact-row route included, K range by K range - then repair themselves on the device in every
+    replay (a memset node, the product, a repair kernel that returns at once unless the product tripped, the reduce pass -
+    all nodes of the graph), the flag stays down and the replayed gradients are the repaired ones.
 
 PyTorch supplies the capture machinery (``torch.cuda.CUDAGraph`` is hipGraph on ROCm: stream capture, a private memory
 pool for what the step allocates); nothing of the step's arithmetic runs in torch.

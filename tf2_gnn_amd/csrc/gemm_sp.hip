@@ -872,6 +872,8 @@ struct SpTnArgs {
   const float* inv_b;  // [K] or NULL
   float* ref_split;    // [splits][a_nblk]: the reference scale of (split, block), multiplied back by the reduce pass
   int* spread_flag;
+  int trip_stride;     // a split beyond the guard stores 1 to spread_flag[split * trip_stride]: 0 = one word for the whole launch
+                       // (the library-wide flag, a plain product's trip word); 1 = a word per K range (the armed grouped product)
   float* partial;     // [splits][M][N]
   int64_t k_chunk;    // rows of K per split (a multiple of 16)
   unsigned n_tiles;
@@ -1372,7 +1374,7 @@ __global__ void __launch_bounds__(SP_NT, 1) gemm_sp_tn_kernel(SpTnArgs g) {
         }
       }
     }
-    if (g.spread_flag && __any(wide) && lane == 0) *g.spread_flag = 1;
+    if (g.spread_flag && __any(wide) && lane == 0) g.spread_flag[split * g.trip_stride] = 1;
   }
   L.wait_landed();
   __builtin_amdgcn_s_barrier();
@@ -1944,7 +1946,7 @@ static int sp_gemm_tn_impl(int64_t M, int64_t N, int64_t K, const void* d_A_sp, 
   int* guard_word = sp_spread_flag_device();
   if (repair) {
     guard_word = (int*)((uint8_t*)d_workspace + slabs_end);
-    if (int rc = tn_repair_begin(guard_word, s)) return rc;
+    if (int rc = tn_repair_begin(guard_word, sizeof(int), s)) return rc;
   }
   _Float16* F = (_Float16*)d_workspace;
   float* ref = (float*)((uint8_t*)d_workspace + f_bytes);
@@ -2051,6 +2053,15 @@ int tfgnn_sp_gemm_tn_wide(int64_t M, int64_t N, int64_t K, const void* d_A_sp, i
                          workspace_bytes, stream, true);
 }
 
+size_t tfgnn_sp_gemm_tn_grouped_workspace_bytes(int64_t M, int64_t N, int64_t a_total_cols, int a_scale_block, int num_splits) {
+  if (!sp_tile_width(N) || M <= 0 || a_total_cols <= 0 || a_scale_block <= 0 || num_splits < 0) return 0;
+  const int64_t Mp = ceil_div(M, SP_BM) * SP_BM;
+  const int64_t nblk = ceil_div(a_total_cols, a_scale_block);
+  const size_t base = (((size_t)nblk * 512 * 4 + 255) & ~(size_t)255) + (size_t)num_splits * (size_t)Mp * (size_t)N * 4;
+  // what a call needs NOW: with repair armed (tn_repair.hpp) the trip words' tail follows the slabs
+  return tn_repair_armed() ? base + kTnRepairGroupedTailBytes : base;
+}
+
 int tfgnn_sp_gemm_tn_grouped(int64_t M, int64_t N, const void* d_A_sp, int64_t lda_bytes, const float* d_a_inv_scale,
                              int64_t a_total_cols, int a_scale_block, const void* d_B_sp, int64_t ldb_bytes, const float* d_b_inv_scale,
                              int num_groups, const int32_t* d_group_split_offsets, int num_splits, const int32_t* d_split_table,
@@ -2071,17 +2082,28 @@ int tfgnn_sp_gemm_tn_grouped(int64_t M, int64_t N, const void* d_A_sp, int64_t l
                 "tfgnn_sp_gemm_tn_grouped: SP16 operands must be 64-byte aligned with rows wide enough");
   const int64_t nblk = a_total_cols / a_scale_block;
   const size_t r_bytes = ((size_t)nblk * 512 * 4 + 255) & ~(size_t)255;
-  const size_t need = r_bytes + (size_t)num_splits * (size_t)Mp * (size_t)N * 4;
+  // repair armed (tfgnn_sp_guard_repair): the guard reports into the tail of this call's own workspace, one word per K range -
+  // zeroed on the stream in front of the product - and sp_tn_repair_kernel, between the product and the reduce pass, rewrites
+  // the slabs of the ranges that tripped, in stream order
+  const bool repair = tn_repair_armed();
+  const size_t slabs_end = r_bytes + (size_t)num_splits * (size_t)Mp * (size_t)N * 4;  // a multiple of 256
+  const size_t need = slabs_end + (repair ? kTnRepairGroupedTailBytes : 0);
   TFGNN_REQUIRE(d_workspace && workspace_bytes >= need && (uintptr_t)d_workspace % 256 == 0,
                 "tfgnn_sp_gemm_tn_grouped: workspace too small or unaligned (need %zu bytes)", need);
   hipStream_t s = (hipStream_t)stream;
+  int* guard_word = sp_spread_flag_device();
+  if (repair && num_splits > 0) {
+    guard_word = (int*)((uint8_t*)d_workspace + slabs_end);
+    if (int rc = tn_repair_begin(guard_word, kTnRepairGroupedTailBytes, s)) return rc;
+  }
   float* ref_split = (float*)d_workspace;  // [num_splits][nblk]
   SpTnArgs g{};
   g.M = Mp; g.N = N; g.K = 0;
   g.A = (const uint8_t*)d_A_sp; g.lda = lda_bytes;
   g.B = (const uint8_t*)d_B_sp; g.ldb = ldb_bytes;
   g.a_sb = a_scale_block; g.a_col0 = 0; g.a_nblk = (int)nblk;
-  g.inv_a = d_a_inv_scale; g.inv_b = d_b_inv_scale; g.ref_split = ref_split; g.spread_flag = sp_spread_flag_device();
+  g.inv_a = d_a_inv_scale; g.inv_b = d_b_inv_scale; g.ref_split = ref_split; g.spread_flag = guard_word;
+  g.trip_stride = repair ? 1 : 0;
   g.partial = (float*)((uint8_t*)d_workspace + r_bytes);
   g.k_chunk = SP_TN_BSC_MAX_CHUNK;
   g.split_table = d_split_table;
@@ -2108,6 +2130,14 @@ int tfgnn_sp_gemm_tn_grouped(int64_t M, int64_t N, const void* d_A_sp, int64_t l
     else SP_LAUNCH_TNG(2);
 #undef SP_LAUNCH_TNG
     TFGNN_LAUNCH_CHECK();
+    if (repair) {
+      TnRepairArgs rp{};
+      rp.M = M; rp.N = N; rp.K = 0; rp.A = g.A; rp.lda = lda_bytes; rp.B = g.B; rp.ldb = ldb_bytes;
+      rp.inv_a = d_a_inv_scale; rp.inv_b = d_b_inv_scale; rp.a_sb = a_scale_block; rp.a_col0 = 0; rp.a_nblk = (int)nblk;
+      rp.partial = g.partial; rp.slab = Mp * N; rp.k_chunk = 0; rp.split_table = d_split_table; rp.splits = num_splits;
+      rp.ref = ref_split; rp.ref_per_split = 1; rp.trip = guard_word;
+      if (int rc = tn_repair_enqueue(rp, s)) return rc;
+    }
   }
   TnReduceArgs ra{};
   ra.partial = g.partial; ra.splits = 0; ra.M = M; ra.N = N; ra.ref = ref_split; ra.a_col0 = 0; ra.a_sb = a_scale_block;

@@ -11,6 +11,10 @@
 //
 // A rare path: plain VALU work, a 64 x 64 output tile per 256-thread workgroup (4 x 4 per thread), 16 rows of K staged through
 // LDS per step.  One workgroup per (output tile, K range) - the product's own decomposition, so the slabs line up.
+//
+// The grouped product (K ranges from its split table) is repaired range by range: workgroup (tile, z) looks at trip word z alone,
+// rewrites slab z alone and sets the references of range z alone.  What a range's slab holds then depends only on the operands
+// and the table, never on which other ranges tripped; the grouped reduce pass adds the slabs in range order as always.
 #include "tn_repair.hpp"
 
 #include "sp16.hpp"
@@ -20,17 +24,22 @@ namespace tfgnn {
 constexpr int RP_TILE = 64, RP_KSTEP = 16;
 
 __global__ void __launch_bounds__(256) sp_tn_repair_kernel(TnRepairArgs a) {
-  // the product kernels (earlier on the stream) stored 1 here if a row was beyond their range; 0 (the memset node): nothing to do
-  if (*reinterpret_cast<const volatile int*>(a.trip) == 0) return;
+  // the product kernels (earlier on the stream) stored 1 here if a row was beyond their range; 0 (zeroed in front of them): nothing to do
+  // (grouped: the word of this workgroup's own K range)
+  const int z = blockIdx.y;
+  if (*reinterpret_cast<const volatile int*>(a.split_table ? a.trip + z : a.trip) == 0) return;
   typedef _Float16 half4 __attribute__((ext_vector_type(4)));
   __shared__ float4 As[RP_KSTEP][RP_TILE / 4];
   __shared__ float4 Bs[RP_KSTEP][RP_TILE / 4];
   const int t = threadIdx.x;
   const int n_tiles = (int)(a.N / RP_TILE);
   const int tm = blockIdx.x / n_tiles, tn = blockIdx.x - tm * n_tiles;
-  const int z = blockIdx.y;
-  const int64_t k0 = (int64_t)z * a.k_chunk;
-  const int64_t k1 = k0 + a.k_chunk < a.K ? k0 + a.k_chunk : a.K;
+  int64_t k0 = (int64_t)z * a.k_chunk;
+  int64_t k1 = k0 + a.k_chunk < a.K ? k0 + a.k_chunk : a.K;
+  if (a.split_table) {
+    k0 = a.split_table[2 * z];
+    k1 = k0 + a.split_table[2 * z + 1];
+  }
   // loads: thread -> (row of the step, 4 columns); products: thread -> 4 x 4 outputs
   const int lr = t >> 4, lc = (t & 15) * 4;
   const int64_t am = (int64_t)tm * RP_TILE + lc;  // first of this thread's 4 columns of A (M % 4 == 0: all four inside or none)
@@ -91,8 +100,19 @@ __global__ void __launch_bounds__(256) sp_tn_repair_kernel(TnRepairArgs a) {
     } else if (z == 0) {
       for (int b = t; b < a.a_nblk; b += 256) a.ref[b] = 1.f;
     }
-    if (z == 0 && t == 0) __hip_atomic_fetch_add(a.repaired, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (a.split_table) {
+      // a grouped launch counts once, however many of its ranges tripped: the first range to flip the tail's last word does it
+      if (t == 0 && __hip_atomic_exchange(a.trip + kTnRepairGroupedMaxRanges, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
+        __hip_atomic_fetch_add(a.repaired, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else if (z == 0 && t == 0) {
+      __hip_atomic_fetch_add(a.repaired, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
   }
+}
+
+// zeroes the grouped product's tail in front of the product (tn_repair_begin)
+__global__ void __launch_bounds__(256) sp_tn_repair_clear_kernel(int* __restrict__ words, int n) {
+  for (int i = threadIdx.x; i < n; i += 256) words[i] = 0;
 }
 
 // ---- state: the switch, the host counter of armed products, one device counter of repaired products per device ----
@@ -141,21 +161,31 @@ static bool repair_stream_capturing(hipStream_t s) {
   return st != hipStreamCaptureStatusNone;
 }
 
-int tn_repair_begin(int* trip_word, hipStream_t s) {
+int tn_repair_begin(int* trip_word, size_t tail_bytes, hipStream_t s) {
   if (!repair_counter(false)) {  // armed through the environment (or on another device): the counter does not exist yet
     TFGNN_REQUIRE(!repair_stream_capturing(s),
                   "tfgnn_sp_gemm_tn: repair is armed but its device counter does not exist yet and the stream is capturing "
                   "(call tfgnn_sp_guard_repair(1) or run one product before the capture)");
     TFGNN_REQUIRE(repair_counter(true), "tfgnn_sp_gemm_tn: no device memory for the repair counter");
   }
-  TFGNN_HIP_CHECK(hipMemsetAsync(trip_word, 0, sizeof(int), s));
+  if (tail_bytes <= sizeof(int)) {
+    TFGNN_HIP_CHECK(hipMemsetAsync(trip_word, 0, tail_bytes, s));
+  } else {
+    // the grouped product's tail (trip words + the counted word).  Not a memset node: measured on the MI355X, a product captured
+    // into a hipGraph behind a 2304-byte memset node lost its trip words in every replay but the first (the 4-byte node of the
+    // plain products never did; eager calls were right with either) - a kernel node orders like the kernels around it
+    const int words = (int)(tail_bytes / sizeof(int));
+    hipLaunchKernelGGL(sp_tn_repair_clear_kernel, dim3(1), dim3(256), 0, s, trip_word, words);
+    TFGNN_LAUNCH_CHECK();
+  }
   ++g_repair_armed_products;
   return TFGNN_OK;
 }
 
 int tn_repair_enqueue(TnRepairArgs a, hipStream_t s) {
   a.repaired = repair_counter(false);
-  TFGNN_REQUIRE(a.repaired && a.trip && a.N % RP_TILE == 0 && a.M % 4 == 0 && a.splits >= 1 && a.splits <= 65535,
+  TFGNN_REQUIRE(a.repaired && a.trip && a.N % RP_TILE == 0 && a.M % 4 == 0 && a.splits >= 1 &&
+                    a.splits <= (a.split_table ? kTnRepairGroupedMaxRanges : 65535) && (!a.split_table || a.ref_per_split),
                 "tfgnn_sp_gemm_tn: repair pass cannot run (no counter, or a shape the product itself rejects)");
   const int64_t tiles = ceil_div(a.M, RP_TILE) * (a.N / RP_TILE);
   hipLaunchKernelGGL(sp_tn_repair_kernel, dim3((unsigned)tiles, (unsigned)a.splits), dim3(256), 0, s, a);

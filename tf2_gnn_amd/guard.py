@@ -155,11 +155,12 @@ def f16x2_guard_tripped_sync() -> bool:
 
 def set_guard_repair(on: bool) -> bool:
     """Arm (True) or disarm the in-stream repair of tripped split-operand weight-gradient products (include/tfgnn.h,
-    tfgnn_sp_guard_repair) -> the previous state.  While armed, ``sp_gemm_tn`` (both forms) and the product inside
-    ``mp_backward`` recompute a product whose spread guard trips in fp32 from the SP16 operands, on the stream and before
-    their reduce pass: the pass's own gradients are right, the host flag stays down, the mode stays ``f16x2`` - also in a
-    replayed ``capture.CapturedStep`` (arm before building it; arming allocates, so not while capturing).  Off by default
-    (environment TFGNN_GUARD_REPAIR=1 arms at start).  ``sp_gemm_tn_grouped`` is not covered."""
+    tfgnn_sp_guard_repair) -> the previous state.  While armed, ``sp_gemm_tn`` (both forms), the product inside
+    ``mp_backward`` and ``sp_gemm_tn_grouped`` recompute what their spread guard reports in fp32 from the SP16 operands, on
+    the stream and before their reduce pass - the plain products whole, the grouped product the K ranges that tripped: the
+    pass's own gradients are right, the host flag stays down, the mode stays ``f16x2`` and no stack's ``GuardPolicy`` takes a
+    stage - also in a replayed ``capture.CapturedStep`` (arm before building it; arming allocates, so not while capturing).
+    Off by default (environment TFGNN_GUARD_REPAIR=1 arms at start)."""
     if capturing():
         raise RuntimeError("tf2_gnn_amd: set_guard_repair is not legal while the stream is capturing (arm before the capture)")
     rc = _lib.load().tfgnn_sp_guard_repair(1 if on else 0)

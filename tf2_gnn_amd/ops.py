@@ -1556,9 +1556,10 @@ def sp_gemm_tn_grouped(a: SplitOperand, b: SplitOperand, groups: RowGroups, out:
     tab = groups.tn_tables()
     if tab[2] > TN_GROUPED_MAX_RANGES:
         raise ValueError(f"sp_gemm_tn_grouped: {tab[2]} K ranges, at most {TN_GROUPED_MAX_RANGES} per launch (callers take another route)")
-    nblk = a.cols // a.scale_block
-    ws_bytes = ((nblk * 512 * 4 + 255) & ~255) + tab[2] * ((M + 127) // 128 * 128) * N * 4 + 256
-    ws = _workspace(a.data.device, ws_bytes)
+    # (with the in-stream repair armed - set_guard_repair - the size includes the tail of the per-range trip words)
+    # (0 for a shape the product rejects: the call below says which)
+    ws_bytes = lib.tfgnn_sp_gemm_tn_grouped_workspace_bytes(M, N, a.cols, a.scale_block, tab[2])
+    ws = _workspace(a.data.device, ws_bytes + 256)
     off = (-ws.data_ptr()) % 256
     sr, sc = (1, M) if transposed else (N, 1)
     _lib.check(lib.tfgnn_sp_gemm_tn_grouped(M, N, _ptr(a.data), a.data.stride(0), _ptr(a.inv_scale), a.cols, a.scale_block, _ptr(b.data),
