@@ -1629,6 +1629,182 @@ static int* sp_spread_flag_device() {
   return g_spread_dev;
 }
 
+// ---- host side of the weight-gradient (TN) product: ONE workspace layout, ONE description of a launch, ONE function that enqueues
+// it - for tfgnn_sp_gemm_tn, tfgnn_sp_gemm_tn_wide (and through them tfgnn_mp_backward) and tfgnn_sp_gemm_tn_grouped ------------
+// K ranges one launch takes: the room for the reference scales of (K range, block), and (tn_repair.hpp) for the trip words of
+// the armed grouped product
+constexpr int kSpTnMaxRanges = 512;
+static_assert(kSpTnMaxRanges == kTnRepairGroupedMaxRanges, "the repair tail holds one trip word per K range of a launch");
+
+// Byte offsets into a product's workspace (256-byte aligned; include/tfgnn.h documents the totals):
+//   [factor table a_nblk x kpad fp16, from 0][reference scales, from `ref`][split-K slabs ranges x Mp x N fp32][repair tail]
+// reference scales: where the separate factor pass may run (`factor_pass`: the plain products), its one scale per block and the
+// a_nblk x SP_TN_MAXCHUNKS slice maxima of its two-stage form; then, from `ref_split`, [kSpTnMaxRanges][a_nblk] for the factors
+// computed in the kernel.  Without `factor_pass` (the grouped product) there is no table and `ref` = `ref_split` = 0.
+struct TnLayout {
+  size_t ref, ref_split, slabs, tail, total;
+  int64_t f_ld;  // row pitch of the factor table (K rounded up to 16), 0 without one
+};
+static TnLayout sp_tn_layout(int64_t Mp, int64_t N, int64_t nblk, int64_t kpad, bool factor_pass, int64_t ranges, size_t tail_bytes) {
+  TnLayout l;
+  const int pass_floats = factor_pass ? 1 + SP_TN_MAXCHUNKS : 0;  // per block
+  l.ref = factor_pass ? ((size_t)nblk * kpad * 2 + 255) & ~(size_t)255 : 0;
+  l.ref_split = l.ref + (size_t)nblk * pass_floats * 4;
+  l.slabs = l.ref + (((size_t)nblk * (pass_floats + kSpTnMaxRanges) * 4 + 255) & ~(size_t)255);
+  l.tail = l.slabs + (size_t)ranges * (size_t)Mp * (size_t)N * 4;  // a multiple of 256
+  l.total = l.tail + tail_bytes;
+  l.f_ld = factor_pass ? kpad : 0;
+  return l;
+}
+
+// Where the per-k factors of a product come from.  FactorPass: sp_tn_factors_kernel's table, one reference scale per block
+// (TFGNN_TN_FIK=0, or K ranges too long for the others); OneFactor: every workgroup normalises its own K range, one combined
+// factor on A's fragments; TwoFactor: ... one factor per operand (tfgnn_sp_gemm_tn_wide, tfgnn_sp_gemm_tn_grouped)
+enum class TnForm { FactorPass, OneFactor, TwoFactor };
+
+template <int TNW, bool FIK, bool BSC>
+static void launch_sp_tn_form(const SpTnArgs& g, dim3 grid, hipStream_t s) {
+  constexpr int lds = SpGeoTN<TNW, FIK, BSC>::LDS_BYTES;
+  [[maybe_unused]] static const hipError_t attr_set =  // once per kernel
+      hipFuncSetAttribute((const void*)gemm_sp_tn_kernel<TNW, FIK, BSC>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  hipLaunchKernelGGL((gemm_sp_tn_kernel<TNW, FIK, BSC>), grid, dim3(SP_NT), lds, s, g);
+}
+
+template <int TNW>
+static void launch_sp_tn(TnForm form, const SpTnArgs& g, dim3 grid, hipStream_t s) {
+  count_launch(TFGNN_KFAM_SP_TN);
+  if (form == TnForm::TwoFactor) launch_sp_tn_form<TNW, true, true>(g, grid, s);
+  else if (form == TnForm::OneFactor) launch_sp_tn_form<TNW, true, false>(g, grid, s);
+  else launch_sp_tn_form<TNW, false, false>(g, grid, s);
+}
+
+// One TN product as its entry point has validated it
+struct TnLaunch {
+  int64_t M, N, K;       // the product's own M (the kernels pad it to whole row tiles of 128); K = 0 with a split_table
+  const uint8_t *A, *B;  // SP16, rows = k; advanced to the product's first columns
+  int64_t lda, ldb;
+  const float *inv_a, *inv_b;
+  int a_sb, a_nblk;  // columns per scale block of A, scale blocks per row
+  int64_t a_col0;
+  // K ranges: `splits` ranges of k_chunk rows, or - split_table - the rows [table[2 z], + table[2 z + 1]) with k_chunk their bound
+  int splits;
+  int64_t k_chunk;
+  const int32_t* split_table;
+  TnForm form;
+  uint8_t* ws;
+  TnLayout lay;
+  // the guard reports into the library-wide flag; armed (tn_repair.hpp), into the workspace tail: one trip word per product
+  // (trip_stride 0), or one per K range (1: the grouped product, whose repair acts range by range)
+  bool repair;
+  int trip_stride;
+  // reduce pass: C[(m / group_rows) * stride_group + (m % group_rows) * stride_row + n * stride_col] (+)= sum over the ranges;
+  // group_split_offsets: group g's ranges are [offsets[g], offsets[g + 1]) and its C starts g * c_group_stride further on
+  float* C;
+  int64_t group_rows, stride_group, stride_row, stride_col;
+  int accumulate;
+  int num_groups;
+  const int32_t* group_split_offsets;
+  int64_t c_group_stride;
+};
+
+// repair begin (armed) - factor pass (that form) - product - repair (armed) - reduce pass, all on s.  Without a K range (a
+// grouping whose groups are all empty) only the reduce pass runs: it writes the zeros.
+static int sp_tn_enqueue(const TnLaunch& t, hipStream_t s) {
+  const int bn = sp_tile_width(t.N);
+  const int64_t Mp = ceil_div(t.M, SP_BM) * SP_BM;
+  const bool armed = t.repair && t.splits > 0, per_split = t.form != TnForm::FactorPass;
+  float* ref = (float*)(t.ws + t.lay.ref);
+  float* ref_split = (float*)(t.ws + t.lay.ref_split);  // [splits][a_nblk]
+  int* guard_word = sp_spread_flag_device();
+  if (armed) {  // zeroed on the stream in front of the product; sp_tn_repair_kernel, between the product and the reduce pass, acts on it
+    guard_word = (int*)(t.ws + t.lay.tail);
+    if (int rc = tn_repair_begin(guard_word, t.trip_stride ? kTnRepairGroupedTailBytes : sizeof(int), s)) return rc;
+  }
+  SpTnArgs g{};
+  g.M = Mp; g.N = t.N; g.K = t.K;
+  g.A = t.A; g.lda = t.lda;
+  g.B = t.B; g.ldb = t.ldb;
+  g.F = t.lay.f_ld ? (const _Float16*)t.ws : nullptr; g.f_ld = t.lay.f_ld;  // (handed to the kernels of every plain product)
+  g.a_sb = t.a_sb; g.a_col0 = t.a_col0; g.a_nblk = t.a_nblk;
+  g.inv_a = t.inv_a; g.inv_b = t.inv_b; g.ref_split = ref_split; g.spread_flag = guard_word;
+  g.trip_stride = t.trip_stride;
+  g.partial = (float*)(t.ws + t.lay.slabs);
+  g.k_chunk = t.k_chunk;
+  g.split_table = t.split_table;
+  g.n_tiles = (unsigned)(t.N / bn);
+  g.tiles = (unsigned)((Mp / SP_BM) * g.n_tiles);
+  g.splits = (unsigned)t.splits;
+  g.per_xcd = (g.tiles * g.splits + 7) / 8;
+  if (t.form == TnForm::FactorPass) {
+    const int fch = sp_tn_fchunks(t.K);
+    float* slice_max = nullptr;
+    if (fch > SP_TN_FCHUNKS) {  // two stages; the slice maxima live behind the reference scales (a_nblk * SP_TN_MAXCHUNKS floats)
+      slice_max = ref + t.a_nblk;
+      hipLaunchKernelGGL(sp_tn_slice_max_kernel, dim3((unsigned)t.a_nblk * fch), dim3(1024), 0, s, t.inv_a, (int64_t)t.a_nblk, t.inv_b,
+                         (int64_t)1, t.K, slice_max, fch);
+    }
+    hipLaunchKernelGGL(sp_tn_factors_kernel, dim3((unsigned)t.a_nblk * fch), dim3(1024), 0, s, t.inv_a, (int64_t)t.a_nblk, t.inv_b,
+                       (int64_t)1, t.K, (_Float16*)t.ws, t.lay.f_ld, ref, guard_word, fch, (const float*)slice_max);
+    TFGNN_LAUNCH_CHECK();
+  }
+  if (t.splits > 0) {
+    const dim3 grid(8 * g.per_xcd);
+    if (bn == 320) launch_sp_tn<5>(t.form, g, grid, s);
+    else if (bn == 256) launch_sp_tn<4>(t.form, g, grid, s);
+    else launch_sp_tn<2>(t.form, g, grid, s);
+    TFGNN_LAUNCH_CHECK();
+  }
+  if (armed) {
+    TnRepairArgs rp{};
+    rp.M = t.M; rp.N = t.N; rp.K = t.K; rp.A = t.A; rp.lda = t.lda; rp.B = t.B; rp.ldb = t.ldb;
+    rp.inv_a = t.inv_a; rp.inv_b = t.inv_b; rp.a_sb = t.a_sb; rp.a_col0 = t.a_col0; rp.a_nblk = t.a_nblk;
+    rp.partial = g.partial; rp.slab = Mp * t.N; rp.splits = t.splits;
+    rp.k_chunk = t.split_table ? 0 : t.k_chunk; rp.split_table = t.split_table;  // (the table's ranges carry their own lengths)
+    rp.ref = per_split ? ref_split : ref; rp.ref_per_split = per_split ? 1 : 0; rp.trip = guard_word;
+    if (int rc = tn_repair_enqueue(rp, s)) return rc;
+  }
+  TnReduceArgs ra{};
+  ra.partial = g.partial; ra.M = t.M; ra.N = t.N; ra.ref = per_split ? ref_split : ref; ra.a_col0 = t.a_col0; ra.a_sb = t.a_sb;
+  ra.ref_ld = per_split ? t.a_nblk : 0;
+  ra.splits = t.group_split_offsets ? 0 : t.splits;  // (per group: every group's workgroups take theirs from the offsets)
+  ra.C = t.C; ra.group_rows = t.group_rows; ra.stride_group = t.stride_group; ra.stride_row = t.stride_row; ra.stride_col = t.stride_col;
+  ra.accumulate = t.accumulate; ra.slab = Mp * t.N;
+  const int64_t rblocks = ceil_div(t.M * t.N, 256);
+  if (t.group_split_offsets) {
+    hipLaunchKernelGGL(sp_tn_reduce_grouped_kernel, dim3((unsigned)std::min<int64_t>(rblocks, 512), (unsigned)t.num_groups), dim3(256), 0, s,
+                       ra, t.group_split_offsets, t.c_group_stride);
+  } else {
+    hipLaunchKernelGGL(sp_tn_reduce_kernel, dim3((unsigned)std::min<int64_t>(rblocks, 2048)), dim3(256), 0, s, ra);
+  }
+  TFGNN_LAUNCH_CHECK();
+  return TFGNN_OK;
+}
+
+// The operand checks the entry points share, reported under the name `who`; first columns of 0 for a product over whole operands
+static int sp_tn_check_operands(const char* who, int64_t M, int64_t N, const void* d_A_sp, int64_t lda_bytes, int64_t a_first_col,
+                                int64_t a_total_cols, int a_scale_block, const void* d_B_sp, int64_t ldb_bytes, int64_t b_first_col,
+                                bool column_ranges) {
+  if (!sp_tile_width(N) || M % 16 || a_scale_block < 32) {
+    set_error("%s: M = %lld must be a multiple of 16, N = %lld of 128, scale blocks of A >= 32 columns", who, (long long)M, (long long)N);
+    return TFGNN_ERR_UNSUPPORTED;
+  }
+  // row tiles are 128 columns of A: the last one may run past M (it reads the neighbouring bytes of the operand rows,
+  // zeros past the operand's end; its surplus result rows stay in the workspace)
+  TFGNN_REQUIRE(lda_bytes % 64 == 0 && ldb_bytes % 64 == 0 && (uintptr_t)d_A_sp % 64 == 0 && (uintptr_t)d_B_sp % 64 == 0 &&
+                    a_first_col % 16 == 0 && b_first_col % 16 == 0 && a_first_col >= 0 && b_first_col >= 0 &&
+                    lda_bytes >= (a_first_col + M) * 4 && ldb_bytes >= (b_first_col + N) * 4 && a_total_cols >= a_first_col + M &&
+                    a_total_cols % a_scale_block == 0,
+                "%s: SP16 operands must be 64-byte aligned%s", who,
+                column_ranges ? ", first columns multiples of 16, rows wide enough" : " with rows wide enough");
+  return TFGNN_OK;
+}
+
+static int sp_tn_check_workspace(const char* who, const void* d_workspace, size_t workspace_bytes, size_t need) {
+  TFGNN_REQUIRE(d_workspace && workspace_bytes >= need && (uintptr_t)d_workspace % 256 == 0,
+                "%s: workspace too small or unaligned (need %zu bytes)", who, need);
+  return TFGNN_OK;
+}
+
 }  // namespace tfgnn
 
 using namespace tfgnn;
@@ -1879,158 +2055,69 @@ int tfgnn_sp_gemm_nt_grouped(int64_t M, int64_t N, int64_t K, const void* d_A_sp
                          b_group_stride_bytes, b_scale_group_stride);
 }
 
+// K ranges of a plain product: what the output tiles leave of one round of workgroups; the two-factor form (wide) takes ranges
+// of at most SP_TN_BSC_MAX_CHUNK rows
+static int64_t sp_tn_plain_ranges(int64_t Mp, int64_t N, int64_t K, int bn, bool wide) {
+  const int64_t splits = sp_tn_splits(Mp, N, K, bn);
+  return wide ? std::max<int64_t>(splits, ceil_div(K, SP_TN_BSC_MAX_CHUNK)) : splits;
+}
+
+// what a call needs NOW: with repair armed (tn_repair.hpp) the trip word's tail follows the slabs
 static size_t sp_gemm_tn_ws_bytes(int64_t M, int64_t N, int64_t K, int64_t a_total_cols, int a_scale_block, bool wide) {
   const int bn = sp_tile_width(N);
   if (!bn || M <= 0 || a_scale_block <= 0) return 0;
   const int64_t Mp = ceil_div(M, SP_BM) * SP_BM;
-  const int64_t nblk = ceil_div(a_total_cols, a_scale_block), kpad = (K + 15) & ~15ll;
-  const size_t factors = (((size_t)nblk * kpad * 2 + 255) & ~(size_t)255) + (((size_t)nblk * (1 + SP_TN_MAXCHUNKS + 512) * 4 + 255) & ~(size_t)255);
-  int64_t splits = sp_tn_splits(Mp, N, K, bn);
-  if (wide) splits = std::max<int64_t>(splits, ceil_div(K, SP_TN_BSC_MAX_CHUNK));
-  return factors + (size_t)splits * (size_t)Mp * (size_t)N * 4;
-}
-// what a call needs NOW: with repair armed (tn_repair.hpp) the trip word's tail follows the slabs
-static size_t sp_gemm_tn_ws_need(int64_t M, int64_t N, int64_t K, int64_t a_total_cols, int a_scale_block, bool wide, bool repair) {
-  const size_t base = sp_gemm_tn_ws_bytes(M, N, K, a_total_cols, a_scale_block, wide);
-  return base && repair ? base + kTnRepairTailBytes : base;
+  return sp_tn_layout(Mp, N, ceil_div(a_total_cols, a_scale_block), (K + 15) & ~15ll, true, sp_tn_plain_ranges(Mp, N, K, bn, wide),
+                      tn_repair_armed() ? kTnRepairTailBytes : 0).total;
 }
 
 size_t tfgnn_sp_gemm_tn_workspace_bytes(int64_t M, int64_t N, int64_t K, int64_t a_total_cols, int a_scale_block) {
-  return sp_gemm_tn_ws_need(M, N, K, a_total_cols, a_scale_block, false, tn_repair_armed());
+  return sp_gemm_tn_ws_bytes(M, N, K, a_total_cols, a_scale_block, false);
 }
 
 size_t tfgnn_sp_gemm_tn_wide_workspace_bytes(int64_t M, int64_t N, int64_t K, int64_t a_total_cols, int a_scale_block) {
-  return sp_gemm_tn_ws_need(M, N, K, a_total_cols, a_scale_block, true, tn_repair_armed());
+  return sp_gemm_tn_ws_bytes(M, N, K, a_total_cols, a_scale_block, true);
 }
 
-static int sp_gemm_tn_impl(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, int64_t a_first_col,
-                           const float* d_a_inv_scale, int64_t a_total_cols, int a_scale_block, const void* d_B_sp,
-                           int64_t ldb_bytes, int64_t b_first_col, const float* d_b_inv_scale, float* d_C, int64_t group_rows,
-                           int64_t stride_group, int64_t stride_row, int64_t stride_col, int accumulate, void* d_workspace,
-                           size_t workspace_bytes, void* stream, bool wide = false) {
+static int sp_gemm_tn_plain(bool wide, int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, int64_t a_first_col,
+                            const float* d_a_inv_scale, int64_t a_total_cols, int a_scale_block, const void* d_B_sp,
+                            int64_t ldb_bytes, int64_t b_first_col, const float* d_b_inv_scale, float* d_C, int64_t group_rows,
+                            int64_t stride_group, int64_t stride_row, int64_t stride_col, int accumulate, void* d_workspace,
+                            size_t workspace_bytes, void* stream) {
+  // (the two-factor form reports what it shares with the one-factor form under the latter's name)
   TFGNN_REQUIRE(d_A_sp && d_B_sp && d_C && d_a_inv_scale, "tfgnn_sp_gemm_tn: null pointer");
   TFGNN_REQUIRE(M > 0 && N > 0 && K > 0, "tfgnn_sp_gemm_tn: empty product");
-  const int bn = sp_tile_width(N);
-  if (!bn || M % 16 || a_scale_block < 32) {
-    set_error("tfgnn_sp_gemm_tn: M = %lld must be a multiple of 16, N = %lld of 128, scale blocks of A >= 32 columns",
-              (long long)M, (long long)N);
-    return TFGNN_ERR_UNSUPPORTED;
-  }
-  // row tiles are 128 columns of A: the last one may run past M (it reads the neighbouring bytes of the operand rows,
-  // zeros past the operand's end; its surplus result rows stay in the workspace)
-  const int64_t Mp = ceil_div(M, SP_BM) * SP_BM;
-  TFGNN_REQUIRE(lda_bytes % 64 == 0 && ldb_bytes % 64 == 0 && (uintptr_t)d_A_sp % 64 == 0 && (uintptr_t)d_B_sp % 64 == 0 &&
-                    a_first_col % 16 == 0 && b_first_col % 16 == 0 && a_first_col >= 0 && b_first_col >= 0 &&
-                    lda_bytes >= (a_first_col + M) * 4 && ldb_bytes >= (b_first_col + N) * 4 && a_total_cols >= a_first_col + M &&
-                    a_total_cols % a_scale_block == 0,
-                "tfgnn_sp_gemm_tn: SP16 operands must be 64-byte aligned, first columns multiples of 16, rows wide enough");
+  if (int rc = sp_tn_check_operands("tfgnn_sp_gemm_tn", M, N, d_A_sp, lda_bytes, a_first_col, a_total_cols, a_scale_block, d_B_sp,
+                                    ldb_bytes, b_first_col, true))
+    return rc;
   TFGNN_REQUIRE(group_rows > 0, "tfgnn_sp_gemm_tn: group_rows must be positive");
   TFGNN_REQUIRE(a_scale_block >= 48 || a_first_col % a_scale_block == 0,
                 "tfgnn_sp_gemm_tn: 32-column scale blocks need a block-aligned first column (at most 4 blocks per 128-column tile)");
-  int splits = sp_tn_splits(Mp, N, K, bn);
-  if (wide) {  // two-factor form: factors in the kernel, K ranges of at most SP_TN_BSC_MAX_CHUNK rows
-    splits = (int)std::max<int64_t>(splits, ceil_div(K, SP_TN_BSC_MAX_CHUNK));
-    TFGNN_REQUIRE(splits <= 512 && d_b_inv_scale,
-                  "tfgnn_sp_gemm_tn_wide: K too large (more than 512 ranges of 2016 rows), or no scales of B");
-  }
+  const int64_t Mp = ceil_div(M, SP_BM) * SP_BM;
+  const int64_t splits = sp_tn_plain_ranges(Mp, N, K, sp_tile_width(N), wide);
+  TFGNN_REQUIRE(!wide || (splits <= kSpTnMaxRanges && d_b_inv_scale),
+                "tfgnn_sp_gemm_tn_wide: K too large (more than 512 ranges of 2016 rows), or no scales of B");
   const int64_t nblk = a_total_cols / a_scale_block, kpad = (K + 15) & ~15ll;
-  const size_t f_bytes = ((size_t)nblk * kpad * 2 + 255) & ~(size_t)255, r_bytes = ((size_t)nblk * (1 + SP_TN_MAXCHUNKS + 512) * 4 + 255) & ~(size_t)255;
-  // repair armed (tfgnn_sp_guard_repair): the guard reports into a word of this call's own workspace - zeroed by a memset node
-  // in front of the product - and sp_tn_repair_kernel, between the product and the reduce pass, acts on it in stream order
-  const bool repair = tn_repair_armed();
-  const size_t slabs_end = f_bytes + r_bytes + (size_t)splits * (size_t)Mp * (size_t)N * 4;  // a multiple of 256
-  const size_t need = sp_gemm_tn_ws_need(M, N, K, a_total_cols, a_scale_block, wide, repair);
-  TFGNN_REQUIRE(d_workspace && need >= slabs_end && workspace_bytes >= need && (uintptr_t)d_workspace % 256 == 0,
-                "tfgnn_sp_gemm_tn: workspace too small or unaligned (need %zu bytes)", need);
-  hipStream_t s = (hipStream_t)stream;
-  int* guard_word = sp_spread_flag_device();
-  if (repair) {
-    guard_word = (int*)((uint8_t*)d_workspace + slabs_end);
-    if (int rc = tn_repair_begin(guard_word, sizeof(int), s)) return rc;
-  }
-  _Float16* F = (_Float16*)d_workspace;
-  float* ref = (float*)((uint8_t*)d_workspace + f_bytes);
+  TnLaunch t{};
+  t.repair = tn_repair_armed();
+  t.lay = sp_tn_layout(Mp, N, nblk, kpad, true, splits, t.repair ? kTnRepairTailBytes : 0);
+  if (int rc = sp_tn_check_workspace("tfgnn_sp_gemm_tn", d_workspace, workspace_bytes, t.lay.total)) return rc;
+  t.ws = (uint8_t*)d_workspace;
+  t.M = M; t.N = N; t.K = K;
+  t.A = (const uint8_t*)d_A_sp + a_first_col * 4; t.lda = lda_bytes;
+  t.B = (const uint8_t*)d_B_sp + b_first_col * 4; t.ldb = ldb_bytes;
+  t.inv_a = d_a_inv_scale; t.inv_b = d_b_inv_scale; t.a_sb = a_scale_block; t.a_col0 = a_first_col; t.a_nblk = (int)nblk;
+  t.k_chunk = (((K + 15) / 16 + splits - 1) / splits) * 16;
+  t.splits = (int)ceil_div(K, t.k_chunk);  // rounding the chunk up to whole steps can leave the last splits empty
   // factors in the kernel (FIK): every workgroup normalises its own K range - no factor pass at all
   static const bool fik_env = [] { const char* e = getenv("TFGNN_TN_FIK"); return !e || atoi(e) != 0; }();
-  const int64_t steps_all = (K + 15) / 16;
-  const int64_t k_chunk_all = ((steps_all + splits - 1) / splits) * 16;
-  const bool fik = wide || (fik_env && k_chunk_all <= SP_TN_FIK_MAX_CHUNK && splits <= 512);
-  TFGNN_REQUIRE(!wide || k_chunk_all <= SP_TN_BSC_MAX_CHUNK, "tfgnn_sp_gemm_tn_wide: K range too long");
-  float* ref_split = ref + nblk * (1 + SP_TN_MAXCHUNKS);  // [splits][nblk]
-  if (!fik) {
-    const int fch = sp_tn_fchunks(K);
-    float* slice_max = nullptr;
-    if (fch > SP_TN_FCHUNKS) {  // two stages; the slice maxima live behind the reference scales (r_bytes reserves nblk * SP_TN_MAXCHUNKS floats for them)
-      slice_max = ref + nblk;
-      hipLaunchKernelGGL(sp_tn_slice_max_kernel, dim3((unsigned)nblk * fch), dim3(1024), 0, s, d_a_inv_scale, nblk, d_b_inv_scale, (int64_t)1, K,
-                         slice_max, fch);
-    }
-    hipLaunchKernelGGL(sp_tn_factors_kernel, dim3((unsigned)nblk * fch), dim3(1024), 0, s, d_a_inv_scale, nblk, d_b_inv_scale, (int64_t)1, K, F,
-                       kpad, ref, guard_word, fch, (const float*)slice_max);
-    TFGNN_LAUNCH_CHECK();
-  }
-  SpTnArgs g{};
-  g.M = Mp; g.N = N; g.K = K;
-  g.A = (const uint8_t*)d_A_sp + a_first_col * 4; g.lda = lda_bytes;
-  g.B = (const uint8_t*)d_B_sp + b_first_col * 4; g.ldb = ldb_bytes;
-  g.F = F; g.f_ld = kpad; g.a_sb = a_scale_block; g.a_col0 = a_first_col; g.a_nblk = (int)nblk;
-  g.inv_a = d_a_inv_scale; g.inv_b = d_b_inv_scale; g.ref_split = ref_split; g.spread_flag = guard_word;
-  g.partial = (float*)((uint8_t*)d_workspace + f_bytes + r_bytes);
-  const int64_t steps = (K + 15) / 16;
-  g.k_chunk = ((steps + splits - 1) / splits) * 16;
-  const int splits_used = (int)ceil_div(K, g.k_chunk);  // rounding the chunk up to whole steps can leave the last splits empty
-  g.n_tiles = (unsigned)(N / bn);
-  TFGNN_REQUIRE(g.k_chunk * std::max(lda_bytes, ldb_bytes) < (1ll << 31) && nblk * kpad * 2 < (1ll << 31), "tfgnn_sp_gemm_tn: K chunk too large");
-  g.tiles = (unsigned)((Mp / SP_BM) * g.n_tiles);
-  g.splits = (unsigned)splits_used;
-  g.per_xcd = (g.tiles * g.splits + 7) / 8;
-  dim3 grid(8 * g.per_xcd);
-#define SP_LAUNCH_TN(T, FK, ...)                                                                                   \
-  do {                                                                                                             \
-    static bool attr_set = false;                                                                                  \
-    using TnGeo = SpGeoTN<T, FK, ##__VA_ARGS__>;                                                                   \
-    constexpr int tn_lds = TnGeo::LDS_BYTES;                                                                       \
-    if (!attr_set) {                                                                                               \
-      (void)hipFuncSetAttribute((const void*)gemm_sp_tn_kernel<T, FK, ##__VA_ARGS__>,                              \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, tn_lds);                               \
-      attr_set = true;                                                                                             \
-    }                                                                                                              \
-    hipLaunchKernelGGL((gemm_sp_tn_kernel<T, FK, ##__VA_ARGS__>), grid, dim3(SP_NT), tn_lds, s, g);                \
-  } while (0)
-  count_launch(TFGNN_KFAM_SP_TN);
-  if (wide) {
-    if (bn == 320) SP_LAUNCH_TN(5, true, true);
-    else if (bn == 256) SP_LAUNCH_TN(4, true, true);
-    else SP_LAUNCH_TN(2, true, true);
-  } else if (fik) {
-    if (bn == 320) SP_LAUNCH_TN(5, true);
-    else if (bn == 256) SP_LAUNCH_TN(4, true);
-    else SP_LAUNCH_TN(2, true);
-  } else {
-    if (bn == 320) SP_LAUNCH_TN(5, false);
-    else if (bn == 256) SP_LAUNCH_TN(4, false);
-    else SP_LAUNCH_TN(2, false);
-  }
-  TFGNN_LAUNCH_CHECK();
-#undef SP_LAUNCH_TN
-  if (repair) {
-    TnRepairArgs rp{};
-    rp.M = M; rp.N = N; rp.K = K; rp.A = g.A; rp.lda = lda_bytes; rp.B = g.B; rp.ldb = ldb_bytes;
-    rp.inv_a = d_a_inv_scale; rp.inv_b = d_b_inv_scale; rp.a_sb = a_scale_block; rp.a_col0 = a_first_col; rp.a_nblk = (int)nblk;
-    rp.partial = g.partial; rp.slab = Mp * N; rp.k_chunk = g.k_chunk; rp.splits = splits_used;
-    rp.ref = fik ? ref_split : ref; rp.ref_per_split = fik ? 1 : 0; rp.trip = guard_word;
-    if (int rc = tn_repair_enqueue(rp, s)) return rc;
-  }
-  const int64_t total = M * N;
-  TnReduceArgs ra{};
-  ra.partial = g.partial; ra.splits = splits_used; ra.M = M; ra.N = N; ra.ref = fik ? ref_split : ref; ra.a_col0 = a_first_col; ra.a_sb = a_scale_block;
-  ra.ref_ld = fik ? (int)nblk : 0;
-  ra.C = d_C; ra.group_rows = group_rows; ra.stride_group = stride_group; ra.stride_row = stride_row; ra.stride_col = stride_col;
-  ra.accumulate = accumulate; ra.slab = Mp * N;
-  const unsigned rblocks = (unsigned)std::min<int64_t>(ceil_div(total, 256), 2048);
-  hipLaunchKernelGGL(sp_tn_reduce_kernel, dim3(rblocks), dim3(256), 0, s, ra);
-  TFGNN_LAUNCH_CHECK();
-  return TFGNN_OK;
+  t.form = wide ? TnForm::TwoFactor
+                : (fik_env && t.k_chunk <= SP_TN_FIK_MAX_CHUNK && splits <= kSpTnMaxRanges ? TnForm::OneFactor : TnForm::FactorPass);
+  TFGNN_REQUIRE(!wide || t.k_chunk <= SP_TN_BSC_MAX_CHUNK, "tfgnn_sp_gemm_tn_wide: K range too long");
+  TFGNN_REQUIRE(t.k_chunk * std::max(lda_bytes, ldb_bytes) < (1ll << 31) && nblk * kpad * 2 < (1ll << 31), "tfgnn_sp_gemm_tn: K chunk too large");
+  t.C = d_C; t.group_rows = group_rows; t.stride_group = stride_group; t.stride_row = stride_row; t.stride_col = stride_col;
+  t.accumulate = accumulate;
+  return sp_tn_enqueue(t, (hipStream_t)stream);
 }
 
 int tfgnn_sp_gemm_tn(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, int64_t a_first_col,
@@ -2038,9 +2125,9 @@ int tfgnn_sp_gemm_tn(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_
                      int64_t ldb_bytes, int64_t b_first_col, const float* d_b_inv_scale, float* d_C, int64_t group_rows,
                      int64_t stride_group, int64_t stride_row, int64_t stride_col, int accumulate, void* d_workspace,
                      size_t workspace_bytes, void* stream) {
-  return sp_gemm_tn_impl(M, N, K, d_A_sp, lda_bytes, a_first_col, d_a_inv_scale, a_total_cols, a_scale_block, d_B_sp, ldb_bytes,
-                         b_first_col, d_b_inv_scale, d_C, group_rows, stride_group, stride_row, stride_col, accumulate, d_workspace,
-                         workspace_bytes, stream);
+  return sp_gemm_tn_plain(false, M, N, K, d_A_sp, lda_bytes, a_first_col, d_a_inv_scale, a_total_cols, a_scale_block, d_B_sp, ldb_bytes,
+                          b_first_col, d_b_inv_scale, d_C, group_rows, stride_group, stride_row, stride_col, accumulate, d_workspace,
+                          workspace_bytes, stream);
 }
 
 int tfgnn_sp_gemm_tn_wide(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, int64_t a_first_col,
@@ -2048,18 +2135,19 @@ int tfgnn_sp_gemm_tn_wide(int64_t M, int64_t N, int64_t K, const void* d_A_sp, i
                           int64_t ldb_bytes, int64_t b_first_col, const float* d_b_inv_scale, float* d_C, int64_t group_rows,
                           int64_t stride_group, int64_t stride_row, int64_t stride_col, int accumulate, void* d_workspace,
                           size_t workspace_bytes, void* stream) {
-  return sp_gemm_tn_impl(M, N, K, d_A_sp, lda_bytes, a_first_col, d_a_inv_scale, a_total_cols, a_scale_block, d_B_sp, ldb_bytes,
-                         b_first_col, d_b_inv_scale, d_C, group_rows, stride_group, stride_row, stride_col, accumulate, d_workspace,
-                         workspace_bytes, stream, true);
+  return sp_gemm_tn_plain(true, M, N, K, d_A_sp, lda_bytes, a_first_col, d_a_inv_scale, a_total_cols, a_scale_block, d_B_sp, ldb_bytes,
+                          b_first_col, d_b_inv_scale, d_C, group_rows, stride_group, stride_row, stride_col, accumulate, d_workspace,
+                          workspace_bytes, stream);
+}
+
+// (with repair armed the tail of the trip words, one per K range, follows the slabs)
+static TnLayout sp_tn_grouped_layout(int64_t M, int64_t N, int64_t nblk, int num_splits) {
+  return sp_tn_layout(ceil_div(M, SP_BM) * SP_BM, N, nblk, 0, false, num_splits, tn_repair_armed() ? kTnRepairGroupedTailBytes : 0);
 }
 
 size_t tfgnn_sp_gemm_tn_grouped_workspace_bytes(int64_t M, int64_t N, int64_t a_total_cols, int a_scale_block, int num_splits) {
   if (!sp_tile_width(N) || M <= 0 || a_total_cols <= 0 || a_scale_block <= 0 || num_splits < 0) return 0;
-  const int64_t Mp = ceil_div(M, SP_BM) * SP_BM;
-  const int64_t nblk = ceil_div(a_total_cols, a_scale_block);
-  const size_t base = (((size_t)nblk * 512 * 4 + 255) & ~(size_t)255) + (size_t)num_splits * (size_t)Mp * (size_t)N * 4;
-  // what a call needs NOW: with repair armed (tn_repair.hpp) the trip words' tail follows the slabs
-  return tn_repair_armed() ? base + kTnRepairGroupedTailBytes : base;
+  return sp_tn_grouped_layout(M, N, ceil_div(a_total_cols, a_scale_block), num_splits).total;
 }
 
 int tfgnn_sp_gemm_tn_grouped(int64_t M, int64_t N, const void* d_A_sp, int64_t lda_bytes, const float* d_a_inv_scale,
@@ -2069,87 +2157,29 @@ int tfgnn_sp_gemm_tn_grouped(int64_t M, int64_t N, const void* d_A_sp, int64_t l
                              size_t workspace_bytes, void* stream) {
   TFGNN_REQUIRE(d_A_sp && d_B_sp && d_C && d_a_inv_scale && d_b_inv_scale && d_group_split_offsets && d_split_table,
                 "tfgnn_sp_gemm_tn_grouped: null pointer");
-  TFGNN_REQUIRE(M > 0 && N > 0 && num_groups >= 1 && num_splits >= 0 && num_splits <= 512, "tfgnn_sp_gemm_tn_grouped: 1.. groups, at most 512 K ranges");
-  const int bn = sp_tile_width(N);
-  if (!bn || M % 16 || a_scale_block < 32) {
-    set_error("tfgnn_sp_gemm_tn_grouped: M = %lld must be a multiple of 16, N = %lld of 128, scale blocks of A >= 32 columns",
-              (long long)M, (long long)N);
-    return TFGNN_ERR_UNSUPPORTED;
-  }
-  const int64_t Mp = ceil_div(M, SP_BM) * SP_BM;
-  TFGNN_REQUIRE(lda_bytes % 64 == 0 && ldb_bytes % 64 == 0 && (uintptr_t)d_A_sp % 64 == 0 && (uintptr_t)d_B_sp % 64 == 0 &&
-                    lda_bytes >= M * 4 && ldb_bytes >= N * 4 && a_total_cols >= M && a_total_cols % a_scale_block == 0,
-                "tfgnn_sp_gemm_tn_grouped: SP16 operands must be 64-byte aligned with rows wide enough");
+  TFGNN_REQUIRE(M > 0 && N > 0 && num_groups >= 1 && num_splits >= 0 && num_splits <= kSpTnMaxRanges,
+                "tfgnn_sp_gemm_tn_grouped: 1.. groups, at most 512 K ranges");
+  if (int rc = sp_tn_check_operands("tfgnn_sp_gemm_tn_grouped", M, N, d_A_sp, lda_bytes, 0, a_total_cols, a_scale_block, d_B_sp, ldb_bytes, 0,
+                                    false))
+    return rc;
   const int64_t nblk = a_total_cols / a_scale_block;
-  const size_t r_bytes = ((size_t)nblk * 512 * 4 + 255) & ~(size_t)255;
-  // repair armed (tfgnn_sp_guard_repair): the guard reports into the tail of this call's own workspace, one word per K range -
-  // zeroed on the stream in front of the product - and sp_tn_repair_kernel, between the product and the reduce pass, rewrites
-  // the slabs of the ranges that tripped, in stream order
-  const bool repair = tn_repair_armed();
-  const size_t slabs_end = r_bytes + (size_t)num_splits * (size_t)Mp * (size_t)N * 4;  // a multiple of 256
-  const size_t need = slabs_end + (repair ? kTnRepairGroupedTailBytes : 0);
-  TFGNN_REQUIRE(d_workspace && workspace_bytes >= need && (uintptr_t)d_workspace % 256 == 0,
-                "tfgnn_sp_gemm_tn_grouped: workspace too small or unaligned (need %zu bytes)", need);
-  hipStream_t s = (hipStream_t)stream;
-  int* guard_word = sp_spread_flag_device();
-  if (repair && num_splits > 0) {
-    guard_word = (int*)((uint8_t*)d_workspace + slabs_end);
-    if (int rc = tn_repair_begin(guard_word, kTnRepairGroupedTailBytes, s)) return rc;
-  }
-  float* ref_split = (float*)d_workspace;  // [num_splits][nblk]
-  SpTnArgs g{};
-  g.M = Mp; g.N = N; g.K = 0;
-  g.A = (const uint8_t*)d_A_sp; g.lda = lda_bytes;
-  g.B = (const uint8_t*)d_B_sp; g.ldb = ldb_bytes;
-  g.a_sb = a_scale_block; g.a_col0 = 0; g.a_nblk = (int)nblk;
-  g.inv_a = d_a_inv_scale; g.inv_b = d_b_inv_scale; g.ref_split = ref_split; g.spread_flag = guard_word;
-  g.trip_stride = repair ? 1 : 0;
-  g.partial = (float*)((uint8_t*)d_workspace + r_bytes);
-  g.k_chunk = SP_TN_BSC_MAX_CHUNK;
-  g.split_table = d_split_table;
-  g.n_tiles = (unsigned)(N / bn);
-  g.tiles = (unsigned)((Mp / SP_BM) * g.n_tiles);
-  g.splits = (unsigned)num_splits;
-  g.per_xcd = (g.tiles * g.splits + 7) / 8;
-  if (num_splits > 0) {
-    dim3 grid(8 * g.per_xcd);
-    count_launch(TFGNN_KFAM_SP_TN);
-#define SP_LAUNCH_TNG(T)                                                                                             \
-  do {                                                                                                               \
-    static bool attr_set = false;                                                                                    \
-    using TnGeo = SpGeoTN<T, true, true>;                                                                            \
-    constexpr int tn_lds = TnGeo::LDS_BYTES;                                                                         \
-    if (!attr_set) {                                                                                                 \
-      (void)hipFuncSetAttribute((const void*)gemm_sp_tn_kernel<T, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, tn_lds); \
-      attr_set = true;                                                                                               \
-    }                                                                                                                \
-    hipLaunchKernelGGL((gemm_sp_tn_kernel<T, true, true>), grid, dim3(SP_NT), tn_lds, s, g);                         \
-  } while (0)
-    if (bn == 320) SP_LAUNCH_TNG(5);
-    else if (bn == 256) SP_LAUNCH_TNG(4);
-    else SP_LAUNCH_TNG(2);
-#undef SP_LAUNCH_TNG
-    TFGNN_LAUNCH_CHECK();
-    if (repair) {
-      TnRepairArgs rp{};
-      rp.M = M; rp.N = N; rp.K = 0; rp.A = g.A; rp.lda = lda_bytes; rp.B = g.B; rp.ldb = ldb_bytes;
-      rp.inv_a = d_a_inv_scale; rp.inv_b = d_b_inv_scale; rp.a_sb = a_scale_block; rp.a_col0 = 0; rp.a_nblk = (int)nblk;
-      rp.partial = g.partial; rp.slab = Mp * N; rp.k_chunk = 0; rp.split_table = d_split_table; rp.splits = num_splits;
-      rp.ref = ref_split; rp.ref_per_split = 1; rp.trip = guard_word;
-      if (int rc = tn_repair_enqueue(rp, s)) return rc;
-    }
-  }
-  TnReduceArgs ra{};
-  ra.partial = g.partial; ra.splits = 0; ra.M = M; ra.N = N; ra.ref = ref_split; ra.a_col0 = 0; ra.a_sb = a_scale_block;
-  ra.ref_ld = (int)nblk;
-  ra.C = d_C; ra.group_rows = M; ra.stride_group = 0; ra.stride_row = stride_row; ra.stride_col = stride_col;
-  ra.accumulate = 0; ra.slab = Mp * N;
-  const unsigned rblocks = (unsigned)std::min<int64_t>(ceil_div(M * N, 256), 512);
-  hipLaunchKernelGGL(sp_tn_reduce_grouped_kernel, dim3(rblocks, (unsigned)num_groups), dim3(256), 0, s, ra, d_group_split_offsets,
-                     c_group_stride);
-  TFGNN_LAUNCH_CHECK();
-  return TFGNN_OK;
+  TnLaunch t{};
+  t.repair = tn_repair_armed();
+  t.lay = sp_tn_grouped_layout(M, N, nblk, num_splits);
+  if (int rc = sp_tn_check_workspace("tfgnn_sp_gemm_tn_grouped", d_workspace, workspace_bytes, t.lay.total)) return rc;
+  t.ws = (uint8_t*)d_workspace;
+  t.M = M; t.N = N; t.K = 0;
+  t.A = (const uint8_t*)d_A_sp; t.lda = lda_bytes;
+  t.B = (const uint8_t*)d_B_sp; t.ldb = ldb_bytes;
+  t.inv_a = d_a_inv_scale; t.inv_b = d_b_inv_scale; t.a_sb = a_scale_block; t.a_col0 = 0; t.a_nblk = (int)nblk;
+  t.splits = num_splits; t.k_chunk = SP_TN_BSC_MAX_CHUNK; t.split_table = d_split_table;
+  t.form = TnForm::TwoFactor;
+  t.trip_stride = t.repair ? 1 : 0;  // one trip word per K range: the repair rewrites the slabs of the ranges that tripped
+  t.C = d_C; t.group_rows = M; t.stride_row = stride_row; t.stride_col = stride_col;
+  t.num_groups = num_groups; t.group_split_offsets = d_group_split_offsets; t.c_group_stride = c_group_stride;
+  return sp_tn_enqueue(t, (hipStream_t)stream);
 }
+
 
 int tfgnn_sp_split_rows_job(const float* d_src, int64_t ld, int64_t seg_len, int64_t seg_stride, int64_t rows, int64_t cols,
                             int scale_block, void* d_sp, int64_t ld_sp_bytes, float* d_inv_scale,

@@ -1,7 +1,7 @@
 // In-stream repair of a split-operand weight-gradient (TN) product whose spread guard tripped (tn_repair.hip).
-// The callers are sp_gemm_tn_impl and tfgnn_sp_gemm_tn_grouped (gemm_sp.hip): with repair armed they point the product kernels'
-// guard flag at the tail of their own workspace (zeroed on the stream in front of them: tn_repair_begin) and enqueue
-// sp_tn_repair_kernel between the product and the reduce pass.
+// The one caller is sp_tn_enqueue (gemm_sp.hip), the launch path of tfgnn_sp_gemm_tn, tfgnn_sp_gemm_tn_wide and
+// tfgnn_sp_gemm_tn_grouped: with repair armed it points the product kernels' guard flag at the tail of the call's own workspace
+// (zeroed on the stream in front of them: tn_repair_begin) and enqueues sp_tn_repair_kernel between the product and the reduce pass.
 //   plain products: ONE trip word per product.  The kernel returns at once while it is 0; otherwise it rewrites every split-K
 //     slab in fp32 straight from the SP16 operands and sets the reference scales the reduce pass multiplies to 1.
 //   grouped product: one trip word per K RANGE of the split table (the product stores with a stride of one word per range).  A

@@ -342,6 +342,14 @@ def _workspace(device, nbytes: int) -> torch.Tensor:
     return ws
 
 
+def _aligned_workspace(device, nbytes: int, own: bool = False):
+    """-> (pointer, length, buffer) of ``nbytes`` or more at a 256-byte aligned address, as the TN products take their workspace:
+    in the shared buffer of this stream, or - own - in a buffer of the caller's (``buffer`` keeps it alive)."""
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device) if own else _workspace(device, nbytes + 256)
+    off = (-ws.data_ptr()) % 256
+    return ws.data_ptr() + off, ws.numel() - off, ws
+
+
 @_writes_out
 def gather_reduce(
     rowptr: torch.Tensor,
@@ -1559,12 +1567,11 @@ def sp_gemm_tn_grouped(a: SplitOperand, b: SplitOperand, groups: RowGroups, out:
     # (with the in-stream repair armed - set_guard_repair - the size includes the tail of the per-range trip words)
     # (0 for a shape the product rejects: the call below says which)
     ws_bytes = lib.tfgnn_sp_gemm_tn_grouped_workspace_bytes(M, N, a.cols, a.scale_block, tab[2])
-    ws = _workspace(a.data.device, ws_bytes + 256)
-    off = (-ws.data_ptr()) % 256
+    ws_ptr, ws_len, _ = _aligned_workspace(a.data.device, ws_bytes)
     sr, sc = (1, M) if transposed else (N, 1)
     _lib.check(lib.tfgnn_sp_gemm_tn_grouped(M, N, _ptr(a.data), a.data.stride(0), _ptr(a.inv_scale), a.cols, a.scale_block, _ptr(b.data),
                                             b.data.stride(0), _ptr(b.inv_scale), G, _ptr(tab[1]), tab[2], _ptr(tab[0]), _ptr(out), M * N, sr, sc,
-                                            ctypes.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream()))
+                                            ctypes.c_void_p(ws_ptr), ws_len, _stream()))
     return out
 
 
@@ -1795,9 +1802,7 @@ def mp_backward(graph: "Graph", d_pre: torch.Tensor, W: torch.Tensor, x_sp: Opti
         tn_bytes = lib.tfgnn_sp_gemm_tn_workspace_bytes(L * H, D, V, L * H, H)
         if tn_bytes:
             # (its own buffer: the gather's workspace above is the shared one of this stream)
-            tn_ws = torch.empty(tn_bytes + 256, dtype=torch.uint8, device=dev)
-            off = (-tn_ws.data_ptr()) % 256
-            tn_ptr, tn_len = tn_ws.data_ptr() + off, tn_ws.numel() - off
+            tn_ptr, tn_len, tn_ws = _aligned_workspace(dev, tn_bytes, own=True)
     _ensure_splitk_workspace(dev, V)
     stream = _stream()
     skip = skip or {}
@@ -1875,11 +1880,10 @@ def sp_gemm_tn(a: SplitOperand, b: SplitOperand, *, a_cols=None, b_cols=None, ou
         raise ValueError(f"out must be contiguous with {M * N} elements")
     gr, sg, sr, sc = scatter if scatter is not None else (M, 0, N, 1)
     ws_bytes = (lib.tfgnn_sp_gemm_tn_wide_workspace_bytes if wide else lib.tfgnn_sp_gemm_tn_workspace_bytes)(M, N, K, a.cols, a.scale_block)
-    ws = _workspace(a.data.device, ws_bytes + 256) if ws_bytes else None
-    ws_ptr, ws_len = None, 0
-    if ws is not None:
-        off = (-ws.data_ptr()) % 256
-        ws_ptr, ws_len = ctypes.c_void_p(ws.data_ptr() + off), ws.numel() - off
+    ws_ptr, ws_len = None, 0  # (0 bytes for a shape the product rejects: the call below says which)
+    if ws_bytes:
+        ws_ptr, ws_len, _ = _aligned_workspace(a.data.device, ws_bytes)
+        ws_ptr = ctypes.c_void_p(ws_ptr)
     _lib.check(
         (lib.tfgnn_sp_gemm_tn_wide if wide else lib.tfgnn_sp_gemm_tn)(
             M, N, K, _ptr(a.data), a.data.stride(0), a0, _ptr(a.inv_scale), a.cols, a.scale_block, _ptr(b.data),
