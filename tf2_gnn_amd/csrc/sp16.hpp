@@ -26,6 +26,14 @@ __device__ __forceinline__ float sp_scale_for_max(float mx, float* inv) {
   return __uint_as_float((unsigned)(127 + e) << 23);
 }
 
+// Running maximum of |v| for sp_scale_for_max, kept as the bits of a non-negative float: their unsigned order is the float
+// order, with a NaN above inf.  fmaxf drops a NaN: a block holding one would be scaled by its finite entries, and a block of
+// nothing but NaNs would take the all-zero marker, which the spread guard below reads as "holds nothing".
+__device__ __forceinline__ unsigned sp_absmax_bits(unsigned mx, float v) {
+  const unsigned b = __float_as_uint(v) & 0x7fffffffu;
+  return b > mx ? b : mx;
+}
+
 // the spread guard of the weight-gradient product: is a row's factor f = inv_a * inv_b / (largest such product) more than 2^20
 // below the reference although the row holds something?  All-zero rows are recognised by THEIR OWN scale - the marker
 // 2^-126 sp_scale_for_max gives them (also rows whose largest entry is below 2^-112: nothing) - not by the size of f: with

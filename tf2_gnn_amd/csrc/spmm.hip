@@ -192,17 +192,17 @@ struct GatherArgs {
   bool multi_pairs;  // host only: the short rows go two to a lane group, one edge of each per round (gather_rows_block_multi)
 };
 
-// scale of one output row from the maximum over its LANES lanes (lanes of one group are contiguous)
+// scale of one output row from the maximum (sp_absmax_bits) over its LANES lanes (lanes of one group are contiguous)
 template <int LANES>
-__device__ __forceinline__ float sp_row_scale(const GatherArgs& a, float mx, int64_t orow, bool writer) {
+__device__ __forceinline__ float sp_row_scale(const GatherArgs& a, unsigned mx, int64_t orow, bool writer) {
   float iv, sc;
   if (a.fixed_inv) {
     iv = a.fixed_inv[0];
     sc = 1.f / iv;
   } else {
 #pragma unroll
-    for (int o = LANES / 2; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, LANES));
-    sc = sp_scale_for_max(mx, &iv);
+    for (int o = LANES / 2; o; o >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, o, LANES));
+    sc = sp_scale_for_max(__uint_as_float(mx), &iv);
     if (writer) a.inv_out[orow] = iv;
   }
   return sc;
@@ -370,13 +370,13 @@ __device__ __forceinline__ void gather_rows_block(const GatherArgs& a, unsigned 
 
   const float rs = a.row_scale ? a.row_scale[row] : 1.f;
   if constexpr (SP) {  // VEC == 4, one window: the lane group holds the whole row
-    float mx = 0.f;
+    unsigned mx = 0u;
 #pragma unroll
     for (int i = 0; i < VPL; ++i)
 #pragma unroll
       for (int c = 0; c < VEC; ++c) {
         acc[i][c] *= rs;
-        if (live[i]) mx = fmaxf(mx, fabsf(acc[i][c]));
+        if (live[i]) mx = sp_absmax_bits(mx, acc[i][c]);
       }
     const float sc = sp_row_scale<LPR>(a, mx, orow, gl == 0);
     uint8_t* drow = a.out_sp + orow * a.ld_out_sp;
@@ -508,13 +508,13 @@ __device__ __forceinline__ void gather_rows_block_multi(const GatherArgs& a, uns
   for (int r = 0; r < R; ++r) {
     if (!on[r]) continue;
     if constexpr (SP) {
-      float mx = 0.f;
+      unsigned mx = 0u;
 #pragma unroll
       for (int i = 0; i < VPL; ++i)
 #pragma unroll
         for (int c = 0; c < VEC; ++c) {
           acc[r][i][c] *= rs[r];
-          if (live[i]) mx = fmaxf(mx, fabsf(acc[r][i][c]));
+          if (live[i]) mx = sp_absmax_bits(mx, acc[r][i][c]);
         }
       const float sc = sp_row_scale<LPR>(a, mx, orow[r], gl == 0);
       uint8_t* drow = a.out_sp + orow[r] * a.ld_out_sp;
@@ -553,7 +553,7 @@ __device__ __forceinline__ float load_partial1(const GatherArgs& a, int64_t slot
 // lane (width <= 2048 floats).  Sums in item order, four partial rows in flight.
 __device__ __forceinline__ void combine_sp_row(const GatherArgs& a, int64_t row, int32_t base, int32_t n, float rs, int lane) {
   float4 sum[8];
-  float mx = 0.f;
+  unsigned mx = 0u;
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const int c = (lane + i * 64) * 4;
@@ -572,7 +572,7 @@ __device__ __forceinline__ void combine_sp_row(const GatherArgs& a, int64_t row,
         sum[i].x += p.x; sum[i].y += p.y; sum[i].z += p.z; sum[i].w += p.w;
       }
       sum[i].x *= rs; sum[i].y *= rs; sum[i].z *= rs; sum[i].w *= rs;
-      mx = fmaxf(mx, fmaxf(fmaxf(fabsf(sum[i].x), fabsf(sum[i].y)), fmaxf(fabsf(sum[i].z), fabsf(sum[i].w))));
+      mx = sp_absmax_bits(sp_absmax_bits(sp_absmax_bits(sp_absmax_bits(mx, sum[i].x), sum[i].y), sum[i].z), sum[i].w);
     }
   }
   const int64_t orow = a.out_row_map ? a.out_row_map[row] : row;
@@ -582,8 +582,8 @@ __device__ __forceinline__ void combine_sp_row(const GatherArgs& a, int64_t row,
     sc = 1.f / iv;
   } else {
 #pragma unroll
-    for (int o = 32; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    sc = sp_scale_for_max(mx, &iv);
+    for (int o = 32; o; o >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, o, 64));
+    sc = sp_scale_for_max(__uint_as_float(mx), &iv);
     if (lane == 0) a.inv_out[orow] = iv;
   }
   uint8_t* drow = a.out_sp + orow * a.ld_out_sp;
@@ -688,7 +688,7 @@ __device__ __forceinline__ void gather_item_block(const GatherArgs& a, int item,
   const float rs = a.row_scale ? a.row_scale[row] : 1.f;
   if constexpr (SP) {
     if (slot < 0) {  // the item is the whole row: sums -> red[0], row maximum, split store
-      float mx = 0.f;
+      unsigned mx = 0u;  // (sp_absmax_bits)
       for (int f = tid; f < WINDOW; f += 256) {
         if (w0 + f >= a.width) break;
         float v = red[0][f];
@@ -696,21 +696,21 @@ __device__ __forceinline__ void gather_item_block(const GatherArgs& a, int item,
         for (int g = 1; g < GROUPS; ++g) v += red[g][f];
         v *= rs;
         red[0][f] = v;
-        mx = fmaxf(mx, fabsf(v));
+        mx = sp_absmax_bits(mx, v);
       }
 #pragma unroll
-      for (int o = 32; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+      for (int o = 32; o; o >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, o, 64));
       __syncthreads();  // every sum over red[1..] has been taken
-      if ((tid & 63) == 0) red[1][tid >> 6] = mx;
+      if ((tid & 63) == 0) red[1][tid >> 6] = __uint_as_float(mx);
       __syncthreads();
-      mx = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
+      mx = max(max(__float_as_uint(red[1][0]), __float_as_uint(red[1][1])), max(__float_as_uint(red[1][2]), __float_as_uint(red[1][3])));
       const int64_t orow = a.out_row_map ? a.out_row_map[row] : row;
       float iv, sc;
       if (a.fixed_inv) {
         iv = a.fixed_inv[0];
         sc = 1.f / iv;
       } else {
-        sc = sp_scale_for_max(mx, &iv);
+        sc = sp_scale_for_max(__uint_as_float(mx), &iv);
         if (tid == 0) a.inv_out[orow] = iv;
       }
       uint8_t* drow = a.out_sp + orow * a.ld_out_sp;
