@@ -961,6 +961,44 @@ int tfgnn_binary_ce_metrics(const float* d_logits, const float* d_target, int64_
                             int64_t* d_counts, float* d_dlogits, void* d_workspace, size_t workspace_bytes,
                             void* stream);
 
+/* tfgnn_softmax_ce_metrics: weighted softmax cross-entropy of per-node logits against ONE class per node, with its
+ * accuracy counts, argmax and gradient (NodeClassificationTask; the reference has no counterpart, PARITY UNPINNED).
+ * d_logits [V, C] fp32, row stride ld_logits >= C.  The class of node v is the fp32 d_labels[v * ld_labels], its weight
+ * w_v the fp32 d_weights[v * ld_weights], or 1 when d_weights is NULL: element strides, so labels and weights may be two
+ * columns of one [V, 2] array.  d_workspace: tfgnn_softmax_ce_workspace_bytes() bytes, 8-byte aligned.
+ *   counted   node v is counted iff w_v > 0 and its label is an integer in [0, C).  A label of -1, one >= C, a fractional
+ *             or NaN label, and a zero, negative or NaN weight all make the node uncounted: it adds nothing to any sum,
+ *             its d_dlogits row is exactly 0, its d_pred is still written.
+ *   W         sum of w_v over the counted nodes, added in double in a fixed order.
+ *   loss      d_metrics[0] = sum over counted v of w_v (logsumexp(x_v) - x_v[y_v]) / W.  With m the row maximum and
+ *             s = sum_c expf(x_v[c] - m) in fp32, the row's value is (double)m - (double)x_v[y_v] + (double)logf(s);
+ *             rows are added in double.  W == 0 (no counted node): loss = 0 and every d_dlogits entry is 0.
+ *   pred      d_pred[v] (optional, int32 [V]) = the lowest index of the row maximum (the tie rule of np.argmax); a NaN
+ *             entry takes part as -inf.
+ *   counts    d_counts (optional, int64 [2]) = {counted nodes with pred == label, counted nodes};
+ *             d_metrics[1] = accuracy = correct / counted in double, 0 / 0 -> nan like the micro-F1.
+ *   gradient  d_dlogits (optional, row stride ld_dlogits >= C; columns >= C are not touched):
+ *             d_dlogits[v, c] = (w_v / W) (softmax(x_v)[c] - [c == y_v]) for counted v.
+ *   NaN       a NaN logit in a counted row makes the loss NaN (and that row's gradient); it is not hidden.
+ *   C == 1    is legal: loss 0, gradient 0, prediction 0.
+ * Refused before any launch: V <= 0 or C <= 0 ("empty batch"), C > 2^24 (fp32 labels stop being exact), NULL d_logits /
+ * d_labels / d_metrics, ld_logits < C, ld_dlogits < C, an element stride < 1, a short or misaligned workspace.
+ * At most three launches, no allocation, no host synchronisation, capturable: (1) the weight pass reduces W and the number
+ * of counted nodes over the V labels and weights (4 - 8 bytes per node against 8 C for the main pass), at most 64 partials;
+ * (2) the main pass - every wave adds those partials up in the same fixed order, so the gradient is scaled by the same W
+ * everywhere - leaves one partial per workgroup; (3) the fixed-order final stage.  d_metrics and d_counts are bit-identical
+ * run to run and whether or not d_dlogits / d_pred are requested.
+ * Row strategy of the main pass, by C: a row is shared by a group of G lanes, lane j of the group holding columns j, j + G,
+ * ... in 8 registers, and a wave works on 64 / G consecutive rows at once: G = 4 for C <= 32, 8 for C <= 64, 16 for
+ * C <= 128, 32 for C <= 256, 64 for C <= 512; every logit is read once and all reductions are cross-lane.  C > 512: one
+ * wave per row, a running maximum and rescaled sum per lane merged across the wave, and a second read of the row for the
+ * gradient.  The switches are at C = 32, 64, 128, 256 and 512. */
+size_t tfgnn_softmax_ce_workspace_bytes(void);
+int tfgnn_softmax_ce_metrics(const float* d_logits, int64_t ld_logits, const float* d_labels, int64_t ld_labels,
+                             const float* d_weights, int64_t ld_weights, int64_t V, int64_t C, float* d_metrics,
+                             int64_t* d_counts, float* d_dlogits, int64_t ld_dlogits, int32_t* d_pred,
+                             void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Layer-level entry points (round 6): one call per message-passing layer and pass.
  * Replaces, for one layer, MessagePassing.call (message_passing.py:95-133) with

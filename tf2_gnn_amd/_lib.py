@@ -226,6 +226,13 @@ _SIGNATURES = [
         c_int,
         [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
     ),
+    ("tfgnn_softmax_ce_workspace_bytes", c_size_t, []),
+    (
+        "tfgnn_softmax_ce_metrics",
+        c_int,
+        [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+         c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
     (
         "tfgnn_graph_gather_reduce_sp",
         c_int,

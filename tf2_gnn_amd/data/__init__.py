@@ -7,3 +7,4 @@ from .jsonl_graph_dataset import JsonLGraphDataset
 from .jsonl_graph_property_dataset import GraphWithPropertySample, JsonLGraphPropertyDataset
 from .ppi_dataset import PPIDataset, PPIGraphSample
 from .qm9_dataset import QM9Dataset, QM9GraphSample
+from .node_classification_dataset import NodeClassificationDataset

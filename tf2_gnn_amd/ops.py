@@ -1263,6 +1263,57 @@ def binary_ce_metrics(logits: torch.Tensor, target: torch.Tensor, need_grad: boo
     return metrics, counts, prob, grad
 
 
+def _node_column(t: torch.Tensor, V: int, what: str):
+    """One fp32 value per node - [V], [V, 1] or a strided column view of either - as (tensor, element stride); no copy."""
+    if t.dim() == 2 and t.shape[1] == 1:
+        t = t[:, 0]
+    if t.dim() != 1 or t.shape[0] != V:
+        raise ValueError(f"{what} {tuple(t.shape)} must hold one value per node: [{V}] or [{V}, 1]")
+    stride = t.stride(0) if V > 1 else 1
+    if stride < 1:  # an expanded (stride 0) or flipped view
+        t, stride = t.contiguous(), 1
+    return t, stride
+
+
+@_writes_out
+def softmax_ce_metrics(logits: torch.Tensor, labels: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                       need_grad: bool = True, want_pred: bool = False, out: Optional[torch.Tensor] = None):
+    """Weighted softmax cross-entropy of per-node logits [V, C] against one class per node (include/tfgnn.h
+    tfgnn_softmax_ce_metrics: a node is counted iff its weight is > 0 and its label an integer in [0, C)) ->
+    (metrics [2] = (loss, accuracy) on the device, counts [2] int64 = (correct, counted), d loss / d logits or None,
+    argmax int32 [V] or None).  ``labels`` / ``weights``: [V], [V, 1] or a strided column view (passed by stride, not
+    copied); integer labels are cast to float32 once.  ``out``: where the gradient goes instead of a new tensor - a float32
+    [V, C] with unit inner stride, e.g. C columns of a wider array, whose other columns stay as they are."""
+    lib = _lib.load()
+    _require_dev(logits, torch.float32, "logits")
+    if not labels.is_floating_point():
+        labels = labels.to(torch.float32)
+    _require_dev(labels, torch.float32, "labels")
+    if weights is not None:
+        _require_dev(weights, torch.float32, "weights")
+    logits, ldx = _rowmajor(logits, "logits")
+    V, C = logits.shape
+    labels, ldy = _node_column(labels, V, "labels")
+    ldw = 0
+    if weights is not None:
+        weights, ldw = _node_column(weights, V, "weights")
+    metrics = torch.empty(2, dtype=torch.float32, device=logits.device)
+    counts = torch.empty(2, dtype=torch.int64, device=logits.device)
+    grad, ldd = None, max(C, 1)
+    if out is not None:
+        _require_dev(out, torch.float32, "out")
+        if tuple(out.shape) != (V, C) or (C > 1 and out.stride(1) != 1) or (V > 1 and out.stride(0) < C):
+            raise ValueError(f"out must be a float32 [{V}, {C}] with unit inner stride, got {tuple(out.shape)} / {out.stride()}")
+        grad, ldd = out, (out.stride(0) if V > 1 else max(C, 1))
+    elif need_grad:
+        grad = torch.empty((V, C), dtype=torch.float32, device=logits.device)
+    pred = torch.empty(V, dtype=torch.int32, device=logits.device) if want_pred else None
+    ws = _workspace(logits.device, lib.tfgnn_softmax_ce_workspace_bytes())
+    _lib.check(lib.tfgnn_softmax_ce_metrics(_ptr(logits), ldx, _ptr(labels), ldy, _ptr(weights), ldw, V, C, _ptr(metrics),
+                                            _ptr(counts), _ptr(grad), ldd, _ptr(pred), _ptr(ws), ws.numel(), _stream()))
+    return metrics, counts, grad, pred
+
+
 # ---- split-operand ("f16x2") products: include/tfgnn.h tfgnn_sp_*, csrc/gemm_sp.hip ------------------------------
 class SplitOperand:
     """An fp32 matrix [rows, cols] in the SP16 operand format: ``data`` uint8 [rows, 4 * cols] (per row and 16 columns

@@ -302,6 +302,57 @@ class NodeMulticlassTask(GraphTaskModel):
         return ops.gemm(d, self._kernel.value, trans_b=True), None
 
 
+class NodeClassificationTask(NodeMulticlassTask):
+    """One class per node, labels known for part of the nodes, folds as node masks over the same graph (ogbn-arxiv style);
+    the reference has no counterpart.  Dense(num_node_classes) on the final node representations - the head, its variable
+    names and its backward pass are NodeMulticlassTask's - and the weighted softmax cross-entropy of include/tfgnn.h
+    tfgnn_softmax_ce_metrics: a node is counted iff its ``node_label_weights`` entry (1 when the batch has none) is > 0 and
+    its ``node_labels`` entry is an integer in [0, num_node_classes).  Labels and weights are read from device memory by the
+    kernel, so a captured step follows in-place changes of either (capture.py)."""
+
+    def __init__(self, params: Dict[str, Any], dataset: Any = None, name: Optional[str] = None, *,
+                 num_edge_types: Optional[int] = None, num_node_classes: Optional[int] = None):
+        if num_node_classes is None:
+            if not hasattr(dataset, "num_node_classes"):
+                raise ValueError(f"Provided dataset of type {type(dataset)} does not provide num_node_classes information.")
+            num_node_classes = dataset.num_node_classes
+        super().__init__(params, dataset=dataset, name=name, num_edge_types=num_edge_types,
+                         num_node_target_labels=num_node_classes)
+
+    @property
+    def num_node_classes(self) -> int:
+        return self._num_labels
+
+    def compute_task_metrics(self, batch_features, task_output, batch_labels) -> Dict[str, torch.Tensor]:
+        """-> "loss", "accuracy" (of this batch's counted nodes), "num_correct", "num_labelled" (int64): device tensors."""
+        (per_node_logits,) = task_output
+        metrics, counts, dlogits, _ = ops.softmax_ce_metrics(per_node_logits, batch_labels["node_labels"],
+                                                             batch_labels.get("node_label_weights"))
+        if self._step is not None:
+            self._step["dloss"] = dlogits
+        return {"loss": metrics[0], "accuracy": metrics[1], "num_correct": counts[0], "num_labelled": counts[1]}
+
+    def compute_epoch_metrics(self, task_results: List[Any]) -> Tuple[float, str]:
+        """Correct predictions over counted nodes, across steps of different sizes; the smaller the better, so -accuracy."""
+        total_correct = sum(int(r["num_correct"]) for r in task_results)
+        total_labelled = sum(int(r["num_labelled"]) for r in task_results)
+        epoch_acc = float(total_correct) / float(total_labelled) if total_labelled else float("nan")
+        return -epoch_acc, f"Accuracy = {epoch_acc:.3f}"
+
+    def evaluate_model(self, dataset) -> Dict[str, float]:
+        """-> acc, macro_f1 (utils/eval_metrics.py multiclass_metrics) of the argmax of ``predict(dataset)`` over the counted
+        nodes of ``dataset``."""
+        predictions = np.argmax(self.predict(dataset).cpu().numpy(), axis=1)  # the lowest index among equal logits, as the kernel
+        labels, weights = [], []
+        for _, batch_labels in dataset:
+            y = batch_labels["node_labels"].reshape(-1)
+            w = batch_labels.get("node_label_weights")
+            labels.append(y)
+            weights.append(torch.ones_like(y) if w is None else w.reshape(-1))
+        return eval_metrics.multiclass_metrics(torch.cat(labels).cpu().numpy(), predictions, self._num_labels,
+                                               weights=torch.cat(weights).cpu().numpy())
+
+
 def _regression_task_metrics(task, task_output, batch_features, batch_labels):
     """graph_regression_task.py:150-166 / qm9_regression.py:116-130."""
     metrics, dpred = ops.regression_metrics(task_output, batch_labels["target_value"])

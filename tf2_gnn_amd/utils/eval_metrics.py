@@ -105,6 +105,32 @@ def binary_classification_metrics(labels, predictions) -> Dict[str, float]:
     }
 
 
+# ---- multiclass classification -----------------------------------------------------------------------------------------
+def multiclass_metrics(labels, predictions, num_classes: int, weights=None) -> Dict[str, float]:
+    """What NodeClassificationTask.evaluate_model reports from one class per sample (``labels``) and predicted classes
+    (``predictions``).  A sample is counted iff its weight (1 without ``weights``) is > 0 and its label is an integer in
+    [0, num_classes) - the rule of tfgnn_softmax_ce_metrics (include/tfgnn.h); weights select, they do not scale.  ``acc``:
+    the share of counted samples with prediction == label.  ``macro_f1``: the unweighted mean of the per-class
+    F1 = 2 tp / (2 tp + fp + fn) over the classes that occur among the counted labels or predictions
+    (``sklearn.metrics.f1_score(average="macro")`` without a ``labels`` argument).  Both are ``nan`` without a counted sample."""
+    y, p = _as_vectors(labels, predictions)
+    w = np.ones_like(y) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
+    if w.shape != y.shape:
+        raise ValueError(f"weights {w.shape} and labels {y.shape} differ in length")
+    with np.errstate(invalid="ignore"):
+        counted = (w > 0) & (y >= 0) & (y < num_classes) & (y == np.floor(y))
+    if not counted.any():
+        return {"acc": float("nan"), "macro_f1": float("nan")}
+    y, p = y[counted].astype(np.int64), p[counted].astype(np.int64)
+    f1 = []
+    for c in np.union1d(y, p):
+        tp = int(np.sum((p == c) & (y == c)))
+        fp = int(np.sum((p == c) & (y != c)))
+        fn = int(np.sum((p != c) & (y == c)))
+        f1.append(_ratio(2 * tp, 2 * tp + fp + fn))
+    return {"acc": float(np.mean(p == y)), "macro_f1": float(np.mean(f1))}
+
+
 # ---- regression --------------------------------------------------------------------------------------------------------
 def _one_minus_ratio(num: float, den: float) -> float:
     """1 - num / den; for a constant target (den = 0) a perfect fit scores 1.0 and anything else 0.0, scikit-learn's

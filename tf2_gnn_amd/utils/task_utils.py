@@ -4,8 +4,9 @@ from __future__ import annotations
 
 from typing import Any, Dict, Iterable, NamedTuple, Tuple, Type
 
-from ..data import GraphDataset, JsonLGraphPropertyDataset, PPIDataset, QM9Dataset
-from ..tasks import GraphBinaryClassificationTask, GraphRegressionTask, GraphTaskModel, NodeMulticlassTask, QM9RegressionTask
+from ..data import GraphDataset, JsonLGraphPropertyDataset, NodeClassificationDataset, PPIDataset, QM9Dataset
+from ..tasks import (GraphBinaryClassificationTask, GraphRegressionTask, GraphTaskModel, NodeClassificationTask, NodeMulticlassTask,
+                     QM9RegressionTask)
 
 
 class TaskInfo(NamedTuple):
@@ -66,6 +67,12 @@ def register_default_tasks() -> None:
     register_task("GraphRegression", JsonLGraphPropertyDataset, {"threshold_for_classification": None}, GraphRegressionTask, {})
     register_task("GraphBinaryClassification", JsonLGraphPropertyDataset, {"threshold_for_classification": 23.0},
                   GraphBinaryClassificationTask, {})
+
+
+def register_node_classification_task() -> None:
+    """One class per node with fold masks over one graph.  The reference has no such task, so it is not among the
+    defaults: whoever wants it by name registers it."""
+    register_task("NodeClassification", NodeClassificationDataset, {}, NodeClassificationTask, {})
 
 
 register_default_tasks()
