@@ -356,6 +356,33 @@ BATCH_MAX_EDGE_TYPES = 48  # TFGNN_BATCH_MAX_EDGE_TYPES
 BATCH_MAX_COLUMNS = 8  # TFGNN_BATCH_MAX_COLUMNS
 BATCH_MAX_NODE_COLUMNS = 4  # TFGNN_BATCH_MAX_NODE_COLUMNS
 
+# link prediction with a DistMult decoder (include/tfgnn.h, csrc/link.hip)
+_SIGNATURES += [
+    ("tfgnn_distmult_ce_workspace_bytes", c_size_t, []),
+    (
+        "tfgnn_distmult_ce_metrics",
+        c_int,
+        [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    ("tfgnn_distmult_backward_workspace_bytes", c_size_t, [c_int64, c_int64]),
+    (
+        "tfgnn_distmult_backward",
+        c_int,
+        [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
+         c_void_p, c_int64, c_int, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    ("tfgnn_distmult_rank_workspace_bytes", c_size_t, [c_int64]),
+    (
+        "tfgnn_distmult_rank",
+        c_int,
+        [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+         c_void_p, c_size_t, c_void_p],
+    ),
+    ("tfgnn_link_launch_counts", c_int, [POINTER(c_int64), c_int]),
+]
+LINK_CHUNK = 256  # csrc/link.hip LINK_CHUNK: list positions per chunk of the backward passes
+
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
 ABI_VERSION = 5  # include/tfgnn.h TFGNN_ABI_VERSION
 

@@ -217,10 +217,10 @@ class TorchNodesToGraphRepresentation(_AutogradModule):
 
 class TorchGraphTaskModel(_AutogradModule):
     """A task model of ``tf2_gnn_amd.tasks`` (NodeMulticlassTask, NodeClassificationTask, QM9RegressionTask,
-    GraphRegressionTask, GraphBinaryClassificationTask): ``module(batch_features)`` returns the task output (per-node logits / per-graph
-    predictions / per-graph probabilities), differentiable with respect to every weight of the GNN and of the head - compute
-    any torch loss on it and call ``loss.backward()``.  (The models' own ``compute_task_metrics`` + ``backward()`` stay
-    available: they fuse the reference's losses with their gradients.)"""
+    GraphRegressionTask, GraphBinaryClassificationTask, LinkPredictionTask): ``module(batch_features)`` returns the task output
+    (per-node logits / per-graph predictions / per-graph probabilities / per-triple scores), differentiable with respect to
+    every weight of the GNN and of the head - compute any torch loss on it and call ``loss.backward()``.  (The models' own
+    ``compute_task_metrics`` + ``backward()`` stay available: they fuse the reference's losses with their gradients.)"""
 
     def __init__(self, model):
         super().__init__(model)

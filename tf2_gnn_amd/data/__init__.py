@@ -8,3 +8,4 @@ from .jsonl_graph_property_dataset import GraphWithPropertySample, JsonLGraphPro
 from .ppi_dataset import PPIDataset, PPIGraphSample
 from .qm9_dataset import QM9Dataset, QM9GraphSample
 from .node_classification_dataset import NodeClassificationDataset
+from .link_prediction_dataset import LinkPredictionDataset

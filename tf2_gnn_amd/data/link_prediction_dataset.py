@@ -1,0 +1,289 @@
+"""Transductive link prediction: one graph, typed edges, and folds that are sets of true triples (source, relation, target)
+over the SAME node set (FB15k / WN18 style, the second experiment of the R-GCN paper).  The reference has no such dataset.
+
+A data directory holds numpy files only:
+  ``node_features.npy`` [V, F];
+  ``edges.npy`` [E, 2] (one forward edge type) or ``edges_0.npy``, ``edges_1.npy``, ... (one file per forward edge type),
+  (source, target) pairs: the message-passing graph, and at the same time the TRAIN positives;
+  ``valid_edges_<t>.npy`` / ``test_edges_<t>.npy`` (``valid_edges.npy`` / ``test_edges.npy`` with a single type): the
+  positives of the other two folds; a missing file of a loaded fold stands for no edge of that type.
+
+A triple's relation is its FORWARD edge type: ``num_relations`` is the number of ``edges`` files, whatever backward and
+self-loop types message passing adds.  TRAIN positives are edges of the message-passing graph, as in the R-GCN paper: no
+edge is held out of the graph while its score is trained.
+
+Every fold is the whole graph and ONE batch (a ``max_nodes_per_batch`` below the node count raises ValueError); the graph
+part of a batch comes out of the single tfgnn_batch_assemble launch like every dataset's.  On top, a batch carries, in
+``batch_labels`` and - the same tensors - in ``batch_features``:
+  ``triples`` int32 [N, 3]: the fold's P positives followed by ``num_negatives_per_positive`` negatives per positive;
+  ``triple_labels`` float32 [N] (1 / 0), ``triple_weights`` float32 [N] (1);
+  ``triple_tables``: the four int32 tables of ops.build_triple_tables for these triples;
+and in ``batch_labels`` alone what ``LinkPredictionTask.evaluate_model`` ranks: ``positive_triples`` int32 [P, 3] and
+``rank_filters`` = {"dst": (offsets, ids), "src": (offsets, ids)}, per positive the sorted entities that make a KNOWN true
+triple in the corrupted slot - known: a positive of any loaded fold.
+
+A negative copies its positive and replaces the source or the target - a fair coin - with a node drawn uniformly from the
+other V - 1 nodes, so exactly one slot differs; it is not filtered against the known triples.  TRAIN draws its negatives
+anew from numpy's global generator at every ``iter()`` (where the other datasets draw the epoch's graph order, so
+np.random.seed seeds it), rebuilds the tables on the host and copies everything IN PLACE into the same device buffers - N is
+fixed - so a CapturedStep of a training step follows.  VALIDATION and TEST draw once, from a fixed seed."""
+from __future__ import annotations
+
+from pathlib import Path
+from typing import Any, Dict, Iterator, List, Optional, Sequence, Set, Tuple
+
+import numpy as np
+import torch
+
+from .. import ops
+from .graph_dataset import DataFold, GraphDataset, PackedFold, assemble_batch
+from .utils import compute_number_of_edge_types, get_tied_edge_types
+
+_EVAL_NEGATIVES_SEED = {DataFold.VALIDATION: 0x5EED0001, DataFold.TEST: 0x5EED0002}
+
+
+def sample_negatives(positives: np.ndarray, num_nodes: int, per_positive: int, rng) -> np.ndarray:
+    """``per_positive`` negatives for every positive, in the positives' order ([P * per_positive, 3]): a copy with the source or
+    the target - a fair coin - replaced by a node drawn uniformly from the OTHER num_nodes - 1 nodes, so exactly one slot
+    differs.  ``rng``: np.random or a RandomState."""
+    neg = np.repeat(np.asarray(positives, dtype=np.int32).reshape(-1, 3), per_positive, axis=0)
+    n = neg.shape[0]
+    if n == 0:
+        return neg
+    if num_nodes < 2:
+        raise ValueError("a negative needs a second node to put in place of the first")
+    rows = np.arange(n)
+    slot = np.where(rng.randint(0, 2, size=n) == 0, 0, 2)
+    draw = rng.randint(0, num_nodes - 1, size=n)
+    neg[rows, slot] = draw + (draw >= neg[rows, slot])
+    return neg
+
+
+def _filter_csr(positives: np.ndarray, known: np.ndarray, slot: int, num_nodes: int, num_relations: int):
+    """per positive (u, t, v): the sorted unique entities x such that the triple with x in ``slot`` (0: source, 2: target) is
+    known -> (offsets int32 [P + 1], ids int32)"""
+    keep = 2 - slot  # the slot that stays
+    key = lambda a: a[:, keep].astype(np.int64) * num_relations + a[:, 1].astype(np.int64)
+    pairs = np.unique(np.stack([key(known), known[:, slot].astype(np.int64)], axis=1), axis=0)  # sorted by key, then entity
+    starts = np.searchsorted(pairs[:, 0], key(positives), side="left")
+    ends = np.searchsorted(pairs[:, 0], key(positives), side="right")
+    offsets = np.zeros(len(positives) + 1, dtype=np.int64)
+    np.cumsum(ends - starts, out=offsets[1:])
+    take = np.repeat(starts - offsets[:-1], ends - starts) + np.arange(offsets[-1])
+    return offsets.astype(np.int32), pairs[take, 1].astype(np.int32)
+
+
+class _LinkBatches:
+    """What ``LinkPredictionDataset.get_batches`` returns: every ``iter()`` is one epoch of the fold's single batch."""
+
+    def __init__(self, dataset: "LinkPredictionDataset", data_fold: DataFold, device=None):
+        self._dataset, self._data_fold, self._device = dataset, data_fold, device
+
+    def __iter__(self) -> Iterator[Tuple[Dict[str, Any], Dict[str, Any]]]:
+        ds, fold = self._dataset, self._data_fold
+        plan = ds.plan_epoch(fold, self._device)
+        assert plan.batches == [(0, 1)]
+        features, labels = assemble_batch(plan, 0, 1, bad_flag=plan.bad_flags[0:1])
+        triple_part = ds.triple_batch(fold, plan.store.device)
+        labels.update(triple_part)
+        features.update({k: triple_part[k] for k in ("triples", "triple_labels", "triple_weights", "triple_tables")})
+        yield features, labels
+
+
+class LinkPredictionDataset(GraphDataset):
+    @classmethod
+    def get_default_hyperparameters(cls) -> Dict[str, Any]:
+        hypers = super().get_default_hyperparameters()
+        hypers.update({
+            "max_nodes_per_batch": 2 ** 31 - 1,  # no graph of int32 node ids reaches it: the fold is one batch
+            "add_self_loop_edges": True,
+            "tie_fwd_bkwd_edges": False,
+            "num_negatives_per_positive": 1,
+        })
+        return hypers
+
+    @staticmethod
+    def default_data_path() -> str:
+        return "data/link_prediction"
+
+    def __init__(self, params: Dict[str, Any], metadata: Optional[Dict[str, Any]] = None, **kwargs):
+        super().__init__(params, metadata=metadata, **kwargs)
+        self._num_fwd_edge_types: Optional[int] = None
+        self._num_nodes = 0
+        self._positives: Dict[DataFold, np.ndarray] = {}
+        self._filters: Dict[DataFold, Dict[str, Tuple[np.ndarray, np.ndarray]]] = {}
+        self._triple_buffers: Dict[Tuple[DataFold, str], Dict[str, Any]] = {}
+
+    def _loaded(self, what: str):
+        if self._num_fwd_edge_types is None:
+            raise ValueError(f"{what} is known once data has been loaded")
+
+    @property
+    def num_edge_types(self) -> int:
+        self._loaded("num_edge_types")
+        return compute_number_of_edge_types(
+            tied_fwd_bkwd_edge_types=get_tied_edge_types(self.params["tie_fwd_bkwd_edges"], self._num_fwd_edge_types),
+            num_fwd_edge_types=self._num_fwd_edge_types,
+            add_self_loop_edges=self.params["add_self_loop_edges"],
+        )
+
+    @property
+    def num_relations(self) -> int:
+        self._loaded("num_relations")
+        return self._num_fwd_edge_types
+
+    @property
+    def num_nodes(self) -> int:
+        self._loaded("num_nodes")
+        return self._num_nodes
+
+    @property
+    def node_feature_shape(self) -> Tuple:
+        self._loaded("node_feature_shape")
+        some_fold = next(iter(self._loaded_data.values()))
+        return (int(some_fold.features.shape[1]),)
+
+    # ---- loading ------------------------------------------------------------------------------------------------------------
+    def load_data(self, path, folds_to_load: Optional[Set[DataFold]] = None) -> None:
+        data_dir = Path(path)
+        if (data_dir / "edges.npy").exists():
+            edges, single = [np.load(data_dir / "edges.npy")], True
+        else:
+            edges, single = [], False
+            while (data_dir / f"edges_{len(edges)}.npy").exists():
+                edges.append(np.load(data_dir / f"edges_{len(edges)}.npy"))
+            if not edges:
+                raise ValueError(f"{data_dir}: neither edges.npy nor edges_0.npy")
+
+        def fold_edges(name: str):
+            files = [data_dir / (f"{name}_edges.npy" if single else f"{name}_edges_{t}.npy") for t in range(len(edges))]
+            if not any(f.exists() for f in files):
+                raise ValueError(f"{data_dir}: no {name}_edges file")
+            return [np.load(f) if f.exists() else np.zeros((0, 2), dtype=np.int64) for f in files]
+
+        wanted = lambda fold: folds_to_load is None or fold in folds_to_load
+        self.load_data_from_arrays(
+            np.load(data_dir / "node_features.npy"), edges,
+            valid_edges=fold_edges("valid") if wanted(DataFold.VALIDATION) else None,
+            test_edges=fold_edges("test") if wanted(DataFold.TEST) else None,
+            load_train=wanted(DataFold.TRAIN), what=str(data_dir),
+        )
+
+    def load_data_from_list(self, datapoints: List[Dict[str, Any]], target_fold: DataFold = DataFold.TEST):
+        raise NotImplementedError()
+
+    @staticmethod
+    def _edge_lists(edges, num_types: Optional[int], V: int, what: str) -> List[np.ndarray]:
+        if isinstance(edges, np.ndarray) and edges.ndim == 2:
+            edges = [edges]
+        edges = [np.asarray(e) for e in edges]
+        if num_types is not None and len(edges) != num_types:
+            raise ValueError(f"{what}: {len(edges)} edge lists for {num_types} forward edge types")
+        for t, e in enumerate(edges):
+            if e.ndim != 2 or e.shape[1] != 2 or e.dtype.kind not in "iu":
+                raise ValueError(f"{what}: the edges of type {t} must be an integer [E, 2] array, not {e.dtype} {list(e.shape)}")
+            if e.shape[0] and (e.min() < 0 or e.max() >= V):
+                k = int(np.flatnonzero((e < 0).any(axis=1) | (e >= V).any(axis=1))[0])
+                raise ValueError(f"{what}: edge {k} of type {t} ({e[k, 0]} -> {e[k, 1]}) names a node outside the {V} nodes")
+        return edges
+
+    @staticmethod
+    def _as_triples(edges: Sequence[np.ndarray]) -> np.ndarray:
+        parts = [np.stack([e[:, 0], np.full(e.shape[0], t), e[:, 1]], axis=1) for t, e in enumerate(edges)]
+        return np.ascontiguousarray(np.concatenate(parts), dtype=np.int32)
+
+    def load_data_from_arrays(self, node_features, edges, valid_edges=None, test_edges=None, load_train: bool = True,
+                              what: str = "arrays") -> None:
+        """The files of ``load_data`` as arrays.  ``edges`` / ``valid_edges`` / ``test_edges``: one [E, 2] array, or a sequence
+        of them, one per forward edge type; a fold whose edges are None is not loaded."""
+        feats = np.asarray(node_features, dtype=np.float32)
+        if feats.ndim != 2 or feats.shape[0] < 1:
+            raise ValueError(f"{what}: node features must be [V, F] with V >= 1, not {list(feats.shape)}")
+        V = feats.shape[0]
+        if self.params["max_nodes_per_batch"] < V:
+            raise ValueError(f"{what}: max_nodes_per_batch = {self.params['max_nodes_per_batch']} would cut the graph of {V} nodes; "
+                             "a link-prediction fold is one batch")
+        K = self.params["num_negatives_per_positive"]
+        if not isinstance(K, (int, np.integer)) or K < 0:
+            raise ValueError(f"{what}: num_negatives_per_positive must be an integer >= 0, not {K!r}")
+        if V < 2 and K > 0:
+            raise ValueError(f"{what}: negatives need at least two nodes")
+        graph = self._edge_lists(edges, None, V, what)
+        if not graph:
+            raise ValueError(f"{what}: no edge type")
+        T = len(graph)
+        positives = {}
+        if load_train:
+            positives[DataFold.TRAIN] = self._as_triples(graph)
+        for fold, name, e in ((DataFold.VALIDATION, "valid", valid_edges), (DataFold.TEST, "test", test_edges)):
+            if e is not None:
+                positives[fold] = self._as_triples(self._edge_lists(e, T, V, f"{what} ({name})"))
+        for fold, p in positives.items():
+            if p.shape[0] == 0:
+                raise ValueError(f"{what}: the {fold.name} fold has no edge")
+            if p.shape[0] * (1 + int(K)) > 2 ** 30:
+                raise ValueError(f"{what}: more than 2^30 triples in the {fold.name} fold")
+        base = PackedFold.from_raw_graphs(
+            node_features=[feats],
+            raw_adjacency_lists=[[e.astype(np.int32) for e in graph]],
+            num_fwd_edge_types=T,
+            add_self_loop_edges=self.params["add_self_loop_edges"],
+            tied_fwd_bkwd_edge_types=get_tied_edge_types(self.params["tie_fwd_bkwd_edges"], T),
+            feature_dim=int(feats.shape[1]),
+        )
+        self._num_fwd_edge_types, self._num_nodes = T, V
+        self._positives, self._triple_buffers = positives, {}
+        known = np.concatenate(list(positives.values())) if positives else np.zeros((0, 3), dtype=np.int32)
+        self._filters = {fold: {"dst": _filter_csr(p, known, 2, V, T), "src": _filter_csr(p, known, 0, V, T)}
+                         for fold, p in positives.items()}
+        for fold in positives:  # the same host arrays for every fold
+            self._set_fold(fold, base)
+
+    # ---- triples ------------------------------------------------------------------------------------------------------------
+    def positive_triples(self, data_fold: DataFold) -> np.ndarray:
+        return self._positives[data_fold]
+
+    def rank_filters(self, data_fold: DataFold) -> Dict[str, Tuple[np.ndarray, np.ndarray]]:
+        return self._filters[data_fold]
+
+    def draw_triples(self, data_fold: DataFold) -> np.ndarray:
+        """positives followed by freshly drawn negatives (TRAIN: numpy's global generator; the other folds: their fixed seed)"""
+        pos = self._positives[data_fold]
+        rng = np.random if data_fold == DataFold.TRAIN else np.random.RandomState(_EVAL_NEGATIVES_SEED[data_fold])
+        return np.concatenate([pos, sample_negatives(pos, self._num_nodes, int(self.params["num_negatives_per_positive"]), rng)])
+
+    def triple_batch(self, data_fold: DataFold, device=None) -> Dict[str, Any]:
+        """The triple part of the fold's batch on ``device`` (any torch device; the kernels need a ROCm one).  The buffers are
+        allocated at the first call and kept; every call for TRAIN draws new negatives and rewrites triples and tables in
+        place, the other folds are written once."""
+        self._loaded("triple_batch")
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        key = (data_fold, str(dev))
+        buffers = self._triple_buffers.get(key)
+        if buffers is not None and data_fold != DataFold.TRAIN:
+            return buffers
+        V, T = self._num_nodes, self._num_fwd_edge_types
+        triples = self.draw_triples(data_fold)
+        tables = ops.build_triple_tables(triples, V, T)
+        if buffers is None:
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            pos = self._positives[data_fold]
+            P, N = pos.shape[0], triples.shape[0]
+            labels = np.zeros(N, dtype=np.float32)
+            labels[:P] = 1.0
+            buffers = self._triple_buffers[key] = {
+                "triples": up(triples),
+                "triple_labels": up(labels),
+                "triple_weights": up(np.ones(N, dtype=np.float32)),
+                "triple_tables": {name: up(tables[name]) for name in ops.TRIPLE_TABLE_NAMES},
+                "positive_triples": up(pos),
+                "rank_filters": {side: (up(off), up(ids)) for side, (off, ids) in self._filters[data_fold].items()},
+            }
+        else:  # the positives, labels and weights stay; the negatives and with them the tables change
+            buffers["triples"].copy_(torch.from_numpy(triples))
+            for name in ops.TRIPLE_TABLE_NAMES:
+                buffers["triple_tables"][name].copy_(torch.from_numpy(tables[name]))
+        return buffers
+
+    def get_batches(self, data_fold: DataFold, device=None) -> _LinkBatches:
+        return _LinkBatches(self, data_fold, device)

@@ -7,8 +7,9 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Optional, Sequence
+from typing import Dict, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1312,6 +1313,189 @@ def softmax_ce_metrics(logits: torch.Tensor, labels: torch.Tensor, weights: Opti
     _lib.check(lib.tfgnn_softmax_ce_metrics(_ptr(logits), ldx, _ptr(labels), ldy, _ptr(weights), ldw, V, C, _ptr(metrics),
                                             _ptr(counts), _ptr(grad), ldd, _ptr(pred), _ptr(ws), ws.numel(), _stream()))
     return metrics, counts, grad, pred
+
+
+# ---- link prediction with a DistMult decoder: include/tfgnn.h tfgnn_distmult_*, csrc/link.hip ------------------------------
+def check_triples(triples, V: int, T: int, what: str = "triples") -> np.ndarray:
+    """Host triples [N, 3] (source, relation, target) as a contiguous int32 array, every index in range - the check the
+    kernels leave to the host (include/tfgnn.h).  Raises ValueError otherwise."""
+    a = np.asarray(triples)
+    if a.ndim != 2 or a.shape[1] != 3 or a.dtype.kind not in "iu":
+        raise ValueError(f"{what} must be an integer [N, 3] array of (source, relation, target), not {a.dtype} {list(a.shape)}")
+    if a.shape[0] > 2 ** 30:
+        raise ValueError(f"{what}: more than 2^30 triples")
+    if not (1 <= V < 2 ** 31 and 1 <= T < 2 ** 31):
+        raise ValueError(f"{what}: the numbers of nodes ({V}) and relations ({T}) must be in [1, 2^31)")
+    a = a.astype(np.int64)
+    if a.shape[0]:
+        bad = (a[:, 0] < 0) | (a[:, 0] >= V) | (a[:, 2] < 0) | (a[:, 2] >= V) | (a[:, 1] < 0) | (a[:, 1] >= T)
+        if bad.any():
+            k = int(np.flatnonzero(bad)[0])
+            raise ValueError(f"{what}: row {k} {tuple(int(x) for x in a[k])} is outside {V} nodes / {T} relations")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def build_triple_tables(triples, V: int, T: int) -> Dict[str, np.ndarray]:
+    """The int32 tables tfgnn_distmult_backward walks (include/tfgnn.h "Triple tables"), from host triples [N, 3]:
+    ``node_offsets`` [V + 1] / ``node_entries`` [2 N] (entry 2 e + role, role 0 = source, 1 = target, ascending within a
+    node) and ``rel_offsets`` [T + 1] / ``rel_order`` [N] (triples grouped by relation, stably).  Validates the triples."""
+    a = check_triples(triples, V, T).astype(np.int64)
+    N = a.shape[0]
+    nodes = np.stack([a[:, 0], a[:, 2]], axis=1).reshape(-1)  # position 2 e + role holds the node of that role
+    node_entries = np.argsort(nodes, kind="stable")
+    node_offsets = np.zeros(V + 1, dtype=np.int64)
+    np.cumsum(np.bincount(nodes, minlength=V), out=node_offsets[1:])
+    rel_order = np.argsort(a[:, 1], kind="stable")
+    rel_offsets = np.zeros(T + 1, dtype=np.int64)
+    np.cumsum(np.bincount(a[:, 1], minlength=T), out=rel_offsets[1:])
+    as_i32 = lambda x: x.astype(np.uint32).view(np.int32)  # 2 N = 2^31 at the limit: the kernels read offsets as unsigned
+    return {"node_offsets": as_i32(node_offsets), "node_entries": node_entries.astype(np.int32),
+            "rel_offsets": as_i32(rel_offsets), "rel_order": rel_order.astype(np.int32)}
+
+
+TRIPLE_TABLE_NAMES = ("node_offsets", "node_entries", "rel_offsets", "rel_order")
+
+
+def _link_common(H: torch.Tensor, R: torch.Tensor, triples, what: str):
+    """-> (H, ld_H, R, triples on the device, V, T, N, D).  Host triples (numpy) are validated and uploaded; a device tensor is
+    taken as validated by whoever uploaded it (build_triple_tables / check_triples): reading it back would synchronise."""
+    _require_dev(H, torch.float32, "H")
+    _require_dev(R, torch.float32, "R")
+    H, ldh = _rowmajor(H, "H")
+    if R.dim() != 2 or R.shape[1] != H.shape[1]:
+        raise ValueError(f"R {tuple(R.shape)} must be [T, {H.shape[1]}]")
+    R = R.contiguous()
+    V, D = H.shape
+    T = R.shape[0]
+    if not isinstance(triples, torch.Tensor):
+        triples = torch.from_numpy(check_triples(triples, V, T, what)).to(H.device)
+    _require_dev(triples, torch.int32, what)
+    if triples.dim() != 2 or triples.shape[1] != 3:
+        raise ValueError(f"{what} must be [N, 3], got {tuple(triples.shape)}")
+    triples = triples.contiguous()
+    return H, ldh, R, triples, V, T, triples.shape[0], D
+
+
+def distmult_ce_metrics(H: torch.Tensor, R: torch.Tensor, triples, labels: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                        need_grad: bool = True, want_scores: bool = True, want_counts: bool = True):
+    """DistMult scores of ``triples`` [N, 3] from node representations H [V, D] and relation embeddings R [T, D], their
+    weighted sigmoid cross-entropy against ``labels`` (0 / 1), confusion counts and d loss / d score (include/tfgnn.h
+    tfgnn_distmult_ce_metrics: a triple is counted iff its weight is > 0 and its label exactly 0 or 1) ->
+    (metrics [2] = (loss, accuracy), counts int64 [4] = (tp, fp, tn, fn) or None, scores [N] or None, gscore [N] or None),
+    all on the device.  ``labels`` / ``weights``: [N], [N, 1] or a strided column view, passed by stride."""
+    lib = _lib.load()
+    H, ldh, R, triples, V, T, N, D = _link_common(H, R, triples, "triples")
+    _require_dev(labels, torch.float32, "labels")
+    labels, ldy = _node_column(labels, N, "labels")
+    ldw = 0
+    if weights is not None:
+        _require_dev(weights, torch.float32, "weights")
+        weights, ldw = _node_column(weights, N, "weights")
+    dev = H.device
+    metrics = torch.empty(2, dtype=torch.float32, device=dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev) if want_counts else None
+    scores = torch.empty(N, dtype=torch.float32, device=dev) if want_scores else None
+    gscore = torch.empty(N, dtype=torch.float32, device=dev) if need_grad else None
+    ws = _workspace(dev, lib.tfgnn_distmult_ce_workspace_bytes())
+    _lib.check(lib.tfgnn_distmult_ce_metrics(_ptr(H), ldh, _ptr(R), _ptr(triples), _ptr(labels), ldy, _ptr(weights), ldw, V, T, N, D,
+                                             _ptr(metrics), _ptr(counts), _ptr(scores), _ptr(gscore), _ptr(ws), ws.numel(),
+                                             _stream()))
+    return metrics, counts, scores, gscore
+
+
+@_writes_out
+def distmult_backward(H: torch.Tensor, R: torch.Tensor, triples, gscore: torch.Tensor, tables: Dict[str, torch.Tensor],
+                      want_dH: bool = True, want_dR: bool = True, accumulate: bool = False, out: Optional[torch.Tensor] = None):
+    """d loss / d H [V, D] and d loss / d R [T, D] from ``gscore`` [N] (include/tfgnn.h tfgnn_distmult_backward; the sum order is
+    stated there) -> (dH or None, dR or None).  ``tables``: the four int32 device tensors of ``build_triple_tables``.  ``out``:
+    where dH goes instead of a new tensor - a float32 [V, D] with unit inner stride, e.g. D columns of a wider array whose
+    other columns stay as they are; with ``accumulate`` the sums are added to what it holds."""
+    lib = _lib.load()
+    H, ldh, R, triples, V, T, N, D = _link_common(H, R, triples, "triples")
+    _require_dev(gscore, torch.float32, "gscore")
+    if gscore.dim() != 1 or gscore.shape[0] != N:
+        raise ValueError(f"gscore {tuple(gscore.shape)} must be [{N}]")
+    gscore = gscore.contiguous()
+    sizes = {"node_offsets": V + 1, "node_entries": 2 * N, "rel_offsets": T + 1, "rel_order": N}
+    tabs = {}
+    for name in TRIPLE_TABLE_NAMES:
+        t = tables[name]
+        _require_dev(t, torch.int32, name)
+        if t.dim() != 1 or t.shape[0] != sizes[name] or not t.is_contiguous():
+            raise ValueError(f"{name} {tuple(t.shape)} must be a contiguous int32 [{sizes[name]}]")
+        tabs[name] = t
+    dev = H.device
+    dH, ldd = None, max(D, 1)
+    if out is not None:
+        _require_dev(out, torch.float32, "out")
+        if tuple(out.shape) != (V, D) or (D > 1 and out.stride(1) != 1) or (V > 1 and out.stride(0) < D):
+            raise ValueError(f"out must be a float32 [{V}, {D}] with unit inner stride, got {tuple(out.shape)} / {out.stride()}")
+        dH, ldd = out, (out.stride(0) if V > 1 else max(D, 1))
+    elif want_dH:
+        if accumulate:
+            raise ValueError("accumulate needs the tensor to add to: out=")
+        dH = torch.empty((V, D), dtype=torch.float32, device=dev)
+    dR = torch.empty((T, D), dtype=torch.float32, device=dev) if want_dR else None
+    ws = _workspace(dev, lib.tfgnn_distmult_backward_workspace_bytes(N, D))
+    _lib.check(lib.tfgnn_distmult_backward(_ptr(H), ldh, _ptr(R), _ptr(triples), _ptr(gscore), _ptr(tabs["node_offsets"]),
+                                           _ptr(tabs["node_entries"]), _ptr(tabs["rel_offsets"]), _ptr(tabs["rel_order"]), V, T, N, D,
+                                           _ptr(dH), ldd, int(bool(accumulate)), _ptr(dR), _ptr(ws), ws.numel(), _stream()))
+    return dH, dR
+
+
+def check_rank_filter(filter_offsets, filter_ids, Q: int, V: int):
+    """Host filter CSR of tfgnn_distmult_rank as two contiguous int32 arrays: offsets [Q + 1] ascending from 0, ids in [0, V),
+    strictly ascending within a query.  Raises ValueError otherwise."""
+    off = np.asarray(filter_offsets).astype(np.int64).reshape(-1)
+    ids = np.asarray(filter_ids).astype(np.int64).reshape(-1)
+    if off.shape[0] != Q + 1 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != ids.shape[0] or ids.shape[0] >= 2 ** 31:
+        raise ValueError(f"filter_offsets must be [{Q + 1}], ascending from 0 to the number of filter ids ({ids.shape[0]})")
+    if ids.shape[0]:
+        if ids.min() < 0 or ids.max() >= V:
+            raise ValueError(f"a filter id is outside the {V} nodes")
+        inner = np.ones(ids.shape[0], dtype=bool)
+        inner[off[:-1][off[:-1] < ids.shape[0]]] = False  # first id of a query
+        if (np.diff(ids) <= 0)[inner[1:]].any():
+            raise ValueError("filter ids must be sorted and unique within a query")
+    return np.ascontiguousarray(off, dtype=np.int32), np.ascontiguousarray(ids, dtype=np.int32)
+
+
+def distmult_rank(H: torch.Tensor, R: torch.Tensor, queries, corrupt: str = "dst", filter_offsets=None, filter_ids=None):
+    """For every query triple, how many candidate entities in the corrupted slot (``corrupt``: "dst" or "src") score above /
+    exactly as the true triple, the true entity and the filter's ids left out (include/tfgnn.h tfgnn_distmult_rank) ->
+    (greater int32 [Q], equal int32 [Q]) on the device.  Host arrays (numpy) are validated and uploaded; device tensors are
+    taken as validated."""
+    lib = _lib.load()
+    if corrupt not in ("dst", "src"):
+        raise ValueError(f"corrupt must be 'dst' or 'src', not {corrupt!r}")
+    H, ldh, R, queries, V, T, Q, D = _link_common(H, R, queries, "queries")
+    if (filter_offsets is None) != (filter_ids is None):
+        raise ValueError("a filter needs both filter_offsets and filter_ids")
+    if filter_offsets is not None:
+        if not isinstance(filter_offsets, torch.Tensor) or not isinstance(filter_ids, torch.Tensor):
+            to_np = lambda a: a.cpu().numpy() if isinstance(a, torch.Tensor) else a
+            off, ids = check_rank_filter(to_np(filter_offsets), to_np(filter_ids), Q, V)
+            filter_offsets, filter_ids = torch.from_numpy(off).to(H.device), torch.from_numpy(ids).to(H.device)
+        _require_dev(filter_offsets, torch.int32, "filter_offsets")
+        _require_dev(filter_ids, torch.int32, "filter_ids")
+        if filter_offsets.dim() != 1 or filter_offsets.shape[0] != Q + 1 or filter_ids.dim() != 1:
+            raise ValueError(f"filter_offsets must be [{Q + 1}] and filter_ids 1-D")
+        filter_offsets, filter_ids = filter_offsets.contiguous(), filter_ids.contiguous()
+        if filter_ids.numel() == 0:  # an empty tensor has no address; the kernel never reads an id then
+            filter_ids = torch.zeros(1, dtype=torch.int32, device=H.device)
+    greater = torch.empty(Q, dtype=torch.int32, device=H.device)
+    equal = torch.empty(Q, dtype=torch.int32, device=H.device)
+    ws = _workspace(H.device, lib.tfgnn_distmult_rank_workspace_bytes(Q))
+    _lib.check(lib.tfgnn_distmult_rank(_ptr(H), ldh, _ptr(R), _ptr(queries), Q, 0 if corrupt == "dst" else 1, _ptr(filter_offsets),
+                                       _ptr(filter_ids), V, T, D, _ptr(greater), _ptr(equal), _ptr(ws), ws.numel(), _stream()))
+    return greater, equal
+
+
+def link_launch_counts() -> dict:
+    """tfgnn_link_launch_counts: kernel launches of the three DistMult calls so far (host counters)."""
+    buf = (ctypes.c_int64 * 3)()
+    _lib.check(_lib.load().tfgnn_link_launch_counts(buf, 3))
+    return {"distmult_fwd": int(buf[0]), "distmult_bwd": int(buf[1]), "distmult_rank": int(buf[2])}
 
 
 # ---- split-operand ("f16x2") products: include/tfgnn.h tfgnn_sp_*, csrc/gemm_sp.hip ------------------------------

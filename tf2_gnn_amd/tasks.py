@@ -353,6 +353,125 @@ class NodeClassificationTask(NodeMulticlassTask):
                                                weights=torch.cat(weights).cpu().numpy())
 
 
+class LinkPredictionTask(GraphTaskModel):
+    """Edge-level task: score typed edges (source, relation, target) from the final node representations with a DistMult
+    decoder, s = sum_d h_u[d] R[t, d] h_v[d] (the link-prediction experiment of the R-GCN paper); the reference has no
+    counterpart.  One task variable, ``relation_embeddings`` [num_relations, gnn_hidden_dim].  Loss: the weighted sigmoid
+    cross-entropy of the scores against ``triple_labels`` (1 for a true edge, 0 for a sampled negative) of include/tfgnn.h
+    tfgnn_distmult_ce_metrics: a triple is counted iff its ``triple_weights`` entry (1 when absent) is > 0 and its label is
+    0 or 1.
+
+    The triples travel in BOTH dictionaries of a batch (LinkPredictionDataset puts the same tensors into each): the forward
+    pass needs them for its output, ``compute_task_metrics`` takes the labels from ``batch_labels`` like every task.  When
+    ``batch_features`` also carries ``triple_labels`` - the dataset's batches do - the forward pass runs the fused kernel once
+    (scores, loss, counts, d loss / d score) and ``compute_task_metrics`` on that output with the same label tensor reuses its
+    results; otherwise it runs the kernel again on the node representations of the last forward pass.  Triples, labels,
+    weights and tables are read from device memory by the kernels, so a captured step follows in-place changes (new
+    negatives) of all of them."""
+
+    def __init__(self, params: Dict[str, Any], dataset: Any = None, name: Optional[str] = None, *,
+                 num_edge_types: Optional[int] = None, num_relations: Optional[int] = None):
+        super().__init__(params, dataset=dataset, name=name, num_edge_types=num_edge_types)
+        if num_relations is None:
+            if not hasattr(dataset, "num_relations"):
+                raise ValueError(f"Provided dataset of type {type(dataset)} does not provide num_relations information.")
+            num_relations = dataset.num_relations
+        self._num_relations = int(num_relations)
+        if self._num_relations < 1:
+            raise ValueError("LinkPredictionTask needs at least one relation")
+
+    @property
+    def num_relations(self) -> int:
+        return self._num_relations
+
+    def build(self, input_shapes):
+        H = int(self._params["gnn_hidden_dim"])
+        self._relation_embeddings = Variable(f"{self.__class__.__name__}/relation_embeddings",
+                                             glorot_uniform((self._num_relations, H), device=default_device()))
+        super().build(input_shapes)
+
+    def _task_variables(self):
+        return [self._relation_embeddings]
+
+    @staticmethod
+    def _final(final_node_representations):
+        return final_node_representations[0] if isinstance(final_node_representations, tuple) else final_node_representations
+
+    def _fused(self, h, triples, labels, weights, need_grad=True):
+        metrics, counts, scores, gscore = ops.distmult_ce_metrics(h, self._relation_embeddings.value, triples, labels, weights,
+                                                                  need_grad=need_grad)
+        return {"scores": scores, "metrics": metrics, "counts": counts, "gscore": gscore, "triples": triples, "labels": labels,
+                "weights": weights}
+
+    def compute_task_output(self, batch_features, final_node_representations, training: bool):
+        h = self._final(final_node_representations)
+        triples = batch_features["triples"]
+        labels = batch_features.get("triple_labels")
+        # triples and tables of the forward pass: what backward() walks when the gradient of the scores comes from elsewhere
+        # (TorchGraphTaskModel); compute_task_metrics replaces them with the ones it was given
+        self._step = {"h": h, "triples": triples, "tables": batch_features.get("triple_tables")}
+        if labels is None:  # scores only: no triple is counted against an all-zero weight column
+            zeros = torch.zeros(triples.shape[0], dtype=torch.float32, device=h.device)
+            return (self._fused(h, triples, zeros, zeros, need_grad=False)["scores"],)
+        self._step["fused"] = self._fused(h, triples, labels, batch_features.get("triple_weights"))
+        return (self._step["fused"]["scores"],)
+
+    def compute_task_metrics(self, batch_features, task_output, batch_labels) -> Dict[str, torch.Tensor]:
+        """-> "loss", "accuracy" (of this batch's counted triples), "counts" (int64 [4]: tp, fp, tn, fn): device tensors."""
+        step = self._step
+        if step is None:
+            raise RuntimeError("compute_task_metrics() needs the node representations of a forward pass")
+        fused = step.get("fused")
+        labels, weights = batch_labels["triple_labels"], batch_labels.get("triple_weights")
+        if not (fused is not None and task_output[0] is fused["scores"] and labels is fused["labels"]
+                and weights is fused["weights"] and batch_labels["triples"] is fused["triples"]):
+            fused = self._fused(step["h"], batch_labels["triples"], labels, weights)
+        step["dloss"] = fused["gscore"]
+        step["triples"], step["tables"] = fused["triples"], batch_labels.get("triple_tables")
+        return {"loss": fused["metrics"][0], "accuracy": fused["metrics"][1], "counts": fused["counts"]}
+
+    def compute_epoch_metrics(self, task_results: List[Any]) -> Tuple[float, str]:
+        """Correct predictions over counted triples, from the summed confusion counts; the smaller the better: -accuracy."""
+        tp, fp, tn, fn = (sum(int(r["counts"][i]) for r in task_results) for i in range(4))
+        total = tp + fp + tn + fn
+        epoch_acc = float(tp + tn) / float(total) if total else float("nan")
+        return -epoch_acc, f"Accuracy = {epoch_acc:.3f}"
+
+    def _task_backward(self):
+        s = self._step
+        if s.get("tables") is None:
+            raise RuntimeError("backward() needs batch_labels['triple_tables'] (ops.build_triple_tables, on the device)")
+        d_h, d_r = ops.distmult_backward(s["h"], self._relation_embeddings.value, s["triples"], s["dloss"], s["tables"])
+        self._relation_embeddings.grad = d_r
+        if self._use_intermediate_gnn_results:
+            return d_h, [None] * (int(self._params["gnn_num_layers"]) + 1)
+        return d_h, None
+
+    def rank_counts(self, batch_features, batch_labels) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(greater, equal) of tfgnn_distmult_rank for the batch's ``positive_triples``, filtered by ``rank_filters``: the
+        queries with the target corrupted, then the same queries with the source corrupted (int32 [2 P] each, on the device)."""
+        h = self._final(self.compute_final_node_representations(batch_features, training=False))
+        greater, equal = [], []
+        for side in ("dst", "src"):
+            offsets, ids = batch_labels["rank_filters"][side]
+            g, e = ops.distmult_rank(h, self._relation_embeddings.value, batch_labels["positive_triples"], side, offsets, ids)
+            greater.append(g)
+            equal.append(e)
+        return torch.cat(greater), torch.cat(equal)
+
+    def evaluate_model(self, dataset) -> Dict[str, float]:
+        """-> mrr, hits@1, hits@3, hits@10 (utils/eval_metrics.py ranking_metrics) of the fold's true triples: filtered ranking
+        - every known true triple of the loaded folds is left out of the candidates - with both sides corrupted in turn."""
+        if not self.built:
+            raise RuntimeError("evaluate_model() needs a built model")
+        greater, equal = [], []
+        for batch_features, batch_labels in dataset:
+            g, e = self.rank_counts(batch_features, batch_labels)
+            greater.append(g)
+            equal.append(e)
+        return eval_metrics.ranking_metrics(torch.cat(greater).cpu().numpy(), torch.cat(equal).cpu().numpy())
+
+
 def _regression_task_metrics(task, task_output, batch_features, batch_labels):
     """graph_regression_task.py:150-166 / qm9_regression.py:116-130."""
     metrics, dpred = ops.regression_metrics(task_output, batch_labels["target_value"])

@@ -131,6 +131,27 @@ def multiclass_metrics(labels, predictions, num_classes: int, weights=None) -> D
     return {"acc": float(np.mean(p == y)), "macro_f1": float(np.mean(f1))}
 
 
+# ---- ranking ------------------------------------------------------------------------------------------------------------
+def ranking_metrics(greater, equal) -> Dict[str, float]:
+    """What LinkPredictionTask.evaluate_model reports from the counts of tfgnn_distmult_rank (include/tfgnn.h): per query the
+    number of candidates scoring above the true triple (``greater``) and exactly as it (``equal``).  The rank of a query is
+    1 + greater + equal / 2 - ties split evenly, so a model that scores everything alike ranks in the middle, not first.
+    ``mrr``: the mean of 1 / rank; ``hits@k`` (k = 1, 3, 10): the share of queries with rank <= k.  ``nan`` without a query."""
+    g = np.asarray(greater, dtype=np.float64).reshape(-1)
+    e = np.asarray(equal, dtype=np.float64).reshape(-1)
+    if g.shape != e.shape:
+        raise ValueError(f"greater {g.shape} and equal {e.shape} differ in length")
+    if g.size and (g.min() < 0 or e.min() < 0):
+        raise ValueError("negative count")
+    if g.size == 0:
+        return {"mrr": float("nan"), "hits@1": float("nan"), "hits@3": float("nan"), "hits@10": float("nan")}
+    rank = 1.0 + g + e / 2.0
+    out = {"mrr": float(np.mean(1.0 / rank))}
+    for k in (1, 3, 10):
+        out[f"hits@{k}"] = float(np.mean(rank <= k))
+    return out
+
+
 # ---- regression --------------------------------------------------------------------------------------------------------
 def _one_minus_ratio(num: float, den: float) -> float:
     """1 - num / den; for a constant target (den = 0) a perfect fit scores 1.0 and anything else 0.0, scikit-learn's

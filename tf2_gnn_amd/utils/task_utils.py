@@ -4,9 +4,10 @@ from __future__ import annotations
 
 from typing import Any, Dict, Iterable, NamedTuple, Tuple, Type
 
-from ..data import GraphDataset, JsonLGraphPropertyDataset, NodeClassificationDataset, PPIDataset, QM9Dataset
-from ..tasks import (GraphBinaryClassificationTask, GraphRegressionTask, GraphTaskModel, NodeClassificationTask, NodeMulticlassTask,
-                     QM9RegressionTask)
+from ..data import (GraphDataset, JsonLGraphPropertyDataset, LinkPredictionDataset, NodeClassificationDataset, PPIDataset,
+                    QM9Dataset)
+from ..tasks import (GraphBinaryClassificationTask, GraphRegressionTask, GraphTaskModel, LinkPredictionTask, NodeClassificationTask,
+                     NodeMulticlassTask, QM9RegressionTask)
 
 
 class TaskInfo(NamedTuple):
@@ -73,6 +74,12 @@ def register_node_classification_task() -> None:
     """One class per node with fold masks over one graph.  The reference has no such task, so it is not among the
     defaults: whoever wants it by name registers it."""
     register_task("NodeClassification", NodeClassificationDataset, {}, NodeClassificationTask, {})
+
+
+def register_link_prediction_task() -> None:
+    """Typed-edge scoring with a DistMult decoder over one graph.  The reference has no such task, so it is not among the
+    defaults: whoever wants it by name registers it."""
+    register_task("LinkPrediction", LinkPredictionDataset, {}, LinkPredictionTask, {})
 
 
 register_default_tasks()
