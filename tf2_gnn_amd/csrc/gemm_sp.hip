@@ -522,6 +522,18 @@ __global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(S
     cfac[c] = g.b_inv ? g.b_inv[grp * g.group_stride_scale + col] : 1.f;
     cbias[c] = g.bias ? g.bias[grp * g.group_stride_scale + col] : 0.f;
   }
+  // output row of row `lane` of this wave's 64 rows (rows past the end clamp to the last one; without a row map the row
+  // itself): loaded here, ahead of the ring's DMAs - the counted vmcnt waits of the main loop see only older loads - and
+  // handed to the epilogue's lanes by a lane exchange.  (Rows fit 32 bits: row_map and tile_table are int32, and 2^31 rows
+  // of 128 columns are more bytes than a device holds.)
+  int wave_row;
+  {
+    const int64_t r = row0 + wm * 64 + lane;
+    const int64_t rc = r < m_end ? r : m_end - 1;
+    wave_row = g.row_map ? g.row_map[rc] : (int)rc;
+  }
+  const int64_t wave_left = m_end - (row0 + wm * 64);
+  const int wave_rows = wave_left < 0 ? 0 : (wave_left < 64 ? (int)wave_left : 64);  // how many of the wave's 64 rows exist
 
   // ---- prologue: three steps in flight, fragments of step 0 in set 0 ----------------------------------------
   constexpr int NR = SpLoop<TNW>::NR;
@@ -612,16 +624,116 @@ __global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(S
   // ---- epilogue ------------------------------------------------------------------------------------------------
   // Scales, bias and activation are applied in the accumulator layout (their operands were fetched before the main
   // loop: column factors / bias per (lane, column tile), row factors by a lane exchange of a_rmax), then a 32-row
-  // block goes through the wave's LDS patch so that every lane stores 16 contiguous bytes; the gradient factors and the
-  // accumulate operand are fetched four float4 ahead of their use.
+  // block goes through the wave's LDS patch so that every lane stores 16 contiguous bytes.  Output rows come from
+  // wave_row by a lane exchange: no index load is left in here.  The gradient factors, the saved tensor and the
+  // accumulate operand are fetched half a row tile (16 rows) at a time, behind the tile's patch phase: one flight holds
+  // every load of the three operands - FL float4 each per lane, issued back to back - and is waited for once; act'(saved)
+  // is one wave-uniform dispatch per flight.  (A whole tile per flight, or a flight issued above the patch phase, does not
+  // fit: at TNW = 5 three operands of a tile are 240 registers beside the 80 accumulators of the other tile.)
+  // The second row tile's accumulators are held in the accumulation registers while the first tile's epilogue runs (the K
+  // split's additions above would otherwise leave them in VGPRs).
+#pragma unroll
+  for (int c = 0; c < TNW; ++c) asm volatile("" : "+a"(L.acc[1][c]));
+  // The epilogue reads its own arguments again, from the kernel-argument segment (the first explicit argument lies at its
+  // start), through a pointer the compiler cannot see through: loaded at the top with the rest they would sit in SGPRs
+  // across the main loop, and the kernels with both the gradient operands and the split output ran out of them.
+  typedef const __attribute__((address_space(4))) SpArgs* SpArgsK;
+  SpArgsK ep = (SpArgsK)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(ep));
+  const __attribute__((address_space(4))) SpArgs& e = *ep;
   float* patch = reinterpret_cast<float*>(lds) + wave * 32 * G::PATCH_LD;
   const int64_t wcol0 = col0 + wn * 32 * TNW;
-  const DropoutKey dkey = g.drop_on == 1 ? dropout_resolve(g.drop) : g.drop;  // the mask of the current epoch (common.hpp)
+  const DropoutKey dkey = e.drop_on == 1 ? dropout_resolve(g.drop) : g.drop;  // the mask of the current epoch (common.hpp)
   constexpr int C4 = 8 * TNW;             // float4 per patch row
   constexpr int NIT = 32 * C4 / 64;       // float4 per lane and row tile
-  static_assert(NIT % 4 == 0, "epilogue chunking");
+  constexpr int FL = NIT / 2;             // float4 per lane and operand in one flight: half a row tile
+  constexpr int QF = FL / TNW;            // OUT_SP: row groups per flight
+  static_assert(NIT % FL == 0 && FL % TNW == 0, "epilogue flights");
   auto epilogue_tile = [&](auto t_c) {
     constexpr int t = decltype(t_c)::value;
+    const int tile_rows = wave_rows - t * 32;  // patch rows below it are rows of the product
+    const float* __restrict__ mulp = e.mul;
+    const float* __restrict__ savp = e.saved;
+    float* __restrict__ cptr = e.C;
+    // float4 `it` of this lane sits at patch row slot_pr(it), float4 column slot_c4(it).  Plain output: consecutive lanes walk
+    // a patch row.  OUT_SP: 8 lanes own a row (TNW float4 each, it = q * TNW + j), four row groups q per 32-row block.
+    // Either way float4 0 .. FL-1 lie in the block's first 16 rows and FL .. NIT-1 in its last 16.
+    auto slot_pr = [&](int it) { return OUT_SP ? (it / TNW) * 8 + (lane >> 3) : (lane + it * 64) / C4; };
+    auto slot_c4 = [&](int it) { return OUT_SP ? (lane & 7) + 8 * (it % TNW) : (lane + it * 64) % C4; };
+    int orow[FL];               // output row of float4 h * FL + i (clamped and mapped: always a row that exists)
+    float4 fm[FL], fs[FL], fo[FL];  // its factor, its saved value (then act' of it) and its accumulate operand
+    auto flight = [&](int h) {  // every operand load of half h: all issued before anything waits for one of them
+#pragma unroll
+      for (int i = 0; i < FL; ++i) {
+        const int it = h * FL + i;
+        orow[i] = (OUT_SP && it % TNW) ? orow[i - it % TNW] : __shfl(wave_row, t * 32 + slot_pr(it), 64);
+      }
+      if (GRAD) {
+        if (mulp) {
+#pragma unroll
+          for (int i = 0; i < FL; ++i)
+            fm[i] = *reinterpret_cast<const float4*>(mulp + (int64_t)orow[i] * e.ld_mul + wcol0 + slot_c4(h * FL + i) * 4);
+        } else {
+#pragma unroll
+          for (int i = 0; i < FL; ++i) fm[i] = float4{1.f, 1.f, 1.f, 1.f};
+        }
+        if (savp) {
+#pragma unroll
+          for (int i = 0; i < FL; ++i)
+            fs[i] = *reinterpret_cast<const float4*>(savp + (int64_t)orow[i] * e.ld_saved + wcol0 + slot_c4(h * FL + i) * 4);
+        } else {
+#pragma unroll
+          for (int i = 0; i < FL; ++i) fs[i] = float4{0.f, 0.f, 0.f, 0.f};
+        }
+      }
+      if (!OUT_SP) {
+        if (e.accumulate) {
+#pragma unroll
+          for (int i = 0; i < FL; ++i)
+            fo[i] = *reinterpret_cast<const float4*>(cptr + (int64_t)orow[i] * e.ldc + wcol0 + slot_c4(h * FL + i) * 4);
+        } else {
+#pragma unroll
+          for (int i = 0; i < FL; ++i) fo[i] = float4{0.f, 0.f, 0.f, 0.f};
+        }
+      }
+    };
+    auto dact_flight = [&]() {  // fs <- act'(saved * saved_scale): one wave-uniform dispatch per flight
+      if (!(GRAD && savp)) return;
+      if (e.saved_scale != 1.f) {
+#pragma unroll
+        for (int i = 0; i < FL; ++i) { fs[i].x *= e.saved_scale; fs[i].y *= e.saved_scale; fs[i].z *= e.saved_scale; fs[i].w *= e.saved_scale; }
+      }
+      auto dact_all = [&](auto act_c) {
+#pragma unroll
+        for (int i = 0; i < FL; ++i) {
+          fs[i].x = act_grad(decltype(act_c)::value, fs[i].x); fs[i].y = act_grad(decltype(act_c)::value, fs[i].y);
+          fs[i].z = act_grad(decltype(act_c)::value, fs[i].z); fs[i].w = act_grad(decltype(act_c)::value, fs[i].w);
+        }
+      };
+      switch (e.dact) {
+        case TFGNN_ACT_RELU: dact_all(std::integral_constant<int, TFGNN_ACT_RELU>{}); break;
+        case TFGNN_ACT_TANH: dact_all(std::integral_constant<int, TFGNN_ACT_TANH>{}); break;
+        case TFGNN_ACT_LEAKY_RELU: dact_all(std::integral_constant<int, TFGNN_ACT_LEAKY_RELU>{}); break;
+        case TFGNN_ACT_ELU: dact_all(std::integral_constant<int, TFGNN_ACT_ELU>{}); break;
+        case TFGNN_ACT_SELU: dact_all(std::integral_constant<int, TFGNN_ACT_SELU>{}); break;
+        case TFGNN_ACT_GELU: dact_all(std::integral_constant<int, TFGNN_ACT_GELU>{}); break;
+        case TFGNN_ACT_SIGMOID: dact_all(std::integral_constant<int, TFGNN_ACT_SIGMOID>{}); break;
+        default: dact_all(std::integral_constant<int, TFGNN_ACT_NONE>{}); break;
+      }
+    };
+    auto factors = [&](int h, int i, float4 w) {  // the gradient factors and the dropout of float4 h * FL + i, in their order
+      if (GRAD) {
+        w.x *= fm[i].x; w.y *= fm[i].y; w.z *= fm[i].z; w.w *= fm[i].w;
+        if (savp) { w.x *= fs[i].x; w.y *= fs[i].y; w.z *= fs[i].z; w.w *= fs[i].w; }
+      }
+      if (e.drop_on == 1) {
+        const float4 dm = dropout_mask4(dkey, (uint64_t)((int64_t)orow[i] * e.drop_ld + wcol0 + slot_c4(h * FL + i) * 4));  // N % 4 == 0
+        w.x *= dm.x; w.y *= dm.y; w.z *= dm.z; w.w *= dm.w;
+      } else if (e.drop_on == 2) {  // the mask is in the saved tensor (see SpArgs)
+        w.x *= g.drop.scale; w.y *= g.drop.scale; w.z *= g.drop.scale; w.w *= g.drop.scale;
+      }
+      return w;
+    };
     float rf[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) rf[r] = __shfl(L.a_rmax[t], (r & 3) + 8 * (r >> 2) + 4 * kg, 64);
@@ -637,7 +749,7 @@ __global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(S
 #pragma unroll
         for (int r = 0; r < 16; ++r) L.acc[t][c][r] = act_apply(decltype(act_c)::value, L.acc[t][c][r]);
     };
-    switch (g.act) {
+    switch (e.act) {
       case TFGNN_ACT_RELU: act_tile(std::integral_constant<int, TFGNN_ACT_RELU>{}); break;
       case TFGNN_ACT_TANH: act_tile(std::integral_constant<int, TFGNN_ACT_TANH>{}); break;
       case TFGNN_ACT_LEAKY_RELU: act_tile(std::integral_constant<int, TFGNN_ACT_LEAKY_RELU>{}); break;
@@ -655,10 +767,6 @@ __global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(S
         patch[prow * G::PATCH_LD + c * 32 + fi] = L.acc[t][c][r];
       }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    const int64_t wrow0 = row0 + wm * 64 + t * 32;
-    const float* __restrict__ mulp = g.mul;
-    const float* __restrict__ savp = g.saved;
-    float* __restrict__ cptr = g.C;
     if constexpr (OUT_SP) {
       // The result as a split operand of the next product (one scale per row): 8 lanes own a row of this wave's
       // 32 TNW columns (TNW float4 each), four row groups per 32-row block; the row maximum of the FINAL values (after
@@ -668,70 +776,28 @@ __global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(S
       const int rgrp = lane >> 3, l8 = lane & 7;
       float4 w[4][TNW];
       float rmax[4];
-      bool okq[4];
       int64_t rowq[4];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int pr = q * 8 + rgrp;
-        const int64_t row = wrow0 + pr;
-        okq[q] = row < m_end;
-        rowq[q] = okq[q] ? row : m_end - 1;
-        if (g.row_map) rowq[q] = g.row_map[rowq[q]];
-        float4 m[TNW], sv[TNW];
+      for (int h = 0; h < NIT / FL; ++h) {
+        flight(h);
+        dact_flight();
 #pragma unroll
-        for (int j = 0; j < TNW; ++j) {
-          const int c4 = l8 + 8 * j;
-          const int64_t col = wcol0 + c4 * 4;
-          w[q][j] = *reinterpret_cast<const float4*>(patch + pr * G::PATCH_LD + c4 * 4);
-          if (GRAD) {
-            m[j] = mulp ? *reinterpret_cast<const float4*>(mulp + rowq[q] * g.ld_mul + col) : float4{1.f, 1.f, 1.f, 1.f};
-            sv[j] = savp ? *reinterpret_cast<const float4*>(savp + rowq[q] * g.ld_saved + col) : float4{0.f, 0.f, 0.f, 0.f};
+        for (int q = QF * h; q < QF * h + QF; ++q) {
+          const int pr = q * 8 + rgrp;
+          rowq[q] = orow[(q - QF * h) * TNW];
+          float mx = 0.f;
+#pragma unroll
+          for (int j = 0; j < TNW; ++j) {
+            w[q][j] = factors(h, (q - QF * h) * TNW + j, *reinterpret_cast<const float4*>(patch + pr * G::PATCH_LD + (l8 + 8 * j) * 4));
+            mx = fmaxf(mx, fmaxf(fmaxf(fabsf(w[q][j].x), fabsf(w[q][j].y)), fmaxf(fabsf(w[q][j].z), fabsf(w[q][j].w))));
+            if (w[q][j].x != w[q][j].x || w[q][j].y != w[q][j].y || w[q][j].z != w[q][j].z || w[q][j].w != w[q][j].w)
+              mx = __builtin_inff();
           }
+#pragma unroll
+          for (int o = 4; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+          rmax[q] = mx;
+          if (l8 == 0) xmax[wave * 32 + pr] = mx;
         }
-        if (GRAD && savp) {
-          if (g.saved_scale != 1.f) {
-#pragma unroll
-            for (int j = 0; j < TNW; ++j) { sv[j].x *= g.saved_scale; sv[j].y *= g.saved_scale; sv[j].z *= g.saved_scale; sv[j].w *= g.saved_scale; }
-          }
-          auto dact_row = [&](auto act_c) {
-#pragma unroll
-            for (int j = 0; j < TNW; ++j) {
-              sv[j].x = act_grad(decltype(act_c)::value, sv[j].x); sv[j].y = act_grad(decltype(act_c)::value, sv[j].y);
-              sv[j].z = act_grad(decltype(act_c)::value, sv[j].z); sv[j].w = act_grad(decltype(act_c)::value, sv[j].w);
-            }
-          };
-          switch (g.dact) {
-            case TFGNN_ACT_RELU: dact_row(std::integral_constant<int, TFGNN_ACT_RELU>{}); break;
-            case TFGNN_ACT_TANH: dact_row(std::integral_constant<int, TFGNN_ACT_TANH>{}); break;
-            case TFGNN_ACT_LEAKY_RELU: dact_row(std::integral_constant<int, TFGNN_ACT_LEAKY_RELU>{}); break;
-            case TFGNN_ACT_ELU: dact_row(std::integral_constant<int, TFGNN_ACT_ELU>{}); break;
-            case TFGNN_ACT_SELU: dact_row(std::integral_constant<int, TFGNN_ACT_SELU>{}); break;
-            case TFGNN_ACT_GELU: dact_row(std::integral_constant<int, TFGNN_ACT_GELU>{}); break;
-            case TFGNN_ACT_SIGMOID: dact_row(std::integral_constant<int, TFGNN_ACT_SIGMOID>{}); break;
-            default: dact_row(std::integral_constant<int, TFGNN_ACT_NONE>{}); break;
-          }
-        }
-        float mx = 0.f;
-#pragma unroll
-        for (int j = 0; j < TNW; ++j) {
-          if (GRAD) {
-            w[q][j].x *= m[j].x; w[q][j].y *= m[j].y; w[q][j].z *= m[j].z; w[q][j].w *= m[j].w;
-            if (savp) { w[q][j].x *= sv[j].x; w[q][j].y *= sv[j].y; w[q][j].z *= sv[j].z; w[q][j].w *= sv[j].w; }
-          }
-          if (g.drop_on == 1) {
-            const float4 dm = dropout_mask4(dkey, (uint64_t)(rowq[q] * g.drop_ld + wcol0 + (l8 + 8 * j) * 4));  // N % 4 == 0
-            w[q][j].x *= dm.x; w[q][j].y *= dm.y; w[q][j].z *= dm.z; w[q][j].w *= dm.w;
-          } else if (g.drop_on == 2) {  // the mask is in the saved tensor (see SpArgs)
-            w[q][j].x *= g.drop.scale; w[q][j].y *= g.drop.scale; w[q][j].z *= g.drop.scale; w[q][j].w *= g.drop.scale;
-          }
-          mx = fmaxf(mx, fmaxf(fmaxf(fabsf(w[q][j].x), fabsf(w[q][j].y)), fmaxf(fabsf(w[q][j].z), fabsf(w[q][j].w))));
-          if (w[q][j].x != w[q][j].x || w[q][j].y != w[q][j].y || w[q][j].z != w[q][j].z || w[q][j].w != w[q][j].w)
-            mx = __builtin_inff();
-        }
-#pragma unroll
-        for (int o = 4; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-        rmax[q] = mx;
-        if (l8 == 0) xmax[wave * 32 + pr] = mx;
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();  // all four waves run the two row tiles in step
@@ -741,13 +807,13 @@ __global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(S
         const float full = fmaxf(rmax[q], xmax[(wave ^ 1) * 32 + pr]);  // the wave with the other column half: same wm
         float iv;
         const float sc = sp_scale_for_max(full, &iv);
-        if (okq[q]) {
-          if (wn == 0 && l8 == 0) g.out_inv[rowq[q] * g.n_tiles + tile_n] = iv;  // one scale per row and column tile
-          uint8_t* drow = g.out_sp + rowq[q] * g.ld_out_sp;
+        if (pr < tile_rows) {
+          if (wn == 0 && l8 == 0) e.out_inv[rowq[q] * e.n_tiles + tile_n] = iv;  // one scale per row and column tile
+          uint8_t* drow = e.out_sp + rowq[q] * e.ld_out_sp;
 #pragma unroll
           for (int j = 0; j < TNW; ++j) {
             const int64_t col = wcol0 + (l8 + 8 * j) * 4;
-            if (cptr) *reinterpret_cast<float4*>(cptr + rowq[q] * g.ldc + col) = w[q][j];
+            if (cptr) *reinterpret_cast<float4*>(cptr + rowq[q] * e.ldc + col) = w[q][j];
             sp_store4(drow, col, w[q][j], sc);
           }
         }
@@ -756,65 +822,16 @@ __global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(S
       return;
     }
 #pragma unroll
-    for (int it0 = 0; it0 < NIT; it0 += 4) {
-      float4 v[4], m[4], sv[4], o[4];
-      bool ok[4];
-      int64_t coff[4], doff[4];
+    for (int h = 0; h < NIT / FL; ++h) {
+      flight(h);
+      dact_flight();
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int idx = lane + (it0 + j) * 64;
-        const int pr = idx / C4, c4 = idx - pr * C4;
-        const int64_t row = wrow0 + pr, col = wcol0 + c4 * 4;
-        ok[j] = row < m_end;
-        int64_t rr = ok[j] ? row : m_end - 1;
-        if (g.row_map) rr = g.row_map[rr];
-        coff[j] = rr * g.ldc + col;
-        doff[j] = rr * g.drop_ld + col;
-        v[j] = *reinterpret_cast<const float4*>(patch + pr * G::PATCH_LD + c4 * 4);
-        if (GRAD) {
-          m[j] = mulp ? *reinterpret_cast<const float4*>(mulp + rr * g.ld_mul + col) : float4{1.f, 1.f, 1.f, 1.f};
-          if (savp) sv[j] = *reinterpret_cast<const float4*>(savp + rr * g.ld_saved + col);
-        }
-        if (g.accumulate) o[j] = *reinterpret_cast<const float4*>(cptr + coff[j]);
-      }
-      if (GRAD && savp) {  // sv <- act'(saved), one dispatch per four float4
-        if (g.saved_scale != 1.f) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) { sv[j].x *= g.saved_scale; sv[j].y *= g.saved_scale; sv[j].z *= g.saved_scale; sv[j].w *= g.saved_scale; }
-        }
-        auto dact_chunk = [&](auto act_c) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            sv[j].x = act_grad(decltype(act_c)::value, sv[j].x); sv[j].y = act_grad(decltype(act_c)::value, sv[j].y);
-            sv[j].z = act_grad(decltype(act_c)::value, sv[j].z); sv[j].w = act_grad(decltype(act_c)::value, sv[j].w);
-          }
-        };
-        switch (g.dact) {
-          case TFGNN_ACT_RELU: dact_chunk(std::integral_constant<int, TFGNN_ACT_RELU>{}); break;
-          case TFGNN_ACT_TANH: dact_chunk(std::integral_constant<int, TFGNN_ACT_TANH>{}); break;
-          case TFGNN_ACT_LEAKY_RELU: dact_chunk(std::integral_constant<int, TFGNN_ACT_LEAKY_RELU>{}); break;
-          case TFGNN_ACT_ELU: dact_chunk(std::integral_constant<int, TFGNN_ACT_ELU>{}); break;
-          case TFGNN_ACT_SELU: dact_chunk(std::integral_constant<int, TFGNN_ACT_SELU>{}); break;
-          case TFGNN_ACT_GELU: dact_chunk(std::integral_constant<int, TFGNN_ACT_GELU>{}); break;
-          case TFGNN_ACT_SIGMOID: dact_chunk(std::integral_constant<int, TFGNN_ACT_SIGMOID>{}); break;
-          default: dact_chunk(std::integral_constant<int, TFGNN_ACT_NONE>{}); break;
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float4 w = v[j];
-        if (GRAD) {
-          w.x *= m[j].x; w.y *= m[j].y; w.z *= m[j].z; w.w *= m[j].w;
-          if (savp) { w.x *= sv[j].x; w.y *= sv[j].y; w.z *= sv[j].z; w.w *= sv[j].w; }
-        }
-        if (g.drop_on == 1) {
-          const float4 dm = dropout_mask4(dkey, (uint64_t)doff[j]);
-          w.x *= dm.x; w.y *= dm.y; w.z *= dm.z; w.w *= dm.w;
-        } else if (g.drop_on == 2) {
-          w.x *= g.drop.scale; w.y *= g.drop.scale; w.z *= g.drop.scale; w.w *= g.drop.scale;
-        }
-        if (g.accumulate) { w.x += o[j].x; w.y += o[j].y; w.z += o[j].z; w.w += o[j].w; }
-        if (ok[j]) *reinterpret_cast<float4*>(cptr + coff[j]) = w;
+      for (int i = 0; i < FL; ++i) {
+        const int it = h * FL + i;
+        float4 w = factors(h, i, *reinterpret_cast<const float4*>(patch + slot_pr(it) * G::PATCH_LD + slot_c4(it) * 4));
+        if (e.accumulate) { w.x += fo[i].x; w.y += fo[i].y; w.z += fo[i].z; w.w += fo[i].w; }
+        if (slot_pr(it) < tile_rows)
+          *reinterpret_cast<float4*>(cptr + (int64_t)orow[i] * e.ldc + wcol0 + slot_c4(it) * 4) = w;
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
