@@ -18,8 +18,9 @@
 // (fp32), SB = columns per scale block (a multiple of 16; SB = C: one scale per row).
 //
 // NT kernel (both operands K-contiguous: activations [M, K] against weights kept as [N, K]):
-//   128 x BN output tile per 256-thread workgroup (BN = 320 / 256 / 128), one wave per SIMD, each wave a
-//   64 x BN/2 block of 32x32 MFMA tiles (160 accumulator registers at BN = 320).  K advances in steps of 16 (one
+//   128 x BN output tile per workgroup (BN = 320 / 256 / 128).  BN = 256 / 128: 256 threads, one wave per SIMD, each wave a
+//   64 x BN/2 block of 32x32 MFMA tiles.  BN = 320: 512 threads, two waves per SIMD, each wave 32 x 160 (80 accumulator
+//   registers, architectural VGPRs), the ring's DMAs issued every other step for two steps.  K advances in steps of 16 (one
 //   MFMA k-step = one granule per row); a ring of five or six LDS stages is filled by LDS-DMA only
 //   (buffer_load_dwordx4 ... lds: no VALU, no registers), four or five steps ahead; the per-lane SOURCE address is
 //   permuted so that the lane-linear LDS image is XOR-swizzled and every ds_read_b128 fragment read is
@@ -110,7 +111,7 @@ struct SpArgs {
   // multiplies 1/S of the tile's k16 steps; splits 1 .. S-1 publish their raw accumulators (write-through stores into
   // ws_partial + a flag word), split 0 adds them IN SPLIT ORDER (bit-reproducible) and runs the one epilogue.
   int ksplit;
-  float* ws_partial;    // [tiles][S - 1][4 waves x 2 x TNW x 16 x 64 floats]
+  float* ws_partial;    // [tiles][S - 1][NW waves x TM x TNW x 16 x 64 floats] (128 x BN floats per slab at either geometry)
   unsigned* ws_flags;   // [tiles][S - 1], zero when the kernel starts (split 0 clears what it consumed)
   int* ws_timeout;      // host-mapped: set to 1 if a reducer gave up waiting (never expected; the result is then wrong)
   // XCD-aware tile order (round 6, products over several column tiles: N = 512 / 1024).  Workgroup b runs on XCD b % 8; with
@@ -186,15 +187,32 @@ __global__ void __launch_bounds__(256) sp_split_cols_kernel(const float* __restr
 // ------------------------------------------------------------------------------------------------------
 // NT kernel
 // ------------------------------------------------------------------------------------------------------
+// Row tiles of 32 rows per wave of the NT kernel.  BN = 320 (round 10): one - eight waves of 32 x 160, two per SIMD (<= 256
+// registers each), so that one wave's epilogue loads and LDS exchanges run under the other's arithmetic (tools/nt8_probe.hip
+// V2).  BN = 256 / 128 stay on four waves of 64 x BN/2 (BN = 128 already runs two workgroups per CU).
 template <int TNW>
+constexpr int sp_nt_tm = TNW == 5 ? 1 : 2;
+
+template <int TNW, int TM = 2>
 struct SpGeo {
   static constexpr int BN = 64 * TNW;
   static constexpr int ROWS = SP_BM + BN;      // rows per stage
   static constexpr int STG = ROWS * 64;        // bytes per stage
-  static constexpr int ND_A = 2;               // DMA instructions per wave and step for A (8 x 16 rows / 4 waves)
-  static constexpr int ND_B = TNW;             // ... for B (4 TNW x 16 rows / 4 waves)
+  static constexpr int NW = 8 / TM;            // waves per workgroup: wave (wm, wn) owns rows wm * 32 TM .., columns wn * BN/2 ..
+  static constexpr int NT = 64 * NW;           // threads
+  static constexpr int ND_A = 8 / NW;          // whole DMA units (16 rows x 64 bytes) per wave and step for A (8 units)
+  static constexpr int ND_B = 4 * TNW / NW;    // ... for B (4 TNW units)
   static constexpr int ND = ND_A + ND_B;
-  static constexpr int PATCH_LD = 32 * TNW + 4;  // floats per patch row (wave-private epilogue patch: 32 rows)
+  // TM = 1: the DMAs are issued every OTHER step for two steps - both 64-byte halves of a 128-byte line back to back - and
+  // the B units left over (4 at TNW = 5) are shared by wave pairs: wave 2j fetches unit NW ND_B + j for the first step of the
+  // pair, wave 2j + 1 for the second
+  static constexpr bool PAIR = TM == 1;
+  static constexpr bool SHARED = (4 * TNW) % NW != 0;
+  static constexpr int NI = PAIR ? 2 * ND + (SHARED ? 1 : 0) : ND;  // DMA instructions per wave and issuing step
+  static_assert(!SHARED || (PAIR && 4 * TNW - NW * ND_B == NW / 2), "left-over units go to wave pairs");
+  static constexpr int PATCH_ROWS = 16 * TM;     // rows of the wave-private epilogue patch: a wave's 32-row tile goes through
+                                                 // it in 32 / PATCH_ROWS rounds (eight 32-row patches do not fit the ring)
+  static constexpr int PATCH_LD = 32 * TNW + 4;  // floats per patch row
   // LDS ring: one k16 step per stage, as many stages as 160 KB hold (at most 6).  The DMA of a step is issued NST-1
   // steps before the step and has to have landed two steps before it: NST - 3 steps (and the rest of the issuing
   // one) cover its latency - ~1 us under load, a step is ~0.45 us (with four stages the loop waited for its DMAs).
@@ -204,29 +222,34 @@ struct SpGeo {
   static constexpr int NST_MAX = TNW == 2 ? 4 : 6;
   static constexpr int NST = (163840 / STG) < NST_MAX ? (163840 / STG) : NST_MAX;
   static constexpr int UNR = NST % 2 == 0 ? NST : 2 * NST;  // steps per unrolled loop body (register sets alternate)
-  static constexpr int VMW = (NST - 3) * ND;                // DMAs that may still be in flight at the end of a step
+  // DMAs that may still be in flight at the end of a step (pair issue: only the pair issued in this or the previous step)
+  static constexpr int VMW = PAIR ? NI : (NST - 3) * ND;
   static constexpr int LDS_BYTES = NST * STG;
   static_assert(NST >= 4 && VMW < 64, "ring depth");
-  static_assert(4 * 32 * PATCH_LD * 4 <= LDS_BYTES, "epilogue patch must fit the ring");
+  static_assert(!PAIR || NST % 2 == 1, "pair issue fills the ring NST - 1 steps ahead, two steps at a time");
+  static_assert(NW * PATCH_ROWS * PATCH_LD * 4 + TM * NW * 32 * 4 <= LDS_BYTES, "epilogue patch and row maxima must fit the ring");
 };
 
 // Register state of the main loop.  The loop is pinned instruction by instruction with small volatile asm statements
 // (hipcc's scheduler otherwise sinks the fragment reads to their uses and puts dependent MFMAs back to back); the
 // member templates have every index as a template argument so that each operand is a fixed register.
-template <int TNW>
+template <int TNW, int TM>
 struct SpLoop {
-  using G = SpGeo<TNW>;
+  using G = SpGeo<TNW, TM>;
   // references to arrays that live in the kernel's frame (one alloca each: the optimizer's scalar replacement gives
   // up on one big aggregate with this many uses and would keep the whole state in scratch memory)
-  half8 (&fa)[2][2][2];    // [set][row tile][plane]
+  half8 (&fa)[2][TM][2];   // [set][row tile][plane]
   half8 (&fb)[2][TNW][2];  // [set][col tile][plane]
-  floatx16 (&acc)[2][TNW];  // one accumulator for the three piece products (tools/mfma_acc_probe.hip, K = 1280: rms
+  floatx16 (&acc)[TM][TNW];  // one accumulator for the three piece products (tools/mfma_acc_probe.hip, K = 1280: rms
                             // accumulation error 7.0e-7, fp32-MFMA chain 1.14e-6, bf16x3 9.8e-7; a second accumulator for
                             // the l*h + h*l terms would give 4.1e-7 but 320 accumulator registers exceed the 256 AGPRs)
   unsigned (&a_addr)[G::NST][2], (&b_addr)[G::NST][2];  // LDS byte address of this lane's fragment slot per stage / plane
-  unsigned (&voff_a)[G::ND_A], (&voff_b)[G::ND_B];      // DMA source offsets of this lane
+  static constexpr int NVB = G::ND_B + (G::SHARED ? 1 : 0);
+  unsigned (&voff_a)[G::ND_A], (&voff_b)[NVB];          // DMA source offsets of this lane (the last of B: the shared unit)
   uint4v rs_a, rs_b;       // buffer descriptors of this tile's A / B rows (wave-uniform)
   unsigned m0_a, m0_b;     // LDS byte address of this wave's first DMA slot in stage 0 (A part / B part)
+  unsigned m0_s;           // ... of the B unit it shares with its neighbour wave, which of the pair's two steps it fetches
+  int half_s;
   int nsteps;
   // zero-block skipping: logical step s = (position q in the tile's list of non-empty blocks, step r inside the block) runs
   // physical step blk[q] * bsteps + r (blk: 4 bits each).  bsteps == 0: identity.  brecip = ceil(2^16 / bsteps): s / bsteps
@@ -239,28 +262,33 @@ struct SpLoop {
     const unsigned q = (s * brecip) >> 16;
     return ((blkmap >> (4u * q)) & 15u) * bsteps + (s - q * bsteps);
   }
-  __device__ __forceinline__ SpLoop(half8 (&fa_)[2][2][2], half8 (&fb_)[2][TNW][2], floatx16 (&acc_)[2][TNW],
+  __device__ __forceinline__ SpLoop(half8 (&fa_)[2][TM][2], half8 (&fb_)[2][TNW][2], floatx16 (&acc_)[TM][TNW],
                                     unsigned (&aa)[G::NST][2], unsigned (&ba)[G::NST][2], unsigned (&va)[G::ND_A],
-                                    unsigned (&vb)[G::ND_B])
+                                    unsigned (&vb)[NVB])
       : fa(fa_), fb(fb_), acc(acc_), a_addr(aa), b_addr(ba), voff_a(va), voff_b(vb) {}
 
   template <int I, int SET, int ST>
   __device__ __forceinline__ void read_one() {
-    if constexpr (I < 4) {
+    if constexpr (I < 2 * TM) {
       constexpr int t = I >> 1, p = I & 1;
       asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fa[SET][t][p]) : "v"(a_addr[ST][p]), "n"(t * 2048) : "memory");
     } else {
-      constexpr int c = (I - 4) >> 1, p = (I - 4) & 1;
+      constexpr int c = (I - 2 * TM) >> 1, p = (I - 2 * TM) & 1;
       asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fb[SET][c][p]) : "v"(b_addr[ST][p]), "n"(c * 2048) : "memory");
     }
   }
-  // MFMA order: the three piece products (l*h, h*l, h*h) each over all 2 x TNW tiles - consecutive MFMAs never share
+  // MFMA order: the three piece products (l*h, h*l, h*h) each over all TM x TNW tiles - consecutive MFMAs never share
   // an accumulator; smallest terms first
   template <int I, int SET>
   __device__ __forceinline__ void mfma_one() {
-    constexpr int prod = I / (2 * TNW), j = I % (2 * TNW), t = j / TNW, c = j % TNW;
+    constexpr int prod = I / (TM * TNW), j = I % (TM * TNW), t = j / TNW, c = j % TNW;
     constexpr int pa = prod == 0 ? 1 : 0, pb = prod == 1 ? 1 : 0;
-    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(acc[t][c]) : "v"(fa[SET][t][pa]), "v"(fb[SET][c][pb]));
+    // TM = 1: the accumulators are architectural VGPRs (gfx950 MFMAs take them) - with accumulation registers in the kernel
+    // hipcc splits a 256-register wave 128 + 128, and the loop state beside the 80 accumulators does not fit 128
+    if constexpr (TM == 1)
+      asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc[t][c]) : "v"(fa[SET][t][pa]), "v"(fb[SET][c][pb]));
+    else
+      asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(acc[t][c]) : "v"(fa[SET][t][pa]), "v"(fb[SET][c][pb]));
   }
   // steps past the end of K re-load the last step into a stage nobody reads any more: the count of outstanding DMAs
   // per step stays constant, which is what the counted vmcnt waits rely on
@@ -277,6 +305,46 @@ struct SpLoop {
       asm volatile("s_add_u32 m0, %0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds"
                    :: "s"(m0_b), "n"(ST * G::STG + SP_BM * 64 + (I - G::ND_A) * 1024), "v"(voff_b[I - G::ND_A]), "s"(rs_b), "s"(so)
                    : "memory");
+  }
+  // Pair issue (G::PAIR): instruction J of the issuing step `step` (the one being multiplied, S = step mod UNR).  Whole unit
+  // J / 2 is fetched for step + NST - 1 (J even) and for step + NST (J odd: into the stage of `step` itself - its fragments are
+  // in registers); the last instruction fetches the shared unit for one of the two (half_s).  pair_offsets(step) first: the
+  // source offsets of the two steps, once for the seven instructions
+  unsigned so_pair[2];
+  __device__ __forceinline__ void pair_offsets(int step) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int tgt = step + G::NST - 1 + h;
+      so_pair[h] = phys_step((unsigned)(tgt < nsteps ? tgt : nsteps - 1)) * 64u;
+    }
+  }
+  template <int J, int S>
+  __device__ __forceinline__ void dma_pair() {
+    constexpr int ST0 = (S + G::NST - 1) % G::NST, ST1 = S % G::NST;
+    if constexpr (J < 2 * G::ND) {
+      constexpr int U = J / 2, ST = (J & 1) ? ST1 : ST0;
+      const unsigned so = so_pair[J & 1];
+      if constexpr (U < G::ND_A)
+        asm volatile("s_add_u32 m0, %0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds"
+                     :: "s"(m0_a), "n"(ST * G::STG + U * 1024), "v"(voff_a[U]), "s"(rs_a), "s"(so) : "memory", "scc");
+      else
+        asm volatile("s_add_u32 m0, %0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds"
+                     :: "s"(m0_b), "n"(ST * G::STG + SP_BM * 64 + (U - G::ND_A) * 1024), "v"(voff_b[U - G::ND_A]), "s"(rs_b), "s"(so)
+                     : "memory", "scc");
+    } else {
+      // (s_add_u32 writes SCC: the statements above name it, or the selects below would be split round them)
+      const unsigned so = half_s ? so_pair[1] : so_pair[0];
+      const unsigned m0v = m0_s + (unsigned)(half_s ? ST1 * G::STG : ST0 * G::STG);
+      asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
+                   :: "s"(m0v), "v"(voff_b[NVB - 1]), "s"(rs_b), "s"(so) : "memory");
+    }
+  }
+  template <int J, int S>
+  __device__ __forceinline__ void dma_pair_all() {
+    if constexpr (J < G::NI) {
+      dma_pair<J, S>();
+      dma_pair_all<J + 1, S>();
+    }
   }
   template <int I, int N, int ST>
   __device__ __forceinline__ void dma_all(int step) {
@@ -296,9 +364,9 @@ struct SpLoop {
   // block scaling of A: fragments of scale block b are multiplied by inv[row][b] / max_b inv[row][b] <= 1
   const float* a_inv;
   int a_nblk, a_blk_steps;
-  int64_t a_row[2];
-  float a_rmax[2];
-  half2v afac[2];
+  int64_t a_row[TM];
+  float a_rmax[TM];
+  half2v afac[TM];
   template <int SET>
   __device__ __forceinline__ void scale_frags(int step) {  // plain VALU on the freshly read A fragments
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -308,14 +376,14 @@ struct SpLoop {
       const int b = bsteps ? (int)((blkmap >> (4u * (unsigned)q)) & 15u) : q;
       if (step < nsteps && b < a_nblk) {
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
+        for (int t = 0; t < TM; ++t) {
           const _Float16 f = (_Float16)(a_inv[a_row[t] * a_nblk + b] / a_rmax[t]);  // (a_inv_ld == a_nblk here)
           afac[t] = half2v{f, f};
         }
       }
     }
 #pragma unroll
-    for (int t = 0; t < 2; ++t)
+    for (int t = 0; t < TM; ++t)
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
         half2v* v = reinterpret_cast<half2v*>(&fa[SET][t][p]);
@@ -325,23 +393,36 @@ struct SpLoop {
   }
 
   // one k16 step S (mod UNR; stage S % NST, register set S & 1):  MFMA i (i < NR) + fragment read i of the NEXT step
-  // (other register set);  MFMA NR + i (i < ND) + LDS-DMA i of step s + NST - 1;  the remaining MFMAs bare;
-  // s_waitcnt vmcnt(VMW) lgkmcnt(0) (step s+2 has landed, the fragments of s+1 are in registers);  barrier.
-  static constexpr int NR = 4 + 2 * TNW;  // fragment reads per step
-  static constexpr int NM = 6 * TNW;      // MFMAs per step
-  static_assert(NR + G::ND <= NM, "issue pattern");
+  // (other register set);  MFMA DMA0 + i (i < NI) + LDS-DMA i;  the remaining MFMAs bare;
+  // s_waitcnt vmcnt(VMW) lgkmcnt(0);  barrier.
+  // Single issue (TM = 2): DMA0 = NR - the ND DMAs of step s + NST - 1 follow the reads; at the end of the step, step s + 2
+  // has landed and the fragments of s + 1 are in registers.
+  // Pair issue (TM = 1): the NI DMAs of steps s + NST - 1 and s + NST ride on the last NI MFMAs of the EVEN steps (DMA0 =
+  // NM - NI = 8 at TNW = 5: the first four share their MFMA with the last fragment reads); at the end of every step the pair
+  // issued before the latest one has landed: steps s + 1 .. s + 2 (s even: .. s + 3).  The DMAs of step s + NST go into the
+  // stage of step s itself: every wave read that stage in step s - 1 and passed that step's lgkmcnt(0) and barrier - for
+  // step 0 the kernel's prologue supplies that barrier.
+  static constexpr int NR = 2 * TM + 2 * TNW;  // fragment reads per step
+  static constexpr int NM = 3 * TM * TNW;      // MFMAs per step
+  static constexpr int DMA0 = NM - G::NI < NR ? NM - G::NI : NR;  // first MFMA slot that carries a DMA
+  static_assert(DMA0 >= 0 && DMA0 + G::NI <= NM, "issue pattern");
   template <int S, int I, bool ABLK>
   __device__ __forceinline__ void step_items(int sbase) {
     if constexpr (I < NM) {
       mfma_one<I, (S & 1)>();
       if constexpr (I < NR) read_one<I, ((S + 1) & 1), ((S + 1) % G::NST)>();
-      else if constexpr (I < NR + G::ND) dma_one<I - NR, ((S + G::NST - 1) % G::NST)>(sbase + S + G::NST - 1);
+      if constexpr (G::PAIR) {
+        if constexpr ((S & 1) == 0 && I >= DMA0 && I < DMA0 + G::NI) dma_pair<I - DMA0, S>();
+      } else {
+        if constexpr (I >= DMA0 && I < DMA0 + G::NI) dma_one<I - DMA0, ((S + G::NST - 1) % G::NST)>(sbase + S + G::NST - 1);
+      }
       if constexpr (ABLK && I == NM - 1) scale_frags<((S + 1) & 1)>(sbase + S + 1);  // after the last read was issued
       step_items<S, I + 1, ABLK>(sbase);
     }
   }
   template <int S, bool ABLK>
   __device__ __forceinline__ void step(int sbase) {
+    if constexpr (G::PAIR && (S & 1) == 0) pair_offsets(sbase + S);
     step_items<S, 0, ABLK>(sbase);
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(G::VMW) : "memory");
     __builtin_amdgcn_s_barrier();
@@ -355,7 +436,13 @@ struct SpLoop {
   }
   template <int J>
   __device__ __forceinline__ void dma_prologue() {  // steps 0 .. NST-2 in flight
-    if constexpr (J < G::NST - 1) {
+    if constexpr (G::PAIR) {  // pairs (0, 1), (2, 3), ..: through the "issuing steps" -(NST - 1), -(NST - 1) + 2, ..
+      if constexpr (2 * J < G::NST - 1) {
+        pair_offsets(-(G::NST - 1) + 2 * J);
+        dma_pair_all<0, (G::NST + 1 + 2 * J) % G::UNR>();
+        dma_prologue<J + 1>();
+      }
+    } else if constexpr (J < G::NST - 1) {
       dma_all<0, G::ND, J>(J);
       dma_prologue<J + 1>();
     }
@@ -363,8 +450,10 @@ struct SpLoop {
 };
 
 template <int TNW, bool ABLK, bool GRAD, bool OUT_SP = false>
-__global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(SpArgs g) {  // (BN = 128: two workgroups per CU, see SpGeo::NST)
-  using G = SpGeo<TNW>;
+__global__ void __launch_bounds__((SpGeo<TNW, sp_nt_tm<TNW>>::NT), (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(SpArgs g) {  // (BN = 128: two workgroups per CU, see SpGeo::NST)
+  constexpr int TM = sp_nt_tm<TNW>;
+  using G = SpGeo<TNW, TM>;
+  constexpr int WR = 32 * TM;  // rows per wave
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -450,16 +539,18 @@ __global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(S
   // (a_rows: the descriptor spans the whole operand - its rows come from anywhere; host: M * lda < 2^32)
   const uint4v rs_a = g.a_rows ? make_rsrc(g.A, g.a_src_rows * g.lda) : make_rsrc(g.A + row0 * g.lda, rows_a * g.lda);
   const uint4v rs_b = make_rsrc(g.B + grp * g.group_stride_b + col0 * g.ldb, rows_b * g.ldb);
-  half8 r_fa[2][2][2];
+  half8 r_fa[2][TM][2];
   half8 r_fb[2][TNW][2];
-  floatx16 r_acc[2][TNW];
-  unsigned r_aa[G::NST][2], r_ba[G::NST][2], r_va[G::ND_A], r_vb[G::ND_B];
-  SpLoop<TNW> L(r_fa, r_fb, r_acc, r_aa, r_ba, r_va, r_vb);
+  floatx16 r_acc[TM][TNW];
+  unsigned r_aa[G::NST][2], r_ba[G::NST][2], r_va[G::ND_A], r_vb[SpLoop<TNW, TM>::NVB];
+  SpLoop<TNW, TM> L(r_fa, r_fb, r_acc, r_aa, r_ba, r_va, r_vb);
   L.rs_a = rs_a;
   L.rs_b = rs_b;
   const unsigned lds_base = (unsigned)(uintptr_t)(lds_void*)lds;
   L.m0_a = __builtin_amdgcn_readfirstlane(lds_base + wave * G::ND_A * 1024);
   L.m0_b = __builtin_amdgcn_readfirstlane(lds_base + wave * G::ND_B * 1024);
+  L.m0_s = __builtin_amdgcn_readfirstlane(lds_base + SP_BM * 64 + (G::NW * G::ND_B + (wave >> 1)) * 1024);
+  L.half_s = wave & 1;
   L.nsteps = nsteps;
   L.blkmap = blkmap;
   L.step0 = step0;
@@ -481,6 +572,7 @@ __global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(S
   }
 #pragma unroll
   for (int i = 0; i < G::ND_B; ++i) L.voff_b[i] = (unsigned)(((wave * G::ND_B + i) * 16 + drow) * g.ldb + dq * 16);
+  if constexpr (G::SHARED) L.voff_b[G::ND_B] = (unsigned)(((G::NW * G::ND_B + (wave >> 1)) * 16 + drow) * g.ldb + dq * 16);
 
   // ---- fragment addresses (one base register per stage and operand plane; tiles are immediate offsets) ---------
   const int fi = lane & 31, kg = lane >> 5;
@@ -489,21 +581,21 @@ __global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(S
   for (int st = 0; st < G::NST; ++st)
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
-      L.a_addr[st][p] = (unsigned)(st * G::STG + (wm * 64 + fi) * 64 + (((p * 2 + kg) ^ sw) * 16));
+      L.a_addr[st][p] = (unsigned)(st * G::STG + (wm * WR + fi) * 64 + (((p * 2 + kg) ^ sw) * 16));
       L.b_addr[st][p] = (unsigned)(st * G::STG + SP_BM * 64 + (wn * 32 * TNW + fi) * 64 + (((p * 2 + kg) ^ sw) * 16));
     }
 #pragma unroll
-  for (int t = 0; t < 2; ++t)
+  for (int t = 0; t < TM; ++t)
 #pragma unroll
     for (int c = 0; c < TNW; ++c)
 #pragma unroll
       for (int r = 0; r < 16; ++r) L.acc[t][c][r] = 0.f;
 
   L.a_inv = g.a_inv; L.a_nblk = g.a_nblk; L.a_blk_steps = g.a_blk_steps;
-  L.afac[0] = L.afac[1] = half2v{(_Float16)1.f, (_Float16)1.f};
 #pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    int64_t r = row0 + wm * 64 + t * 32 + fi;
+  for (int t = 0; t < TM; ++t) {
+    L.afac[t] = half2v{(_Float16)1.f, (_Float16)1.f};
+    int64_t r = row0 + wm * WR + t * 32 + fi;
     L.a_row[t] = r < m_end ? r : m_end - 1;
     if (g.a_rows) L.a_row[t] = g.a_rows[L.a_row[t]];  // the scales of the operand row this product row reads
     float m = 1.f;
@@ -522,21 +614,21 @@ __global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(S
     cfac[c] = g.b_inv ? g.b_inv[grp * g.group_stride_scale + col] : 1.f;
     cbias[c] = g.bias ? g.bias[grp * g.group_stride_scale + col] : 0.f;
   }
-  // output row of row `lane` of this wave's 64 rows (rows past the end clamp to the last one; without a row map the row
-  // itself): loaded here, ahead of the ring's DMAs - the counted vmcnt waits of the main loop see only older loads - and
+  // output row of row `lane` (TM = 1: lane % 32) of this wave's WR rows (rows past the end clamp to the last one; without a
+  // row map the row itself): loaded here, ahead of the ring's DMAs - the counted vmcnt waits of the main loop see only older loads - and
   // handed to the epilogue's lanes by a lane exchange.  (Rows fit 32 bits: row_map and tile_table are int32, and 2^31 rows
   // of 128 columns are more bytes than a device holds.)
   int wave_row;
   {
-    const int64_t r = row0 + wm * 64 + lane;
+    const int64_t r = row0 + wm * WR + (lane & (WR - 1));
     const int64_t rc = r < m_end ? r : m_end - 1;
     wave_row = g.row_map ? g.row_map[rc] : (int)rc;
   }
-  const int64_t wave_left = m_end - (row0 + wm * 64);
-  const int wave_rows = wave_left < 0 ? 0 : (wave_left < 64 ? (int)wave_left : 64);  // how many of the wave's 64 rows exist
+  const int64_t wave_left = m_end - (row0 + wm * WR);
+  const int wave_rows = wave_left < 0 ? 0 : (wave_left < WR ? (int)wave_left : WR);  // how many of the wave's WR rows exist
 
-  // ---- prologue: three steps in flight, fragments of step 0 in set 0 ----------------------------------------
-  constexpr int NR = SpLoop<TNW>::NR;
+  // ---- prologue: NST - 1 steps in flight (pair issue: two pairs), fragments of step 0 in set 0 ------------------
+  constexpr int NR = SpLoop<TNW, TM>::NR;
   if (nsteps > 0) {  // (a late K split of a short tile has nothing to multiply: its accumulators stay zero)
     L.template dma_prologue<0>();
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::VMW) : "memory");  // steps 0 and 1 have landed
@@ -544,6 +636,9 @@ __global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(S
     L.template read_all<0, NR, 0, 0>();
     if (ABLK) L.template scale_frags<0>(0);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    // pair issue: step 0 fetches step NST into stage 0 - not before EVERY wave has its fragments of step 0 out of that stage
+    // (the four-wave schedule never writes the stage of the step it multiplies)
+    if constexpr (G::PAIR) __builtin_amdgcn_s_barrier();
 
     for (int s = 0; s < nsteps; s += G::UNR) L.template steps<0, ABLK>(s);
   }
@@ -559,17 +654,17 @@ __global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(S
   // [wave][t][c][q][l] - so every store / load instruction moves 1 KB of consecutive bytes and split 0 adds register to
   // register.  Sum order: own share, then splits 1, 2, ..: fixed, so the result is bit-reproducible.
   if (S > 1) {
-    constexpr int WAVE_F4 = 2 * TNW * 4 * 64;  // float4 per wave and slab
+    constexpr int WAVE_F4 = TM * TNW * 4 * 64;  // float4 per wave and slab (NW waves: 128 x BN floats per slab at either TM)
     const unsigned tile_lin = bid;
     auto make_rsrc_ws = [](const float* ptr, int bytes) {  // raw buffer over one wave's share of a slab
       return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ptr), (short)0, bytes, 0x00020000);
     };
     unsigned* flags = g.ws_flags + (size_t)tile_lin * (unsigned)(S - 1);
     if (split != 0) {
-      float* slab = g.ws_partial + ((size_t)(tile_lin * (unsigned)(S - 1) + (unsigned)(split - 1)) * 4 + wave) * (WAVE_F4 * 4);
+      float* slab = g.ws_partial + ((size_t)(tile_lin * (unsigned)(S - 1) + (unsigned)(split - 1)) * G::NW + wave) * (WAVE_F4 * 4);
       const __amdgpu_buffer_rsrc_t rs = make_rsrc_ws(slab, WAVE_F4 * 16);
 #pragma unroll
-      for (int t = 0; t < 2; ++t)
+      for (int t = 0; t < TM; ++t)
 #pragma unroll
         for (int c = 0; c < TNW; ++c)
 #pragma unroll
@@ -595,16 +690,16 @@ __global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(S
     }
     __syncthreads();
     for (int sp = 1; sp < S; ++sp) {
-      const float* slab = g.ws_partial + ((size_t)(tile_lin * (unsigned)(S - 1) + (unsigned)(sp - 1)) * 4 + wave) * (WAVE_F4 * 4);
+      const float* slab = g.ws_partial + ((size_t)(tile_lin * (unsigned)(S - 1) + (unsigned)(sp - 1)) * G::NW + wave) * (WAVE_F4 * 4);
       const __amdgpu_buffer_rsrc_t rs = make_rsrc_ws(slab, WAVE_F4 * 16);
-      // the whole slab in flight at once (2 TNW x 4 loads of 16 bytes per lane: the fragment registers are dead here) - a
+      // the whole slab in flight at once (TM TNW x 4 loads of 16 bytes per lane: the fragment registers are dead here) - a
       // first version waited for four loads at a time and spent ~25 us per launch on 30 dependent round trips
-      uint4v v[2 * TNW * 4];
+      uint4v v[TM * TNW * 4];
 #pragma unroll
-      for (int i = 0; i < 2 * TNW * 4; ++i)
+      for (int i = 0; i < TM * TNW * 4; ++i)
         v[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, (unsigned)((i * 64 + lane) * 16), 0, 16 /* sc1 */);
 #pragma unroll
-      for (int t = 0; t < 2; ++t)
+      for (int t = 0; t < TM; ++t)
 #pragma unroll
         for (int c = 0; c < TNW; ++c)
 #pragma unroll
@@ -624,7 +719,8 @@ __global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(S
   // ---- epilogue ------------------------------------------------------------------------------------------------
   // Scales, bias and activation are applied in the accumulator layout (their operands were fetched before the main
   // loop: column factors / bias per (lane, column tile), row factors by a lane exchange of a_rmax), then a 32-row
-  // block goes through the wave's LDS patch so that every lane stores 16 contiguous bytes.  Output rows come from
+  // block goes through the wave's LDS patch - whole at TM = 2, 16 rows at a time at TM = 1: the accumulators are dead once
+  // they are in the patch - so that every lane stores 16 contiguous bytes.  Output rows come from
   // wave_row by a lane exchange: no index load is left in here.  The gradient factors, the saved tensor and the
   // accumulate operand are fetched half a row tile (16 rows) at a time, behind the tile's patch phase: one flight holds
   // every load of the three operands - FL float4 each per lane, issued back to back - and is waited for once; act'(saved)
@@ -632,8 +728,10 @@ __global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(S
   // fit: at TNW = 5 three operands of a tile are 240 registers beside the 80 accumulators of the other tile.)
   // The second row tile's accumulators are held in the accumulation registers while the first tile's epilogue runs (the K
   // split's additions above would otherwise leave them in VGPRs).
+  if constexpr (TM == 2) {
 #pragma unroll
-  for (int c = 0; c < TNW; ++c) asm volatile("" : "+a"(L.acc[1][c]));
+    for (int c = 0; c < TNW; ++c) asm volatile("" : "+a"(L.acc[TM - 1][c]));
+  }
   // The epilogue reads its own arguments again, from the kernel-argument segment (the first explicit argument lies at its
   // start), through a pointer the compiler cannot see through: loaded at the top with the rest they would sit in SGPRs
   // across the main loop, and the kernels with both the gradient operands and the split output ran out of them.
@@ -641,13 +739,15 @@ __global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(S
   SpArgsK ep = (SpArgsK)__builtin_amdgcn_kernarg_segment_ptr();
   asm volatile("" : "+s"(ep));
   const __attribute__((address_space(4))) SpArgs& e = *ep;
-  float* patch = reinterpret_cast<float*>(lds) + wave * 32 * G::PATCH_LD;
+  float* patch = reinterpret_cast<float*>(lds) + wave * G::PATCH_ROWS * G::PATCH_LD;
   const int64_t wcol0 = col0 + wn * 32 * TNW;
   const DropoutKey dkey = e.drop_on == 1 ? dropout_resolve(g.drop) : g.drop;  // the mask of the current epoch (common.hpp)
   constexpr int C4 = 8 * TNW;             // float4 per patch row
   constexpr int NIT = 32 * C4 / 64;       // float4 per lane and row tile
   constexpr int FL = NIT / 2;             // float4 per lane and operand in one flight: half a row tile
   constexpr int QF = FL / TNW;            // OUT_SP: row groups per flight
+  constexpr int PR = G::PATCH_ROWS;       // rows per patch round
+  constexpr int HR = PR / 16;             // flights per patch round
   static_assert(NIT % FL == 0 && FL % TNW == 0, "epilogue flights");
   auto epilogue_tile = [&](auto t_c) {
     constexpr int t = decltype(t_c)::value;
@@ -662,6 +762,20 @@ __global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(S
     auto slot_c4 = [&](int it) { return OUT_SP ? (lane & 7) + 8 * (it % TNW) : (lane + it * 64) % C4; };
     int orow[FL];               // output row of float4 h * FL + i (clamped and mapped: always a row that exists)
     float4 fm[FL], fs[FL], fo[FL];  // its factor, its saved value (then act' of it) and its accumulate operand
+    // (TM = 1: the accumulate operand follows act' in a flight of its own - beside the second half tile's accumulators the
+    // three operands and the temporaries of the longer act' forms exceed the 256 registers of a wave: 4 - 6 spilled)
+    auto flight_acc = [&](int h) {
+      if (!OUT_SP) {
+        if (e.accumulate) {
+#pragma unroll
+          for (int i = 0; i < FL; ++i)
+            fo[i] = *reinterpret_cast<const float4*>(cptr + (int64_t)orow[i] * e.ldc + wcol0 + slot_c4(h * FL + i) * 4);
+        } else {
+#pragma unroll
+          for (int i = 0; i < FL; ++i) fo[i] = float4{0.f, 0.f, 0.f, 0.f};
+        }
+      }
+    };
     auto flight = [&](int h) {  // every operand load of half h: all issued before anything waits for one of them
 #pragma unroll
       for (int i = 0; i < FL; ++i) {
@@ -686,16 +800,7 @@ __global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(S
           for (int i = 0; i < FL; ++i) fs[i] = float4{0.f, 0.f, 0.f, 0.f};
         }
       }
-      if (!OUT_SP) {
-        if (e.accumulate) {
-#pragma unroll
-          for (int i = 0; i < FL; ++i)
-            fo[i] = *reinterpret_cast<const float4*>(cptr + (int64_t)orow[i] * e.ldc + wcol0 + slot_c4(h * FL + i) * 4);
-        } else {
-#pragma unroll
-          for (int i = 0; i < FL; ++i) fo[i] = float4{0.f, 0.f, 0.f, 0.f};
-        }
-      }
+      if constexpr (TM == 2) flight_acc(h);
     };
     auto dact_flight = [&]() {  // fs <- act'(saved * saved_scale): one wave-uniform dispatch per flight
       if (!(GRAD && savp)) return;
@@ -759,26 +864,30 @@ __global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(S
       case TFGNN_ACT_SIGMOID: act_tile(std::integral_constant<int, TFGNN_ACT_SIGMOID>{}); break;
       default: break;
     }
+    // rows rd * PR .. + PR - 1 of the tile into the patch: accumulator elements rd * PR / 2 .. of every column tile
+    auto patch_round = [&](int rd) {
 #pragma unroll
-    for (int c = 0; c < TNW; ++c)
+      for (int c = 0; c < TNW; ++c)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int prow = (r & 3) + 8 * (r >> 2) + 4 * kg;
-        patch[prow * G::PATCH_LD + c * 32 + fi] = L.acc[t][c][r];
-      }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        for (int r = rd * (PR / 2); r < (rd + 1) * (PR / 2); ++r) {
+          const int prow = (r & 3) + 8 * (r >> 2) + 4 * kg - rd * PR;
+          patch[prow * G::PATCH_LD + c * 32 + fi] = L.acc[t][c][r];
+        }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    };
     if constexpr (OUT_SP) {
       // The result as a split operand of the next product (one scale per row): 8 lanes own a row of this wave's
       // 32 TNW columns (TNW float4 each), four row groups per 32-row block; the row maximum of the FINAL values (after
       // the gradient factors) is reduced over the 8 lanes, exchanged with the wave that holds the other half of the
       // row through LDS, then every lane splits and stores its chunks (and the fp32 form when C is given).
-      float* xmax = reinterpret_cast<float*>(lds) + 4 * 32 * G::PATCH_LD + t * 4 * 32;  // [tile][wave][32 rows]
+      float* xmax = reinterpret_cast<float*>(lds) + G::NW * PR * G::PATCH_LD + t * G::NW * 32;  // [tile][wave][32 rows]
       const int rgrp = lane >> 3, l8 = lane & 7;
       float4 w[4][TNW];
       float rmax[4];
       int64_t rowq[4];
 #pragma unroll
       for (int h = 0; h < NIT / FL; ++h) {
+        if (h % HR == 0) patch_round(h / HR);
         flight(h);
         dact_flight();
 #pragma unroll
@@ -788,7 +897,8 @@ __global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(S
           float mx = 0.f;
 #pragma unroll
           for (int j = 0; j < TNW; ++j) {
-            w[q][j] = factors(h, (q - QF * h) * TNW + j, *reinterpret_cast<const float4*>(patch + pr * G::PATCH_LD + (l8 + 8 * j) * 4));
+            w[q][j] = factors(h, (q - QF * h) * TNW + j,
+                              *reinterpret_cast<const float4*>(patch + (pr - h / HR * PR) * G::PATCH_LD + (l8 + 8 * j) * 4));
             mx = fmaxf(mx, fmaxf(fmaxf(fabsf(w[q][j].x), fabsf(w[q][j].y)), fmaxf(fabsf(w[q][j].z), fabsf(w[q][j].w))));
             if (w[q][j].x != w[q][j].x || w[q][j].y != w[q][j].y || w[q][j].z != w[q][j].z || w[q][j].w != w[q][j].w)
               mx = __builtin_inff();
@@ -800,7 +910,9 @@ __global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(S
         }
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();  // all four waves run the two row tiles in step
+      // every wave of the workgroup runs its row tiles in step and meets this barrier once per tile - also a wave whose rows
+      // all lie past m_end (its loads are clamped, its stores masked); the two waves that exchange are (wm, 0) and (wm, 1)
+      __builtin_amdgcn_s_barrier();
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int pr = q * 8 + rgrp;
@@ -823,12 +935,14 @@ __global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(S
     }
 #pragma unroll
     for (int h = 0; h < NIT / FL; ++h) {
+      if (h % HR == 0) patch_round(h / HR);
       flight(h);
       dact_flight();
+      if constexpr (TM == 1) flight_acc(h);
 #pragma unroll
       for (int i = 0; i < FL; ++i) {
         const int it = h * FL + i;
-        float4 w = factors(h, i, *reinterpret_cast<const float4*>(patch + slot_pr(it) * G::PATCH_LD + slot_c4(it) * 4));
+        float4 w = factors(h, i, *reinterpret_cast<const float4*>(patch + (slot_pr(it) - h / HR * PR) * G::PATCH_LD + slot_c4(it) * 4));
         if (e.accumulate) { w.x += fo[i].x; w.y += fo[i].y; w.z += fo[i].z; w.w += fo[i].w; }
         if (slot_pr(it) < tile_rows)
           *reinterpret_cast<float4*>(cptr + (int64_t)orow[i] * e.ldc + wcol0 + slot_c4(it) * 4) = w;
@@ -837,7 +951,7 @@ __global__ void __launch_bounds__(SP_NT, (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(S
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   };
   epilogue_tile(std::integral_constant<int, 0>{});
-  epilogue_tile(std::integral_constant<int, 1>{});
+  if constexpr (TM == 2) epilogue_tile(std::integral_constant<int, 1>{});
 }
 
 
@@ -1509,7 +1623,7 @@ static int sp_tn_splits(int64_t M, int64_t N, int64_t K, int bn) {
 
 template <int TNW>
 static void launch_sp_nt(const SpArgs& g_in, dim3 grid, hipStream_t s) {
-  using G = SpGeo<TNW>;
+  using G = SpGeo<TNW, sp_nt_tm<TNW>>;
   SpArgs g = g_in;
   g.xcd_per = g.xcd_total = 0;
   static const bool xcd_order = [] { const char* e = getenv("TFGNN_SP_NT_XCD"); return !(e && atoi(e) == 0); }();
@@ -1529,7 +1643,7 @@ static void launch_sp_nt(const SpArgs& g_in, dim3 grid, hipStream_t s) {
                                 G::LDS_BYTES);                                                                     \
       attr_set = true;                                                                                             \
     }                                                                                                              \
-    hipLaunchKernelGGL((gemm_sp_nt_kernel<TNW, AB, GR, OS>), grid, dim3(SP_NT), G::LDS_BYTES, s, g);               \
+    hipLaunchKernelGGL((gemm_sp_nt_kernel<TNW, AB, GR, OS>), grid, dim3(G::NT), G::LDS_BYTES, s, g);               \
   } while (0)
   if (g.out_sp) {
     if (ablk) {

@@ -12,7 +12,16 @@ all-empty, second full, others partial).  Every route runs the forward and gradi
 and - but for the accumulating ones, which the split output excludes - with split output.  Grouped calls (tile table): groups of
 1, 70 (ends inside the second wave's 64 rows), 0, 130 and 63 rows.  All inputs come from seeded host generators and the dropout
 epoch is set to 0, so the hashes depend on the kernels alone.  tests/test_gpu_nt_epilogue_flight.py builds the same cases
-through ``shapes()`` / ``run_shape()`` / ``run_grouped()`` and compares with the committed record."""
+through ``shapes()`` / ``run_shape()`` / ``run_grouped()`` and compares with the committed record.
+
+A second shape list pins the products of the 320-column tile across a change of its wave geometry (eight waves of 32 x 160):
+
+    python tools/record_nt_epilogue_bits.py eight-waves > tests/golden/nt_eight_waves_parent_bits.json
+
+N = 320; M in {31, 32, 33, 96, 97, 127, 128, 129} (the 32-row boundaries of a wave and the tile edge); K in {16, 48, 80, 112,
+320} (one k16 step, fewer steps than ring stages, odd and even step counts); the same routes and forms; grouped calls at
+K = 48 and 320; and products at M = 257 that split K inside their launch in two (K = 480) and in four (K = 960), each
+launched twice (``run_ksplit``).  tests/test_gpu_nt_eight_waves.py compares with that record."""
 from __future__ import annotations
 
 import hashlib
@@ -30,7 +39,12 @@ M_SIZES = (1, 63, 130, 257)
 N_SIZES = (128, 256, 320)
 K_SIZES = (32, 320)
 ROUTES = ("plain", "map", "map_rows", "mask_map", "mask_map_rows")
-SCALE_BLOCK = {32: 16, 320: 80}  # masked routes: 2 / 4 scale blocks that tile K
+SCALE_BLOCK = {32: 16, 320: 80, 16: 16, 48: 16, 80: 16, 112: 16}  # masked routes: scale blocks that tile K (1 .. 7 of them)
+EIGHT_WAVES = dict(m_sizes=(31, 32, 33, 96, 97, 127, 128, 129), n_sizes=(320,), k_sizes=(16, 48, 80, 112, 320))
+EIGHT_WAVES_GROUPED_K = (48, 320)
+KSPLIT_M, KSPLIT_N = 257, 320
+KSPLIT_K = {2: 480, 4: 960}  # splits -> K (gemm_sp.hip: min(4, k16 steps / 15) splits while the grid fits the chip)
+KSPLIT_FORMS = ("fwd", "both")
 # name -> may also run with split output
 FORMS = {"fwd": True, "fwd_bias_tanh_drop": True, "mul": True, "relu": True, "tanh09": True, "both": True, "acc": False,
          "acc_both": False, "drop": True, "drop_saved": True}
@@ -42,13 +56,18 @@ GROUP_SIZES = (1, 70, 0, 130, 63)
 GROUPED_FORMS = ("relu_fwd_rows", "relu_grad", "tanh_grad_fp32")
 
 
-def shapes():
+def shapes(m_sizes=M_SIZES, n_sizes=N_SIZES, k_sizes=K_SIZES):
     """-> [(name, M, N, K, route)]"""
-    return [(f"M{M} N{N} K{K} {route}", M, N, K, route) for M in M_SIZES for N in N_SIZES for K in K_SIZES for route in ROUTES]
+    return [(f"M{M} N{N} K{K} {route}", M, N, K, route) for M in m_sizes for N in n_sizes for K in k_sizes for route in ROUTES]
 
 
-def grouped_shapes():
-    return [(f"grouped N{N} K{K}", N, K) for N in N_SIZES for K in K_SIZES]
+def grouped_shapes(n_sizes=N_SIZES, k_sizes=K_SIZES):
+    return [(f"grouped N{N} K{K}", N, K) for N in n_sizes for K in k_sizes]
+
+
+def ksplit_shapes():
+    """-> [(name, M, N, K, "plain", splits)]: products that split K inside their launch"""
+    return [(f"ksplit{S} M{KSPLIT_M} N{KSPLIT_N} K{K}", KSPLIT_M, KSPLIT_N, K, "plain", S) for S, K in KSPLIT_K.items()]
 
 
 def tile_masks(M: int, K: int):
@@ -180,6 +199,24 @@ def run_grouped(shape, dev, d=None):
     return out
 
 
+def run_ksplit(shape, dev, d=None, after_launch=None):
+    """KSPLIT_FORMS of one K-split shape, each launched twice back to back -> {"<form> first" | "<form> second": tensor}.
+    ``after_launch(key)`` is called behind every launch (the test reads the split's flag words there)"""
+    from tf2_gnn_amd import ops
+
+    if d is None:
+        d = device_inputs(shape[:5], dev)
+    a_op = ops.sp_split_rows(d["a"])
+    b_op = ops.sp_split_rows(d["bt"])
+    out = {}
+    for form in KSPLIT_FORMS:
+        for turn in ("first", "second"):
+            out[f"{form} {turn}"] = ops.sp_gemm_nt(a_op, b_op, **form_kwargs(form, d, dev))
+            if after_launch is not None:
+                after_launch(f"{form} {turn}")
+    return out
+
+
 def sha(tensors) -> str:
     """one hash over the bytes of several tensors, in the order given"""
     h = hashlib.sha256()
@@ -196,22 +233,30 @@ def hashes(name: str, results) -> dict:
     return {f"{name} | {form}": sha(ts) for form, ts in by_form.items()}
 
 
-def record(dev):
+def record(dev, shape_list=None, grouped_list=None, ksplit_list=()):
     import torch
 
     from tf2_gnn_amd import ops
 
     ops.dropout_epoch_set(0)
     out = {}
-    for shape in shapes():
+    for shape in (shapes() if shape_list is None else shape_list):
         out.update(hashes(shape[0], run_shape(shape, dev)))
-    for shape in grouped_shapes():
+    for shape in (grouped_shapes() if grouped_list is None else grouped_list):
         out.update(hashes(shape[0], run_grouped(shape, dev)))
+    for shape in ksplit_list:
+        out.update(hashes(shape[0], run_ksplit(shape, dev)))
     torch.cuda.synchronize()
     return out
+
+
+def eight_waves_lists():
+    """-> (shapes, grouped shapes, K-split shapes) of the eight-waves record"""
+    return shapes(**EIGHT_WAVES), grouped_shapes(EIGHT_WAVES["n_sizes"], EIGHT_WAVES_GROUPED_K), ksplit_shapes()
 
 
 if __name__ == "__main__":
     import torch
 
-    print(json.dumps(record(torch.device("cuda", 0)), indent=0, sort_keys=True))
+    lists = eight_waves_lists() if sys.argv[1:] == ["eight-waves"] else ()
+    print(json.dumps(record(torch.device("cuda", 0), *lists), indent=0, sort_keys=True))
