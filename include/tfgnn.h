@@ -1409,6 +1409,134 @@ int tfgnn_batch_assemble(const tfgnn_batch_assemble_args* args, void* stream);
 /* host-side count of the kernel launches tfgnn_batch_assemble has enqueued in this process: out[0]; further slots are zero */
 int tfgnn_batch_assemble_launch_counts(int64_t* out_counts, int n);
 
+/* ------------------------------------------------------------------------------------------
+ * Neighbour sampling (csrc/sample.hip): a batch of seed nodes of ONE big graph -> one sampled K-hop subgraph, an ordinary
+ * batch.  The reference has no such thing (its graphs are small); this is the GraphSAGE route for transductive tasks.
+ *
+ * Store (plain device arrays the caller owns; V = num_nodes < 2^31; built once per fold):
+ *   per processed edge type t:  in_ptr[t] int32 [V + 1], in_src[t] int32 [E_t]: the sources of the in-edges of node v of
+ *                               type t are in_src[t][in_ptr[t][v] .. in_ptr[t][v + 1]), in the fold's edge-list order (a
+ *                               stable sort of the list by target).  store_edges[t] = E_t; sum_t E_t < 2^31.
+ * One subgraph serves all K layers (the GNN runs every layer on the same adjacency lists): the in-neighbourhood of a node
+ * is drawn ONCE per call, when the node is a frontier node, and the draw is a pure function of (seed, v, t).
+ *
+ * Order (all of it fixed: tests/neighbor_sample_reference.py reproduces the outputs exactly):
+ *   nodes[0:S] = seeds, in the given order (distinct, in [0, V): see the status bits).  Frontier 1 = the seeds.
+ *   hop h = 1..K, fanout f = fanouts[h - 1]: for every frontier node v in `nodes` order and every type t, with d the
+ *   in-degree of type t of v:  c = d if f < 0 or d <= f, else f  (f = 0: no edges).  Edge j < c of row (v, t) is
+ *       (in_src[t][in_ptr[t][v] + p_j], v)
+ *   at position (edges of type t of earlier hops) + (sum of c over frontier nodes before v) + j of adjacency_lists[t].
+ *   The sources that are not in `nodes` yet are appended to it in INCREASING GLOBAL ID; they are frontier h + 1.  After
+ *   hop K nothing more is sampled: nodes first reached at hop K have no in-edges in the subgraph.
+ *   p_j = j when c = d.  Otherwise p_j = (pi(j) + off) mod d, where, with k the row key,
+ *       pi   a bijection of [0, d): an 8-round balanced Feistel network on b bits, b the smallest even number
+ *            >= max(2, bit_length(d - 1)), x = (l << b/2) | r, round i = 0..7: (l, r) <- (r, l ^ F_i(r)),
+ *            F_i(r) = (lowbias32(r ^ (k + i * 0x9E3779B9)) >> 7) & (2^(b/2) - 1); applied again while the value is >= d
+ *       off  = lowbias32(k ^ 0xA5A5A5A5) mod d
+ *       k    = lowbias32(lowbias32(v ^ s0) + (t + 1) * 0x9E3779B9) ^ s1     (32-bit wrap-around arithmetic)
+ *       s0, s1: the low and high word of splitmix64's output for `seed` (z = seed + 0x9E3779B97F4A7C15;
+ *            z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >> 31 - the step the
+ *            dropout keys use); lowbias32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16.
+ *   These are c distinct positions, each computed by one thread on its own.
+ * Outputs: nodes (global ids), adjacency_lists[t] int32 [*, 2] rows (source, target) in LOCAL ids (positions in `nodes`),
+ * and meta, int32 [TFGNN_SAMPLE_META_WORDS(L, K)], for ONE device-to-host copy:
+ *   meta[TFGNN_SAMPLE_META_STATUS]      0, or an OR of the TFGNN_SAMPLE_* bits below
+ *   meta[TFGNN_SAMPLE_META_NODES]       n, the number of nodes
+ *   meta[TFGNN_SAMPLE_META_EDGES + t]   the number of edges of type t
+ *   meta[TFGNN_SAMPLE_META_EDGES + L + h], h = 0..K+1: hop_ptr - nodes[hop_ptr[h] : hop_ptr[h + 1]] were first reached at hop h
+ *                                       (h = 0: the seeds), hop_ptr[K + 1] = n
+ * Capacities: nothing is written at or beyond nodes[node_capacity] or row edge_capacity[t] of adjacency_lists[t].  What does
+ * not fit is dropped and sets an overflow bit; the counts then stop at the capacities and the rest of the outputs is
+ * unspecified (but written inside the capacities).  S <= node_capacity <= V.  A row is drawn once per call, so V nodes
+ * and E_t edges always suffice; ops.sample_capacities gives the tighter bound from S, the fanouts and the largest in-degrees.
+ * Status bits: a repeated seed (its rows are drawn more than once), a seed outside [0, V) (it has no in-edges), store
+ * arrays that disagree with their sizes (the element is skipped or written as -1).
+ *
+ * Workspace: tfgnn_neighbor_sample_workspace_bytes(V, L, node_capacity) bytes, 16-byte aligned (0: arguments outside the
+ * limits above).  Its first V int32 words are the local-id table: ALL -1 ON ENTRY - the caller fills it once, when it
+ * allocates - and LEFT ALL -1 ON EXIT, by a pass over `nodes` (no memset of V), so calls follow one another on one
+ * workspace.  The rest needs no initialisation.  A call that overflowed restores the table as well.
+ *
+ * 3 + 6 K launches on `stream` per call, whatever the fanouts (seeds; per hop: count, scan of the chunk totals, edge slots,
+ * count of the marked ids, scan of those, assignment; translate; restore), every grid sized from the capacities: the sizes
+ * exist on the device only.  No allocation, no copy, no synchronisation.  Parallel over output edge slots, a row found by
+ * binary search in the scanned counts: a hub of thousands of in-edges is not one wave's loop.  "New nodes in increasing id"
+ * is a scan over the table, where the slot pass marked them by plain stores of one value.  No float atomics; the only
+ * atomic is an OR into the status word.
+ * The pointer tables (in_ptr, in_src, store_edges, edge_capacity, adjacency_lists) and fanouts are HOST arrays read during
+ * the call.
+ * Rejected on the host before any HIP call: NULL args, another struct_size, num_hops outside [1, TFGNN_SAMPLE_MAX_HOPS],
+ * num_seeds < 1, num_nodes < 1 or >= 2^31, negative sizes or capacities, sum_t E_t >= 2^31, a node capacity below S or
+ * above V, NULL pointers, edge lists that are not 8-byte aligned, a workspace too small or unaligned.  More than
+ * TFGNN_BATCH_MAX_EDGE_TYPES types: TFGNN_ERR_UNSUPPORTED.
+ *
+ * tfgnn_gather_node_rows: the rows of a sampled batch, ONE launch (none for num_rows == 0):
+ *   node_features[i, :] = features[nodes[i], :],  node_column_out[c][i, :] = node_columns[c][nodes[i], :]   for i < num_rows,
+ *   except that a column with seed_only[c] != 0 gets zeros in the rows i >= num_seeds.
+ * The rules of tfgnn_batch_assemble: consecutive lanes on consecutive floats, per array float4 when its width % 4 == 0 and
+ * both of its buffers are 16-byte aligned, rows_per_tile = clamp(8192 / width, 1, 256) rows to a workgroup, 64-bit element
+ * offsets into the store.  A node id outside [0, store_nodes) skips its row and sets *bad_flag (nullable, zeroed by the
+ * caller).  Nothing is written beyond num_rows rows.  Rejected on the host before any HIP call: NULL args, another
+ * struct_size, negative sizes, store_nodes or num_rows >= 2^31, widths outside [1, 2^31), NULL pointers where num_rows > 0,
+ * a NULL table when there are node columns.  More than TFGNN_BATCH_MAX_NODE_COLUMNS node columns: TFGNN_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------ */
+#define TFGNN_SAMPLE_MAX_HOPS 8
+#define TFGNN_SAMPLE_META_STATUS 0
+#define TFGNN_SAMPLE_META_NODES 1
+#define TFGNN_SAMPLE_META_EDGES 2
+#define TFGNN_SAMPLE_META_WORDS(L, K) (2 + (L) + (K) + 2)
+#define TFGNN_SAMPLE_NODE_OVERFLOW 1
+#define TFGNN_SAMPLE_EDGE_OVERFLOW 2
+#define TFGNN_SAMPLE_REPEATED_SEED 4
+#define TFGNN_SAMPLE_BAD_SEED 8
+#define TFGNN_SAMPLE_BAD_STORE 16
+typedef struct tfgnn_neighbor_sample_args {
+  size_t struct_size;
+  int num_edge_types; /* L */
+  int num_hops;       /* K */
+  int64_t num_nodes;  /* V */
+  /* store */
+  const int32_t* const* in_ptr;
+  const int32_t* const* in_src;
+  const int64_t* store_edges; /* E_t */
+  /* call */
+  const int32_t* fanouts; /* [K], < 0: every in-edge */
+  uint64_t seed;
+  int64_t num_seeds;    /* S */
+  const int32_t* seeds; /* device [S] */
+  /* outputs */
+  int64_t node_capacity;
+  const int64_t* edge_capacity;    /* [L] */
+  int32_t* nodes;                  /* device [node_capacity] */
+  int32_t* const* adjacency_lists; /* device [edge_capacity[t], 2] each */
+  int32_t* meta;                   /* device [TFGNN_SAMPLE_META_WORDS(L, K)] */
+  void* workspace;
+  size_t workspace_bytes;
+} tfgnn_neighbor_sample_args;
+size_t tfgnn_neighbor_sample_workspace_bytes(int64_t num_nodes, int num_edge_types, int64_t node_capacity);
+int tfgnn_neighbor_sample(const tfgnn_neighbor_sample_args* args, void* stream);
+
+typedef struct tfgnn_gather_node_rows_args {
+  size_t struct_size;
+  int64_t store_nodes;  /* rows of `features` and of every node column */
+  int64_t num_rows;     /* n */
+  int64_t num_seeds;    /* S: the rows a seed_only column keeps */
+  const int32_t* nodes; /* device [n], global ids */
+  int64_t feature_dim;  /* F */
+  const float* features;
+  float* node_features; /* [n, F] contiguous */
+  int num_node_columns;
+  const int64_t* node_column_widths; /* W_c */
+  const float* const* node_columns;  /* store [store_nodes, W_c] each */
+  float* const* node_column_out;     /* [n, W_c] contiguous each */
+  const int32_t* seed_only;          /* host [num_node_columns] */
+  int* bad_flag;
+} tfgnn_gather_node_rows_args;
+int tfgnn_gather_node_rows(const tfgnn_gather_node_rows_args* args, void* stream);
+/* host-side counts of the kernel launches enqueued in this process: out[0] by tfgnn_neighbor_sample (3 + 6 K per call),
+ * out[1] by tfgnn_gather_node_rows (1 per call with rows); further slots are zero */
+int tfgnn_sample_launch_counts(int64_t* out_counts, int n);
+
 #ifdef __cplusplus
 }
 #endif

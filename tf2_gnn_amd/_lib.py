@@ -383,6 +383,23 @@ _SIGNATURES += [
 ]
 LINK_CHUNK = 256  # csrc/link.hip LINK_CHUNK: list positions per chunk of the backward passes
 
+# neighbour sampling and the row gather of a sampled batch (include/tfgnn.h "Neighbour sampling", csrc/sample.hip)
+_SIGNATURES += [
+    ("tfgnn_neighbor_sample_workspace_bytes", c_size_t, [c_int64, c_int, c_int64]),
+    ("tfgnn_neighbor_sample", c_int, [c_void_p, c_void_p]),
+    ("tfgnn_gather_node_rows", c_int, [c_void_p, c_void_p]),
+    ("tfgnn_sample_launch_counts", c_int, [POINTER(c_int64), c_int]),
+]
+SAMPLE_MAX_HOPS = 8  # TFGNN_SAMPLE_MAX_HOPS
+SAMPLE_META_STATUS, SAMPLE_META_NODES, SAMPLE_META_EDGES = 0, 1, 2  # TFGNN_SAMPLE_META_*
+SAMPLE_NODE_OVERFLOW, SAMPLE_EDGE_OVERFLOW, SAMPLE_REPEATED_SEED, SAMPLE_BAD_SEED, SAMPLE_BAD_STORE = 1, 2, 4, 8, 16
+
+
+def sample_meta_words(num_edge_types: int, num_hops: int) -> int:
+    """TFGNN_SAMPLE_META_WORDS: status, node count, the edge counts, hop_ptr [K + 2]"""
+    return 2 + num_edge_types + num_hops + 2
+
+
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
 ABI_VERSION = 5  # include/tfgnn.h TFGNN_ABI_VERSION
 
@@ -455,6 +472,29 @@ class BatchAssembleArgs(ctypes.Structure):
         ("node_features", c_void_p), ("node_to_graph_map", c_void_p), ("adjacency_lists", c_void_p), ("column_out", c_void_p),
         ("bad_flag", c_void_p), ("num_node_columns", c_int), ("node_column_widths", c_void_p), ("node_columns", c_void_p),
         ("node_column_out", c_void_p),
+    ]
+
+
+class NeighborSampleArgs(ctypes.Structure):
+    """tfgnn_neighbor_sample_args (include/tfgnn.h), field for field.  The pointer tables and ``fanouts`` are host arrays
+    that the caller keeps alive for the duration of the call."""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t), ("num_edge_types", c_int), ("num_hops", c_int), ("num_nodes", c_int64),
+        ("in_ptr", c_void_p), ("in_src", c_void_p), ("store_edges", c_void_p), ("fanouts", c_void_p), ("seed", ctypes.c_uint64),
+        ("num_seeds", c_int64), ("seeds", c_void_p), ("node_capacity", c_int64), ("edge_capacity", c_void_p), ("nodes", c_void_p),
+        ("adjacency_lists", c_void_p), ("meta", c_void_p), ("workspace", c_void_p), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
+class GatherNodeRowsArgs(ctypes.Structure):
+    """tfgnn_gather_node_rows_args (include/tfgnn.h), field for field"""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t), ("store_nodes", c_int64), ("num_rows", c_int64), ("num_seeds", c_int64), ("nodes", c_void_p),
+        ("feature_dim", c_int64), ("features", c_void_p), ("node_features", c_void_p), ("num_node_columns", c_int),
+        ("node_column_widths", c_void_p), ("node_columns", c_void_p), ("node_column_out", c_void_p), ("seed_only", c_void_p),
+        ("bad_flag", c_void_p),
     ]
 
 

@@ -7,5 +7,6 @@ from .jsonl_graph_dataset import JsonLGraphDataset
 from .jsonl_graph_property_dataset import GraphWithPropertySample, JsonLGraphPropertyDataset
 from .ppi_dataset import PPIDataset, PPIGraphSample
 from .qm9_dataset import QM9Dataset, QM9GraphSample
+from .neighbor_sampling import NeighborStore, batch_key, build_in_csr, plan_seed_chunks, sampled_batch
 from .node_classification_dataset import NodeClassificationDataset
 from .link_prediction_dataset import LinkPredictionDataset

@@ -18,15 +18,30 @@ fold's ``node_label_weights`` over the batch's column in place evaluates that fo
 ``max_nodes_per_batch`` cuts batches between graphs by the reference's rule, plan_batches - the empty batch in front of a
 first graph over the limit included.)
 
-The fold is processed at once with numpy, as in PPIDataset; inputs that do not describe such a dataset raise ValueError."""
+The fold is processed at once with numpy, as in PPIDataset; inputs that do not describe such a dataset raise ValueError.
+
+Neighbour-sampled mini-batches.  With the hyper-parameter ``neighbor_fanouts`` set (a list of K fanouts, one per hop, -1 for
+every in-edge; the default None is the route above, untouched) ``get_batches(fold)`` yields one batch per chunk of
+``seeds_per_batch`` of the fold's indices - the last, partial chunk included - each the K-hop subgraph the device sampler
+draws around its seeds (data/neighbor_sampling.py, include/tfgnn.h "Neighbour sampling"): the seeds are rows
+0 .. ``num_seed_nodes`` - 1, ``node_label_weights`` is the fold's weight there and 0 below, ``sampled_node_ids`` names the rows'
+nodes.  TRAIN draws a fresh np.random permutation of ``train_idx`` per ``iter()`` and samples with the key
+``batch_key(sampling_seed, epoch counter, batch index)``, the counter advancing with every ``iter()``; VALIDATION and TEST keep
+file order and epoch 0 (with ``eval_neighbor_fanouts``, default: the training fanouts), so their batches are the same on
+every ``iter()``.  K should be at least the number of message passing layers: then a seed's output is exact for the sampled
+graph (all of it at fanout -1).  A sampled batch is one graph of a single-graph dataset, so ``node_graph_id`` with several
+graphs raises ValueError, and so do repeated indices in a fold; graph-global exchange sees only the sampled subgraph; the
+counts of every batch are read back once, so a sampled batch cannot be captured in a CapturedStep."""
 from __future__ import annotations
 
 from pathlib import Path
-from typing import Any, Dict, List, Optional, Sequence, Set, Tuple
+from typing import Any, Dict, Iterator, List, Optional, Sequence, Set, Tuple
 
 import numpy as np
+import torch
 
 from .graph_dataset import DataFold, GraphDataset, PackedFold
+from .neighbor_sampling import NeighborStore, batch_key, check_fanouts, plan_seed_chunks, sampled_batch
 from .utils import compute_number_of_edge_types, get_tied_edge_types
 
 _FOLD_NAMES = ((DataFold.TRAIN, "train"), (DataFold.VALIDATION, "valid"), (DataFold.TEST, "test"))
@@ -41,6 +56,10 @@ class NodeClassificationDataset(GraphDataset):
             "add_self_loop_edges": True,
             "tie_fwd_bkwd_edges": False,
             "num_node_classes": None,  # None: the largest label + 1
+            "neighbor_fanouts": None,  # None: full-batch; a list of K fanouts (-1: every in-edge): neighbour-sampled batches
+            "eval_neighbor_fanouts": None,  # None: the same fanouts as training
+            "seeds_per_batch": 1024,
+            "sampling_seed": 0,
         })
         return hypers
 
@@ -52,6 +71,9 @@ class NodeClassificationDataset(GraphDataset):
         super().__init__(params, metadata=metadata, **kwargs)
         self._num_fwd_edge_types: Optional[int] = None
         self._num_node_classes: Optional[int] = None
+        self._fold_indices: Dict[DataFold, np.ndarray] = {}
+        self._neighbor_stores: Dict[Tuple[DataFold, str], NeighborStore] = {}
+        self._sampling_epoch = 0
 
     def _loaded(self, what: str):
         if self._num_fwd_edge_types is None:
@@ -140,6 +162,8 @@ class NodeClassificationDataset(GraphDataset):
             unknown = labels[idx] < 0
             if unknown.any():
                 raise ValueError(f"{what}: {fold.name} index {idx[unknown][0]} names a node without a label")
+            if self.sampled and np.unique(idx).shape[0] != idx.shape[0]:
+                raise ValueError(f"{what}: the {fold.name} indices repeat a node; neighbour sampling needs distinct seeds")
             w = np.zeros((V, 1), dtype=np.float32)
             w[idx] = 1.0
             weights[fold] = w
@@ -147,11 +171,17 @@ class NodeClassificationDataset(GraphDataset):
         if isinstance(edges, np.ndarray) and edges.ndim == 2:
             edges = [edges]
         base = self._pack_graphs(feats, [np.asarray(e) for e in edges], node_graph_id, labels.astype(np.float32), what)
+        if self.sampled and base.num_graphs != 1:
+            raise ValueError(f"{what}: neighbour sampling (neighbor_fanouts) needs a single graph, node_graph_id describes "
+                             f"{base.num_graphs}: a sampled batch is one graph and node_to_graph_map must be sorted")
         self._num_fwd_edge_types, self._num_node_classes = len(edges), num_classes
         for fold, w in weights.items():
             # the same host arrays for every fold; only the weight column is the fold's own
             self._set_fold(fold, PackedFold(base.node_counts, base.features, base.edge_counts, base.edges,
                                             node_columns={"node_labels": base.node_columns["node_labels"], "node_label_weights": w}))
+            self._fold_indices[fold] = np.asarray(fold_indices[fold]).reshape(-1).astype(np.int64)
+            for key in [k for k in self._neighbor_stores if k[0] == fold]:
+                del self._neighbor_stores[key]
 
     def _pack_graphs(self, feats: np.ndarray, edges: Sequence[np.ndarray], node_graph_id, labels: np.ndarray, what: str) -> PackedFold:
         V = feats.shape[0]
@@ -193,3 +223,60 @@ class NodeClassificationDataset(GraphDataset):
             feature_dim=int(feats.shape[1]),
             node_columns={"node_labels": labels.reshape(-1, 1)},
         )
+
+    # ---- neighbour-sampled batches ----------------------------------------------------------------------------------------
+    @property
+    def sampled(self) -> bool:
+        return self.params.get("neighbor_fanouts") is not None
+
+    def fanouts(self, data_fold: DataFold) -> List[int]:
+        """The fold's fanouts: ``eval_neighbor_fanouts`` for VALIDATION and TEST when it is set, else ``neighbor_fanouts``."""
+        fanouts = self.params.get("neighbor_fanouts")
+        if data_fold != DataFold.TRAIN and self.params.get("eval_neighbor_fanouts") is not None:
+            fanouts = self.params["eval_neighbor_fanouts"]
+        if fanouts is None:
+            raise ValueError("neighbor_fanouts is not set: the dataset is full-batch")
+        return check_fanouts(fanouts)
+
+    def neighbor_store(self, data_fold: DataFold, device=None) -> NeighborStore:
+        """The fold in the sampler's form on the device; built at the first request, the graph, features and labels shared
+        between the folds."""
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        key = (data_fold, str(dev))
+        if key not in self._neighbor_stores:
+            other = next((s for (_, d), s in self._neighbor_stores.items() if d == str(dev)), None)
+            self._neighbor_stores[key] = NeighborStore(self._loaded_data[data_fold], dev, share=other)
+        return self._neighbor_stores[key]
+
+    def plan_sampled_epoch(self, data_fold: DataFold) -> Tuple[np.ndarray, List[Tuple[int, int]], int]:
+        """(seed order, chunk ranges, epoch number) of a new epoch: TRAIN permutes its indices with numpy's global generator
+        and takes the next epoch number; the other folds keep file order and epoch 0."""
+        idx = self._fold_indices[data_fold]
+        if data_fold == DataFold.TRAIN:
+            order, epoch = idx[np.random.permutation(idx.shape[0])], self._sampling_epoch
+            self._sampling_epoch += 1
+        else:
+            order, epoch = idx, 0
+        return order, plan_seed_chunks(idx.shape[0], int(self.params.get("seeds_per_batch", 1024))), epoch
+
+    def get_batches(self, data_fold: DataFold, device=None):
+        if not self.sampled:
+            return super().get_batches(data_fold, device)
+        return _SampledBatches(self, data_fold, device)
+
+
+class _SampledBatches:
+    """What ``get_batches`` returns with ``neighbor_fanouts`` set: every ``iter()`` is one epoch of sampled batches; the
+    epoch's seed order goes to the device in one copy."""
+
+    def __init__(self, dataset: NodeClassificationDataset, data_fold: DataFold, device=None):
+        self._dataset, self._data_fold, self._device = dataset, data_fold, device
+
+    def __iter__(self) -> Iterator[Tuple[Dict[str, Any], Dict[str, Any]]]:
+        ds, fold = self._dataset, self._data_fold
+        fanouts = ds.fanouts(fold)
+        store = ds.neighbor_store(fold, self._device)
+        order, chunks, epoch = ds.plan_sampled_epoch(fold)
+        seeds = torch.from_numpy(order.astype(np.int32)).to(store.device)
+        for b, (s, e) in enumerate(chunks):
+            yield sampled_batch(store, seeds[s:e], fanouts, batch_key(ds.params.get("sampling_seed", 0), epoch, b))

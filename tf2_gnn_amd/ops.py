@@ -2246,3 +2246,130 @@ def _cache_weight_operand(w: torch.Tensor, kind: str, op) -> None:
         _sp_weight_cache.clear()
     base = w._base if w._base is not None else w  # views are temporaries: the entry lives as long as the parameter buffer
     _sp_weight_cache[_weight_key(w, kind)] = (w._version, op, weakref.ref(base), _weight_checksum(w))
+
+
+# ---- neighbour sampling (include/tfgnn.h "Neighbour sampling", csrc/sample.hip) -----------------------------------------------
+class NeighborSample:
+    """What ``neighbor_sample`` returns: ``nodes`` int32 [n] (device, global ids, the seeds first), ``hop_ptr`` (host numpy
+    int32 [K + 2]), ``adjacency_lists`` (device int32 [E_t, 2], local ids), ``status`` (int, the TFGNN_SAMPLE_* bits).  The
+    device tensors are prefix views of buffers allocated at the capacity."""
+
+    __slots__ = ("nodes", "hop_ptr", "adjacency_lists", "status", "num_seeds")
+
+    def __init__(self, nodes, hop_ptr, adjacency_lists, status, num_seeds):
+        self.nodes, self.hop_ptr, self.adjacency_lists, self.status, self.num_seeds = nodes, hop_ptr, adjacency_lists, status, num_seeds
+
+
+def sample_capacities(num_seeds: int, fanouts: Sequence[int], num_nodes: int, store_edges: Sequence[int],
+                      max_in_degree: Sequence[int]):
+    """(node capacity, [edge capacity per type]) that a sample of ``num_seeds`` distinct seeds can never exceed: a frontier
+    of B nodes draws at most B * min(f, largest in-degree of the type) edges of a type (f < 0: the largest in-degree) and
+    reaches at most as many new nodes as it draws edges; a row is drawn once per call, so a type never yields more than its
+    E_t edges, and there are no more than V nodes."""
+    frontier, nodes = int(num_seeds), int(num_seeds)
+    edges = [0] * len(store_edges)
+    for f in fanouts:
+        drawn = 0
+        for t, (e, deg) in enumerate(zip(store_edges, max_in_degree)):
+            per_row = int(deg) if f < 0 else min(int(f), int(deg))
+            n = min(frontier * per_row, int(e))
+            edges[t] = min(edges[t] + n, int(e))
+            drawn += n
+        frontier = min(drawn, num_nodes)
+        nodes = min(nodes + frontier, num_nodes)
+    return max(nodes, min(int(num_seeds), num_nodes)), edges
+
+
+def sample_launch_counts():
+    """(launches enqueued by tfgnn_neighbor_sample, by tfgnn_gather_node_rows) in this process: host counters"""
+    buf = (ctypes.c_int64 * 2)()
+    _lib.check(_lib.load().tfgnn_sample_launch_counts(buf, 2))
+    return int(buf[0]), int(buf[1])
+
+
+def neighbor_sample(store, seeds: torch.Tensor, fanouts: Sequence[int], seed: int, out=None) -> NeighborSample:
+    """One K-hop neighbour sample (K = len(fanouts); a fanout < 0 takes every in-edge) of the int32 device tensor ``seeds``
+    on ``store`` (data.NeighborStore: the in-CSR per edge type, kept on the device): 3 + 6 K launches on the current stream,
+    then ONE small device-to-host copy of the counts - the sizes are data-dependent and the graph build needs them on the
+    host.  That copy synchronises, so a sampled batch cannot be captured in a CapturedStep.  Buffers are allocated at
+    ``sample_capacities`` - they cannot overflow - unless ``out`` = (nodes [cap], [adjacency_list [cap_t, 2]]) brings smaller
+    ones; what does not fit then sets an overflow bit in ``status``.  The draw is a pure function of (seed, node, type)."""
+    _require_dev(seeds, torch.int32, "seeds")
+    seeds = seeds.contiguous().view(-1)
+    S, L, K, V = int(seeds.shape[0]), store.num_edge_types, len(fanouts), store.num_nodes
+    dev = seeds.device
+    if out is None:
+        node_cap, edge_cap = sample_capacities(S, fanouts, V, store.store_edges, store.max_in_degree)
+        nodes = torch.empty(node_cap, dtype=torch.int32, device=dev)
+        flat = torch.empty(2 * sum(-(-e // 32) * 32 for e in edge_cap), dtype=torch.int32, device=dev)
+        adj, at = [], 0
+        for e in edge_cap:  # every list starts on a 256-byte boundary
+            adj.append(flat[at:at + 2 * e].view(e, 2))
+            at += 2 * (-(-e // 32) * 32)
+    else:
+        nodes, adj = out
+        node_cap, edge_cap = int(nodes.shape[0]), [int(a.shape[0]) for a in adj]
+        for a in [nodes] + list(adj):
+            _require_dev(a, torch.int32, "a sample output")
+            if not a.is_contiguous():
+                raise ValueError("sample outputs must be contiguous")
+    meta = torch.empty(_lib.sample_meta_words(L, K), dtype=torch.int32, device=dev)
+    workspace = store.workspace(node_cap)
+    a = _lib.NeighborSampleArgs()
+    a.struct_size = ctypes.sizeof(_lib.NeighborSampleArgs)
+    a.num_edge_types, a.num_hops, a.num_nodes = L, K, V
+    a.in_ptr, a.in_src = ctypes.addressof(store._in_ptr_tab), ctypes.addressof(store._in_src_tab)
+    a.store_edges = ctypes.addressof(store._store_edges_tab)
+    fan = (ctypes.c_int32 * max(K, 1))(*[int(f) for f in fanouts])
+    caps = (ctypes.c_int64 * max(L, 1))(*edge_cap)
+    adj_tab = (ctypes.c_void_p * max(L, 1))(*[t.data_ptr() for t in adj])
+    a.fanouts, a.seed, a.num_seeds, a.seeds = ctypes.addressof(fan), int(seed) & (2 ** 64 - 1), S, seeds.data_ptr()
+    a.node_capacity, a.edge_capacity, a.nodes = node_cap, ctypes.addressof(caps), nodes.data_ptr()
+    a.adjacency_lists, a.meta = ctypes.addressof(adj_tab), meta.data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * 4
+    _lib.check(_lib.load().tfgnn_neighbor_sample(ctypes.byref(a), _stream()))
+    host = meta.cpu().numpy()  # the one copy
+    n = int(host[_lib.SAMPLE_META_NODES])
+    counts = host[_lib.SAMPLE_META_EDGES:_lib.SAMPLE_META_EDGES + L]
+    hop_ptr = host[_lib.SAMPLE_META_EDGES + L:].copy()
+    return NeighborSample(nodes[:n], hop_ptr, [t[:int(c)] for t, c in zip(adj, counts)], int(host[_lib.SAMPLE_META_STATUS]), S)
+
+
+def gather_node_rows(nodes: torch.Tensor, num_seeds: int, features: torch.Tensor, columns: Sequence[torch.Tensor] = (),
+                     seed_only: Sequence[bool] = (), out=None, bad_flag: Optional[torch.Tensor] = None):
+    """The rows of a sampled batch by one tfgnn_gather_node_rows launch: -> (features[nodes], [column[nodes] ...]), where a
+    column whose ``seed_only`` flag is set is zero in the rows >= ``num_seeds``.  ``out`` = (node_features, [columns]) may
+    bring the outputs; ``bad_flag`` (zeroed int32 [1]) is set by a node id outside the store."""
+    _require_dev(nodes, torch.int32, "nodes")
+    _require_dev(features, torch.float32, "features")
+    nodes = nodes.contiguous().view(-1)
+    n, V, F = int(nodes.shape[0]), int(features.shape[0]), int(features.shape[1])
+    columns, seed_only = list(columns), [bool(s) for s in seed_only] + [False] * (len(columns) - len(seed_only))
+    for c in [features] + columns:
+        _require_dev(c, torch.float32, "a node column")
+        if c.dim() != 2 or int(c.shape[0]) != V or c.stride(1) != 1 or c.stride(0) != c.shape[1]:
+            raise ValueError("features and node columns must be row-contiguous [V, W] over the same nodes")
+    widths = [int(c.shape[1]) for c in columns]
+    if out is None:
+        out = (torch.empty((n, F), dtype=torch.float32, device=nodes.device),
+               [torch.empty((n, w), dtype=torch.float32, device=nodes.device) for w in widths])
+    nf, cols = out
+    for t, w in zip([nf] + list(cols), [F] + widths):
+        _require_dev(t, torch.float32, "a gather output")
+        if tuple(t.shape) != (n, w) or t.stride(1) != 1 or t.stride(0) != w:
+            raise ValueError(f"a gather output must be a row-contiguous float32 [{n}, {w}]")
+    NC = len(columns)
+    a = _lib.GatherNodeRowsArgs()
+    a.struct_size = ctypes.sizeof(_lib.GatherNodeRowsArgs)
+    a.store_nodes, a.num_rows, a.num_seeds, a.nodes = V, n, int(num_seeds), nodes.data_ptr()
+    a.feature_dim, a.features, a.node_features = F, features.data_ptr(), nf.data_ptr()
+    if NC:
+        width_tab = (ctypes.c_int64 * NC)(*widths)
+        col_tab = (ctypes.c_void_p * NC)(*[c.data_ptr() for c in columns])
+        out_tab = (ctypes.c_void_p * NC)(*[c.data_ptr() for c in cols])
+        flag_tab = (ctypes.c_int32 * NC)(*[int(s) for s in seed_only])
+        a.num_node_columns, a.node_column_widths = NC, ctypes.addressof(width_tab)
+        a.node_columns, a.node_column_out, a.seed_only = ctypes.addressof(col_tab), ctypes.addressof(out_tab), ctypes.addressof(flag_tab)
+    a.bad_flag = bad_flag.data_ptr() if bad_flag is not None else None
+    _lib.check(_lib.load().tfgnn_gather_node_rows(ctypes.byref(a), _stream()))
+    return nf, list(cols)
