@@ -34,6 +34,7 @@
 
 #include "aux_jobs.hpp"
 #include "common.hpp"
+#include "gemm_sp.hpp"
 #include "sp16.hpp"
 #include "tn_repair.hpp"
 
@@ -1635,32 +1636,21 @@ static void launch_sp_nt(const SpArgs& g_in, dim3 grid, hipStream_t s) {
   const bool ablk = g.a_inv && g.a_nblk > 1;
   const bool grad = g.mul || g.saved;
   count_launch(TFGNN_KFAM_SP_NT);
-#define SP_LAUNCH(AB, GR, OS)                                                                                      \
-  do {                                                                                                             \
-    static bool attr_set = false;                                                                                  \
-    if (!attr_set) {                                                                                               \
-      (void)hipFuncSetAttribute((const void*)gemm_sp_nt_kernel<TNW, AB, GR, OS>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                G::LDS_BYTES);                                                                     \
-      attr_set = true;                                                                                             \
-    }                                                                                                              \
-    hipLaunchKernelGGL((gemm_sp_nt_kernel<TNW, AB, GR, OS>), grid, dim3(G::NT), G::LDS_BYTES, s, g);               \
-  } while (0)
-  if (g.out_sp) {
-    if (ablk) {
-      if (grad) SP_LAUNCH(true, true, true);
-      else SP_LAUNCH(true, false, true);
-    } else {
-      if (grad) SP_LAUNCH(false, true, true);
-      else SP_LAUNCH(false, false, true);
-    }
-  } else if (ablk) {
-    if (grad) SP_LAUNCH(true, true, false);
-    else SP_LAUNCH(true, false, false);
-  } else {
-    if (grad) SP_LAUNCH(false, true, false);
-    else SP_LAUNCH(false, false, false);
+  // the eight kernels of this tile width, [ablk][grad][out_sp]
+  using Kernel = void (*)(SpArgs);
+  static const Kernel kernels[2][2][2] = {
+      {{gemm_sp_nt_kernel<TNW, false, false, false>, gemm_sp_nt_kernel<TNW, false, false, true>},
+       {gemm_sp_nt_kernel<TNW, false, true, false>, gemm_sp_nt_kernel<TNW, false, true, true>}},
+      {{gemm_sp_nt_kernel<TNW, true, false, false>, gemm_sp_nt_kernel<TNW, true, false, true>},
+       {gemm_sp_nt_kernel<TNW, true, true, false>, gemm_sp_nt_kernel<TNW, true, true, true>}}};
+  static bool attr_set[2][2][2] = {};
+  const bool out_sp = g.out_sp != nullptr;
+  const Kernel kernel = kernels[ablk][grad][out_sp];
+  if (!attr_set[ablk][grad][out_sp]) {
+    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
+    attr_set[ablk][grad][out_sp] = true;
   }
-#undef SP_LAUNCH
+  hipLaunchKernelGGL(kernel, grid, dim3(G::NT), G::LDS_BYTES, s, g);
 }
 
 // Workspace of the in-launch K split of the NT product (tfgnn_sp_gemm_nt_set_splitk_workspace): [flags 64 KB][slabs].
@@ -1936,6 +1926,144 @@ static int sp_tn_check_workspace(const char* who, const void* d_workspace, size_
   return TFGNN_OK;
 }
 
+// ---- host side of the NT product: ONE description of a call (gemm_sp.hpp NtCall) and ONE function that enqueues it, for the
+// five tfgnn_sp_gemm_nt* entry points and the two products of mp_layer.hip: the checks, NtCall -> SpArgs, the K-split plan ----
+// what the checks work out on the way, defaults resolved; the later steps use it
+struct NtShape {
+  int bn;             // tile width
+  int a_scale_block;  // K where the call says "one block per row"
+  bool a_uniform;     // one scale for the whole tensor
+  int64_t a_src_rows;
+  int64_t group_stride_b;
+  int drop_on;        // SpArgs::drop_on
+  DropoutKey drop;
+  int64_t tiles;      // of the output: the grid before the K split
+};
+
+// Every rejection of a call, in the order and with the texts tests/test_nt_host_contract.py pins: several texts name the entry
+// point that exposes the operand, not the caller's.
+static int sp_nt_check(const NtCall& c, NtShape* d) {
+  const int64_t M = c.M, N = c.N, K = c.K;
+  TFGNN_REQUIRE(c.A && c.B && (c.C || c.out_sp), "tfgnn_sp_gemm_nt: null pointer");
+  d->a_src_rows = (!c.a_rows || c.a_src_rows <= 0) ? M : c.a_src_rows;
+  TFGNN_REQUIRE(!c.a_rows || d->a_src_rows * c.lda_bytes < (1ll << 32) - 65536, "tfgnn_sp_gemm_nt_rows: the operand read through a row index must be below 4 GB");
+  TFGNN_REQUIRE(!c.tile_table || (c.num_tiles_m > 0 && c.num_groups >= 1 && !c.tile_kmask && !c.row_map),
+                "tfgnn_sp_gemm_nt_grouped: a tile table needs its tile count and excludes the tile mask / row map");
+  TFGNN_REQUIRE(c.dropout_rate >= 0.f && c.dropout_rate < 1.f, "tfgnn_sp_gemm_nt: dropout rate must be in [0, 1), got %f", (double)c.dropout_rate);
+  TFGNN_REQUIRE(M > 0 && N > 0 && K > 0 && K % 16 == 0, "tfgnn_sp_gemm_nt: K must be a positive multiple of 16");
+  d->bn = sp_tile_width(N);
+  if (!d->bn) {
+    set_error("tfgnn_sp_gemm_nt: N = %lld is not a multiple of 128", (long long)N);
+    return TFGNN_ERR_UNSUPPORTED;
+  }
+  TFGNN_REQUIRE(c.lda_bytes % 64 == 0 && c.ldb_bytes % 64 == 0 && c.lda_bytes >= K * 4 && c.ldb_bytes >= K * 4 &&
+                    (uintptr_t)c.A % 64 == 0 && (uintptr_t)c.B % 64 == 0,
+                "tfgnn_sp_gemm_nt: SP16 operands must be 64-byte aligned with leading dimensions >= 4 K bytes");
+  TFGNN_REQUIRE((!c.C || (c.ldc % 4 == 0 && (uintptr_t)c.C % 16 == 0)) && (!c.bias || (uintptr_t)c.bias % 16 == 0) &&
+                    (!c.b_inv_scale || (uintptr_t)c.b_inv_scale % 16 == 0) && (!c.mul || (c.ld_mul % 4 == 0 && (uintptr_t)c.mul % 16 == 0)) &&
+                    (!c.saved || (c.ld_saved % 4 == 0 && (uintptr_t)c.saved % 16 == 0)),
+                "tfgnn_sp_gemm_nt: C / bias / scale / factor operands must be 16-byte aligned with ld %% 4 == 0");
+  TFGNN_REQUIRE(128 * c.lda_bytes < (1ll << 31) && 320 * c.ldb_bytes < (1ll << 31), "tfgnn_sp_gemm_nt: K too large");
+  d->a_uniform = c.a_scale_block < 0;
+  d->a_scale_block = (c.a_scale_block <= 0 || c.a_scale_block >= K) ? (int)K : c.a_scale_block;
+  TFGNN_REQUIRE(d->a_scale_block % 16 == 0 && K % d->a_scale_block == 0, "tfgnn_sp_gemm_nt: a_scale_block must divide K and be a multiple of 16");
+  if (c.tile_kmask) {
+    const int a_nblk = (int)(K / d->a_scale_block), a_blk_steps = d->a_scale_block / 16;
+    TFGNN_REQUIRE(a_nblk >= 1 && a_nblk <= 8 && a_blk_steps <= 64 && a_blk_steps * a_nblk == (int)(K >> 4) && c.a_inv_scale &&
+                      !d->a_uniform,
+                  "tfgnn_sp_gemm_nt: the tile mask needs 1..8 scale blocks of A (of at most 1024 columns) that tile K");
+  }
+  d->group_stride_b = c.b_group_stride_bytes >= 0 ? c.b_group_stride_bytes : N * c.ldb_bytes;
+  TFGNN_REQUIRE(d->group_stride_b % 64 == 0, "tfgnn_sp_gemm_nt_grouped: group stride of B must be a multiple of 64 bytes");
+  d->drop_on = c.dropout_rate > 0.f ? (c.dropout_seed == ~0ull ? 2 : 1) : 0;
+  if (d->drop_on == 2)
+    TFGNN_REQUIRE(c.saved && c.act_of_saved == TFGNN_ACT_RELU, "tfgnn_sp_gemm_nt_dropout: the mask-from-saved form needs a relu saved tensor");
+  d->drop = dropout_key(c.dropout_seed, c.dropout_rate);
+  TFGNN_REQUIRE(c.dropout_rate <= 0.f || d->drop.epoch, "tfgnn_sp_gemm_nt_dropout: no device memory for this device's epoch word");
+  if (c.out_sp) {
+    // one scale per row and COLUMN TILE (N = bn: one per row; N = 512 = 2 x 256: scale blocks of 256 columns - round 5)
+    TFGNN_REQUIRE(!c.accumulate && c.out_inv_scale, "tfgnn_sp_gemm_nt_sp: the split result needs no accumulation and an inverse-scale array");
+    TFGNN_REQUIRE(c.ld_out_sp_bytes >= N * 4 && c.ld_out_sp_bytes % 64 == 0 && (uintptr_t)c.out_sp % 64 == 0,
+                  "tfgnn_sp_gemm_nt_sp: SP16 result rows must be 64-byte aligned and at least 4 N bytes");
+  }
+  d->tiles = (c.tile_table ? c.num_tiles_m : ceil_div(M, SP_BM)) * (unsigned)(N / d->bn);
+  TFGNN_REQUIRE(d->tiles <= 0x7fffffff, "tfgnn_sp_gemm_nt: too many tiles");
+  return TFGNN_OK;
+}
+
+// a checked call as the kernel's arguments, unsplit (ksplit = 1; launch_sp_nt sets the XCD order)
+static SpArgs sp_nt_args(const NtCall& c, const NtShape& d) {
+  SpArgs g{};
+  g.M = c.M; g.N = c.N; g.K = c.K;
+  g.A = (const uint8_t*)c.A; g.lda = c.lda_bytes; g.a_inv = c.a_inv_scale;
+  g.a_nblk = (int)(c.K / d.a_scale_block);
+  g.a_inv_ld = d.a_uniform ? 0 : g.a_nblk;
+  g.a_blk_steps = d.a_scale_block / 16;
+  g.B = (const uint8_t*)c.B; g.ldb = c.ldb_bytes; g.b_inv = c.b_inv_scale;
+  g.C = c.C; g.ldc = c.ldc; g.bias = c.bias; g.act = c.act; g.accumulate = c.accumulate;
+  g.mul = c.mul; g.ld_mul = c.ld_mul; g.saved = c.saved; g.ld_saved = c.ld_saved; g.dact = c.act_of_saved;
+  g.saved_scale = c.saved_scale;
+  g.tile_kmask = c.tile_kmask;
+  g.row_map = c.row_map;
+  g.a_rows = c.a_rows;
+  g.a_src_rows = d.a_src_rows;
+  g.tile_table = c.tile_table;
+  g.group_stride_b = d.group_stride_b;
+  g.group_stride_scale = c.b_scale_group_stride >= 0 ? c.b_scale_group_stride : c.N;
+  g.drop_on = d.drop_on;
+  g.drop_ld = c.N;
+  g.drop = d.drop;
+  g.n_tiles = (unsigned)(c.N / d.bn);
+  if (c.out_sp) {
+    g.out_sp = (uint8_t*)c.out_sp; g.ld_out_sp = c.ld_out_sp_bytes; g.out_inv = c.out_inv_scale;
+  }
+  g.ksplit = 1;
+  return g;
+}
+
+// K split inside the launch (SpArgs::ksplit): only where one wave of workgroups leaves most of the chip idle - every
+// workgroup of a split launch must be RESIDENT (the reducers wait for the producers), one per CU
+constexpr int kSplitkMaxSplits = 4;
+// k16 steps a split must keep (K = 320 split in two measured slower: 52 vs 51 us at 56 tiles - the hand-off costs what 10 steps do)
+constexpr int64_t kSplitkMinSteps = 15;
+constexpr int64_t kSplitkMaxWorkgroups = 232;  // of a split launch: all resident, one per CU
+constexpr int64_t kSplitkMaxTiles = 112;       // above this, one wave of workgroups no longer leaves most of the chip idle
+
+// Gives g its K split where the shape asks for one, the workspace has the room and splitk_admit lets this stream have it
+static int sp_nt_plan_splitk(SpArgs& g, const NtShape& d, hipStream_t s) {
+  const int64_t steps = g.K >> 4;
+  int S = (int)std::min<int64_t>(kSplitkMaxSplits, steps / kSplitkMinSteps);
+  while (S > 1 && d.tiles * S > kSplitkMaxWorkgroups) --S;
+  if (!(g_splitk.enabled && g_splitk.base && S > 1 && d.tiles <= kSplitkMaxTiles && !g.tile_table)) return TFGNN_OK;
+  const size_t slab = (size_t)SP_BM * d.bn * 4;
+  const size_t need = kSplitkFlagBytes + (size_t)d.tiles * (S - 1) * slab;
+  const int admit = (need <= g_splitk.bytes && (size_t)d.tiles * (S - 1) * 4 <= kSplitkFlagBytes) ? splitk_admit(s) : 0;
+  if (admit < 0) return TFGNN_ERR_HIP;
+  if (admit > 0) {
+    g.ksplit = S;
+    ++g_splitk.split_launches;
+    g.ws_flags = (unsigned*)g_splitk.base;
+    g.ws_partial = (float*)((char*)g_splitk.base + kSplitkFlagBytes);
+    g.ws_timeout = g_splitk.timeout_dev;
+  }
+  return TFGNN_OK;
+}
+
+int sp_nt_enqueue(const NtCall& c, hipStream_t s) {
+  NtShape d;
+  int rc = sp_nt_check(c, &d);
+  if (rc) return rc;
+  SpArgs g = sp_nt_args(c, d);
+  rc = sp_nt_plan_splitk(g, d, s);
+  if (rc) return rc;
+  const dim3 grid((unsigned)(d.tiles * g.ksplit));
+  if (d.bn == 320) launch_sp_nt<5>(g, grid, s);
+  else if (d.bn == 256) launch_sp_nt<4>(g, grid, s);
+  else launch_sp_nt<2>(g, grid, s);
+  TFGNN_LAUNCH_CHECK();
+  return TFGNN_OK;
+}
+
 }  // namespace tfgnn
 
 using namespace tfgnn;
@@ -1993,108 +2121,6 @@ int tfgnn_sp_split_cols(const float* d_src, int64_t ld, int64_t K, int64_t N, vo
   return TFGNN_OK;
 }
 
-static int sp_gemm_nt_impl(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, const float* d_a_inv_scale,
-                           int a_scale_block, const void* d_B_sp, int64_t ldb_bytes, const float* d_b_inv_scale, float* d_C,
-                           int64_t ldc, const float* d_bias, int act, int accumulate, const float* d_mul, int64_t ld_mul,
-                           int act_of_saved, const float* d_saved, int64_t ld_saved, void* d_out_sp, int64_t ld_out_sp_bytes,
-                           float* d_out_inv_scale, void* stream, float dropout_rate = 0.f, uint64_t dropout_seed = 0,
-                           float saved_scale = 1.f, const uint8_t* d_tile_kmask = nullptr, const int32_t* d_row_map = nullptr,
-                           const int32_t* d_a_rows = nullptr, int64_t a_src_rows = 0, const int32_t* d_tile_table = nullptr,
-                           int64_t num_tiles_m = 0, int num_groups = 1, int64_t b_group_stride_bytes = -1,
-                           int64_t b_scale_group_stride = -1) {
-  TFGNN_REQUIRE(d_A_sp && d_B_sp && (d_C || d_out_sp), "tfgnn_sp_gemm_nt: null pointer");
-  if (!d_a_rows || a_src_rows <= 0) a_src_rows = M;
-  TFGNN_REQUIRE(!d_a_rows || a_src_rows * lda_bytes < (1ll << 32) - 65536, "tfgnn_sp_gemm_nt_rows: the operand read through a row index must be below 4 GB");
-  TFGNN_REQUIRE(!d_tile_table || (num_tiles_m > 0 && num_groups >= 1 && !d_tile_kmask && !d_row_map),
-                "tfgnn_sp_gemm_nt_grouped: a tile table needs its tile count and excludes the tile mask / row map");
-  TFGNN_REQUIRE(dropout_rate >= 0.f && dropout_rate < 1.f, "tfgnn_sp_gemm_nt: dropout rate must be in [0, 1), got %f", (double)dropout_rate);
-  TFGNN_REQUIRE(M > 0 && N > 0 && K > 0 && K % 16 == 0, "tfgnn_sp_gemm_nt: K must be a positive multiple of 16");
-  const int bn = sp_tile_width(N);
-  if (!bn) {
-    set_error("tfgnn_sp_gemm_nt: N = %lld is not a multiple of 128", (long long)N);
-    return TFGNN_ERR_UNSUPPORTED;
-  }
-  TFGNN_REQUIRE(lda_bytes % 64 == 0 && ldb_bytes % 64 == 0 && lda_bytes >= K * 4 && ldb_bytes >= K * 4 &&
-                    (uintptr_t)d_A_sp % 64 == 0 && (uintptr_t)d_B_sp % 64 == 0,
-                "tfgnn_sp_gemm_nt: SP16 operands must be 64-byte aligned with leading dimensions >= 4 K bytes");
-  TFGNN_REQUIRE((!d_C || (ldc % 4 == 0 && (uintptr_t)d_C % 16 == 0)) && (!d_bias || (uintptr_t)d_bias % 16 == 0) &&
-                    (!d_b_inv_scale || (uintptr_t)d_b_inv_scale % 16 == 0) && (!d_mul || (ld_mul % 4 == 0 && (uintptr_t)d_mul % 16 == 0)) &&
-                    (!d_saved || (ld_saved % 4 == 0 && (uintptr_t)d_saved % 16 == 0)),
-                "tfgnn_sp_gemm_nt: C / bias / scale / factor operands must be 16-byte aligned with ld %% 4 == 0");
-  TFGNN_REQUIRE(128 * lda_bytes < (1ll << 31) && 320 * ldb_bytes < (1ll << 31), "tfgnn_sp_gemm_nt: K too large");
-  SpArgs g{};
-  g.M = M; g.N = N; g.K = K;
-  g.A = (const uint8_t*)d_A_sp; g.lda = lda_bytes; g.a_inv = d_a_inv_scale;
-  const bool a_uniform = a_scale_block < 0;  // one scale for the whole tensor
-  if (a_scale_block <= 0 || a_scale_block >= K) a_scale_block = (int)K;
-  TFGNN_REQUIRE(a_scale_block % 16 == 0 && K % a_scale_block == 0, "tfgnn_sp_gemm_nt: a_scale_block must divide K and be a multiple of 16");
-  g.a_nblk = (int)(K / a_scale_block);
-  g.a_inv_ld = a_uniform ? 0 : g.a_nblk;
-  g.a_blk_steps = a_scale_block / 16;
-  g.B = (const uint8_t*)d_B_sp; g.ldb = ldb_bytes; g.b_inv = d_b_inv_scale;
-  g.C = d_C; g.ldc = ldc; g.bias = d_bias; g.act = act; g.accumulate = accumulate;
-  g.mul = d_mul; g.ld_mul = ld_mul; g.saved = d_saved; g.ld_saved = ld_saved; g.dact = act_of_saved;
-  g.saved_scale = saved_scale;
-  if (d_tile_kmask) {
-    TFGNN_REQUIRE(g.a_nblk >= 1 && g.a_nblk <= 8 && g.a_blk_steps <= 64 && g.a_blk_steps * g.a_nblk == (int)(K >> 4) && g.a_inv &&
-                      !a_uniform,
-                  "tfgnn_sp_gemm_nt: the tile mask needs 1..8 scale blocks of A (of at most 1024 columns) that tile K");
-    g.tile_kmask = d_tile_kmask;
-  }
-  g.row_map = d_row_map;
-  g.a_rows = d_a_rows;
-  g.a_src_rows = a_src_rows;
-  g.tile_table = d_tile_table;
-  g.group_stride_b = b_group_stride_bytes >= 0 ? b_group_stride_bytes : N * ldb_bytes;
-  g.group_stride_scale = b_scale_group_stride >= 0 ? b_scale_group_stride : N;
-  TFGNN_REQUIRE(g.group_stride_b % 64 == 0, "tfgnn_sp_gemm_nt_grouped: group stride of B must be a multiple of 64 bytes");
-  g.drop_on = dropout_rate > 0.f ? (dropout_seed == ~0ull ? 2 : 1) : 0;
-  if (g.drop_on == 2)
-    TFGNN_REQUIRE(d_saved && act_of_saved == TFGNN_ACT_RELU, "tfgnn_sp_gemm_nt_dropout: the mask-from-saved form needs a relu saved tensor");
-  g.drop_ld = N;
-  g.drop = dropout_key(dropout_seed, dropout_rate);
-  TFGNN_REQUIRE(dropout_rate <= 0.f || g.drop.epoch, "tfgnn_sp_gemm_nt_dropout: no device memory for this device's epoch word");
-  g.n_tiles = (unsigned)(N / bn);
-  if (d_out_sp) {
-    // one scale per row and COLUMN TILE (N = bn: one per row; N = 512 = 2 x 256: scale blocks of 256 columns - round 5)
-    TFGNN_REQUIRE(!accumulate && d_out_inv_scale, "tfgnn_sp_gemm_nt_sp: the split result needs no accumulation and an inverse-scale array");
-    TFGNN_REQUIRE(ld_out_sp_bytes >= N * 4 && ld_out_sp_bytes % 64 == 0 && (uintptr_t)d_out_sp % 64 == 0,
-                  "tfgnn_sp_gemm_nt_sp: SP16 result rows must be 64-byte aligned and at least 4 N bytes");
-    g.out_sp = (uint8_t*)d_out_sp; g.ld_out_sp = ld_out_sp_bytes; g.out_inv = d_out_inv_scale;
-  }
-  const int64_t tiles = (d_tile_table ? num_tiles_m : ceil_div(M, SP_BM)) * g.n_tiles;
-  TFGNN_REQUIRE(tiles <= 0x7fffffff, "tfgnn_sp_gemm_nt: too many tiles");
-  // K split inside the launch (SpArgs::ksplit): only where one wave of workgroups leaves most of the chip idle - every
-  // workgroup of a split launch must be RESIDENT (the reducers wait for the producers), one per CU
-  g.ksplit = 1;
-  {
-    const int64_t steps = K >> 4;
-    int S = (int)std::min<int64_t>(4, steps / 15);  // (K = 320 split in two measured slower: 52 vs 51 us at 56 tiles - the hand-off costs what 10 steps do)
-    while (S > 1 && tiles * S > 232) --S;
-    if (g_splitk.enabled && g_splitk.base && S > 1 && tiles <= 112 && !d_tile_table) {
-      const size_t slab = (size_t)SP_BM * bn * 4;
-      const size_t need = kSplitkFlagBytes + (size_t)tiles * (S - 1) * slab;
-      const int admit = (need <= g_splitk.bytes && (size_t)tiles * (S - 1) * 4 <= kSplitkFlagBytes) ? splitk_admit((hipStream_t)stream) : 0;
-      if (admit < 0) return TFGNN_ERR_HIP;
-      if (admit > 0) {
-        g.ksplit = S;
-        ++g_splitk.split_launches;
-        g.ws_flags = (unsigned*)g_splitk.base;
-        g.ws_partial = (float*)((char*)g_splitk.base + kSplitkFlagBytes);
-        g.ws_timeout = g_splitk.timeout_dev;
-      }
-    }
-  }
-  dim3 grid((unsigned)(tiles * g.ksplit));
-  hipStream_t s = (hipStream_t)stream;
-  if (bn == 320) launch_sp_nt<5>(g, grid, s);
-  else if (bn == 256) launch_sp_nt<4>(g, grid, s);
-  else launch_sp_nt<2>(g, grid, s);
-  TFGNN_LAUNCH_CHECK();
-  return TFGNN_OK;
-}
-
-
 int tfgnn_sp_gemm_nt_set_splitk_workspace(void* d_workspace, size_t bytes) {
   // (waits for the device: nothing in flight may still be using the previous workspace)
   TFGNN_HIP_CHECK(hipDeviceSynchronize());
@@ -2137,8 +2163,14 @@ int tfgnn_sp_gemm_nt(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_
                      int64_t ldc, const float* d_bias, int act, int accumulate, const float* d_mul, int64_t ld_mul,
                      int act_of_saved, const float* d_saved, int64_t ld_saved, void* stream) {
   TFGNN_REQUIRE(d_C, "tfgnn_sp_gemm_nt: null pointer");
-  return sp_gemm_nt_impl(M, N, K, d_A_sp, lda_bytes, d_a_inv_scale, a_scale_block, d_B_sp, ldb_bytes, d_b_inv_scale, d_C, ldc, d_bias,
-                         act, accumulate, d_mul, ld_mul, act_of_saved, d_saved, ld_saved, nullptr, 0, nullptr, stream);
+  NtCall c;
+  c.M = M; c.N = N; c.K = K;
+  c.A = d_A_sp; c.lda_bytes = lda_bytes; c.a_inv_scale = d_a_inv_scale; c.a_scale_block = a_scale_block;
+  c.B = d_B_sp; c.ldb_bytes = ldb_bytes; c.b_inv_scale = d_b_inv_scale;
+  c.C = d_C; c.ldc = ldc; c.accumulate = accumulate;
+  c.bias = d_bias; c.act = act;
+  c.mul = d_mul; c.ld_mul = ld_mul; c.act_of_saved = act_of_saved; c.saved = d_saved; c.ld_saved = ld_saved;
+  return sp_nt_enqueue(c, (hipStream_t)stream);
 }
 
 int tfgnn_sp_gemm_nt_sp(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, const float* d_a_inv_scale,
@@ -2147,8 +2179,15 @@ int tfgnn_sp_gemm_nt_sp(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int
                         const float* d_saved, int64_t ld_saved, void* d_out_sp, int64_t ld_out_sp_bytes,
                         float* d_out_inv_scale, void* stream) {
   TFGNN_REQUIRE(d_out_sp, "tfgnn_sp_gemm_nt_sp: null pointer");
-  return sp_gemm_nt_impl(M, N, K, d_A_sp, lda_bytes, d_a_inv_scale, a_scale_block, d_B_sp, ldb_bytes, d_b_inv_scale, d_C, ldc, d_bias,
-                         act, 0, d_mul, ld_mul, act_of_saved, d_saved, ld_saved, d_out_sp, ld_out_sp_bytes, d_out_inv_scale, stream);
+  NtCall c;
+  c.M = M; c.N = N; c.K = K;
+  c.A = d_A_sp; c.lda_bytes = lda_bytes; c.a_inv_scale = d_a_inv_scale; c.a_scale_block = a_scale_block;
+  c.B = d_B_sp; c.ldb_bytes = ldb_bytes; c.b_inv_scale = d_b_inv_scale;
+  c.C = d_C; c.ldc = ldc;
+  c.out_sp = d_out_sp; c.ld_out_sp_bytes = ld_out_sp_bytes; c.out_inv_scale = d_out_inv_scale;
+  c.bias = d_bias; c.act = act;
+  c.mul = d_mul; c.ld_mul = ld_mul; c.act_of_saved = act_of_saved; c.saved = d_saved; c.ld_saved = ld_saved;
+  return sp_nt_enqueue(c, (hipStream_t)stream);
 }
 
 int tfgnn_sp_gemm_nt_dropout(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, const float* d_a_inv_scale,
@@ -2157,9 +2196,17 @@ int tfgnn_sp_gemm_nt_dropout(int64_t M, int64_t N, int64_t K, const void* d_A_sp
                              int act_of_saved, const float* d_saved, int64_t ld_saved, float saved_scale, void* d_out_sp,
                              int64_t ld_out_sp_bytes, float* d_out_inv_scale, float dropout_rate, uint64_t dropout_seed,
                              const uint8_t* d_tile_kmask, const int32_t* d_row_map, void* stream) {
-  return sp_gemm_nt_impl(M, N, K, d_A_sp, lda_bytes, d_a_inv_scale, a_scale_block, d_B_sp, ldb_bytes, d_b_inv_scale, d_C, ldc, d_bias,
-                         act, accumulate, d_mul, ld_mul, act_of_saved, d_saved, ld_saved, d_out_sp, ld_out_sp_bytes, d_out_inv_scale,
-                         stream, dropout_rate, dropout_seed, saved_scale, d_tile_kmask, d_row_map);
+  NtCall c;
+  c.M = M; c.N = N; c.K = K;
+  c.A = d_A_sp; c.lda_bytes = lda_bytes; c.a_inv_scale = d_a_inv_scale; c.a_scale_block = a_scale_block;
+  c.B = d_B_sp; c.ldb_bytes = ldb_bytes; c.b_inv_scale = d_b_inv_scale;
+  c.C = d_C; c.ldc = ldc; c.accumulate = accumulate;
+  c.out_sp = d_out_sp; c.ld_out_sp_bytes = ld_out_sp_bytes; c.out_inv_scale = d_out_inv_scale;
+  c.bias = d_bias; c.act = act;
+  c.mul = d_mul; c.ld_mul = ld_mul; c.act_of_saved = act_of_saved; c.saved = d_saved; c.ld_saved = ld_saved;
+  c.saved_scale = saved_scale; c.dropout_rate = dropout_rate; c.dropout_seed = dropout_seed;
+  c.tile_kmask = d_tile_kmask; c.row_map = d_row_map;
+  return sp_nt_enqueue(c, (hipStream_t)stream);
 }
 
 int tfgnn_sp_gemm_nt_rows(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, const float* d_a_inv_scale,
@@ -2168,9 +2215,17 @@ int tfgnn_sp_gemm_nt_rows(int64_t M, int64_t N, int64_t K, const void* d_A_sp, i
                           int act_of_saved, const float* d_saved, int64_t ld_saved, float saved_scale, void* d_out_sp,
                           int64_t ld_out_sp_bytes, float* d_out_inv_scale, float dropout_rate, uint64_t dropout_seed,
                           const uint8_t* d_tile_kmask, const int32_t* d_row_map, void* stream) {
-  return sp_gemm_nt_impl(M, N, K, d_A_sp, lda_bytes, d_a_inv_scale, a_scale_block, d_B_sp, ldb_bytes, d_b_inv_scale, d_C, ldc, d_bias,
-                         act, accumulate, d_mul, ld_mul, act_of_saved, d_saved, ld_saved, d_out_sp, ld_out_sp_bytes, d_out_inv_scale,
-                         stream, dropout_rate, dropout_seed, saved_scale, d_tile_kmask, d_row_map, d_a_rows);
+  NtCall c;
+  c.M = M; c.N = N; c.K = K;
+  c.A = d_A_sp; c.lda_bytes = lda_bytes; c.a_inv_scale = d_a_inv_scale; c.a_scale_block = a_scale_block; c.a_rows = d_a_rows;
+  c.B = d_B_sp; c.ldb_bytes = ldb_bytes; c.b_inv_scale = d_b_inv_scale;
+  c.C = d_C; c.ldc = ldc; c.accumulate = accumulate;
+  c.out_sp = d_out_sp; c.ld_out_sp_bytes = ld_out_sp_bytes; c.out_inv_scale = d_out_inv_scale;
+  c.bias = d_bias; c.act = act;
+  c.mul = d_mul; c.ld_mul = ld_mul; c.act_of_saved = act_of_saved; c.saved = d_saved; c.ld_saved = ld_saved;
+  c.saved_scale = saved_scale; c.dropout_rate = dropout_rate; c.dropout_seed = dropout_seed;
+  c.tile_kmask = d_tile_kmask; c.row_map = d_row_map;
+  return sp_nt_enqueue(c, (hipStream_t)stream);
 }
 
 int tfgnn_sp_gemm_nt_grouped(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, const float* d_a_inv_scale,
@@ -2180,10 +2235,18 @@ int tfgnn_sp_gemm_nt_grouped(int64_t M, int64_t N, int64_t K, const void* d_A_sp
                              int act, const float* d_mul, int64_t ld_mul, int act_of_saved, const float* d_saved, int64_t ld_saved,
                              void* d_out_sp, int64_t ld_out_sp_bytes, float* d_out_inv_scale, void* stream) {
   TFGNN_REQUIRE(d_tile_table && num_tiles > 0 && num_groups >= 1, "tfgnn_sp_gemm_nt_grouped: tile table missing");
-  return sp_gemm_nt_impl(M, N, K, d_A_sp, lda_bytes, d_a_inv_scale, a_scale_block, d_B_sp, ldb_bytes, d_b_inv_scale, d_C, ldc, d_bias,
-                         act, 0, d_mul, ld_mul, act_of_saved, d_saved, ld_saved, d_out_sp, ld_out_sp_bytes, d_out_inv_scale, stream,
-                         0.f, 0, 1.f, nullptr, nullptr, d_a_rows, a_src_rows, d_tile_table, num_tiles, num_groups,
-                         b_group_stride_bytes, b_scale_group_stride);
+  NtCall c;
+  c.M = M; c.N = N; c.K = K;
+  c.A = d_A_sp; c.lda_bytes = lda_bytes; c.a_inv_scale = d_a_inv_scale; c.a_scale_block = a_scale_block;
+  c.a_rows = d_a_rows; c.a_src_rows = a_src_rows;
+  c.B = d_B_sp; c.ldb_bytes = ldb_bytes; c.b_inv_scale = d_b_inv_scale;
+  c.b_group_stride_bytes = b_group_stride_bytes; c.b_scale_group_stride = b_scale_group_stride;
+  c.C = d_C; c.ldc = ldc;
+  c.out_sp = d_out_sp; c.ld_out_sp_bytes = ld_out_sp_bytes; c.out_inv_scale = d_out_inv_scale;
+  c.bias = d_bias; c.act = act;
+  c.mul = d_mul; c.ld_mul = ld_mul; c.act_of_saved = act_of_saved; c.saved = d_saved; c.ld_saved = ld_saved;
+  c.tile_table = d_tile_table; c.num_tiles_m = num_tiles; c.num_groups = num_groups;
+  return sp_nt_enqueue(c, (hipStream_t)stream);
 }
 
 // K ranges of a plain product: what the output tiles leave of one round of workgroups; the two-factor form (wide) takes ranges

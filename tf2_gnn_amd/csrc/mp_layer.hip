@@ -18,6 +18,7 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "gemm_sp.hpp"
 #include "tfgnn.h"
 
 using namespace tfgnn;
@@ -53,9 +54,16 @@ extern "C" int tfgnn_mp_forward(const tfgnn_mp_forward_args* a, void* stream) {
     if (rc) return rc;
   }
   // 3. the product with its epilogue
-  return tfgnn_sp_gemm_nt_rows(V, H, K, a->agg_sp, K * 4, a->agg_inv_scale, (int)D, nullptr, a->wt_sp, a->ld_wt_sp_bytes, a->wt_inv_scale,
-                               a->out, a->ld_out, a->bias, a->act, 0, nullptr, 0, TFGNN_ACT_NONE, nullptr, 0, 1.f, a->out_sp,
-                               a->ld_out_sp_bytes, a->out_inv_scale, a->dropout_rate, a->dropout_seed, a->tile_kmask, a->row_map, stream);
+  NtCall c;
+  c.M = V; c.N = H; c.K = K;
+  c.A = a->agg_sp; c.lda_bytes = K * 4; c.a_inv_scale = a->agg_inv_scale; c.a_scale_block = (int)D;
+  c.B = a->wt_sp; c.ldb_bytes = a->ld_wt_sp_bytes; c.b_inv_scale = a->wt_inv_scale;
+  c.C = a->out; c.ldc = a->ld_out;
+  c.out_sp = a->out_sp; c.ld_out_sp_bytes = a->ld_out_sp_bytes; c.out_inv_scale = a->out_inv_scale;
+  c.bias = a->bias; c.act = a->act;
+  c.dropout_rate = a->dropout_rate; c.dropout_seed = a->dropout_seed;
+  c.tile_kmask = a->tile_kmask; c.row_map = a->row_map;
+  return sp_nt_enqueue(c, (hipStream_t)stream);
 }
 
 extern "C" int tfgnn_mp_backward(const tfgnn_mp_backward_args* a, void* stream) {
@@ -85,10 +93,16 @@ extern "C" int tfgnn_mp_backward(const tfgnn_mp_backward_args* a, void* stream) 
     if (rc) return rc;
   }
   // 3. dX = G W^T with the gradient factors of the op below in the epilogue; rows in by-source pattern order when asked
-  rc = tfgnn_sp_gemm_nt_rows(V, D, K, a->g_sp, K * 4, a->g_inv_scale, (int)H, a->a_rows, a->wh_sp, a->ld_wh_sp_bytes, a->wh_inv_scale, a->dx,
-                             a->ld_dx, nullptr, TFGNN_ACT_NONE, a->accumulate, a->mul, a->ld_mul, a->act_of_saved, a->saved, a->ld_saved,
-                             a->saved_scale, a->dx_sp, a->ld_dx_sp_bytes, a->dx_inv_scale, a->dropout_rate, a->dropout_seed, a->tile_kmask,
-                             a->row_map, stream);
+  NtCall c;
+  c.M = V; c.N = D; c.K = K;
+  c.A = a->g_sp; c.lda_bytes = K * 4; c.a_inv_scale = a->g_inv_scale; c.a_scale_block = (int)H; c.a_rows = a->a_rows;
+  c.B = a->wh_sp; c.ldb_bytes = a->ld_wh_sp_bytes; c.b_inv_scale = a->wh_inv_scale;
+  c.C = a->dx; c.ldc = a->ld_dx; c.accumulate = a->accumulate;
+  c.out_sp = a->dx_sp; c.ld_out_sp_bytes = a->ld_dx_sp_bytes; c.out_inv_scale = a->dx_inv_scale;
+  c.mul = a->mul; c.ld_mul = a->ld_mul; c.act_of_saved = a->act_of_saved; c.saved = a->saved; c.ld_saved = a->ld_saved;
+  c.saved_scale = a->saved_scale; c.dropout_rate = a->dropout_rate; c.dropout_seed = a->dropout_seed;
+  c.tile_kmask = a->tile_kmask; c.row_map = a->row_map;
+  rc = sp_nt_enqueue(c, (hipStream_t)stream);
   if (rc) return rc;
   // 4. dW[l, d, h] = sum_v X[v, d] G[v, l, h]: element ((l, h), d) of G^T X scattered into the kernels' [L, D, H] layout
   if (a->dw)
