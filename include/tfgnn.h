@@ -888,6 +888,46 @@ int tfgnn_sp_gemm_tn(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_
                      int64_t ldb_bytes, int64_t b_first_col, const float* d_b_inv_scale, float* d_C, int64_t group_rows,
                      int64_t stride_group, int64_t stride_row, int64_t stride_col, int accumulate, void* d_workspace,
                      size_t workspace_bytes, void* stream);
+/* The reduce pass of a weight-gradient product carried by the NT product that follows it.  A weight gradient dW = X^T G and
+ * the input gradient dX = G W^T of one layer are independent, and nothing on the critical path reads dW - so the reduce pass
+ * (its own launch behind tfgnn_sp_gemm_tn: splits x M x N partial floats summed in split order) can run on the CUs the NT
+ * product's row tiles leave free, as extra workgroups BEHIND the product's own in the same grid.
+ *   tfgnn_sp_gemm_tn_product   tfgnn_sp_gemm_tn up to and including the product (and the armed repair pass); *job receives the
+ *                               reduce pass instead of a launch.  Same operands, checks, workspace and arithmetic: dW comes out
+ *                               bit for bit as tfgnn_sp_gemm_tn writes it.  A product whose reduction cannot be carried
+ *                               runs it at once and hands back an empty job (num_blocks 0).
+ *   tfgnn_sp_gemm_nt_rows_tail  tfgnn_sp_gemm_nt_rows whose launch carries *job (NULL or empty: exactly tfgnn_sp_gemm_nt_rows) on
+ *                               job->num_blocks extra workgroups; they wait for nothing - stream order has finished the TN
+ *                               product - so the call must be enqueued on the stream of, and after, the deferred product.
+ *                               M = 0 (nothing to multiply) runs the job in a launch of its own.
+ *   tfgnn_tn_reduce_launch      the job in a launch of its own (what tfgnn_sp_gemm_tn does); an empty job: nothing.
+ * The caller that takes a job runs it exactly once, through one of the two, before anything reads dW or reuses the product's
+ * workspace: a job holds device pointers into that workspace (partials, reference scales, trip words), which stays untouched
+ * until the job has been issued.  It may NOT overlap the K-split workspace of the NT product
+ * (tfgnn_sp_gemm_nt_set_splitk_workspace) - both are live in the carrying launch; an overlap is refused.  The library keeps
+ * no queue of jobs.  num_blocks is filled from the size of the reduction (one workgroup per 512 elements, at most 1024);
+ * a caller may change it (> 0).  tfgnn_tn_reduce_counts: out_counts[0] = reduce passes launched on their own so far (the plain
+ * and the grouped), [1] = passes carried by an NT launch (host counters, like tfgnn_launch_counts - whose TFGNN_KFAM_SP_TN /
+ * TFGNN_KFAM_SP_NT keep counting products and NT launches). */
+typedef struct tfgnn_tn_reduce_job {
+  unsigned num_blocks; /* 0: nothing to do */
+  unsigned reserved;
+  unsigned char payload[184];
+} tfgnn_tn_reduce_job;
+int tfgnn_sp_gemm_tn_product(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, int64_t a_first_col,
+                              const float* d_a_inv_scale, int64_t a_total_cols, int a_scale_block, const void* d_B_sp,
+                              int64_t ldb_bytes, int64_t b_first_col, const float* d_b_inv_scale, float* d_C, int64_t group_rows,
+                              int64_t stride_group, int64_t stride_row, int64_t stride_col, int accumulate, void* d_workspace,
+                              size_t workspace_bytes, tfgnn_tn_reduce_job* job, void* stream);
+int tfgnn_tn_reduce_launch(const tfgnn_tn_reduce_job* job, void* stream);
+int tfgnn_tn_reduce_counts(int64_t* out_counts, int n);
+int tfgnn_sp_gemm_nt_rows_tail(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, const float* d_a_inv_scale,
+                               int a_scale_block, const int32_t* d_a_rows, const void* d_B_sp, int64_t ldb_bytes,
+                               const float* d_b_inv_scale, float* d_C, int64_t ldc, const float* d_bias, int act, int accumulate,
+                               const float* d_mul, int64_t ld_mul, int act_of_saved, const float* d_saved, int64_t ld_saved,
+                               float saved_scale, void* d_out_sp, int64_t ld_out_sp_bytes, float* d_out_inv_scale, float dropout_rate,
+                               uint64_t dropout_seed, const uint8_t* d_tile_kmask, const int32_t* d_row_map,
+                               const tfgnn_tn_reduce_job* job, void* stream);
 
 /* Tensor-wide scales (d_fixed_inv_scale of the SP16 producers; tfgnn_sp_gemm_nt takes such an operand with a_scale_block < 0):
  * tfgnn_absmax gives *d_out = max(*d_out, scale * max |x|)
@@ -1184,11 +1224,17 @@ typedef struct tfgnn_mp_backward_args {
   size_t tn_workspace_bytes;
   void* workspace;          /* tfgnn_graph_gather_workspace_bytes(graph, TFGNN_VIEW_BY_SRC_TYPED, H) bytes */
   size_t workspace_bytes;
+  /* Up to 1024 row tiles of 128 nodes the pass runs gather - weight-gradient product - input-gradient product, and the
+   * latter's launch carries the reduce pass of the former (tfgnn_sp_gemm_nt_rows_tail): tn_workspace is read while the
+   * input-gradient product runs.  tn_workspace may overlap neither workspace nor the K-split workspace of the NT product
+   * (tfgnn_sp_gemm_nt_set_splitk_workspace); a call where it does is refused.  Over more nodes the order is gather - input-
+   * gradient product - tfgnn_sp_gemm_tn, its reduce pass in its own launch.  Same results either way, bit for bit. */
 } tfgnn_mp_backward_args;
 
 /* = tfgnn_graph_gather_reduce_sp_deferred + tfgnn_sp_split_cols_job + tfgnn_aux_launch + tfgnn_sp_gemm_nt_rows */
 int tfgnn_mp_forward(const tfgnn_mp_forward_args* args, void* stream);
-/* = tfgnn_graph_gather_reduce_sp_deferred + tfgnn_sp_split_rows_job + tfgnn_aux_launch + tfgnn_sp_gemm_nt_rows + tfgnn_sp_gemm_tn */
+/* = tfgnn_graph_gather_reduce_sp_deferred + tfgnn_sp_split_rows_job + tfgnn_aux_launch + tfgnn_sp_gemm_tn_product +
+ *   tfgnn_sp_gemm_nt_rows_tail */
 int tfgnn_mp_backward(const tfgnn_mp_backward_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------

@@ -328,6 +328,25 @@ _SIGNATURES += [
     ("tfgnn_mp_backward", c_int, [c_void_p, c_void_p]),
 ]
 
+# the reduce pass of a weight-gradient product carried by the next NT launch (include/tfgnn.h tfgnn_tn_reduce_job)
+_SIGNATURES += [
+    (
+        "tfgnn_sp_gemm_tn_product",
+        c_int,
+        [c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p,
+         c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_size_t, c_void_p, c_void_p],
+    ),
+    ("tfgnn_tn_reduce_launch", c_int, [c_void_p, c_void_p]),
+    ("tfgnn_tn_reduce_counts", c_int, [POINTER(c_int64), c_int]),
+    (
+        "tfgnn_sp_gemm_nt_rows_tail",
+        c_int,
+        [c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+         c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_void_p, c_int64, c_float, c_void_p, c_int64, c_void_p, c_float,
+         ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+]
+
 # graph readout (include/tfgnn.h "Graph readout", csrc/pool_fused.hip)
 _SIGNATURES += [
     ("tfgnn_pool_workspace_bytes", c_size_t, [c_int64, c_int64, c_int, c_int, c_int]),
@@ -408,6 +427,12 @@ class AuxJob(ctypes.Structure):
     """tfgnn_aux_job (include/tfgnn.h): one small pass of a merged launch"""
 
     _fields_ = [("kind", c_int), ("num_blocks", ctypes.c_uint), ("payload", ctypes.c_ubyte * 248)]
+
+
+class TnReduceJob(ctypes.Structure):
+    """tfgnn_tn_reduce_job (include/tfgnn.h): the reduce pass a deferred weight-gradient product hands back"""
+
+    _fields_ = [("num_blocks", ctypes.c_uint), ("reserved", ctypes.c_uint), ("payload", ctypes.c_ubyte * 184)]
 
 
 class MpForwardArgs(ctypes.Structure):

@@ -28,7 +28,9 @@
 //   barrier per step only orders buffer reuse.  Epilogue: scales, bias, activation, gradient factors, through a
 //   wave-private LDS patch so that every lane stores 16 contiguous bytes.
 #include <algorithm>
+#include <cstddef>
 #include <cstdlib>
+#include <cstring>
 
 #include <type_traits>
 
@@ -121,6 +123,16 @@ struct SpArgs {
   // != 0: tile = (b % 8) * xcd_per + b / 8 - an XCD walks whole row tiles, their column tiles back to back - and workgroups
   // past xcd_total leave at once (the grid is padded to 8 xcd_per).  Set by launch_sp_nt (never together with ksplit).
   unsigned xcd_per, xcd_total;
+};
+
+// The reduce pass of the weight-gradient product that ran in front of an NT launch, carried by the LAST `blocks` workgroups
+// of the grid (behind all product workgroups, all S x tiles of them under a K split): they run on the CUs the tiles leave
+// free - 21 of 256 at 235 row tiles, more once the light tiles of a masked product are done - and the pass needs no launch
+// of its own.  first = the product workgroups of the grid (XCD padding included; launch_sp_nt sets it for every launch),
+// blocks = 0: none - the grid ends at `first`.  The kernel's second argument, filled by sp_nt_enqueue from NtCall::tail.
+struct SpTail {
+  unsigned first, blocks;
+  TnReduceArgs args;
 };
 
 // ------------------------------------------------------------------------------------------------------
@@ -450,12 +462,79 @@ struct SpLoop {
   }
 };
 
+// ---- split-K partials of a weight gradient -> dW -----------------------------------------------------------------------
+// C[(m / group_rows) * stride_group + (m % group_rows) * stride_row + n * stride_col] (+)= ref[blk(m)] * sum_z partial[z][m][n]
+// (`block` of `nblocks` workgroups of `nthreads` threads walk the M * N elements: sp_tn_reduce_kernel's, or the workgroups an
+// NT launch carries behind its tiles - every element is summed by one thread in the same order whichever grid walks them)
+__device__ __forceinline__ void sp_tn_reduce_body(const TnReduceArgs& a, unsigned block, unsigned nblocks, unsigned nthreads) {
+  const int64_t total = a.M * a.N;  // slab >= total: floats per split (the product pads M to a multiple of 128)
+  for (int64_t i = (int64_t)block * nthreads + threadIdx.x; i < total; i += (int64_t)nblocks * nthreads) {
+    const int64_t m = i / a.N, n = i - m * a.N;
+    const int64_t blk = (a.a_col0 + m) / a.a_sb;
+    float s = 0.f;
+    int z = 0;
+    if (a.ref_ld > 0) {  // every split carries its own reference scale (factors computed inside the product kernel)
+      for (; z + 8 <= a.splits; z += 8) {  // eight loads in flight; the sum stays in split order
+        float v[8], r[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          v[u] = a.partial[(int64_t)(z + u) * a.slab + i];
+          r[u] = a.ref[(int64_t)(z + u) * a.ref_ld + blk];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += v[u] * r[u];
+      }
+      for (; z < a.splits; ++z) s += a.partial[(int64_t)z * a.slab + i] * a.ref[(int64_t)z * a.ref_ld + blk];
+    } else {
+      for (; z + 8 <= a.splits; z += 8) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = a.partial[(int64_t)(z + u) * a.slab + i];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += v[u];
+      }
+      for (; z < a.splits; ++z) s += a.partial[(int64_t)z * a.slab + i];
+      s *= a.ref[blk];
+    }
+    const int64_t gi = m / a.group_rows, mi = m - gi * a.group_rows;
+    float* dst = a.C + gi * a.stride_group + mi * a.stride_row + n * a.stride_col;
+    *dst = a.accumulate ? *dst + s : s;
+  }
+}
+
+// The carried pass as the NT kernels run it: a function of its own, NOT inlined.  Inlined, the pass never shares a live range
+// with the product - it sits in a branch that returns - yet the gradient kernels at 256 and 320 columns came out with 10 - 26
+// spilled scalar registers in their epilogues (tools/kernel_resources.py).  The pass's 30 argument dwords (`args`: where they
+// lie in the kernel-argument segment) are read here, by the workgroups that need them, not at the kernel's entry.
+__device__ __attribute__((noinline)) void sp_nt_tail_pass(const __attribute__((address_space(4))) unsigned* args, unsigned block,
+                                                          unsigned nblocks, unsigned nthreads) {
+  static_assert(sizeof(SpArgs) % 8 == 0 && offsetof(SpTail, args) % 4 == 0 && sizeof(TnReduceArgs) % 4 == 0, "the pass's arguments are read as dwords");
+  union {
+    TnReduceArgs a;
+    unsigned w[sizeof(TnReduceArgs) / 4];
+  } ta;
+#pragma unroll
+  for (unsigned i = 0; i < sizeof(TnReduceArgs) / 4; ++i) ta.w[i] = (unsigned)__builtin_amdgcn_readfirstlane((int)args[i]);
+  // (arguments of a call travel in vector registers: back to scalars, as the stand-alone kernel holds them)
+  sp_tn_reduce_body(ta.a, (unsigned)__builtin_amdgcn_readfirstlane((int)block), (unsigned)__builtin_amdgcn_readfirstlane((int)nblocks),
+                    (unsigned)__builtin_amdgcn_readfirstlane((int)nthreads));
+}
+
 template <int TNW, bool ABLK, bool GRAD, bool OUT_SP = false>
-__global__ void __launch_bounds__((SpGeo<TNW, sp_nt_tm<TNW>>::NT), (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(SpArgs g) {  // (BN = 128: two workgroups per CU, see SpGeo::NST)
+__global__ void __launch_bounds__((SpGeo<TNW, sp_nt_tm<TNW>>::NT), (TNW == 2 ? 2 : 1)) gemm_sp_nt_kernel(SpArgs g, SpTail t) {  // (BN = 128: two workgroups per CU, see SpGeo::NST)
   constexpr int TM = sp_nt_tm<TNW>;
   using G = SpGeo<TNW, TM>;
   constexpr int WR = 32 * TM;  // rows per wave
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+  // the workgroups behind the product's own run the reduce pass the launch carries (SpTail) and leave: the whole
+  // workgroup takes the branch, before LDS, the DMA setup or any barrier - and waits for nothing (stream order: the TN product
+  // that wrote the partials finished before this launch began)
+  if (blockIdx.x >= t.first) {
+    sp_nt_tail_pass((const __attribute__((address_space(4))) unsigned*)__builtin_amdgcn_kernarg_segment_ptr() +
+                        (sizeof(SpArgs) + offsetof(SpTail, args)) / 4,
+                    blockIdx.x - t.first, t.blocks, G::NT);
+    return;
+  }
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -469,7 +548,7 @@ __global__ void __launch_bounds__((SpGeo<TNW, sp_nt_tm<TNW>>::NT), (TNW == 2 ? 2
   int split = 0;
   int S = g.ksplit;
   if (S > 1) {
-    const unsigned nt_all = gridDim.x / (unsigned)S;
+    const unsigned nt_all = t.first / (unsigned)S;
     if (bid < nt_all * (unsigned)(S - 1)) {
       split = 1 + (int)(bid / nt_all);
       bid -= (unsigned)(split - 1) * nt_all;
@@ -1549,60 +1628,8 @@ __global__ void __launch_bounds__(SP_NT, 1) gemm_sp_tn_kernel(SpTnArgs g) {
   store_tile(std::integral_constant<int, 1>{});
 }
 
-struct TnReduceArgs {
-  const float* partial;
-  int splits;
-  int64_t M, N;
-  const float* ref;
-  int64_t a_col0;
-  int a_sb;
-  float* C;
-  int64_t group_rows, stride_group, stride_row, stride_col;
-  int accumulate;
-  int64_t slab;
-  int ref_ld;  // 0: one reference scale per block (ref[blk]); > 0: one per (split, block) at ref[z * ref_ld + blk]
-};
-
-// ---- split-K partials of a weight gradient -> dW -----------------------------------------------------------------------
-// C[(m / group_rows) * stride_group + (m % group_rows) * stride_row + n * stride_col] (+)= ref[blk(m)] * sum_z partial[z][m][n]
-// (`block` of `nblocks` workgroups of 256 threads walk the M * N elements)
-__device__ __forceinline__ void sp_tn_reduce_body(const TnReduceArgs& a, unsigned block, unsigned nblocks) {
-  const int64_t total = a.M * a.N;  // slab >= total: floats per split (the product pads M to a multiple of 128)
-  for (int64_t i = (int64_t)block * 256 + threadIdx.x; i < total; i += (int64_t)nblocks * 256) {
-    const int64_t m = i / a.N, n = i - m * a.N;
-    const int64_t blk = (a.a_col0 + m) / a.a_sb;
-    float s = 0.f;
-    int z = 0;
-    if (a.ref_ld > 0) {  // every split carries its own reference scale (factors computed inside the product kernel)
-      for (; z + 8 <= a.splits; z += 8) {  // eight loads in flight; the sum stays in split order
-        float v[8], r[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          v[u] = a.partial[(int64_t)(z + u) * a.slab + i];
-          r[u] = a.ref[(int64_t)(z + u) * a.ref_ld + blk];
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s += v[u] * r[u];
-      }
-      for (; z < a.splits; ++z) s += a.partial[(int64_t)z * a.slab + i] * a.ref[(int64_t)z * a.ref_ld + blk];
-    } else {
-      for (; z + 8 <= a.splits; z += 8) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = a.partial[(int64_t)(z + u) * a.slab + i];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s += v[u];
-      }
-      for (; z < a.splits; ++z) s += a.partial[(int64_t)z * a.slab + i];
-      s *= a.ref[blk];
-    }
-    const int64_t gi = m / a.group_rows, mi = m - gi * a.group_rows;
-    float* dst = a.C + gi * a.stride_group + mi * a.stride_row + n * a.stride_col;
-    *dst = a.accumulate ? *dst + s : s;
-  }
-}
-
-__global__ void __launch_bounds__(256) sp_tn_reduce_kernel(TnReduceArgs a) { sp_tn_reduce_body(a, blockIdx.x, gridDim.x); }
+// ---- split-K partials of a weight gradient -> dW: sp_tn_reduce_body (in front of gemm_sp_nt_kernel, which can carry it) ----
+__global__ void __launch_bounds__(256) sp_tn_reduce_kernel(TnReduceArgs a) { sp_tn_reduce_body(a, blockIdx.x, gridDim.x, 256); }
 // blockIdx.y = row group: the K ranges [split_off[g], split_off[g + 1]) of the grouped product belong to output g
 __global__ void __launch_bounds__(256) sp_tn_reduce_grouped_kernel(TnReduceArgs a, const int32_t* __restrict__ split_off,
                                                                    int64_t c_group_stride) {
@@ -1612,7 +1639,7 @@ __global__ void __launch_bounds__(256) sp_tn_reduce_grouped_kernel(TnReduceArgs 
   a.ref += (int64_t)s0 * a.ref_ld;
   a.splits = s1 - s0;
   a.C += (int64_t)gq * c_group_stride;
-  sp_tn_reduce_body(a, blockIdx.x, gridDim.x);
+  sp_tn_reduce_body(a, blockIdx.x, gridDim.x, 256);
 }
 
 static int sp_tn_splits(int64_t M, int64_t N, int64_t K, int bn) {
@@ -1623,7 +1650,7 @@ static int sp_tn_splits(int64_t M, int64_t N, int64_t K, int bn) {
 }
 
 template <int TNW>
-static void launch_sp_nt(const SpArgs& g_in, dim3 grid, hipStream_t s) {
+static void launch_sp_nt(const SpArgs& g_in, SpTail t, dim3 grid, hipStream_t s) {
   using G = SpGeo<TNW, sp_nt_tm<TNW>>;
   SpArgs g = g_in;
   g.xcd_per = g.xcd_total = 0;
@@ -1633,11 +1660,13 @@ static void launch_sp_nt(const SpArgs& g_in, dim3 grid, hipStream_t s) {
     g.xcd_per = (grid.x + 7u) / 8u;
     grid.x = g.xcd_per * 8u;
   }
+  t.first = grid.x;
+  grid.x += t.blocks;  // the carried reduce pass: behind every product workgroup (and the XCD padding)
   const bool ablk = g.a_inv && g.a_nblk > 1;
   const bool grad = g.mul || g.saved;
   count_launch(TFGNN_KFAM_SP_NT);
   // the eight kernels of this tile width, [ablk][grad][out_sp]
-  using Kernel = void (*)(SpArgs);
+  using Kernel = void (*)(SpArgs, SpTail);
   static const Kernel kernels[2][2][2] = {
       {{gemm_sp_nt_kernel<TNW, false, false, false>, gemm_sp_nt_kernel<TNW, false, false, true>},
        {gemm_sp_nt_kernel<TNW, false, true, false>, gemm_sp_nt_kernel<TNW, false, true, true>}},
@@ -1650,7 +1679,7 @@ static void launch_sp_nt(const SpArgs& g_in, dim3 grid, hipStream_t s) {
     (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
     attr_set[ablk][grad][out_sp] = true;
   }
-  hipLaunchKernelGGL(kernel, grid, dim3(G::NT), G::LDS_BYTES, s, g);
+  hipLaunchKernelGGL(kernel, grid, dim3(G::NT), G::LDS_BYTES, s, g, t);
 }
 
 // Workspace of the in-launch K split of the NT product (tfgnn_sp_gemm_nt_set_splitk_workspace): [flags 64 KB][slabs].
@@ -1828,9 +1857,32 @@ struct TnLaunch {
   int64_t c_group_stride;
 };
 
-// repair begin (armed) - factor pass (that form) - product - repair (armed) - reduce pass, all on s.  Without a K range (a
-// grouping whose groups are all empty) only the reduce pass runs: it writes the zeros.
-static int sp_tn_enqueue(const TnLaunch& t, hipStream_t s) {
+// reduce passes enqueued so far: in a launch of their own / carried by an NT launch (tfgnn_tn_reduce_counts)
+static int64_t g_tn_reduce_own = 0, g_tn_reduce_carried = 0;
+
+// Workgroups an NT launch gives a reduce pass over `total` = M * N elements: one per 512 elements (an element per thread of
+// the 320-column geometry, two at the others), at most 1024.  They queue behind the product's workgroups and take CUs as
+// those free up - one per CU at 320 columns, whose workgroups hold 143 KB of LDS - so the count sets the grain of that
+// hand-over: few, long workgroups finish well after the tiles (25 of them behind the unmasked K = 320 product: 108 us against
+// 75 us for the separate launches), many short ones fill what the tiles leave; from the sweep of tools/nt_tail_reduce_probe.py
+// (profiles/nt_tail_reduce_probe.txt, NOTEBOOK 36).
+static unsigned sp_nt_tail_blocks(int64_t total) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(1024, ceil_div(total, 512))); }
+
+// the plain reduce pass in its own launch
+static int sp_tn_reduce_launch(const TnReduceArgs& ra, hipStream_t s) {
+  const int64_t rblocks = ceil_div(ra.M * ra.N, 256);
+  hipLaunchKernelGGL(sp_tn_reduce_kernel, dim3((unsigned)std::min<int64_t>(rblocks, 2048)), dim3(256), 0, s, ra);
+  TFGNN_LAUNCH_CHECK();
+  __atomic_fetch_add(&g_tn_reduce_own, 1, __ATOMIC_RELAXED);
+  return TFGNN_OK;
+}
+
+int sp_tn_reduce_enqueue(const TnReduceJob& job, hipStream_t s) { return sp_tn_reduce_launch(job.args, s); }
+
+// repair begin (armed) - factor pass (that form) - product - repair (armed), all on s; *ra receives the reduce pass that has
+// to follow (sp_tn_enqueue).  Without a K range (a grouping whose groups are all empty) nothing is launched here: the reduce
+// pass writes the zeros.
+static int sp_tn_enqueue_product(const TnLaunch& t, hipStream_t s, TnReduceArgs* ra_out) {
   const int bn = sp_tile_width(t.N);
   const int64_t Mp = ceil_div(t.M, SP_BM) * SP_BM;
   const bool armed = t.repair && t.splits > 0, per_split = t.form != TnForm::FactorPass;
@@ -1890,14 +1942,24 @@ static int sp_tn_enqueue(const TnLaunch& t, hipStream_t s) {
   ra.splits = t.group_split_offsets ? 0 : t.splits;  // (per group: every group's workgroups take theirs from the offsets)
   ra.C = t.C; ra.group_rows = t.group_rows; ra.stride_group = t.stride_group; ra.stride_row = t.stride_row; ra.stride_col = t.stride_col;
   ra.accumulate = t.accumulate; ra.slab = Mp * t.N;
+  *ra_out = ra;
+  return TFGNN_OK;
+}
+
+// May the reduce pass of this product ride on a later NT launch?  The grouped reduction keeps its own kernel (its workgroups
+// take their ranges from the offsets), and so does a product without a K range.
+static bool sp_tn_reduce_can_defer(const TnLaunch& t) { return !t.group_split_offsets && t.splits > 0; }
+
+// product (above) - reduce pass, all on s
+static int sp_tn_enqueue(const TnLaunch& t, hipStream_t s) {
+  TnReduceArgs ra{};
+  if (int rc = sp_tn_enqueue_product(t, s, &ra)) return rc;
+  if (!t.group_split_offsets) return sp_tn_reduce_launch(ra, s);
   const int64_t rblocks = ceil_div(t.M * t.N, 256);
-  if (t.group_split_offsets) {
-    hipLaunchKernelGGL(sp_tn_reduce_grouped_kernel, dim3((unsigned)std::min<int64_t>(rblocks, 512), (unsigned)t.num_groups), dim3(256), 0, s,
-                       ra, t.group_split_offsets, t.c_group_stride);
-  } else {
-    hipLaunchKernelGGL(sp_tn_reduce_kernel, dim3((unsigned)std::min<int64_t>(rblocks, 2048)), dim3(256), 0, s, ra);
-  }
+  hipLaunchKernelGGL(sp_tn_reduce_grouped_kernel, dim3((unsigned)std::min<int64_t>(rblocks, 512), (unsigned)t.num_groups), dim3(256), 0, s,
+                     ra, t.group_split_offsets, t.c_group_stride);
   TFGNN_LAUNCH_CHECK();
+  __atomic_fetch_add(&g_tn_reduce_own, 1, __ATOMIC_RELAXED);
   return TFGNN_OK;
 }
 
@@ -2050,16 +2112,30 @@ static int sp_nt_plan_splitk(SpArgs& g, const NtShape& d, hipStream_t s) {
 }
 
 int sp_nt_enqueue(const NtCall& c, hipStream_t s) {
+  const TnReduceJob* tail = (c.tail && c.tail->blocks) ? c.tail : nullptr;
+  if (tail) {
+    // the launch reads the TN product's workspace while a K split writes its slabs and flags: the two must be apart
+    const uintptr_t t0 = (uintptr_t)tail->ws, t1 = t0 + tail->ws_bytes, k0 = (uintptr_t)g_splitk.base, k1 = k0 + g_splitk.bytes;
+    TFGNN_REQUIRE(!(g_splitk.base && t0 < k1 && k0 < t1),
+                  "tfgnn_sp_gemm_nt: the workspace of the carried TN reduction overlaps the K-split workspace of the NT product");
+    if (c.M == 0) return sp_tn_reduce_enqueue(*tail, s);  // nothing to multiply: the pass gets its own launch
+  }
   NtShape d;
   int rc = sp_nt_check(c, &d);
   if (rc) return rc;
   SpArgs g = sp_nt_args(c, d);
   rc = sp_nt_plan_splitk(g, d, s);
   if (rc) return rc;
-  const dim3 grid((unsigned)(d.tiles * g.ksplit));
-  if (d.bn == 320) launch_sp_nt<5>(g, grid, s);
-  else if (d.bn == 256) launch_sp_nt<4>(g, grid, s);
-  else launch_sp_nt<2>(g, grid, s);
+  dim3 grid((unsigned)(d.tiles * g.ksplit));
+  SpTail t{};
+  if (tail) {
+    t.args = tail->args;
+    t.blocks = tail->blocks;
+    __atomic_fetch_add(&g_tn_reduce_carried, 1, __ATOMIC_RELAXED);
+  }
+  if (d.bn == 320) launch_sp_nt<5>(g, t, grid, s);
+  else if (d.bn == 256) launch_sp_nt<4>(g, t, grid, s);
+  else launch_sp_nt<2>(g, t, grid, s);
   TFGNN_LAUNCH_CHECK();
   return TFGNN_OK;
 }
@@ -2277,7 +2353,7 @@ static int sp_gemm_tn_plain(bool wide, int64_t M, int64_t N, int64_t K, const vo
                             const float* d_a_inv_scale, int64_t a_total_cols, int a_scale_block, const void* d_B_sp,
                             int64_t ldb_bytes, int64_t b_first_col, const float* d_b_inv_scale, float* d_C, int64_t group_rows,
                             int64_t stride_group, int64_t stride_row, int64_t stride_col, int accumulate, void* d_workspace,
-                            size_t workspace_bytes, void* stream) {
+                            size_t workspace_bytes, void* stream, TnReduceJob* job = nullptr) {
   // (the two-factor form reports what it shares with the one-factor form under the latter's name)
   TFGNN_REQUIRE(d_A_sp && d_B_sp && d_C && d_a_inv_scale, "tfgnn_sp_gemm_tn: null pointer");
   TFGNN_REQUIRE(M > 0 && N > 0 && K > 0, "tfgnn_sp_gemm_tn: empty product");
@@ -2311,7 +2387,90 @@ static int sp_gemm_tn_plain(bool wide, int64_t M, int64_t N, int64_t K, const vo
   TFGNN_REQUIRE(t.k_chunk * std::max(lda_bytes, ldb_bytes) < (1ll << 31) && nblk * kpad * 2 < (1ll << 31), "tfgnn_sp_gemm_tn: K chunk too large");
   t.C = d_C; t.group_rows = group_rows; t.stride_group = stride_group; t.stride_row = stride_row; t.stride_col = stride_col;
   t.accumulate = accumulate;
-  return sp_tn_enqueue(t, (hipStream_t)stream);
+  if (!job) return sp_tn_enqueue(t, (hipStream_t)stream);
+  *job = TnReduceJob{};
+  if (!sp_tn_reduce_can_defer(t)) return sp_tn_enqueue(t, (hipStream_t)stream);  // (the job stays empty)
+  if (int rc = sp_tn_enqueue_product(t, (hipStream_t)stream, &job->args)) return rc;
+  job->blocks = sp_nt_tail_blocks(M * N);
+  job->ws = d_workspace;
+  job->ws_bytes = t.lay.total;
+  return TFGNN_OK;
+}
+
+}  // extern "C"
+
+namespace tfgnn {
+int sp_gemm_tn_product(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, int64_t a_first_col,
+                        const float* d_a_inv_scale, int64_t a_total_cols, int a_scale_block, const void* d_B_sp, int64_t ldb_bytes,
+                        int64_t b_first_col, const float* d_b_inv_scale, float* d_C, int64_t group_rows, int64_t stride_group,
+                        int64_t stride_row, int64_t stride_col, int accumulate, void* d_workspace, size_t workspace_bytes,
+                        TnReduceJob* job, hipStream_t s) {
+  TFGNN_REQUIRE(job, "tfgnn_sp_gemm_tn_product: null job");
+  return sp_gemm_tn_plain(false, M, N, K, d_A_sp, lda_bytes, a_first_col, d_a_inv_scale, a_total_cols, a_scale_block, d_B_sp, ldb_bytes,
+                          b_first_col, d_b_inv_scale, d_C, group_rows, stride_group, stride_row, stride_col, accumulate, d_workspace,
+                          workspace_bytes, (void*)s, job);
+}
+}  // namespace tfgnn
+
+extern "C" {
+
+static_assert(sizeof(tfgnn_tn_reduce_job) >= sizeof(TnReduceJob) && offsetof(TnReduceJob, blocks) == 0,
+              "tfgnn_tn_reduce_job holds a TnReduceJob, the workgroup count first");
+
+int tfgnn_sp_gemm_tn_product(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, int64_t a_first_col,
+                              const float* d_a_inv_scale, int64_t a_total_cols, int a_scale_block, const void* d_B_sp,
+                              int64_t ldb_bytes, int64_t b_first_col, const float* d_b_inv_scale, float* d_C, int64_t group_rows,
+                              int64_t stride_group, int64_t stride_row, int64_t stride_col, int accumulate, void* d_workspace,
+                              size_t workspace_bytes, tfgnn_tn_reduce_job* job, void* stream) {
+  TFGNN_REQUIRE(job, "tfgnn_sp_gemm_tn_product: null job");
+  TnReduceJob j{};
+  std::memset(job, 0, sizeof(*job));
+  if (int rc = sp_gemm_tn_product(M, N, K, d_A_sp, lda_bytes, a_first_col, d_a_inv_scale, a_total_cols, a_scale_block, d_B_sp, ldb_bytes,
+                                   b_first_col, d_b_inv_scale, d_C, group_rows, stride_group, stride_row, stride_col, accumulate,
+                                   d_workspace, workspace_bytes, &j, (hipStream_t)stream))
+    return rc;
+  std::memcpy(job, &j, sizeof(j));
+  return TFGNN_OK;
+}
+
+int tfgnn_tn_reduce_launch(const tfgnn_tn_reduce_job* job, void* stream) {
+  TFGNN_REQUIRE(job, "tfgnn_tn_reduce_launch: null job");
+  TnReduceJob j;
+  std::memcpy(&j, job, sizeof(j));
+  if (!j.blocks) return TFGNN_OK;
+  return sp_tn_reduce_enqueue(j, (hipStream_t)stream);
+}
+
+int tfgnn_tn_reduce_counts(int64_t* out_counts, int n) {
+  TFGNN_REQUIRE(out_counts && n >= 0, "tfgnn_tn_reduce_counts: bad argument");
+  const int64_t v[2] = {__atomic_load_n(&g_tn_reduce_own, __ATOMIC_RELAXED), __atomic_load_n(&g_tn_reduce_carried, __ATOMIC_RELAXED)};
+  for (int i = 0; i < n; ++i) out_counts[i] = i < 2 ? v[i] : 0;
+  return TFGNN_OK;
+}
+
+int tfgnn_sp_gemm_nt_rows_tail(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, const float* d_a_inv_scale,
+                               int a_scale_block, const int32_t* d_a_rows, const void* d_B_sp, int64_t ldb_bytes,
+                               const float* d_b_inv_scale, float* d_C, int64_t ldc, const float* d_bias, int act, int accumulate,
+                               const float* d_mul, int64_t ld_mul, int act_of_saved, const float* d_saved, int64_t ld_saved,
+                               float saved_scale, void* d_out_sp, int64_t ld_out_sp_bytes, float* d_out_inv_scale, float dropout_rate,
+                               uint64_t dropout_seed, const uint8_t* d_tile_kmask, const int32_t* d_row_map,
+                               const tfgnn_tn_reduce_job* job, void* stream) {
+  NtCall c;
+  c.M = M; c.N = N; c.K = K;
+  c.A = d_A_sp; c.lda_bytes = lda_bytes; c.a_inv_scale = d_a_inv_scale; c.a_scale_block = a_scale_block; c.a_rows = d_a_rows;
+  c.B = d_B_sp; c.ldb_bytes = ldb_bytes; c.b_inv_scale = d_b_inv_scale;
+  c.C = d_C; c.ldc = ldc; c.accumulate = accumulate;
+  c.out_sp = d_out_sp; c.ld_out_sp_bytes = ld_out_sp_bytes; c.out_inv_scale = d_out_inv_scale;
+  c.bias = d_bias; c.act = act;
+  c.mul = d_mul; c.ld_mul = ld_mul; c.act_of_saved = act_of_saved; c.saved = d_saved; c.ld_saved = ld_saved;
+  c.saved_scale = saved_scale; c.dropout_rate = dropout_rate; c.dropout_seed = dropout_seed;
+  c.tile_kmask = d_tile_kmask; c.row_map = d_row_map;
+  TnReduceJob j{};
+  if (job) {
+    std::memcpy(&j, job, sizeof(j));
+    c.tail = &j;
+  }
+  return sp_nt_enqueue(c, (hipStream_t)stream);
 }
 
 int tfgnn_sp_gemm_tn(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, int64_t a_first_col,

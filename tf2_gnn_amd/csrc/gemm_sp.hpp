@@ -7,6 +7,31 @@
 
 namespace tfgnn {
 
+// The reduce pass of a split-K weight-gradient (TN) product, as sp_tn_reduce_body (gemm_sp.hip) takes it: filled by
+// sp_tn_enqueue, run by sp_tn_reduce_kernel - or by the workgroups an NT launch carries behind its tiles (NtCall::tail).
+struct TnReduceArgs {
+  const float* partial;
+  int splits;
+  int64_t M, N;
+  const float* ref;
+  int64_t a_col0;
+  int a_sb;
+  float* C;
+  int64_t group_rows, stride_group, stride_row, stride_col;
+  int accumulate;
+  int64_t slab;
+  int ref_ld;  // 0: one reference scale per block (ref[blk]); > 0: one per (split, block) at ref[z * ref_ld + blk]
+};
+
+// A reduce pass whose launch its TN product left to the caller: the arguments and the workspace they point into (the product's
+// partials, reference scales and trip words), which stays untouched until the pass has run.
+struct TnReduceJob {
+  unsigned blocks;  // workgroups an NT launch gives the pass (from the reduction's size); 0: nothing left to run
+  TnReduceArgs args;
+  const void* ws;
+  size_t ws_bytes;
+};
+
 struct NtCall {
   int64_t M = 0, N = 0, K = 0;
   // operand A [M, K]
@@ -46,9 +71,23 @@ struct NtCall {
   const int32_t* tile_table = nullptr;
   int64_t num_tiles_m = 0;
   int num_groups = 1;
+  // optional: the reduce pass of a TN product enqueued BEFORE this call on the same stream, run by extra workgroups behind the
+  // product's own (sp_nt_tail_blocks of them); a call that launches nothing (M = 0) gives the pass its own launch
+  const TnReduceJob* tail = nullptr;
 };
 
 // checks the call, plans the in-launch K split and enqueues the product on s; TFGNN_OK or the code of the first check that fails
 int sp_nt_enqueue(const NtCall& c, hipStream_t s);
+
+// the reduce pass in a launch of its own (what a TN product without a carrier does)
+int sp_tn_reduce_enqueue(const TnReduceJob& job, hipStream_t s);
+
+// tfgnn_sp_gemm_tn with the reduce pass handed back: everything up to and including the product (and the armed repair pass) is
+// enqueued on s, *job receives the pass.  Same checks, same workspace, same arithmetic as the stand-alone entry.
+int sp_gemm_tn_product(int64_t M, int64_t N, int64_t K, const void* d_A_sp, int64_t lda_bytes, int64_t a_first_col,
+                        const float* d_a_inv_scale, int64_t a_total_cols, int a_scale_block, const void* d_B_sp, int64_t ldb_bytes,
+                        int64_t b_first_col, const float* d_b_inv_scale, float* d_C, int64_t group_rows, int64_t stride_group,
+                        int64_t stride_row, int64_t stride_col, int accumulate, void* d_workspace, size_t workspace_bytes,
+                        TnReduceJob* job, hipStream_t s);
 
 }  // namespace tfgnn

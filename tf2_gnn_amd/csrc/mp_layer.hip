@@ -6,8 +6,9 @@
 //             out        = epilogue([A_0 | .. | A_{L-1}] @ [W_0; ..; W_{L-1}])   gemm_sp_nt_kernel (+ bias, activation, the next
 //                                                                                 op's input dropout, the split form of the result)
 //   backward  G[u, l, :] = sum_{(u,v) in A_l} w_e * d_pre[v, :]       the same gather over the by-source buckets
+//             dW_l       = X^T G_l                                      gemm_sp_tn_kernel; its split reduction rides on the next launch
 //             dX         = epilogue(G @ [W_0 | .. | W_{L-1}]^T)        gemm_sp_nt_kernel (+ gradient factors of the op below)
-//             dW_l       = X^T G_l                                      gemm_sp_tn_kernel + split reduction
+//             (over more than kCarryMaxRowTiles row tiles: dX first, then dW with its own reduction launch)
 //
 // i.e. the reference's message_passing.py:95-218 + gnn_edge_mlp.py:84-107 for one layer, and its share of
 // tf.GradientTape.gradient (models/graph_task_model.py:347-357).  Host code only: each function walks the launch sequence the
@@ -22,6 +23,10 @@
 #include "tfgnn.h"
 
 using namespace tfgnn;
+
+// row tiles of the input-gradient product up to which tfgnn_mp_backward lets it carry the weight gradient's reduce pass:
+// four rounds of one workgroup per CU
+constexpr int64_t kCarryMaxRowTiles = 4 * 256;
 
 extern "C" int tfgnn_mp_forward(const tfgnn_mp_forward_args* a, void* stream) {
   TFGNN_REQUIRE(a != nullptr && a->struct_size == sizeof(tfgnn_mp_forward_args),
@@ -92,7 +97,23 @@ extern "C" int tfgnn_mp_backward(const tfgnn_mp_backward_args* a, void* stream) 
     rc = tfgnn_aux_launch(&job, 1, stream);
     if (rc) return rc;
   }
-  // 3. dX = G W^T with the gradient factors of the op below in the epilogue; rows in by-source pattern order when asked
+  // 3. dW[l, d, h] = sum_v X[v, d] G[v, l, h]: element ((l, h), d) of G^T X scattered into the kernels' [L, D, H] layout.  The
+  //    product only: its reduce pass rides on the launch of 4. (nothing on the critical path reads dW, and that launch leaves
+  //    CUs free), so tn_workspace stays live through 4.  Only while the dX product is a few rounds of row tiles: past that
+  //    nothing is hidden - the pass's workgroups start when the last tiles do - the launch it saves is below 3 % of the
+  //    product, and the product that comes first behind the gather pays for it (2.3 M rows, 18 000 tiles: the TN product
+  //    63 us slower, the NT product 39 us faster, the step 0.4 % up; NOTEBOOK 36): there the order stays dX, dW.
+  const bool carry = a->dw && (V + 127) / 128 <= kCarryMaxRowTiles;
+  TnReduceJob reduce{};
+  if (carry) {
+    const uintptr_t t0 = (uintptr_t)a->tn_workspace, t1 = t0 + a->tn_workspace_bytes;
+    const uintptr_t w0 = (uintptr_t)a->workspace, w1 = w0 + a->workspace_bytes;
+    TFGNN_REQUIRE(!(a->tn_workspace && a->workspace && t0 < w1 && w0 < t1), "tfgnn_mp_backward: tn_workspace overlaps workspace");
+    rc = sp_gemm_tn_product(K, D, V, a->g_sp, K * 4, 0, a->g_inv_scale, K, (int)H, a->x_sp, a->ld_x_sp_bytes, 0, a->x_inv_scale, a->dw, H,
+                            D * H, 1, H, 0, a->tn_workspace, a->tn_workspace_bytes, &reduce, (hipStream_t)stream);
+    if (rc) return rc;
+  }
+  // 4. dX = G W^T with the gradient factors of the op below in the epilogue; rows in by-source pattern order when asked
   NtCall c;
   c.M = V; c.N = D; c.K = K;
   c.A = a->g_sp; c.lda_bytes = K * 4; c.a_inv_scale = a->g_inv_scale; c.a_scale_block = (int)H; c.a_rows = a->a_rows;
@@ -102,11 +123,11 @@ extern "C" int tfgnn_mp_backward(const tfgnn_mp_backward_args* a, void* stream) 
   c.mul = a->mul; c.ld_mul = a->ld_mul; c.act_of_saved = a->act_of_saved; c.saved = a->saved; c.ld_saved = a->ld_saved;
   c.saved_scale = a->saved_scale; c.dropout_rate = a->dropout_rate; c.dropout_seed = a->dropout_seed;
   c.tile_kmask = a->tile_kmask; c.row_map = a->row_map;
+  c.tail = &reduce;  // (empty without dw, or when the product ran its own reduce pass)
   rc = sp_nt_enqueue(c, (hipStream_t)stream);
-  if (rc) return rc;
-  // 4. dW[l, d, h] = sum_v X[v, d] G[v, l, h]: element ((l, h), d) of G^T X scattered into the kernels' [L, D, H] layout
-  if (a->dw)
-    rc = tfgnn_sp_gemm_tn(K, D, V, a->g_sp, K * 4, 0, a->g_inv_scale, K, (int)H, a->x_sp, a->ld_x_sp_bytes, 0, a->x_inv_scale, a->dw, H, D * H, 1,
+  // a product that was refused launched nothing: the reduce pass still has to run
+  if (rc && reduce.blocks) (void)sp_tn_reduce_enqueue(reduce, (hipStream_t)stream);
+  if (rc || !a->dw || carry) return rc;
+  return tfgnn_sp_gemm_tn(K, D, V, a->g_sp, K * 4, 0, a->g_inv_scale, K, (int)H, a->x_sp, a->ld_x_sp_bytes, 0, a->x_inv_scale, a->dw, H, D * H, 1,
                           H, 0, a->tn_workspace, a->tn_workspace_bytes, stream);
-  return rc;
 }

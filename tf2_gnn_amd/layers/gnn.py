@@ -260,15 +260,19 @@ class GNN:
         d_in, d_out = w.value.shape
         if x.shape[0] > 0 and self._dense_f16x2(d_in, d_out):
             g_sp = ops.sp_rows_of(gpre)  # written by the epilogue of the product above when that is a split-operand product
+            nt_follows = need_input_grad and ops.sp_tiles(d_in)
+            job = None
             if self.guard.dense == "wide":  # (guard policy stage 1a: both operands' rows are un-normalised sums)
                 w.grad = ops.sp_gemm_tn(ops.sp_rows_of(x), g_sp, out=torch.empty_like(w.value), wide=True)
+            elif nt_follows:  # the reduce pass of x^T gpre rides on the launch of gpre w^T below
+                w.grad, job = ops.sp_gemm_tn_product(ops.sp_rows_of(x), g_sp)
             else:
                 w.grad = ops.sp_gemm_tn(ops.sp_rows_of(x), g_sp)  # [in, out] = x^T gpre
             if not need_input_grad:
                 return None
-            if ops.sp_tiles(d_in):
+            if nt_follows:
                 wr = ops.sp_weight_operand(w.value, "rows", lambda: ops.sp_split_rows_jobs(w.value))
-                return ops.sp_gemm_nt(g_sp, wr, act_grad=act_grad)
+                return ops.sp_gemm_nt(g_sp, wr, act_grad=act_grad, tail=job)
             return ops.gemm_grad(gpre, w.value, trans_b=True, act_grad=act_grad)
         w.grad = ops.gemm(x, gpre, trans_a=True)
         return ops.gemm_grad(gpre, w.value, trans_b=True, act_grad=act_grad) if need_input_grad else None

@@ -1833,30 +1833,80 @@ def _nt_shape(who: str, a: SplitOperand, b: SplitOperand):
     return M, K, N
 
 
-def _sp_gemm_nt_rows(a, b, M, N, K, out, ldc, op, bias, act, accumulate, epilogue, tile_kmask, row_map, a_rows) -> None:
+def _sp_gemm_nt_rows(a, b, M, N, K, out, ldc, op, bias, act, accumulate, epilogue, tile_kmask, row_map, a_rows, tail=None) -> None:
     """The one call of tfgnn_sp_gemm_nt_rows: ``out`` (fp32 [M, N], leading dimension ldc) and ``op`` (the split result) may
-    each be None; ``epilogue`` as ``_c_epilogue`` returns it."""
+    each be None; ``epilogue`` as ``_c_epilogue`` returns it.  ``tail``: a ``TnReduceJob`` this launch carries
+    (tfgnn_sp_gemm_nt_rows_tail); the call consumes it."""
     out_mul, act_of_saved, saved, saved_scale, rate, seed = epilogue
     if bias is not None:
         bias = bias.contiguous()
     _ensure_splitk_workspace(a.data.device, M)
-    _lib.check(
-        _lib.load().tfgnn_sp_gemm_nt_rows(
-            M, N, K, _ptr(a.data), a.data.stride(0), _ptr(a.inv_scale), a.scale_block if a.scale_block else -1,
-            _ptr(_row_map(a_rows, M)), _ptr(b.data), b.data.stride(0),
-            _ptr(b.inv_scale), _ptr(out), ldc, _ptr(bias), act_id(act), int(accumulate), _ptr(out_mul),
-            out_mul.stride(0) if out_mul is not None else 0, act_of_saved, _ptr(saved),
-            saved.stride(0) if saved is not None else 0, saved_scale, _ptr(op.data) if op is not None else None,
-            op.data.stride(0) if op is not None else 0, _ptr(op.inv_scale) if op is not None else None, rate, seed,
-            _ptr(_tile_kmask(tile_kmask, M)), _ptr(_row_map(row_map, M)), _stream(),
-        )
+    args = (
+        M, N, K, _ptr(a.data), a.data.stride(0), _ptr(a.inv_scale), a.scale_block if a.scale_block else -1,
+        _ptr(_row_map(a_rows, M)), _ptr(b.data), b.data.stride(0),
+        _ptr(b.inv_scale), _ptr(out), ldc, _ptr(bias), act_id(act), int(accumulate), _ptr(out_mul),
+        out_mul.stride(0) if out_mul is not None else 0, act_of_saved, _ptr(saved),
+        saved.stride(0) if saved is not None else 0, saved_scale, _ptr(op.data) if op is not None else None,
+        op.data.stride(0) if op is not None else 0, _ptr(op.inv_scale) if op is not None else None, rate, seed,
+        _ptr(_tile_kmask(tile_kmask, M)), _ptr(_row_map(row_map, M)),
     )
+    if tail is None:
+        _lib.check(_lib.load().tfgnn_sp_gemm_nt_rows(*args, _stream()))
+        return
+    _lib.check(_lib.load().tfgnn_sp_gemm_nt_rows_tail(*args, ctypes.byref(tail._take()), _stream()))
+    tail._issued()
+
+
+class TnReduceJob:
+    """The reduce pass of a weight-gradient product whose launch ``sp_gemm_tn_product`` left to the caller (tfgnn_tn_reduce_job):
+    hand it to the NT product that follows on the same stream (``sp_gemm_nt(..., tail=job)``) or run it alone
+    (``tn_reduce_launch``) - exactly once, before anything reads ``out``.  Built and consumed by the same caller: nothing
+    queues these.  ``num_blocks``: the workgroups the carrying launch gives the pass (0: the product already ran it)."""
+
+    def __init__(self, c_job, out: torch.Tensor, workspace):
+        self._c, self.out, self._ws, self._done = c_job, out, workspace, False
+
+    @property
+    def num_blocks(self) -> int:
+        return int(self._c.num_blocks)
+
+    @num_blocks.setter
+    def num_blocks(self, n: int) -> None:
+        if self._c.num_blocks and n > 0:  # (an empty job stays empty)
+            self._c.num_blocks = int(n)
+
+    def _take(self):
+        if self._done:
+            raise RuntimeError("TnReduceJob: the reduce pass has been issued already")
+        return self._c
+
+    def _issued(self) -> None:
+        self._done, self._ws = True, None  # (stream order keeps the workspace's memory until the launch is through)
+        torch.autograd.graph.increment_version(self.out)
+
+
+def tn_reduce_launch(job: TnReduceJob) -> torch.Tensor:
+    """The reduce pass of ``job`` in a launch of its own (tfgnn_tn_reduce_launch) -> the product's ``out``."""
+    _lib.check(_lib.load().tfgnn_tn_reduce_launch(ctypes.byref(job._take()), _stream()))
+    job._issued()
+    return job.out
+
+
+def tn_reduce_counts() -> dict:
+    """tfgnn_tn_reduce_counts: reduce passes of the weight-gradient products so far - launched on their own / carried by an NT
+    launch (host counters)."""
+    buf = (ctypes.c_int64 * 2)()
+    _lib.check(_lib.load().tfgnn_tn_reduce_counts(buf, 2))
+    return {"own": int(buf[0]), "carried": int(buf[1])}
 
 
 @_writes_out
 def sp_gemm_nt(a: SplitOperand, b: SplitOperand, *, bias=None, act=ACT_NONE, out=None, accumulate=False, out_mul=None,
-               act_grad=None, dropout=None, saved_scale: float = 1.0, tile_kmask=None, row_map=None, a_rows=None) -> torch.Tensor:
+               act_grad=None, dropout=None, saved_scale: float = 1.0, tile_kmask=None, row_map=None, a_rows=None,
+               tail: Optional["TnReduceJob"] = None) -> torch.Tensor:
     """out [M, N] = epilogue(a [M, K] @ b [N, K]^T) from SP16 operands (tfgnn_sp_gemm_nt / tfgnn_sp_gemm_nt_dropout).
+    tail: the reduce pass of the weight-gradient product enqueued just before on this stream (``sp_gemm_tn_product``), run by
+    extra workgroups of this launch.
     tile_kmask (uint8 [ceil(M / 128)]): bit b = scale block b of ``a`` holds non-zeros in that row tile, the other blocks are
     skipped; row_map (int32 [M]): product row r is written at out[row_map[r]] (Graph pattern order, graph_gather_sp).
     dropout = (rate, seed): the result times the mask ``dropout_forward`` draws for that seed, applied in the epilogue
@@ -1866,7 +1916,7 @@ def sp_gemm_nt(a: SplitOperand, b: SplitOperand, *, bias=None, act=ACT_NONE, out
     M, K, N = _nt_shape("sp_gemm_nt", a, b)
     out, ldc = _product_out(out, M, N, accumulate, a.data.device)
     _sp_gemm_nt_rows(a, b, M, N, K, out, ldc, None, bias, act, accumulate, _c_epilogue(out_mul, act_grad, dropout, saved_scale),
-                     tile_kmask, row_map, a_rows)
+                     tile_kmask, row_map, a_rows, tail)
     return out
 
 
@@ -2126,6 +2176,43 @@ def sp_gemm_tn(a: SplitOperand, b: SplitOperand, *, a_cols=None, b_cols=None, ou
         )
     )
     return out
+
+
+def sp_gemm_tn_product(a: SplitOperand, b: SplitOperand, *, a_cols=None, b_cols=None, out: Optional[torch.Tensor] = None,
+                        scatter=None, accumulate: bool = False):
+    """``sp_gemm_tn`` (the one-factor form) up to and including the product (tfgnn_sp_gemm_tn_product): the reduce pass comes
+    back as a ``TnReduceJob`` for the NT product that follows (``sp_gemm_nt(..., tail=job)``).  ``out`` holds the result
+    once the job has run - bit for bit what ``sp_gemm_tn`` writes.  -> (out, job)"""
+    lib = _lib.load()
+    if a.scale_block <= 0 or b.scale_block != b.cols:
+        raise ValueError("sp_gemm_tn: the left operand needs per-(row, block) scales, the right one one scale per row")
+    if a.rows != b.rows:
+        raise ValueError(f"sp_gemm_tn: K differs ({a.rows} vs {b.rows})")
+    a0, M = a_cols if a_cols is not None else (0, a.cols)
+    b0, N = b_cols if b_cols is not None else (0, b.cols)
+    K = a.rows
+    if out is None:
+        if scatter is not None or accumulate:
+            raise ValueError("scatter / accumulate need out")
+        out = torch.empty((M, N), dtype=torch.float32, device=a.data.device)
+    if not out.is_contiguous() or out.numel() != M * N:
+        raise ValueError(f"out must be contiguous with {M * N} elements")
+    gr, sg, sr, sc = scatter if scatter is not None else (M, 0, N, 1)
+    ws_bytes = lib.tfgnn_sp_gemm_tn_workspace_bytes(M, N, K, a.cols, a.scale_block)
+    ws_ptr, ws_len, ws = None, 0, None
+    if ws_bytes:
+        # (its own buffer: it stays live until the job has been issued, whatever takes the shared one in between)
+        ws_ptr, ws_len, ws = _aligned_workspace(a.data.device, ws_bytes, own=True)
+        ws_ptr = ctypes.c_void_p(ws_ptr)
+    c_job = _lib.TnReduceJob()
+    _lib.check(
+        lib.tfgnn_sp_gemm_tn_product(
+            M, N, K, _ptr(a.data), a.data.stride(0), a0, _ptr(a.inv_scale), a.cols, a.scale_block, _ptr(b.data),
+            b.data.stride(0), b0, _ptr(b.inv_scale), _ptr(out), gr, sg, sr, sc, int(accumulate), ws_ptr, ws_len,
+            ctypes.byref(c_job), _stream(),
+        )
+    )
+    return out, TnReduceJob(c_job, out, ws)
 
 
 def tensor_inv_scale(bound: torch.Tensor) -> torch.Tensor:
