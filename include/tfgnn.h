@@ -1583,6 +1583,92 @@ int tfgnn_gather_node_rows(const tfgnn_gather_node_rows_args* args, void* stream
  * out[1] by tfgnn_gather_node_rows (1 per call with rows); further slots are zero */
 int tfgnn_sample_launch_counts(int64_t* out_counts, int n);
 
+/* ------------------------------------------------------------------------------------------
+ * R-GCN basis decomposition (csrc/basis.hip; Schlichtkrull et al. 2018, eq. 3: W_l = sum_b a[l,b] V_b with B shared bases),
+ * aggregate first.  With s_e / m_v the scales of tfgnn_graph_scales (d_edge_weight_by_dst / d_node_scale), L the handle's
+ * number of edge types and coeff = a [L, B] contiguous:
+ *   tfgnn_basis_gather_forward   Z[v, b*D + d] = m_v * sum over the edges e = (u -> v) of type l of  s_e * a[l,b] * X[u, d]
+ *   tfgnn_basis_gather_backward  dX[u, d]     = sum over the edges e = (u -> v) of type l of  s'_e * sum_b a[l,b] * dZ[v, b*D + d]
+ *                                               (s' = d_edge_weight_by_src, which carries m_v)
+ *                                dcoeff[l, b] = sum over the nodes v of  m_v * < dZ[v, b*D .. b*D + D), S[v, l, :] >,
+ *                                               S[v, l, :] = sum over the edges e = (u -> v) of type l of  s_e * X[u, :]
+ *                                               - recomputed from X, never stored (it is the [V, L*D] operand of the plain layer)
+ * Z feeds one product with the stacked bases [B*D, H] (tfgnn_gemm and friends); the gather writes B*D floats per node instead
+ * of L*D.  X, Z, dZ, dX have row strides (floats); columns outside [0, B*D) / [0, D) of a wider array are left untouched.
+ * edge_weight_* NULL: 1 per edge; node_scale NULL: 1.  dX / dcoeff NULL: not computed.
+ *
+ * The walks use the handle's node views (TFGNN_G_NODEPTR_BY_DST + TFGNN_G_COLL_BY_DST, ..._BY_SRC: other end = coll / L,
+ * type = coll % L; inside a node's row the edges are sorted by type) and their long-row plans (part PLAN_NODE): a row of more
+ * than 32 edges is cut into items of 512 edges, one workgroup per item, whose G lane groups (G = 16, 8 or 4 for rows of at
+ * most 64 (16 on the scalar path), at most 128, or more floats) take ceil(edges / G) consecutive edges each.  A row of at most
+ * 32 edges is one segment.  ORDER OF THE SUMS - fp32, fused multiply-adds, no float atomics; it depends on the graph (and on
+ * B, D, the alignment) alone, so two calls - or an eager call and its replay from a captured graph - give the same bits:
+ *   forward  per segment: the edges in by-target order; inside a run of one type  r = fma(s_e, x, r);  at the end of a run
+ *            acc_b = fma(a[l,b], r, acc_b), runs in ascending type.  The segments of an item are added in order, the items of
+ *            a row in item order (second launch, only when some row has several items), then * m_v.
+ *   dX       per segment: the edges in by-source order;  t = sum_b fma(a[l,b], dz, t) with b ascending;  acc = fma(s'_e, t, acc).
+ *            Segments and items as above.
+ *   dcoeff   per run of one type inside a segment: r as in forward; per lane  p_b = fma(r, dz, p_b)  over the lane's columns
+ *            ascending; the lanes of the group by a butterfly (xor 32/16/8 .. 1); * m_v.  The run's B numbers are stored at the
+ *            run's first edge in a zeroed [E, B] table.  Stage 1: workgroup (chunk c of 1024 nodes, type l), wave w adds the table
+ *            rows of the edges of type l into v = 1024 c + w, + 4, ... in edge order, then ((w0 + w1) + w2) + w3.  Stage 2:
+ *            dcoeff[l, b] = the chunk sums in chunk order.  Partial tables plus an ordered reduce: needs no COMPACT part.
+ * The vector path (16-byte loads) is taken when D % 4 == 0 and the rows involved are 16-byte aligned (base and stride), the
+ * scalar path otherwise.  Neither counts arrivals nor waits on other workgroups, so the concurrency caveat of the
+ * tfgnn_graph_gather_* functions does not apply: calls over one handle may be in flight on several streams as long as
+ * each has a workspace of its own.
+ *
+ * Launches per call: forward 1 (+ 1 when a target row has several items); backward: dX 1 (+ 1), dcoeff 3 and one memset.  No
+ * allocation, no synchronisation, nothing read back: capturable as they are.
+ * workspace: tfgnn_basis_workspace_bytes(V, E, L, B, D, partials_by_dst, partials_by_src) bytes, 16-byte aligned, where
+ * partials_* = tfgnn_graph_gather_workspace_bytes(graph, TFGNN_VIEW_BY_DST_NODE / _BY_SRC_NODE, 1) / 4 (the plans' item counts
+ * of multi-item rows); one size serves both calls (0 for values outside the limits).
+ * LIMITS, checked on the host before the first launch: a struct of another size, NULL graph / pointers, strides smaller than
+ * the rows, a handle without PLAN_NODE, num_bases < 1, D < 1: TFGNN_ERR_INVALID_ARGUMENT; num_bases > 64, D > 2^20,
+ * B * D >= 2^31: TFGNN_ERR_UNSUPPORTED or INVALID_ARGUMENT with a message that names the limit.  L is the handle's (<= 256).
+ * V == 0: nothing launched.  No edges, an edge type without edges, a node without in- / out-edges: zeros (dcoeff[l, :] = 0).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct tfgnn_basis_forward_args {
+  size_t struct_size;
+  const tfgnn_graph* graph;
+  int B, D;                        /* num_bases, input width */
+  const float* coeff;              /* [L, B] */
+  const float* X;                  /* [V, D], row stride ldX */
+  int64_t ldX;
+  const float* edge_weight_by_dst; /* [E] or NULL */
+  const float* node_scale;         /* [V] or NULL */
+  float* Z;                        /* [V, B*D], row stride ldZ */
+  int64_t ldZ;
+  void* workspace;
+  size_t workspace_bytes;
+} tfgnn_basis_forward_args;
+
+typedef struct tfgnn_basis_backward_args {
+  size_t struct_size;
+  const tfgnn_graph* graph;
+  int B, D;
+  const float* coeff;              /* [L, B] */
+  const float* dZ;                 /* [V, B*D], row stride lddZ */
+  int64_t lddZ;
+  const float* X;                  /* [V, D], row stride ldX; read for dcoeff only (may be NULL without it) */
+  int64_t ldX;
+  const float* edge_weight_by_dst; /* [E] or NULL: dcoeff */
+  const float* edge_weight_by_src; /* [E] or NULL: dX */
+  const float* node_scale;         /* [V] or NULL: dcoeff */
+  float* dX;                       /* [V, D], row stride lddX; NULL = not wanted */
+  int64_t lddX;
+  float* dcoeff;                   /* [L, B] contiguous; NULL = not wanted */
+  void* workspace;
+  size_t workspace_bytes;
+} tfgnn_basis_backward_args;
+
+size_t tfgnn_basis_workspace_bytes(int64_t V, int64_t E, int L, int B, int D, int64_t partials_by_dst, int64_t partials_by_src);
+int tfgnn_basis_gather_forward(const tfgnn_basis_forward_args* args, void* stream);
+int tfgnn_basis_gather_backward(const tfgnn_basis_backward_args* args, void* stream);
+/* host-side counts of the kernel launches enqueued in this process: out[0] forward gather ("basis_fwd"), out[1] dX
+ * ("basis_dx"), out[2] dcoeff ("basis_dcoeff"), combining / reducing launches included; further slots are zero */
+int tfgnn_basis_launch_counts(int64_t* out_counts, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@ from .layers import (  # noqa: F401
     NodesToGraphRepresentationInput,
     RGAT,
     RGCN,
+    RGCN_Basis,
     RGIN,
     WASGraphRepresentation,
     WeightedSumGraphRepresentation,

@@ -409,6 +409,14 @@ _SIGNATURES += [
     ("tfgnn_gather_node_rows", c_int, [c_void_p, c_void_p]),
     ("tfgnn_sample_launch_counts", c_int, [POINTER(c_int64), c_int]),
 ]
+# R-GCN basis decomposition (include/tfgnn.h "R-GCN basis decomposition", csrc/basis.hip)
+_SIGNATURES += [
+    ("tfgnn_basis_workspace_bytes", c_size_t, [c_int64, c_int64, c_int, c_int, c_int, c_int64, c_int64]),
+    ("tfgnn_basis_gather_forward", c_int, [c_void_p, c_void_p]),
+    ("tfgnn_basis_gather_backward", c_int, [c_void_p, c_void_p]),
+    ("tfgnn_basis_launch_counts", c_int, [POINTER(c_int64), c_int]),
+]
+BASIS_MAX_BASES = 64  # csrc/basis.hip: 1 <= num_bases <= 64
 SAMPLE_MAX_HOPS = 8  # TFGNN_SAMPLE_MAX_HOPS
 SAMPLE_META_STATUS, SAMPLE_META_NODES, SAMPLE_META_EDGES = 0, 1, 2  # TFGNN_SAMPLE_META_*
 SAMPLE_NODE_OVERFLOW, SAMPLE_EDGE_OVERFLOW, SAMPLE_REPEATED_SEED, SAMPLE_BAD_SEED, SAMPLE_BAD_STORE = 1, 2, 4, 8, 16
@@ -482,6 +490,27 @@ class PoolBackwardArgs(ctypes.Structure):
         ("ptr", c_void_p), ("ids", c_void_p), ("dOut", c_void_p), ("T", c_void_p), ("ldT", c_int64), ("w", c_void_p),
         ("ldw", c_int64), ("lo", c_float), ("hi", c_float), ("dT", c_void_p), ("lddT", c_int64), ("dS", c_void_p),
         ("lddS", c_int64), ("workspace", c_void_p), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
+class BasisForwardArgs(ctypes.Structure):
+    """tfgnn_basis_forward_args (include/tfgnn.h), field for field"""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t), ("graph", c_void_p), ("B", c_int), ("D", c_int), ("coeff", c_void_p), ("X", c_void_p),
+        ("ldX", c_int64), ("edge_weight_by_dst", c_void_p), ("node_scale", c_void_p), ("Z", c_void_p), ("ldZ", c_int64),
+        ("workspace", c_void_p), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
+class BasisBackwardArgs(ctypes.Structure):
+    """tfgnn_basis_backward_args (include/tfgnn.h), field for field"""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t), ("graph", c_void_p), ("B", c_int), ("D", c_int), ("coeff", c_void_p), ("dZ", c_void_p),
+        ("lddZ", c_int64), ("X", c_void_p), ("ldX", c_int64), ("edge_weight_by_dst", c_void_p), ("edge_weight_by_src", c_void_p),
+        ("node_scale", c_void_p), ("dX", c_void_p), ("lddX", c_int64), ("dcoeff", c_void_p), ("workspace", c_void_p),
+        ("workspace_bytes", ctypes.c_size_t),
     ]
 
 

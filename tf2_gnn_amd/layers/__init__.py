@@ -14,6 +14,7 @@ from .message_passing import (
     MessagePassingInput,
     RGAT,
     RGCN,
+    RGCN_Basis,
     RGIN,
     get_known_message_passing_classes,
     get_message_passing_class,

@@ -20,6 +20,7 @@ from .gnn_film import GNN_FiLM  # isort: skip
 from .ggnn import GGNN  # isort: skip
 from .rgat import RGAT  # isort: skip
 from .rgcn import RGCN  # isort: skip
+from .rgcn_basis import RGCN_Basis  # isort: skip
 from .rgin import RGIN  # isort: skip
 
 

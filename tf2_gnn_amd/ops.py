@@ -1054,6 +1054,129 @@ def pool_launch_counts() -> dict:
     return {"pool_fwd": int(buf[0]), "pool_bwd": int(buf[1])}
 
 
+def _basis_common(who: str, graph: "Graph", coeff: torch.Tensor, edge_weights, node_scale):
+    """The checks the two basis-gather wrappers share -> (L, B, contiguous coeff)."""
+    _require_dev(coeff, torch.float32, "coeff")
+    L = graph.num_edge_types
+    if coeff.dim() != 2 or coeff.shape[0] != L:
+        raise ValueError(f"{who}: coeff must be [{L}, num_bases] (one row per edge type), got {tuple(coeff.shape)}")
+    B = int(coeff.shape[1])
+    if not 1 <= B <= _lib.BASIS_MAX_BASES:
+        raise ValueError(f"{who}: num_bases = {B} is outside the limit 1 <= num_bases <= {_lib.BASIS_MAX_BASES}")
+    for name, t, n in [(k, t, graph.num_edges) for k, t in edge_weights] + [("node_scale", node_scale, graph.num_nodes)]:
+        if t is None:
+            continue
+        _require_dev(t, torch.float32, name)
+        if t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous vector of {n} floats, got {tuple(t.shape)}")
+        if t.device != coeff.device:
+            raise ValueError(f"{who}: {name} lives on {t.device}, coeff on {coeff.device}")
+    return L, B, coeff.contiguous()
+
+
+def _basis_matrix(who: str, t: torch.Tensor, rows: int, cols: int, what: str, device, writable: bool = False):
+    _require_dev(t, torch.float32, what)
+    if t.dim() != 2 or tuple(t.shape) != (rows, cols):
+        raise ValueError(f"{who}: {what} must be [{rows}, {cols}], got {tuple(t.shape)}")
+    if t.device != device:
+        raise ValueError(f"{who}: {what} lives on {t.device}, coeff on {device}")
+    t2, ld = _rowmajor(t, what)
+    if writable and t2 is not t:
+        raise ValueError(f"{who}: {what} must have unit inner stride")
+    return t2, ld
+
+
+def _basis_workspace(graph: "Graph", B: int, D: int, device):
+    lib = _lib.load()
+    graph.ensure(G_PART_PLAN_NODE)
+    pd = lib.tfgnn_graph_gather_workspace_bytes(graph._h, VIEW_BY_DST_NODE, 1) // 4  # the plans' multi-item partial rows
+    ps = lib.tfgnn_graph_gather_workspace_bytes(graph._h, VIEW_BY_SRC_NODE, 1) // 4
+    nbytes = lib.tfgnn_basis_workspace_bytes(graph.num_nodes, graph.num_edges, graph.num_edge_types, B, D, pd, ps)
+    return _aligned_workspace(device, nbytes) if nbytes else (None, 0, None)
+
+
+@_writes_out
+def basis_gather_forward(graph: "Graph", coeff: torch.Tensor, X: torch.Tensor, *, edge_weight: Optional[torch.Tensor] = None,
+                         node_scale: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """R-GCN basis decomposition, the gather (tfgnn_basis_gather_forward): Z[v, b*D:(b+1)*D] = node_scale[v] * sum over the
+    edges (u -> v) of type l of edge_weight[e] * coeff[l, b] * X[u].  ``edge_weight`` / ``node_scale``: what ``graph_scales``
+    returns as ``edge_weight_by_dst`` / ``node_scale`` (None = 1).  X and ``out`` may be column slices of wider arrays."""
+    who = "basis_gather_forward"
+    L, B, coeff = _basis_common(who, graph, coeff, [("edge_weight", edge_weight)], node_scale)
+    V = graph.num_nodes
+    if X.dim() != 2 or X.shape[0] != V or X.shape[1] < 1:
+        raise ValueError(f"{who}: X must be [{V}, D] with D >= 1, got {tuple(X.shape)}")
+    D = int(X.shape[1])
+    X, ldX = _basis_matrix(who, X, V, D, "X", coeff.device)
+    if out is None:
+        out = torch.empty((V, B * D), dtype=torch.float32, device=X.device)
+    out, ldZ = _basis_matrix(who, out, V, B * D, "out", coeff.device, writable=True)
+    ws_ptr, ws_len, ws = _basis_workspace(graph, B, D, X.device)
+    a = _lib.BasisForwardArgs()
+    a.struct_size = ctypes.sizeof(a)
+    a.graph, a.B, a.D = graph._h, B, D
+    a.coeff, a.X, a.ldX = coeff.data_ptr(), X.data_ptr(), ldX
+    a.edge_weight_by_dst = None if edge_weight is None else edge_weight.data_ptr()
+    a.node_scale = None if node_scale is None else node_scale.data_ptr()
+    a.Z, a.ldZ = out.data_ptr(), ldZ
+    a.workspace, a.workspace_bytes = ws_ptr, ws_len
+    stream = _stream()
+    with op_scope("basis_gather_forward", X, coeff, out):
+        _lib.check(_lib.load().tfgnn_basis_gather_forward(ctypes.byref(a), stream))
+    return out
+
+
+def basis_gather_backward(graph: "Graph", coeff: torch.Tensor, dZ: torch.Tensor, X: Optional[torch.Tensor] = None, *,
+                          edge_weight_by_dst: Optional[torch.Tensor] = None, edge_weight_by_src: Optional[torch.Tensor] = None,
+                          node_scale: Optional[torch.Tensor] = None, want_dx: bool = True, want_dcoeff: bool = True,
+                          out_dx: Optional[torch.Tensor] = None):
+    """The two reverse passes of ``basis_gather_forward`` (tfgnn_basis_gather_backward) -> (dX [V, D] or None, dcoeff [L, B] or
+    None).  ``edge_weight_by_src`` is ``graph_scales``' (it carries the target's node scale); X is read for dcoeff only.
+    ``out_dx``: write dX there (may be a column slice of a wider array)."""
+    who = "basis_gather_backward"
+    L, B, coeff = _basis_common(who, graph, coeff, [("edge_weight_by_dst", edge_weight_by_dst),
+                                                     ("edge_weight_by_src", edge_weight_by_src)], node_scale)
+    V = graph.num_nodes
+    if dZ.dim() != 2 or dZ.shape[0] != V or dZ.shape[1] < B or dZ.shape[1] % B:
+        raise ValueError(f"{who}: dZ must be [{V}, num_bases * D] with num_bases = {B}, got {tuple(dZ.shape)}")
+    D = int(dZ.shape[1]) // B
+    dZ, lddZ = _basis_matrix(who, dZ, V, B * D, "dZ", coeff.device)
+    a = _lib.BasisBackwardArgs()
+    a.struct_size = ctypes.sizeof(a)
+    a.graph, a.B, a.D = graph._h, B, D
+    a.coeff, a.dZ, a.lddZ = coeff.data_ptr(), dZ.data_ptr(), lddZ
+    dX = dcoeff = None
+    if want_dcoeff:
+        if X is None:
+            raise ValueError(f"{who}: dcoeff needs X")
+        X, ldX = _basis_matrix(who, X, V, D, "X", coeff.device)
+        a.X, a.ldX = X.data_ptr(), ldX
+        dcoeff = torch.empty((L, B), dtype=torch.float32, device=coeff.device)
+        a.dcoeff = dcoeff.data_ptr()
+    if want_dx:
+        dX = out_dx if out_dx is not None else torch.empty((V, D), dtype=torch.float32, device=coeff.device)
+        dX, lddX = _basis_matrix(who, dX, V, D, "out_dx", coeff.device, writable=True)
+        a.dX, a.lddX = dX.data_ptr(), lddX
+    a.edge_weight_by_dst = None if edge_weight_by_dst is None else edge_weight_by_dst.data_ptr()
+    a.edge_weight_by_src = None if edge_weight_by_src is None else edge_weight_by_src.data_ptr()
+    a.node_scale = None if node_scale is None else node_scale.data_ptr()
+    ws_ptr, ws_len, ws = _basis_workspace(graph, B, D, coeff.device)
+    a.workspace, a.workspace_bytes = ws_ptr, ws_len
+    stream = _stream()
+    with op_scope("basis_gather_backward", dZ, X, coeff, dX, dcoeff):
+        _lib.check(_lib.load().tfgnn_basis_gather_backward(ctypes.byref(a), stream))
+    if dX is not None:
+        torch.autograd.graph.increment_version(dX)
+    return dX, dcoeff
+
+
+def basis_launch_counts() -> dict:
+    """tfgnn_basis_launch_counts: kernel launches of the basis gather and its two reverse passes so far (host counters)."""
+    buf = (ctypes.c_int64 * 3)()
+    _lib.check(_lib.load().tfgnn_basis_launch_counts(buf, 3))
+    return {"basis_fwd": int(buf[0]), "basis_dx": int(buf[1]), "basis_dcoeff": int(buf[2])}
+
+
 def mul(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     lib = _lib.load()
     a = a.contiguous()
