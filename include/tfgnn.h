@@ -608,7 +608,36 @@ int tfgnn_segment_softmax_backward(const float* d_w, const float* d_dw, int head
  * 1/(1-rate)).  d_mask receives 0 or 1/(1-rate) per element; the gradient is tfgnn_mul(dy, mask).
  * The stream of random numbers is this library's own (counter-based: element i of a call is a pure function of (seed, i)),
  * not TensorFlow's.  d_mask may be NULL (not stored); d_y == NULL (then d_x is ignored) only (re)generates the mask of
- * (seed, rate) - what tfgnn_sp_gemm_nt_dropout applies in its epilogue. */
+ * (seed, rate) - what tfgnn_sp_gemm_nt_dropout applies in its epilogue.
+ *
+ * The dropout mask generator (all of it fixed: tests/dropout_reference.py reproduces every mask exactly, and every kernel that
+ * draws one - this entry, tfgnn_dropout_forward_sp, the epilogues of tfgnn_sp_gemm_nt_dropout in forward and gradient products,
+ * tfgnn_gru_gates_backward_sp_dropout - draws this one).  32-bit wrap-around arithmetic unless stated:
+ *   s0, s1     the low and the high word of splitmix64's output for `seed` (z = seed + 0x9E3779B97F4A7C15;
+ *              z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >> 31, in 64 bits).
+ *              seed 0: z = 0xE220A8397B1DCDAF.
+ *   threshold  ceil((double)rate * 2^24) of the FLOAT32 rate: 0.1f -> 0x19999A, 0.5f -> 0x800000, rate 0 -> 0 (all kept)
+ *   scale      1.f / (1.f - rate), both operations in float32: the value of a kept mask element
+ *   epoch e    (the device word below; read once per kernel):  e != 0:  s0 ^= lowbias32(e * 0x9E3779B9 + 0x7F4A7C15),
+ *              s1 += e * 0x85EBCA6B;  e = 0: nothing.  rate 0 never reads the epoch.
+ *   word       ONE per aligned group of four elements, g = index / 4 (64 bits):
+ *                  word(g) = lowbias32((uint32)g ^ s0 ^ h) ^ s1,   h = 0 while g < 2^32, else lowbias32((g >> 32) * 0x9E3779B9 + 1)
+ *              (the high-word term: tensors of more than 2^34 elements);
+ *              lowbias32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16.
+ *   element    e = index % 4 takes the 24-bit number  u = rotl(word, 8 e) >> 8  and is KEPT iff u >= threshold: mask = scale,
+ *              else mask = 0.  y = x * mask in float32 (a dropped inf or NaN is NaN, as in tf.nn.dropout).
+ *   index      = row * cols + column of the LOGICAL tensor the call describes (flat entries: the element's position in the
+ *              call; products: output row - the row d_row_map names, where one is given - times N plus column), never an
+ *              address: views, leading dimensions and alignment do not enter.
+ * Every element's number is uniform, so P(kept) = 1 - threshold / 2^24, within 2^-24 of 1 - rate, and E[mask] = 1 within
+ * 2^-23 / (1 - rate).  The four elements of a group are NOT independent: element e decides on a byte of its own (the top byte
+ * of u, byte 3 - e of the word), but when that byte equals the threshold's top byte (probability 2^-8) the decision falls to
+ * the two bytes below it, which are the deciding bytes of elements e + 1 and e + 2 (mod 4).  The correlation of two elements
+ * of a group is at most 2^-8 plus terms of order 2^-16 / (rate (1 - rate)) (tests/test_dropout_reference_host.py derives and
+ * enumerates it); it is 0 at rates whose threshold has sixteen zero low bits (0.5, 0.25, 0.125).  Elements of different
+ * groups, seeds or epochs share no hash input.
+ * seed 2^64 - 1 is RESERVED at the NT product entries (tfgnn_sp_gemm_nt_dropout and the entries built on it), where it selects
+ * the mask-from-saved form; this entry, tfgnn_dropout_forward_sp and tfgnn_gru_gates_backward_sp_dropout take it as a seed. */
 int tfgnn_dropout_forward(const float* d_x, float* d_y, float* d_mask, int64_t n, float rate,
                           uint64_t seed, void* stream);
 /* The same dropout (same random numbers: element (r, c) draws that of flat index r * cols + c) that also writes its result

@@ -8,7 +8,11 @@ One scale block = ``scale_block`` consecutive columns of one row.  With mx = max
   an inf or nan in the block: s = inv = 1
   h = fp16(x * s) (round to nearest even), l = fp16(x * s - h); l = 0 where x * s is inf or nan
 x * s is an fp32 product and x * s - h an fp32 difference, as on the device (both are exact for finite values that do not
-underflow).  Byte layout: row r, column c -> byte (c / 16) * 64 + plane * 32 + (c % 16) * 2 of the row, plane 0 = h, 1 = l."""
+underflow).  Byte layout: row r, column c -> byte (c / 16) * 64 + plane * 32 + (c % 16) * 2 of the row, plane 0 = h, 1 = l.
+The SIGN OF A ZERO in h or l is not part of the format (the value is (h + l) * inv, and a product adds nothing for either zero):
+where x * s is -0 this model writes h = -0, l = +0, while a device producer may write h = +0, l = -0 - the compiler contracts
+fp16(x * s) and fp16(x * s - h) into fused multiply-adds (v_fma_mixlo_f16) whose +0 addend takes the sign off a zero product.
+Byte comparisons against a tensor that holds -0 go through ``without_zero_signs``."""
 from __future__ import annotations
 
 import numpy as np
@@ -82,6 +86,13 @@ def unpack(data, cols: int):
     assert cols % 16 == 0 and data.shape[1] >= 4 * cols
     gran = np.ascontiguousarray(data[:, : 4 * cols]).view(np.float16).reshape(R, cols // 16, 2, 16)
     return gran[:, :, 0, :].reshape(R, cols).copy(), gran[:, :, 1, :].reshape(R, cols).copy()
+
+
+def without_zero_signs(data):
+    """packed SP16 bytes (uint8 [R, 4 * C]) with every fp16 -0 (0x8000) written as +0: nothing else changes"""
+    words = np.ascontiguousarray(data, dtype=np.uint8).view(np.uint16).copy()
+    words[words == 0x8000] = 0
+    return words.view(np.uint8)
 
 
 def blockmax(ref, scale_block: int):

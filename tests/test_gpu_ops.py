@@ -513,6 +513,13 @@ def test_dropout_mask_statistics_and_scaling(dev):
     assert torch.equal(mask, mask2)
     _, mask3 = ops.dropout_forward(x, 0.1, seed=8)
     assert not torch.equal(mask, mask3)
+    # and they are the masks include/tfgnn.h writes out (tests/dropout_reference.py), bit for bit - at the epoch in force: tests
+    # that replayed a captured step before this one have advanced it
+    from tests import dropout_reference
+
+    epoch = ops.dropout_epoch()
+    assert np.array_equal(mask.cpu().numpy(), dropout_reference.mask(200000, 0.1, 7, epoch))
+    assert np.array_equal(mask3.cpu().numpy(), dropout_reference.mask(200000, 0.1, 8, epoch))
     with pytest.raises(ValueError):
         ops.dropout_forward(x, 1.0, seed=0)
 

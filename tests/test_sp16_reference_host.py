@@ -157,3 +157,20 @@ def test_pack_unpack_and_the_byte_layout():
     want = np.zeros((1, 16))
     want[0, 3] = (1.5 + 2.0 ** -12) * 0.25
     assert np.array_equal(decode_sp16(op), want) and np.array_equal(sp.decode(hh, hl, np.array([[0.25]]), 16), want)
+
+
+def test_without_zero_signs_changes_nothing_but_the_sign_of_a_zero():
+    x = np.array([[-0.0, 0.0, -1.5, 1.5, -2.0 ** -30, 3.0, -0.0, 7.0] + [0.0] * 8], dtype=np.float32)
+    h, l, inv = sp.encode(x, 16)
+    data = sp.pack(h, l)
+    assert data[0, 1] == 0x80 and data[0, 13] == 0x80  # the model's h of a -0
+    clean = sp.without_zero_signs(data)
+    assert clean.shape == data.shape and clean.dtype == np.uint8 and data[0, 1] == 0x80  # (a copy)
+    differ = np.flatnonzero(clean != data)
+    assert differ.tolist() == [1, 13]
+    h2, l2 = sp.unpack(clean, 16)
+    assert np.array_equal(sp.decode(h2, l2, inv, 16), sp.decode(h, l, inv, 16))
+    device = data.copy()  # what a device producer writes for a -0: h = +0, l = -0
+    device[0, [1, 13]] = 0
+    device[0, [33, 45]] = 0x80
+    assert np.array_equal(sp.without_zero_signs(device), clean)
