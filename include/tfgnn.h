@@ -1698,6 +1698,109 @@ int tfgnn_basis_gather_backward(const tfgnn_basis_backward_args* args, void* str
  * ("basis_dx"), out[2] dcoeff ("basis_dcoeff"), combining / reducing launches included; further slots are zero */
 int tfgnn_basis_launch_counts(int64_t* out_counts, int n);
 
+/* ------------------------------------------------------------------------------------------
+ * R-GCN block-diagonal decomposition (csrc/blockdiag.hip; Schlichtkrull et al. 2018, eq. 4: W_l = blockdiag(Q_l^0 .. Q_l^{C-1})
+ * with C = num_blocks blocks Q_l^c [di, ho], di = D / C, ho = H / C, both exact), the blocks applied inside the neighbour walk.
+ * The blocks are stored BANDED in one contiguous buffer Qb [L, di, H]:
+ *   W_l[c*di + i, c*ho + j] = Qb[l, i, c*ho + j]          (every other entry of W_l is 0)
+ * so output column h reads Qb[l, i, h], i = 0 .. di-1: rows of H floats.  With s_e / m_v / s'_e the scales of tfgnn_graph_scales
+ * (d_edge_weight_by_dst / d_node_scale / d_edge_weight_by_src, which carries m_v), c(h) = h / ho and c(d) = d / di:
+ *   tfgnn_blockdiag_forward   pre[v, h]    = m_v * sum over the edges e = (u -> v) of type l of
+ *                                            s_e * sum_i X[u, c(h)*di + i] * Qb[l, i, h]
+ *   tfgnn_blockdiag_backward  dX[u, d]     = sum over the edges e = (u -> v) of type l of
+ *                                            s'_e * sum_j dPre[v, c(d)*ho + j] * Qb[l, d % di, c(d)*ho + j]
+ *                             dQb[l, i, h] = sum over the edges e = (u -> v) of type l of  m_v * s_e * X[u, c(h)*di + i] * dPre[v, h]
+ * pre is the layer's output before its activation (tfgnn_activation_forward / _backward stay separate passes).  No per-bucket
+ * operand, no per-edge message and no product: Qb (L * D * H / C floats) is read through the caches.  X, pre, dPre, dX have row
+ * strides (floats); columns outside [0, D) / [0, H) of a wider array are left untouched.  edge_weight_* NULL: 1 per edge;
+ * node_scale NULL: 1.  dX / dQb NULL: not computed; each alone gives the same bits as both together.
+ *
+ * The two walks use the handle's node views and their long-row plans (part PLAN_NODE) exactly as the basis gather above: a row
+ * of more than 32 edges is cut into items of 512 edges, one workgroup per item, whose G lane groups take ceil(edges / G)
+ * consecutive edges each; a row of at most 32 edges is one segment.  A lane group of P lanes owns a WINDOW of cw whole blocks on
+ * both sides (their cw*di input and cw*ho output columns; blockIdx.y walks the ceil(C / cw) windows): with u = 4 on the vector
+ * path and 1 on the scalar path, P is the one of 16, 32, 64 with cw = min(C, floor(P*u / max(di, ho))) >= 1 for which
+ * ceil(C / cw) * P is smallest (ties: the larger P), and G = 256 / P.
+ * ORDER OF THE SUMS - fp32, fused multiply-adds, no float atomics; it depends on the graph, C, D, H and the alignment alone, so
+ * two calls - or an eager call and its replay from a captured graph - give the same bits:
+ *   forward  per segment: the edges in by-target order; inside a run of one type  r[d] = fma(s_e, x[d], r[d]);  at the end of
+ *            the run, once per run,  acc[h] = fma(r[c(h)*di + i], Qb[l, i, h], acc[h])  with i ascending; runs in ascending
+ *            type.  The segments of an item are added in order, the items of a row in item order (second launch, only when
+ *            some row has several items), then * m_v.
+ *   dX       per segment: the edges in by-source order; inside a run  g[h] = fma(s'_e, dPre[v, h], g[h]);  at the end of the run
+ *            acc[d] = fma(g[c(d)*ho + j], Qb[l, d % di, c(d)*ho + j], acc[d])  with j ascending.  Segments and items as above.
+ *   dQb      type-major, two stages.  The concatenation of the caller's edge lists is type-major; chunk k of type l is its list
+ *            positions [first_l + 256 k, first_l + min(E_l, 256 (k + 1))).  Stage 1, one workgroup per chunk (and tile of 64
+ *            columns x 8 block rows): wave w of 4 takes the w-th run of ceil(n / 4) consecutive positions of the chunk's n;
+ *            per edge  t = (m_v * s_e) * dPre[v, h]  (two roundings) and  p[i] = fma(X[u, c(h)*di + i], t, p[i]);  the four
+ *            waves' sums as ((w0 + w1) + w2) + w3.  Stage 2: dQb[l, i, h] = 0 + the chunk partials of type l in chunk order;
+ *            a type without edges gets exact zeros.
+ * The vector path (16-byte loads) is taken when di % 4 == 0, ho % 4 == 0 and the rows involved are 16-byte aligned (base and
+ * stride; forward: X, pre and Qb; dX: dPre and dX), the scalar path otherwise.  Nobody counts arrivals or waits on another
+ * workgroup: calls over one handle may be in flight on several streams as long as each has a workspace of its own.
+ *
+ * dQb reads four int32 device tables that the caller builds once per graph (ops.py keeps them with the Graph): list_to_dst [E],
+ * the inverse of TFGNN_G_EID_BY_DST (position in the concatenated lists -> position in the by-target order); chunk_first and
+ * chunk_count [num_chunks], the first list position and the length (1 .. 256) of every chunk, types ascending, chunks of a type
+ * ascending; type_chunk_ptr [L + 1], the first chunk of every type.  num_chunks = sum_l ceil(E_l / 256).  The tables are trusted.
+ *
+ * Launches per call: forward 1 (+ 1 when a target row has several items); backward: dX 1 (+ 1), dQb 2 (without edges: one
+ * memset instead).  No allocation, no synchronisation, nothing read back: capturable as they are.
+ * workspace: tfgnn_blockdiag_workspace_bytes(C, D, H, partials_by_dst, partials_by_src, num_chunks) bytes, 16-byte aligned:
+ * max(partials_by_dst * H, partials_by_src * D + num_chunks * di * H) floats (each part rounded up to 16 bytes), partials_* as
+ * for the basis gather; one size serves both calls (0 for values outside the limits).
+ * LIMITS, checked on the host before the first launch: a struct of another size, NULL graph / pointers, strides smaller than
+ * the rows, a handle without PLAN_NODE, num_blocks < 1, D or H < 1, num_blocks not dividing D and H:
+ * TFGNN_ERR_INVALID_ARGUMENT; a block wider than the lane mapping holds - D / num_blocks > 64 or H / num_blocks > 64 (D and H
+ * themselves are not capped) - or num_blocks > 65535: TFGNN_ERR_UNSUPPORTED; each with a message that names the limit.
+ * V == 0: nothing launched.  No edges, an edge type without edges, a node without in- / out-edges: zeros.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct tfgnn_blockdiag_forward_args {
+  size_t struct_size;
+  const tfgnn_graph* graph;
+  int C, D, H;                     /* num_blocks, input width, output width */
+  const float* Qb;                 /* [L, D/C, H] contiguous */
+  const float* X;                  /* [V, D], row stride ldX */
+  int64_t ldX;
+  const float* edge_weight_by_dst; /* [E] or NULL */
+  const float* node_scale;         /* [V] or NULL */
+  float* pre;                      /* [V, H], row stride ldpre */
+  int64_t ldpre;
+  void* workspace;
+  size_t workspace_bytes;
+} tfgnn_blockdiag_forward_args;
+
+typedef struct tfgnn_blockdiag_backward_args {
+  size_t struct_size;
+  const tfgnn_graph* graph;
+  int C, D, H;
+  const float* Qb;                 /* [L, D/C, H] contiguous; read for dX only (may be NULL without it) */
+  const float* dPre;               /* [V, H], row stride lddPre */
+  int64_t lddPre;
+  const float* X;                  /* [V, D], row stride ldX; read for dQb only (may be NULL without it) */
+  int64_t ldX;
+  const float* edge_weight_by_dst; /* [E] or NULL: dQb */
+  const float* edge_weight_by_src; /* [E] or NULL: dX */
+  const float* node_scale;         /* [V] or NULL: dQb */
+  float* dX;                       /* [V, D], row stride lddX; NULL = not wanted */
+  int64_t lddX;
+  float* dQb;                      /* [L, D/C, H] contiguous; NULL = not wanted */
+  const int32_t* list_to_dst;      /* [E]; the four tables are read for dQb only */
+  const int32_t* chunk_first;      /* [num_chunks] */
+  const int32_t* chunk_count;      /* [num_chunks] */
+  const int32_t* type_chunk_ptr;   /* [L + 1] */
+  int64_t num_chunks;
+  void* workspace;
+  size_t workspace_bytes;
+} tfgnn_blockdiag_backward_args;
+
+size_t tfgnn_blockdiag_workspace_bytes(int C, int D, int H, int64_t partials_by_dst, int64_t partials_by_src, int64_t num_chunks);
+int tfgnn_blockdiag_forward(const tfgnn_blockdiag_forward_args* args, void* stream);
+int tfgnn_blockdiag_backward(const tfgnn_blockdiag_backward_args* args, void* stream);
+/* host-side counts of the kernel launches enqueued in this process: out[0] forward ("fwd"), out[1] dX ("dx"), out[2] dQb
+ * ("dq"), combining / reducing launches included; further slots are zero */
+int tfgnn_blockdiag_launch_counts(int64_t* out_counts, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@ from .layers import (  # noqa: F401
     RGAT,
     RGCN,
     RGCN_Basis,
+    RGCN_BlockDiag,
     RGIN,
     WASGraphRepresentation,
     WeightedSumGraphRepresentation,

@@ -417,6 +417,15 @@ _SIGNATURES += [
     ("tfgnn_basis_launch_counts", c_int, [POINTER(c_int64), c_int]),
 ]
 BASIS_MAX_BASES = 64  # csrc/basis.hip: 1 <= num_bases <= 64
+# R-GCN block-diagonal decomposition (include/tfgnn.h "R-GCN block-diagonal decomposition", csrc/blockdiag.hip)
+_SIGNATURES += [
+    ("tfgnn_blockdiag_workspace_bytes", c_size_t, [c_int, c_int, c_int, c_int64, c_int64, c_int64]),
+    ("tfgnn_blockdiag_forward", c_int, [c_void_p, c_void_p]),
+    ("tfgnn_blockdiag_backward", c_int, [c_void_p, c_void_p]),
+    ("tfgnn_blockdiag_launch_counts", c_int, [POINTER(c_int64), c_int]),
+]
+BLOCKDIAG_MAX_BLOCK = 64  # csrc/blockdiag.hip MAX_BLOCK: D / num_blocks and H / num_blocks at most
+BLOCKDIAG_CHUNK = 256  # csrc/blockdiag.hip DQ_CHUNK: list positions per chunk of dQb's first stage
 SAMPLE_MAX_HOPS = 8  # TFGNN_SAMPLE_MAX_HOPS
 SAMPLE_META_STATUS, SAMPLE_META_NODES, SAMPLE_META_EDGES = 0, 1, 2  # TFGNN_SAMPLE_META_*
 SAMPLE_NODE_OVERFLOW, SAMPLE_EDGE_OVERFLOW, SAMPLE_REPEATED_SEED, SAMPLE_BAD_SEED, SAMPLE_BAD_STORE = 1, 2, 4, 8, 16
@@ -511,6 +520,28 @@ class BasisBackwardArgs(ctypes.Structure):
         ("lddZ", c_int64), ("X", c_void_p), ("ldX", c_int64), ("edge_weight_by_dst", c_void_p), ("edge_weight_by_src", c_void_p),
         ("node_scale", c_void_p), ("dX", c_void_p), ("lddX", c_int64), ("dcoeff", c_void_p), ("workspace", c_void_p),
         ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
+class BlockdiagForwardArgs(ctypes.Structure):
+    """tfgnn_blockdiag_forward_args (include/tfgnn.h), field for field"""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t), ("graph", c_void_p), ("C", c_int), ("D", c_int), ("H", c_int), ("Qb", c_void_p),
+        ("X", c_void_p), ("ldX", c_int64), ("edge_weight_by_dst", c_void_p), ("node_scale", c_void_p), ("pre", c_void_p),
+        ("ldpre", c_int64), ("workspace", c_void_p), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
+class BlockdiagBackwardArgs(ctypes.Structure):
+    """tfgnn_blockdiag_backward_args (include/tfgnn.h), field for field"""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t), ("graph", c_void_p), ("C", c_int), ("D", c_int), ("H", c_int), ("Qb", c_void_p),
+        ("dPre", c_void_p), ("lddPre", c_int64), ("X", c_void_p), ("ldX", c_int64), ("edge_weight_by_dst", c_void_p),
+        ("edge_weight_by_src", c_void_p), ("node_scale", c_void_p), ("dX", c_void_p), ("lddX", c_int64), ("dQb", c_void_p),
+        ("list_to_dst", c_void_p), ("chunk_first", c_void_p), ("chunk_count", c_void_p), ("type_chunk_ptr", c_void_p),
+        ("num_chunks", c_int64), ("workspace", c_void_p), ("workspace_bytes", ctypes.c_size_t),
     ]
 
 

@@ -15,6 +15,7 @@ from .message_passing import (
     RGAT,
     RGCN,
     RGCN_Basis,
+    RGCN_BlockDiag,
     RGIN,
     get_known_message_passing_classes,
     get_message_passing_class,

@@ -21,6 +21,7 @@ from .ggnn import GGNN  # isort: skip
 from .rgat import RGAT  # isort: skip
 from .rgcn import RGCN  # isort: skip
 from .rgcn_basis import RGCN_Basis  # isort: skip
+from .rgcn_blockdiag import RGCN_BlockDiag  # isort: skip
 from .rgin import RGIN  # isort: skip
 
 

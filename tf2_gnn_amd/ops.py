@@ -1177,6 +1177,160 @@ def basis_launch_counts() -> dict:
     return {"basis_fwd": int(buf[0]), "basis_dx": int(buf[1]), "basis_dcoeff": int(buf[2])}
 
 
+def blockdiag_chunk_table(edges_per_type, chunk: int = _lib.BLOCKDIAG_CHUNK):
+    """The chunk table of the block-diagonal weight gradient, on the host from the per-type edge counts alone: the concatenated
+    edge lists are type-major, chunk k of type l is the list positions [first_l + chunk*k, first_l + min(E_l, chunk*(k+1))).
+    -> (chunk_type, chunk_first, chunk_count, type_chunk_ptr [L + 1]) as lists; types ascending, a type's chunks ascending."""
+    chunk_type, chunk_first, chunk_count, type_chunk_ptr = [], [], [], [0]
+    first = 0
+    for l, n in enumerate(int(n) for n in edges_per_type):
+        for k in range(0, n, chunk):
+            chunk_type.append(l)
+            chunk_first.append(first + k)
+            chunk_count.append(min(chunk, n - k))
+        first += n
+        type_chunk_ptr.append(len(chunk_type))
+    return chunk_type, chunk_first, chunk_count, type_chunk_ptr
+
+
+def _blockdiag_tables(graph: "Graph"):
+    """The per-graph type-major tables tfgnn_blockdiag_backward reads for dQb, built once and kept with the Graph:
+    -> (list_to_dst [E], chunk_first, chunk_count [num_chunks], type_chunk_ptr [L + 1], num_chunks).  list_to_dst inverts
+    G_EID_BY_DST - a permutation, so one scatter without races; the chunk table comes from the host's edge counts (no read-back)."""
+    hit = graph._cache.get("blockdiag_tables")
+    if hit is None:
+        if capturing():
+            raise RuntimeError("tf2_gnn_amd: the block-diagonal layer's per-graph tables cannot be built inside a hipGraph capture; "
+                               "run the step eagerly once on the same graph first (CapturedStep warmup)")
+        E = graph.num_edges
+        eid = graph.array(G_EID_BY_DST)
+        list_to_dst = torch.empty(E, dtype=torch.int32, device=graph.device)
+        if E:
+            list_to_dst[eid.long()] = torch.arange(E, dtype=torch.int32, device=graph.device)
+        _, first, count, ptr = blockdiag_chunk_table(graph.edges_per_type)
+        n = len(first)
+        host = torch.tensor(first + count + ptr, dtype=torch.int32)
+        dev = host.to(graph.device)
+        hit = (list_to_dst, dev[:n], dev[n:2 * n], dev[2 * n:], n)
+        graph._cache["blockdiag_tables"] = hit
+    return hit
+
+
+def _blockdiag_common(who: str, graph: "Graph", Qb: torch.Tensor, num_blocks: int, edge_weights, node_scale):
+    """The checks the two block-diagonal wrappers share -> (L, C, di, H, contiguous Qb)."""
+    _require_dev(Qb, torch.float32, "Qb")
+    L, C = graph.num_edge_types, int(num_blocks)
+    if Qb.dim() != 3 or Qb.shape[0] != L or Qb.shape[1] < 1 or Qb.shape[2] < 1:
+        raise ValueError(f"{who}: Qb must be [{L}, D / num_blocks, H] (banded blocks, one slab per edge type), got {tuple(Qb.shape)}")
+    di, H = int(Qb.shape[1]), int(Qb.shape[2])
+    if C < 1 or H % C:
+        raise ValueError(f"{who}: num_blocks = {C} must be at least 1 and divide H = {H}")
+    if di > _lib.BLOCKDIAG_MAX_BLOCK or H // C > _lib.BLOCKDIAG_MAX_BLOCK:
+        raise ValueError(f"{who}: blocks of {di} x {H // C} are above the limit D / num_blocks <= {_lib.BLOCKDIAG_MAX_BLOCK} and "
+                         f"H / num_blocks <= {_lib.BLOCKDIAG_MAX_BLOCK}")
+    for name, t, n in [(k, t, graph.num_edges) for k, t in edge_weights] + [("node_scale", node_scale, graph.num_nodes)]:
+        if t is None:
+            continue
+        _require_dev(t, torch.float32, name)
+        if t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous vector of {n} floats, got {tuple(t.shape)}")
+        if t.device != Qb.device:
+            raise ValueError(f"{who}: {name} lives on {t.device}, Qb on {Qb.device}")
+    return L, C, di, H, Qb.contiguous()
+
+
+def _blockdiag_workspace(graph: "Graph", C: int, D: int, H: int, num_chunks: int, device):
+    lib = _lib.load()
+    graph.ensure(G_PART_PLAN_NODE)
+    pd = lib.tfgnn_graph_gather_workspace_bytes(graph._h, VIEW_BY_DST_NODE, 1) // 4  # the plans' multi-item partial rows
+    ps = lib.tfgnn_graph_gather_workspace_bytes(graph._h, VIEW_BY_SRC_NODE, 1) // 4
+    nbytes = lib.tfgnn_blockdiag_workspace_bytes(C, D, H, pd, ps, num_chunks)
+    return _aligned_workspace(device, nbytes) if nbytes else (None, 0, None)
+
+
+@_writes_out
+def blockdiag_forward(graph: "Graph", Qb: torch.Tensor, X: torch.Tensor, num_blocks: int, *,
+                      edge_weight: Optional[torch.Tensor] = None, node_scale: Optional[torch.Tensor] = None,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """R-GCN block-diagonal decomposition, forward (tfgnn_blockdiag_forward): pre[v, h] = node_scale[v] * sum over the edges
+    (u -> v) of type l of edge_weight[e] * sum_i X[u, c(h)*di + i] * Qb[l, i, h], Qb [L, di, H] the banded blocks.
+    ``edge_weight`` / ``node_scale``: what ``graph_scales`` returns as ``edge_weight_by_dst`` / ``node_scale`` (None = 1).  X and
+    ``out`` may be column slices of wider arrays."""
+    who = "blockdiag_forward"
+    L, C, di, H, Qb = _blockdiag_common(who, graph, Qb, num_blocks, [("edge_weight", edge_weight)], node_scale)
+    V, D = graph.num_nodes, C * di
+    X, ldX = _basis_matrix(who, X, V, D, "X", Qb.device)
+    if out is None:
+        out = torch.empty((V, H), dtype=torch.float32, device=X.device)
+    out, ldpre = _basis_matrix(who, out, V, H, "out", Qb.device, writable=True)
+    ws_ptr, ws_len, ws = _blockdiag_workspace(graph, C, D, H, 0, X.device)
+    a = _lib.BlockdiagForwardArgs()
+    a.struct_size = ctypes.sizeof(a)
+    a.graph, a.C, a.D, a.H = graph._h, C, D, H
+    a.Qb, a.X, a.ldX = Qb.data_ptr(), X.data_ptr(), ldX
+    a.edge_weight_by_dst = None if edge_weight is None else edge_weight.data_ptr()
+    a.node_scale = None if node_scale is None else node_scale.data_ptr()
+    a.pre, a.ldpre = out.data_ptr(), ldpre
+    a.workspace, a.workspace_bytes = ws_ptr, ws_len
+    stream = _stream()
+    with op_scope("blockdiag_forward", X, Qb, out):
+        _lib.check(_lib.load().tfgnn_blockdiag_forward(ctypes.byref(a), stream))
+    return out
+
+
+def blockdiag_backward(graph: "Graph", Qb: torch.Tensor, dPre: torch.Tensor, X: Optional[torch.Tensor], num_blocks: int, *,
+                       edge_weight_by_dst: Optional[torch.Tensor] = None, edge_weight_by_src: Optional[torch.Tensor] = None,
+                       node_scale: Optional[torch.Tensor] = None, want_dx: bool = True, want_dq: bool = True,
+                       out_dx: Optional[torch.Tensor] = None):
+    """The two reverse passes of ``blockdiag_forward`` (tfgnn_blockdiag_backward) -> (dX [V, D] or None, dQb [L, di, H] or None).
+    ``edge_weight_by_src`` is ``graph_scales``' (it carries the target's node scale); X is read for dQb only.  ``out_dx``: write
+    dX there (may be a column slice of a wider array)."""
+    who = "blockdiag_backward"
+    L, C, di, H, Qb = _blockdiag_common(who, graph, Qb, num_blocks, [("edge_weight_by_dst", edge_weight_by_dst),
+                                                                    ("edge_weight_by_src", edge_weight_by_src)], node_scale)
+    V, D = graph.num_nodes, C * di
+    dPre, lddPre = _basis_matrix(who, dPre, V, H, "dPre", Qb.device)
+    a = _lib.BlockdiagBackwardArgs()
+    a.struct_size = ctypes.sizeof(a)
+    a.graph, a.C, a.D, a.H = graph._h, C, D, H
+    a.Qb, a.dPre, a.lddPre = Qb.data_ptr(), dPre.data_ptr(), lddPre
+    dX = dQb = tables = None
+    num_chunks = 0
+    if want_dq:
+        if X is None:
+            raise ValueError(f"{who}: dQb needs X")
+        X, ldX = _basis_matrix(who, X, V, D, "X", Qb.device)
+        a.X, a.ldX = X.data_ptr(), ldX
+        dQb = torch.empty((L, di, H), dtype=torch.float32, device=Qb.device)
+        a.dQb = dQb.data_ptr()
+        tables = _blockdiag_tables(graph)
+        num_chunks = tables[4]
+        a.list_to_dst, a.chunk_first, a.chunk_count, a.type_chunk_ptr = (t.data_ptr() for t in tables[:4])
+        a.num_chunks = num_chunks
+    if want_dx:
+        dX = out_dx if out_dx is not None else torch.empty((V, D), dtype=torch.float32, device=Qb.device)
+        dX, lddX = _basis_matrix(who, dX, V, D, "out_dx", Qb.device, writable=True)
+        a.dX, a.lddX = dX.data_ptr(), lddX
+    a.edge_weight_by_dst = None if edge_weight_by_dst is None else edge_weight_by_dst.data_ptr()
+    a.edge_weight_by_src = None if edge_weight_by_src is None else edge_weight_by_src.data_ptr()
+    a.node_scale = None if node_scale is None else node_scale.data_ptr()
+    ws_ptr, ws_len, ws = _blockdiag_workspace(graph, C, D, H, num_chunks, Qb.device)
+    a.workspace, a.workspace_bytes = ws_ptr, ws_len
+    stream = _stream()
+    with op_scope("blockdiag_backward", dPre, X, Qb, dX, dQb):
+        _lib.check(_lib.load().tfgnn_blockdiag_backward(ctypes.byref(a), stream))
+    if dX is not None:
+        torch.autograd.graph.increment_version(dX)
+    return dX, dQb
+
+
+def blockdiag_launch_counts() -> dict:
+    """tfgnn_blockdiag_launch_counts: kernel launches of the block-diagonal forward and its two reverse passes so far."""
+    buf = (ctypes.c_int64 * 3)()
+    _lib.check(_lib.load().tfgnn_blockdiag_launch_counts(buf, 3))
+    return {"fwd": int(buf[0]), "dx": int(buf[1]), "dq": int(buf[2])}
+
+
 def mul(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     lib = _lib.load()
     a = a.contiguous()
