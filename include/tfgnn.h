@@ -208,6 +208,40 @@ int tfgnn_graph_scales(const tfgnn_graph* graph, int normalize_by_num_incoming, 
                        float* d_row_scale, float* d_node_scale, float* d_edge_weight_by_src,
                        float* d_edge_weight_by_dst, void* stream);
 
+/* The same three per-node / per-edge arrays for ONE TRAINING STEP WITH EDGE DROPOUT (Schlichtkrull et al. 2018, section 5.2:
+ * edges are dropped "before normalization", per layer and per step; DropEdge, Rong et al. 2020).  The layers that read the
+ * graph through these arrays alone (RGCN_Basis, RGCN_BlockDiag: tfgnn_basis_gather_*, tfgnn_blockdiag_*) take them in place
+ * of tfgnn_graph_scales' and change in nothing else; there is no row scale.
+ *   keep      the edge at position e of concat(adjacency_lists) - the id TFGNN_G_EID_BY_DST / _BY_SRC carry - of type l is
+ *             KEPT iff element e of the mask tfgnn_dropout_forward draws for (seed, d_rates[l]) at the current dropout epoch
+ *             is non-zero ("The dropout mask generator" below: the same key words, hash and epoch step; the threshold
+ *             ceil((double)rate * 2^24) is derived on the device from the float32 d_rates[l]).  The decision hangs on e, so
+ *             it is the same in both edge orders; rate 0 keeps every edge of the type.  d_rates [L] is DEVICE memory: the
+ *             entry reads nothing from the host.  A rate outside [0, 1) cannot be refused without a read-back and is
+ *             clamped: below 0 or NaN counts as 0, 1 or more drops every edge of the type.
+ *   counts    c'_{v,l} = kept edges of type l into v, N'_v = sum_l c'_{v,l} (integers).
+ *   d_node_scale [V]           m_v: mode 0: 1; mode 1: 1.f / max(N'_v, 1); mode 2: 1.f / sqrtf(max(N'_v, 1))
+ *   d_edge_weight_by_dst [E]   s_e: 0 for a dropped edge; for a kept one 1.f / ((float)c'_{v,l} + 1e-7f) with normalize, else
+ *                              1 in modes 1 and 2 (the kept count inside m_v divides), else - mode 0, a plain sum in which no
+ *                              count divides - the inverted-dropout factor 1.f / (1.f - d_rates[l]) of tfgnn_dropout_forward
+ *   d_edge_weight_by_src [E]   s'_e = s_e * m_target of the same edge, at its by-source position
+ * Where a count divides, it is the count of KEPT edges; where none does, kept edges carry 1 / (1 - p).  The float32
+ * expressions are tfgnn_graph_scales': with every rate 0 the three arrays equal its outputs bit for bit, and the values on the
+ * kept edges equal what tfgnn_graph_scales gives on the graph made of the kept edges.  A bucket or a node that lost every
+ * edge holds zeros / m_v = 1: no NaN, no Inf.
+ * Needs part EDGE_MAPS (the inverse of TFGNN_G_SRC2DST_POS carries s'_e to the by-source order; it implies EDGE_IDS) where
+ * E > 0 - tfgnn_graph_ensure it outside a capture.  ONE launch (none when V == 0), one wave per target node over the node's
+ * row of the by-target order, 64 edges at a time: no lane walks a row alone, integer counts, no atomics, no workspace, no
+ * allocation, no copy, no host synchronisation - capturable; every replay of a captured step reads the epoch word again.
+ * Refused before the launch: a NULL graph, an unknown mode, NULL outputs where V or E > 0, NULL d_rates where L > 0, a
+ * handle without the part. */
+int tfgnn_graph_scales_edge_dropout(const tfgnn_graph* graph, int normalize_by_num_incoming, int aggregation_mode,
+                                    const float* d_rates /* [L], device */, uint64_t seed,
+                                    float* d_node_scale /* [V] */, float* d_edge_weight_by_src /* [E] */,
+                                    float* d_edge_weight_by_dst /* [E] */, void* stream);
+/* host-side count of the launches the entry above has enqueued in this process: out[0]; further slots are zero */
+int tfgnn_edge_dropout_launch_counts(int64_t* out_counts, int n);
+
 /* Helper for use_target_state_as_input with a linear edge layer (gnn_edge_mlp.py:92-97):
  * sum_e s_e [x_u | x_v] W = (sum_e s_e x_u) W_s + k_{l,v} x_v W_t with k = c_{l,v} * row_scale.
  *   d_k [V*L], d_ident_ptr [V*L+1] = 0..V*L, d_node_of_row [V*L] = r / L                           */

@@ -424,6 +424,12 @@ _SIGNATURES += [
     ("tfgnn_blockdiag_backward", c_int, [c_void_p, c_void_p]),
     ("tfgnn_blockdiag_launch_counts", c_int, [POINTER(c_int64), c_int]),
 ]
+# edge dropout of the layers that read the graph through graph_scales' arrays (include/tfgnn.h, csrc/edge_dropout.hip)
+_SIGNATURES += [
+    ("tfgnn_graph_scales_edge_dropout", c_int,
+     [c_void_p, c_int, c_int, c_void_p, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("tfgnn_edge_dropout_launch_counts", c_int, [POINTER(c_int64), c_int]),
+]
 BLOCKDIAG_MAX_BLOCK = 64  # csrc/blockdiag.hip MAX_BLOCK: D / num_blocks and H / num_blocks at most
 BLOCKDIAG_CHUNK = 256  # csrc/blockdiag.hip DQ_CHUNK: list positions per chunk of dQb's first stage
 SAMPLE_MAX_HOPS = 8  # TFGNN_SAMPLE_MAX_HOPS

@@ -28,6 +28,9 @@ from .message_passing import MessagePassing, MessagePassingInput, get_message_pa
 from .message_passing.message_passing import Variable, _num_edge_types, default_device, get_graph, glorot_uniform
 
 
+_EDGE_DROPOUT_SEED_SALT = 0xED6E << 48  # keeps the edge dropout seeds of a stack apart from its layer-input dropout seeds
+
+
 class GNNInput(NamedTuple):
     """Input named tuple for the GNN (gnn.py:21-27)."""
 
@@ -98,6 +101,7 @@ class GNN:
         self.built = False
         self._ctx = None
         self._dropout_calls = 0
+        self._edge_dropout_calls = 0  # a count of its own: the seeds of the layer-input and exchange dropout stay what they were
         self.dropout_seed = 0
         # the spread-guard policy of the f16x2 mode (guard.py): which passes backward() checks, what a trip demotes
         self.guard = guard.GuardPolicy(self._advance_guard, sync_passes=int(ops.env("TFGNN_GUARD_SYNC_PASSES", "3")),
@@ -364,6 +368,9 @@ class GNN:
                           and not self._use_inter_layer_layernorm and self._dense_f16x2(self._hidden_dim, self._hidden_dim))
             # ... and the next layer's input dropout, when this layer's output goes straight into it
             direct = not (dense_here or has_ex or self._use_inter_layer_layernorm)
+            if training and getattr(mp_layer, "_edge_dropout_rates", None) is not None:  # edge dropout: one draw per layer and call
+                self._edge_dropout_calls += 1
+                mp_layer.edge_dropout_seed = _EDGE_DROPOUT_SEED_SALT ^ (self.dropout_seed * 1000003 + self._edge_dropout_calls)
             cur, dropped = mp_layer.call_with_epilogue(
                 MessagePassingInput(node_embeddings=cur, adjacency_lists=graph), training=training, want_split_output=want_split,
                 output_dropout=drop_for(layer_idx + 1, need_all_representations) if direct else None)

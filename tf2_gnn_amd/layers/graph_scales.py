@@ -53,6 +53,14 @@ def graph_scales(g: "ops.Graph", normalize: bool, aggregation: str) -> GraphScal
     return res
 
 
+def edge_dropout_scales(g: "ops.Graph", normalize: bool, aggregation: str, rates: torch.Tensor, seed: int) -> GraphScales:
+    """The scales of ONE training step with edge dropout (tfgnn_graph_scales_edge_dropout): dropped edges weigh 0, the counts
+    that divide are those of the kept edges, and where none divides kept edges carry 1 / (1 - rate).  Every call is a new draw,
+    so nothing is cached on the Graph; there is no row scale (the layers that take these read the per-edge weights)."""
+    node_scale, ew_s, ew_d = ops.graph_scales_edge_dropout(g, normalize, _AGG_MODE[aggregation], rates, seed)
+    return GraphScales(None, ew_d, ew_s, node_scale)
+
+
 def target_multiplier(g: "ops.Graph", row_scale):
     """-> (k [V*L], ident_ptr [V*L+1], node_of_row [V*L]) for the target-state term of a linear
     edge layer; cached per row_scale identity."""

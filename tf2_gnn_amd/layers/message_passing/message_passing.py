@@ -155,6 +155,24 @@ def clear_graph_cache():
     _GRAPH_CACHE.clear()
 
 
+_EDGE_DROPOUT_LAYERS = ("RGCN_Basis", "RGCN_BlockDiag")
+
+
+def _edge_dropout_rates(value, cls) -> Tuple[float, ...]:
+    """The hyper-parameter ``edge_dropout_rate`` (absent = 0.0: it is in no defaults dictionary, whose key sets and reprs the
+    tests of every layer pin and seed their weights from) - one float, or one per edge type - as a tuple of floats in [0, 1); a
+    non-zero rate on a layer class that does not read the graph through per-edge weights alone is refused, not ignored."""
+    rates = tuple(float(r) for r in value) if isinstance(value, (list, tuple)) else (float(value),)
+    for r in rates:
+        if not 0.0 <= r < 1.0:  # (NaN fails both comparisons)
+            raise ValueError(f"edge_dropout_rate: every rate must be in [0, 1), got {r!r}")
+    if any(r > 0.0 for r in rates) and not getattr(cls, "supports_edge_dropout", False):
+        raise ValueError(
+            f"{cls.__name__}: edge_dropout_rate = {value!r} is not supported: this layer's kernels normalise by the full in-degrees "
+            f"of the graph handle; the layers that take edge dropout are {' and '.join(_EDGE_DROPOUT_LAYERS)}")
+    return rates
+
+
 class MessagePassing:
     """Abstract class to compute new graph states by neural message passing
     (message_passing.py:20-218).
@@ -206,6 +224,10 @@ class MessagePassing:
         self._activation_fn = get_activation_function(activation_fn_name)
         self._activation_name = None if activation_fn_name is None else activation_fn_name.lower()
 
+        self._edge_dropout_rate = _edge_dropout_rates(params.get("edge_dropout_rate", 0.0), type(self))
+        self._edge_dropout_rates = None  # float32 device tensor [L], made by build() when any rate is non-zero
+        self.edge_dropout_seed = 0       # the seed of the next training call's draw (a GNN stack sets it per call)
+
         self.built = False
         self._variables: List[Variable] = []
         self._ctx = None  # saved tensors of the last recorded forward
@@ -232,6 +254,30 @@ class MessagePassing:
 
     def build(self, input_shapes: MessagePassingInput):
         self.built = True
+
+    # ---- edge dropout (layers with ``supports_edge_dropout``; include/tfgnn.h tfgnn_graph_scales_edge_dropout) ----------
+    supports_edge_dropout = False
+
+    def _build_edge_dropout(self, num_edge_types: int) -> None:
+        rates = self._edge_dropout_rate
+        if len(rates) == 1:
+            rates = rates * num_edge_types
+        elif len(rates) != num_edge_types:
+            raise ValueError(f"edge_dropout_rate: {len(rates)} rates for {num_edge_types} edge types (one float, or one per type)")
+        if any(r > 0.0 for r in rates):
+            self._edge_dropout_rates = torch.tensor(rates, dtype=torch.float32, device=default_device())
+
+    def _edge_dropout_parts(self) -> int:
+        """the graph part the dropped step's scales need (named at creation, it costs no second sort)"""
+        return ops.G_PART_EDGE_MAPS if any(r > 0.0 for r in self._edge_dropout_rate) else 0
+
+    def _step_scales(self, g: "ops.Graph", normalize: bool, training: bool):
+        """graph_scales of this call: the cached ones, or - training with a non-zero rate - one fresh draw of edge dropout"""
+        from ..graph_scales import edge_dropout_scales, graph_scales
+
+        if training and self._edge_dropout_rates is not None:
+            return edge_dropout_scales(g, normalize, self._aggregation_name, self._edge_dropout_rates, self.edge_dropout_seed)
+        return graph_scales(g, normalize, self._aggregation_name)
 
     def _build_for(self, inputs: MessagePassingInput):
         if not self.built:

@@ -5,7 +5,6 @@ from typing import Any, Dict
 import torch
 
 from ... import ops
-from ..graph_scales import graph_scales
 from .message_passing import (
     MessagePassing,
     MessagePassingInput,
@@ -32,6 +31,8 @@ class RGCN_Basis(MessagePassing):
     commutes with sum-like aggregation (sum, mean, sqrt_n) and an activation applied after it.
 
     Weights: ``basis_{b}/kernel`` - views of one [B*D, H] buffer - and ``relation_coefficients`` [L, B]."""
+
+    supports_edge_dropout = True
 
     @classmethod
     def get_default_hyperparameters(cls):
@@ -62,7 +63,7 @@ class RGCN_Basis(MessagePassing):
 
     def graph_parts(self, num_nodes: int, edges_per_type, in_dim: int) -> int:
         # the node views' plans (csrc/basis.hip); the typed plans stay named as the part every stack builds
-        return ops.G_PART_PLAN_TYPED | ops.G_PART_PLAN_NODE
+        return ops.G_PART_PLAN_TYPED | ops.G_PART_PLAN_NODE | self._edge_dropout_parts()
 
     def build(self, input_shapes: MessagePassingInput):
         D = int(input_shapes.node_embeddings[-1])
@@ -76,6 +77,7 @@ class RGCN_Basis(MessagePassing):
             self._basis_kernels.append(self.add_weight(f"basis_{b}/kernel", self._bases[b * D : (b + 1) * D]))
         self._coeff = glorot_uniform((L, B), device=dev)
         self._coefficients = self.add_weight("relation_coefficients", self._coeff)
+        self._build_edge_dropout(L)
         super().build(input_shapes)
 
     def _message_function(self, edge_source_states, edge_target_states, num_incoming_to_node_per_message,
@@ -100,7 +102,7 @@ class RGCN_Basis(MessagePassing):
             raise ValueError(f"layer was built for {self._num_edge_types} edge types, got {g.num_edge_types}")
         if self._bases.shape[0] != self._num_bases * D:
             raise ValueError(f"layer was built for inputs of width {self._bases.shape[0] // self._num_bases}, got {D}")
-        scales = graph_scales(g, self._normalize_by_num_incoming, self._aggregation_name)
+        scales = self._step_scales(g, self._normalize_by_num_incoming, training)
         Z = ops.basis_gather_forward(g, self._coeff, X, edge_weight=scales.edge_weight_by_dst, node_scale=scales.node_scale)
         act = self._activation_name
         ctx = {"graph": g, "X": X, "Z": Z, "scales": scales, "fused_act": act}

@@ -5,7 +5,6 @@ from typing import Any, Dict
 import torch
 
 from ... import ops
-from ..graph_scales import graph_scales
 from .message_passing import (
     MessagePassing,
     MessagePassingInput,
@@ -29,6 +28,8 @@ class RGCN_BlockDiag(MessagePassing):
     applied after it.  Block widths D/C and H/C of at most 64.
 
     Weight: ``block_kernels`` [L, D/C, H], the blocks banded: W_l[c*di + i, c*ho + j] = block_kernels[l, i, c*ho + j]."""
+
+    supports_edge_dropout = True
 
     @classmethod
     def get_default_hyperparameters(cls):
@@ -60,7 +61,7 @@ class RGCN_BlockDiag(MessagePassing):
     def graph_parts(self, num_nodes: int, edges_per_type, in_dim: int) -> int:
         # the node views' plans (csrc/blockdiag.hip) and the edge ids the weight gradient's type-major table inverts; the typed
         # plans stay named as the part every stack builds
-        return ops.G_PART_PLAN_TYPED | ops.G_PART_PLAN_NODE | ops.G_PART_EDGE_IDS
+        return ops.G_PART_PLAN_TYPED | ops.G_PART_PLAN_NODE | ops.G_PART_EDGE_IDS | self._edge_dropout_parts()
 
     def build(self, input_shapes: MessagePassingInput):
         D = int(input_shapes.node_embeddings[-1])
@@ -73,6 +74,7 @@ class RGCN_BlockDiag(MessagePassing):
         # Glorot-uniform per block [di, ho]: limit sqrt(6 / (di + ho))
         self._qb = glorot_uniform((L, di, H), fan_in=di, fan_out=ho, device=default_device())
         self._block_kernels = self.add_weight("block_kernels", self._qb)
+        self._build_edge_dropout(L)
         super().build(input_shapes)
 
     def dense_kernels(self) -> torch.Tensor:
@@ -107,7 +109,7 @@ class RGCN_BlockDiag(MessagePassing):
             raise ValueError(f"layer was built for {self._num_edge_types} edge types, got {g.num_edge_types}")
         if D != self._in_dim:
             raise ValueError(f"layer was built for inputs of width {self._in_dim}, got {D}")
-        scales = graph_scales(g, self._normalize_by_num_incoming, self._aggregation_name)
+        scales = self._step_scales(g, self._normalize_by_num_incoming, training)
         pre = ops.blockdiag_forward(g, self._qb, X, self._num_blocks, edge_weight=scales.edge_weight_by_dst,
                                     node_scale=scales.node_scale)
         act = self._activation_name

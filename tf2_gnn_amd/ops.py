@@ -1331,6 +1331,45 @@ def blockdiag_launch_counts() -> dict:
     return {"fwd": int(buf[0]), "dx": int(buf[1]), "dq": int(buf[2])}
 
 
+def graph_scales_edge_dropout(graph: "Graph", normalize: bool, aggregation_mode: int, rates: torch.Tensor, seed: int):
+    """One step's edge dropout (tfgnn_graph_scales_edge_dropout) -> (node_scale [V], edge_weight_by_src [E], edge_weight_by_dst
+    [E]): edge e of type l is kept iff element e of the mask ``dropout_forward`` draws for (seed, rates[l]) at the current
+    dropout epoch is non-zero; the counts that divide are those of the kept edges, and where none divides (``normalize`` False,
+    mode 0) kept edges carry 1 / (1 - rates[l]).  ``rates``: float32 device tensor [L], every rate in [0, 1) (the caller's to
+    validate: the kernel clamps).  Needs the handle's part EDGE_MAPS, which cannot be built inside a hipGraph capture."""
+    who = "graph_scales_edge_dropout"
+    _require_dev(rates, torch.float32, "rates")
+    L = graph.num_edge_types
+    if rates.dim() != 1 or rates.numel() != L or not rates.is_contiguous():
+        raise ValueError(f"{who}: rates must be a contiguous vector of {L} floats (one per edge type), got {tuple(rates.shape)}")
+    if rates.device != graph.device:
+        raise ValueError(f"{who}: rates live on {rates.device}, the graph on {graph.device}")
+    if aggregation_mode not in (0, 1, 2):
+        raise ValueError(f"{who}: aggregation_mode must be 0 (sum), 1 (mean) or 2 (sqrt_n), got {aggregation_mode!r}")
+    need = G_PART_EDGE_MAPS | G_PART_EDGE_IDS
+    if need & ~graph.parts:
+        if capturing():
+            raise RuntimeError("tf2_gnn_amd: edge dropout needs the graph's part EDGE_MAPS, which cannot be built inside a hipGraph "
+                               "capture (the build reads sizes back); run the step eagerly once on the same graph first "
+                               "(CapturedStep warmup), or name the part when the graph is made (GNN.graph_parts does)")
+        graph.ensure(need)
+    dev = graph.device
+    node_scale = torch.empty(graph.num_nodes, dtype=torch.float32, device=dev)
+    ew_s = torch.empty(graph.num_edges, dtype=torch.float32, device=dev)
+    ew_d = torch.empty(graph.num_edges, dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().tfgnn_graph_scales_edge_dropout(
+        graph._h, int(bool(normalize)), int(aggregation_mode), _ptr(rates), int(seed) & (2**64 - 1), _ptr(node_scale),
+        _ptr(ew_s), _ptr(ew_d), _stream()))
+    return node_scale, ew_s, ew_d
+
+
+def edge_dropout_launch_counts() -> dict:
+    """tfgnn_edge_dropout_launch_counts: launches of ``graph_scales_edge_dropout``'s kernel so far (host counter)."""
+    buf = (ctypes.c_int64 * 1)()
+    _lib.check(_lib.load().tfgnn_edge_dropout_launch_counts(buf, 1))
+    return {"edge_dropout_scales": int(buf[0])}
+
+
 def mul(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     lib = _lib.load()
     a = a.contiguous()
