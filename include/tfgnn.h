@@ -1194,6 +1194,60 @@ int tfgnn_distmult_rank(const float* d_H, int64_t ld_H, const float* d_R, const 
 int tfgnn_link_launch_counts(int64_t* out_counts, int n);
 
 /* ------------------------------------------------------------------------------------------
+ * Negative sampling and triple tables on the device (csrc/negatives.hip): what LinkPredictionDataset does per epoch on the
+ * host - draw the negatives, rebuild the triple tables - as calls on the caller's stream, so that a captured training step
+ * carries its own fresh negatives.  Integers only: no call does float arithmetic.  No call allocates or synchronises with
+ * the host; both are capturable.  Bad arguments are refused before any launch.  The kernels do not validate indices: the
+ * positives are validated on the host when they are loaded, the negatives are in range by construction.
+ *
+ * tfgnn_triples_draw_negatives: d_triples int32 [N, 3], N = P (1 + K); rows 0 .. P - 1 are the positives and are only read,
+ * rows P .. N - 1 are written, each whole row (u, t, v), so the buffer needs no initial content beyond the positives.
+ *   order     negative j (0 <= j < P K) copies positive j / K (np.repeat order) and replaces its source or its target with
+ *             a node drawn from the OTHER V - 1 nodes: exactly one slot differs, the relation is kept.  Negatives are not
+ *             filtered against known triples.
+ *   numbers   "The dropout mask generator" above, nothing else: with word(g) as defined there for (seed, epoch),
+ *               a = word(2 j), b = word(2 j + 1)        (2 j + 1 < 2^31: the high-word term h is always 0)
+ *               slot = the target if a >> 31, else the source
+ *               draw = ((uint64) b * (V - 1)) >> 32      (the multiply-high draw, in [0, V - 1))
+ *               new node = draw + (draw >= old node)     (skips the old node: in [0, V), never the old one)
+ *             Bias of the multiply-high draw: value d is taken by floor or ceil of 2^32 / (V - 1) of the 2^32 words b, so
+ *             every node's probability is within 2^-32 of 1 / (V - 1): a relative bias of at most (V - 1) / 2^32.
+ *   epoch     use_epoch != 0: the kernel reads the dropout epoch word once when it starts, like every kernel that draws a
+ *             mask, so a step replayed from a captured hipGraph after tfgnn_dropout_epoch_advance redraws at every replay.
+ *             use_epoch == 0: the word is ignored (the key of epoch 0): a fixed draw whatever the epoch.
+ * One launch; K == 0 (N == P) is accepted and launches nothing.  Refused: P < 1, N outside [1, 2^30], K < 0 or
+ * N != P (1 + K), NULL d_triples, V outside [1, 2^31), V < 2 with K > 0.
+ *
+ * tfgnn_triple_tables_build: the "Triple tables" above from DEVICE triples [N, 3] - exactly the arrays
+ * ops.build_triple_tables builds on the host: node_entries = the positions 2 e + role stably sorted by the node in that
+ * role, rel_order = the triple ids stably sorted by relation (ascending within a node / a relation), the offsets their row
+ * pointers, stored as unsigned words (node_offsets[V] = 2^31 at N = 2^30).  Either pair (d_node_offsets with
+ * d_node_entries, d_rel_offsets with d_rel_order) may be NULL, not both: a NULL pair is neither built nor touched.  The
+ * tables are a function of the triples alone: a stable LSD radix sort with 9-bit digits over per-tile histograms (the scheme
+ * of csrc/graph.hip), no global atomic, LDS integer atomics only for histogram counts.  A node that owns most of the entries
+ * is many equal keys of the sort, not a row some wave walks.
+ *   launches  passes(X) = max(1, ceil(ceil(log2 X) / 9)) digit passes for keys in [0, X), two launches each (histogram,
+ *             scatter), and one launch for the row pointers:
+ *               node pair 2 passes(V) + 1,  relation pair 2 passes(T) + 1,  both: the sum.   A function of (V, T) and of
+ *             which pairs are requested - not of N, not of the data.
+ *   workspace tfgnn_triple_tables_workspace_bytes(N, V, T) bytes (0 for sizes the build refuses), 16-byte aligned:
+ *             two key and two payload arrays of 2 N words and the [512][tiles] histogram table, tiles = ceil(2 N / 8192).
+ *             A scatter workgroup reads the table's tile columns up to its own, so a pass costs O(tiles^2) table words next to
+ *             the O(N) keys: 0.2 M words per workgroup at N = 1.4 M.
+ * Refused: N < 1 ("empty batch"), N > 2^30, V or T outside [1, 2^31), NULL d_triples, half a pair, both pairs NULL, a short
+ * or misaligned workspace.
+ *
+ * tfgnn_negatives_launch_counts: kernel launches so far of {tfgnn_triples_draw_negatives, tfgnn_triple_tables_build} (host
+ * counters; entries beyond the second are 0). */
+int tfgnn_triples_draw_negatives(int32_t* d_triples, int64_t N, int64_t P, int64_t K, int64_t V, uint64_t seed, int use_epoch,
+                                 void* stream);
+size_t tfgnn_triple_tables_workspace_bytes(int64_t N, int64_t V, int64_t T);
+int tfgnn_triple_tables_build(const int32_t* d_triples, int64_t N, int64_t V, int64_t T, int32_t* d_node_offsets,
+                              int32_t* d_node_entries, int32_t* d_rel_offsets, int32_t* d_rel_order, void* d_workspace,
+                              size_t workspace_bytes, void* stream);
+int tfgnn_negatives_launch_counts(int64_t* out_counts, int n);
+
+/* ------------------------------------------------------------------------------------------
  * Layer-level entry points (round 6): one call per message-passing layer and pass.
  * Replaces, for one layer, MessagePassing.call (message_passing.py:95-133) with
  * _calculate_messages_per_type (:181-218), GNN_Edge_MLP._message_function (gnn_edge_mlp.py:84-107) and

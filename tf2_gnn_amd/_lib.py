@@ -430,6 +430,16 @@ _SIGNATURES += [
      [c_void_p, c_int, c_int, c_void_p, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("tfgnn_edge_dropout_launch_counts", c_int, [POINTER(c_int64), c_int]),
 ]
+# negatives and triple tables of a link-prediction batch on the device (include/tfgnn.h, csrc/negatives.hip)
+_SIGNATURES += [
+    ("tfgnn_triples_draw_negatives", c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, ctypes.c_uint64, c_int, c_void_p]),
+    ("tfgnn_triple_tables_workspace_bytes", c_size_t, [c_int64, c_int64, c_int64]),
+    ("tfgnn_triple_tables_build", c_int,
+     [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    ("tfgnn_negatives_launch_counts", c_int, [POINTER(c_int64), c_int]),
+]
+TRIPLE_SORT_TILE = 8192  # csrc/negatives.hip TS_TILE: keys per workgroup of the table sort
+TRIPLE_SORT_DIGIT_BITS = 9  # csrc/negatives.hip TS_DIGIT_BITS
 BLOCKDIAG_MAX_BLOCK = 64  # csrc/blockdiag.hip MAX_BLOCK: D / num_blocks and H / num_blocks at most
 BLOCKDIAG_CHUNK = 256  # csrc/blockdiag.hip DQ_CHUNK: list positions per chunk of dQb's first stage
 SAMPLE_MAX_HOPS = 8  # TFGNN_SAMPLE_MAX_HOPS

@@ -26,7 +26,21 @@ A negative copies its positive and replaces the source or the target - a fair co
 other V - 1 nodes, so exactly one slot differs; it is not filtered against the known triples.  TRAIN draws its negatives
 anew from numpy's global generator at every ``iter()`` (where the other datasets draw the epoch's graph order, so
 np.random.seed seeds it), rebuilds the tables on the host and copies everything IN PLACE into the same device buffers - N is
-fixed - so a CapturedStep of a training step follows.  VALIDATION and TEST draw once, from a fixed seed."""
+fixed - so a CapturedStep of a training step follows.  VALIDATION and TEST draw once, from a fixed seed.
+
+``negative_sampling`` = "host" (the default, and what an absent key means) is the paragraph above.  With "device" the
+positives are uploaded once and everything after happens on the device: ``triple_batch`` draws the negatives with
+ops.draw_negative_triples (the dropout mask generator's numbers, include/tfgnn.h tfgnn_triples_draw_negatives - not numpy's,
+so the two routes draw different negatives of the same distribution) and builds the tables with
+ops.build_triple_tables_device; the relation tables are built once, since a negative keeps its relation.  VALIDATION and TEST
+draw once from their fixed seed with the dropout epoch ignored.  A TRAIN batch additionally carries
+``batch_features["triple_sampler"]`` (a ``DeviceTripleSampler``), whose ``redraw()`` LinkPredictionTask calls at the start of
+every training step's task part: the draw and the node tables, in place, on the current stream, no allocation and no host
+synchronisation.  Such a sampled batch IS capturable: a CapturedStep of ``_run_step(features, labels, training=True)`` trains
+on new negatives at every ``replay()`` - the draw follows the dropout epoch word the captured step advances - with no
+``next(iter(train))`` in between.  The draw's 64-bit seed is (``negative_sampling_seed`` << 32) | (draws & 0xFFFFFFFF),
+``draws`` counting the sampler's ``redraw()`` calls on the host: eager steps differ through the counter, replays of one
+captured step through the epoch word."""
 from __future__ import annotations
 
 from pathlib import Path
@@ -73,6 +87,29 @@ def _filter_csr(positives: np.ndarray, known: np.ndarray, slot: int, num_nodes: 
     return offsets.astype(np.int32), pairs[take, 1].astype(np.int32)
 
 
+class DeviceTripleSampler:
+    """The TRAIN negatives of the "device" route: ``redraw()`` overwrites the negatives of ``triples`` and the node tables in
+    place, on the current stream (one draw launch and the node pair's table launches; capturable).  ``draws`` counts the calls
+    on the host, ``seed_of_last_draw`` is the 64-bit seed the last one passed; together with the dropout epoch the kernel read
+    it determines the negatives (tests/negative_sample_reference.py restates them)."""
+
+    def __init__(self, triples: torch.Tensor, tables: Dict[str, torch.Tensor], num_positives: int, num_nodes: int,
+                 num_relations: int, seed: int, workspace: torch.Tensor):
+        self.triples, self.tables, self.workspace = triples, tables, workspace
+        self.num_positives, self.num_nodes, self.num_relations = int(num_positives), int(num_nodes), int(num_relations)
+        self.seed = int(seed)
+        self.draws = 0
+        self.seed_of_last_draw: Optional[int] = None
+
+    def redraw(self) -> None:
+        seed = (self.seed << 32) | (self.draws & 0xFFFFFFFF)
+        ops.draw_negative_triples(self.triples, self.num_positives, self.num_nodes, seed, use_epoch=True)
+        ops.build_triple_tables_device(self.triples, self.num_nodes, self.num_relations, out=self.tables, node=True, rel=False,
+                                       workspace=self.workspace)
+        self.seed_of_last_draw = seed
+        self.draws += 1
+
+
 class _LinkBatches:
     """What ``LinkPredictionDataset.get_batches`` returns: every ``iter()`` is one epoch of the fold's single batch."""
 
@@ -85,8 +122,9 @@ class _LinkBatches:
         assert plan.batches == [(0, 1)]
         features, labels = assemble_batch(plan, 0, 1, bad_flag=plan.bad_flags[0:1])
         triple_part = ds.triple_batch(fold, plan.store.device)
-        labels.update(triple_part)
-        features.update({k: triple_part[k] for k in ("triples", "triple_labels", "triple_weights", "triple_tables")})
+        labels.update({k: v for k, v in triple_part.items() if k != "triple_sampler"})
+        features.update({k: triple_part[k] for k in ("triples", "triple_labels", "triple_weights", "triple_tables", "triple_sampler")
+                         if k in triple_part})
         yield features, labels
 
 
@@ -99,6 +137,8 @@ class LinkPredictionDataset(GraphDataset):
             "add_self_loop_edges": True,
             "tie_fwd_bkwd_edges": False,
             "num_negatives_per_positive": 1,
+            "negative_sampling": "host",  # or "device": negatives and tables on the device, redrawn per training step
+            "negative_sampling_seed": 0,
         })
         return hypers
 
@@ -108,6 +148,13 @@ class LinkPredictionDataset(GraphDataset):
 
     def __init__(self, params: Dict[str, Any], metadata: Optional[Dict[str, Any]] = None, **kwargs):
         super().__init__(params, metadata=metadata, **kwargs)
+        self._negative_sampling = params.get("negative_sampling", "host")
+        if self._negative_sampling not in ("host", "device"):
+            raise ValueError(f"negative_sampling must be 'host' or 'device', not {self._negative_sampling!r}")
+        seed = params.get("negative_sampling_seed", 0)
+        if not isinstance(seed, (int, np.integer)) or isinstance(seed, bool) or not 0 <= seed < 2 ** 32:
+            raise ValueError(f"negative_sampling_seed must be an integer in [0, 2^32), not {seed!r}")
+        self._negative_sampling_seed = int(seed)
         self._num_fwd_edge_types: Optional[int] = None
         self._num_nodes = 0
         self._positives: Dict[DataFold, np.ndarray] = {}
@@ -263,6 +310,12 @@ class LinkPredictionDataset(GraphDataset):
         if buffers is not None and data_fold != DataFold.TRAIN:
             return buffers
         V, T = self._num_nodes, self._num_fwd_edge_types
+        if self._negative_sampling == "device":
+            if buffers is None:
+                buffers = self._triple_buffers[key] = self._device_triple_buffers(data_fold, dev)
+            else:  # TRAIN: new negatives and node tables, as every iter() of the host route
+                buffers["triple_sampler"].redraw()
+            return buffers
         triples = self.draw_triples(data_fold)
         tables = ops.build_triple_tables(triples, V, T)
         if buffers is None:
@@ -283,6 +336,38 @@ class LinkPredictionDataset(GraphDataset):
             buffers["triples"].copy_(torch.from_numpy(triples))
             for name in ops.TRIPLE_TABLE_NAMES:
                 buffers["triple_tables"][name].copy_(torch.from_numpy(tables[name]))
+        return buffers
+
+    def _device_triple_buffers(self, data_fold: DataFold, dev: torch.device) -> Dict[str, Any]:
+        """The "device" route's buffers of a fold, first draw and all four tables included: the positives are uploaded, the
+        rest is written by kernels."""
+        V, T, K = self._num_nodes, self._num_fwd_edge_types, int(self.params["num_negatives_per_positive"])
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        pos = self._positives[data_fold]
+        P = pos.shape[0]
+        N = P * (1 + K)
+        triples = torch.empty((N, 3), dtype=torch.int32, device=dev)
+        triples[:P].copy_(torch.from_numpy(pos))
+        labels = np.zeros(N, dtype=np.float32)
+        labels[:P] = 1.0
+        sizes = {"node_offsets": V + 1, "node_entries": 2 * N, "rel_offsets": T + 1, "rel_order": N}
+        tables = {name: torch.empty(sizes[name], dtype=torch.int32, device=dev) for name in ops.TRIPLE_TABLE_NAMES}
+        workspace = ops.triple_tables_workspace(N, V, T, device=dev)
+        buffers = {
+            "triples": triples,
+            "triple_labels": up(labels),
+            "triple_weights": up(np.ones(N, dtype=np.float32)),
+            "triple_tables": tables,
+            "positive_triples": up(pos),
+            "rank_filters": {side: (up(off), up(ids)) for side, (off, ids) in self._filters[data_fold].items()},
+        }
+        if data_fold == DataFold.TRAIN:
+            sampler = buffers["triple_sampler"] = DeviceTripleSampler(triples, tables, P, V, T, self._negative_sampling_seed, workspace)
+            sampler.redraw()
+            ops.build_triple_tables_device(triples, V, T, out=tables, node=False, rel=True, workspace=workspace)  # once
+        else:
+            ops.draw_negative_triples(triples, P, V, _EVAL_NEGATIVES_SEED[data_fold], use_epoch=False)
+            ops.build_triple_tables_device(triples, V, T, out=tables, workspace=workspace)
         return buffers
 
     def get_batches(self, data_fold: DataFold, device=None) -> _LinkBatches:

@@ -1814,6 +1814,91 @@ def link_launch_counts() -> dict:
     return {"distmult_fwd": int(buf[0]), "distmult_bwd": int(buf[1]), "distmult_rank": int(buf[2])}
 
 
+def _device_triples(triples: torch.Tensor, what: str) -> int:
+    _require_dev(triples, torch.int32, what)
+    if triples.dim() != 2 or triples.shape[1] != 3 or not triples.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous int32 [N, 3], got {tuple(triples.shape)}")
+    return triples.shape[0]
+
+
+def draw_negative_triples(triples: torch.Tensor, num_positives: int, V: int, seed: int, use_epoch: bool = True) -> torch.Tensor:
+    """tfgnn_triples_draw_negatives, in place: ``triples`` int32 [N, 3] on the device holds P = ``num_positives`` positives in
+    its first rows and N = P (1 + K); rows P .. N - 1 are written with K negatives per positive, in np.repeat order, each its
+    positive with the source or the target replaced by one of the other V - 1 nodes (include/tfgnn.h states the random
+    numbers: the dropout mask generator's words for ``seed`` and - ``use_epoch`` - the current dropout epoch).  One launch on
+    the current stream, capturable; K = 0 launches nothing.  Returns ``triples``."""
+    N = _device_triples(triples, "triples")
+    P = int(num_positives)
+    if P < 1 or N % P:
+        raise ValueError(f"triples [{N}, 3] are not P (1 + K) rows for P = {P} positives")
+    _lib.check(_lib.load().tfgnn_triples_draw_negatives(_ptr(triples), N, P, N // P - 1, int(V), int(seed) & (2 ** 64 - 1),
+                                                        int(bool(use_epoch)), _stream()))
+    torch.autograd.graph.increment_version(triples)  # written through a raw pointer, which torch does not see
+    return triples
+
+
+def triple_tables_workspace(triples_or_N, V: int, T: int, device=None) -> torch.Tensor:
+    """A workspace of tfgnn_triple_tables_workspace_bytes(N, V, T) bytes for ``build_triple_tables_device`` - to be allocated
+    once by a caller whose builds are captured into a hipGraph."""
+    N = triples_or_N.shape[0] if isinstance(triples_or_N, torch.Tensor) else int(triples_or_N)
+    if device is None:
+        device = triples_or_N.device if isinstance(triples_or_N, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
+    return torch.empty(max(int(_lib.load().tfgnn_triple_tables_workspace_bytes(N, int(V), int(T))), 16), dtype=torch.uint8, device=device)
+
+
+def build_triple_tables_device(triples: torch.Tensor, V: int, T: int, out: Optional[Dict[str, torch.Tensor]] = None,
+                               node: bool = True, rel: bool = True, workspace: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """``build_triple_tables`` on the device (tfgnn_triple_tables_build): from DEVICE triples int32 [N, 3] - taken as validated,
+    like every device triple array - the same int32 tables, bit for bit, as device tensors.  ``node`` / ``rel``: which pair to
+    build (node_offsets + node_entries, rel_offsets + rel_order); a pair that is not requested is neither built nor touched.
+    ``out``: a dict of the tables to write into (the requested names; others are ignored) - else new tensors; the result holds
+    the requested names only.  ``workspace``: a uint8 tensor of ``triple_tables_workspace``'s size; without one the stream's
+    shared workspace is used, which may allocate - pass one when the call is captured.  2 passes(V) + 1 launches for the node
+    pair, 2 passes(T) + 1 for the relation pair (include/tfgnn.h), on the current stream; no host synchronisation."""
+    lib = _lib.load()
+    N = _device_triples(triples, "triples")
+    if not (node or rel):
+        raise ValueError("build_triple_tables_device: neither the node pair nor the relation pair is requested")
+    V, T = int(V), int(T)
+    dev = triples.device
+    sizes = {"node_offsets": V + 1, "node_entries": 2 * N, "rel_offsets": T + 1, "rel_order": N}
+    wanted = (("node_offsets", "node_entries") if node else ()) + (("rel_offsets", "rel_order") if rel else ())
+    tabs: Dict[str, Optional[torch.Tensor]] = dict.fromkeys(TRIPLE_TABLE_NAMES)
+    for name in wanted:
+        if out is not None:
+            t = out[name]
+            _require_dev(t, torch.int32, name)
+            if t.dim() != 1 or t.shape[0] != sizes[name] or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"{name} {tuple(t.shape)} must be a contiguous int32 [{sizes[name]}] on {dev}")
+        else:
+            t = torch.empty(sizes[name], dtype=torch.int32, device=dev)
+        tabs[name] = t
+    need = int(lib.tfgnn_triple_tables_workspace_bytes(N, V, T))
+    if workspace is None:
+        workspace = _workspace(dev, need)
+    else:
+        _require_dev(workspace, torch.uint8, "workspace")
+    _lib.check(lib.tfgnn_triple_tables_build(_ptr(triples), N, V, T, _ptr(tabs["node_offsets"]), _ptr(tabs["node_entries"]),
+                                             _ptr(tabs["rel_offsets"]), _ptr(tabs["rel_order"]), _ptr(workspace),
+                                             workspace.numel(), _stream()))
+    if out is not None:
+        for name in wanted:
+            torch.autograd.graph.increment_version(tabs[name])
+    return {name: tabs[name] for name in wanted}
+
+
+def triple_table_passes(X: int) -> int:
+    """passes(X) of include/tfgnn.h: 9-bit digit passes of the table sort for keys in [0, X)"""
+    return max(1, -(-max(int(X) - 1, 0).bit_length() // _lib.TRIPLE_SORT_DIGIT_BITS))
+
+
+def negatives_launch_counts() -> dict:
+    """tfgnn_negatives_launch_counts: kernel launches of the draws and of the table builds so far (host counters)."""
+    buf = (ctypes.c_int64 * 2)()
+    _lib.check(_lib.load().tfgnn_negatives_launch_counts(buf, 2))
+    return {"draw_negatives": int(buf[0]), "triple_tables": int(buf[1])}
+
+
 # ---- split-operand ("f16x2") products: include/tfgnn.h tfgnn_sp_*, csrc/gemm_sp.hip ------------------------------
 class SplitOperand:
     """An fp32 matrix [rows, cols] in the SP16 operand format: ``data`` uint8 [rows, 4 * cols] (per row and 16 columns

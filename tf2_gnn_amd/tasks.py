@@ -367,7 +367,9 @@ class LinkPredictionTask(GraphTaskModel):
     (scores, loss, counts, d loss / d score) and ``compute_task_metrics`` on that output with the same label tensor reuses its
     results; otherwise it runs the kernel again on the node representations of the last forward pass.  Triples, labels,
     weights and tables are read from device memory by the kernels, so a captured step follows in-place changes (new
-    negatives) of all of them."""
+    negatives) of all of them.  A training step on a batch that carries ``triple_sampler`` (LinkPredictionDataset with
+    ``negative_sampling = "device"``) first calls its ``redraw()``: the negatives and the node tables are rewritten on the
+    device as part of the step, and of every replay of a captured one.  Inference never redraws."""
 
     def __init__(self, params: Dict[str, Any], dataset: Any = None, name: Optional[str] = None, *,
                  num_edge_types: Optional[int] = None, num_relations: Optional[int] = None):
@@ -404,6 +406,9 @@ class LinkPredictionTask(GraphTaskModel):
                 "weights": weights}
 
     def compute_task_output(self, batch_features, final_node_representations, training: bool):
+        sampler = batch_features.get("triple_sampler")
+        if training and sampler is not None:  # negative_sampling = "device": new negatives and node tables, in place, on this stream
+            sampler.redraw()
         h = self._final(final_node_representations)
         triples = batch_features["triples"]
         labels = batch_features.get("triple_labels")
