@@ -1529,6 +1529,12 @@ int64_t tfgnn_optimizer_launch_count(void);
  * zero, edge buffers that are not 8-byte aligned, a negative num_node_columns, a NULL node column table when there are node
  * columns, a node column width < 1 or >= 2^31, a NULL node column when num_nodes > 0.  More than TFGNN_BATCH_MAX_EDGE_TYPES
  * types, TFGNN_BATCH_MAX_COLUMNS columns or TFGNN_BATCH_MAX_NODE_COLUMNS node columns: TFGNN_ERR_UNSUPPORTED.
+ * More than TFGNN_BATCH_MAX_EDGE_TYPES types: the caller chunks.  An edge tile reads pos_node_ptr and node_ptr, never
+ * num_nodes, so a call with num_nodes = 0, num_columns = 0, num_node_columns = 0 and G > 0 launches edge tiles only (the
+ * node outputs may be NULL; feature_dim still has to be >= 1).  A batch of L types is ceil(L / 48) calls on one stream with
+ * the same bad_flag: the first carries the features, the columns, the node columns and types [0, 48), every further one the
+ * next 48 types alone, its tables being the full tables advanced by 48 k entries.  The calls write disjoint outputs, so no
+ * order between them matters; a call whose types are all empty launches nothing.  (data/graph_dataset.py assemble_batch.)
  * The node column fields were appended behind bad_flag: no earlier field moved, and struct_size tells a caller built against
  * the shorter struct apart.
  * ------------------------------------------------------------------------------------------ */
@@ -1888,6 +1894,30 @@ int tfgnn_blockdiag_backward(const tfgnn_blockdiag_backward_args* args, void* st
 /* host-side counts of the kernel launches enqueued in this process: out[0] forward ("fwd"), out[1] dX ("dx"), out[2] dQb
  * ("dq"), combining / reducing launches included; further slots are zero */
 int tfgnn_blockdiag_launch_counts(int64_t* out_counts, int n);
+
+/* ------------------------------------------------------------------------------------------
+ * Node embeddings (csrc/embedding.hip): the gradient of a row lookup with DISTINCT ids, written as a dense table gradient.
+ * The lookup itself is tfgnn_gather_node_rows.
+ *
+ *   table_grad[r, 0:D] = rows[i, 0:D]   if ids[i] == r for some i < n
+ *                      = 0              otherwise,                        for every r < N
+ *
+ * rows fp32 [n, D] with row pitch ld_rows, ids int32 [n], table_grad fp32 [N, D] with row pitch ld_grad (pitches in floats).
+ * Columns >= D of a pitched row are not touched.  An id outside [0, N) skips its row and sets *bad_flag (nullable, zeroed by
+ * the caller).  The ids are distinct by precondition - the neighbour sampler guarantees it (TFGNN_SAMPLE_REPEATED_SEED) -;
+ * with a repeated id ONE of its rows is written, which one is unspecified, and nothing else is affected.
+ *
+ * At most two launches on `stream`: a fill of all N rows and a scatter of the n rows; one (the fill) for n == 0, none for
+ * N == 0.  No allocation, no copy, no synchronisation, no atomics: capturable.  Consecutive lanes work on consecutive floats
+ * of a row, the rule of tfgnn_batch_assemble: float4 when D % 4 == 0, both buffers are 16-byte aligned and both pitches are
+ * multiples of 4; clamp(8192 / D, 1, 256) rows to a workgroup.  Element offsets are 64-bit: N * D may pass 2^31.
+ * Rejected on the host before any HIP call: negative sizes, D < 1 or >= 2^31, a pitch below D, N >= 2^31, n > N, a NULL
+ * table_grad when N > 0, NULL rows or ids when n > 0.
+ * ------------------------------------------------------------------------------------------ */
+int tfgnn_embedding_scatter_rows(const float* rows, int64_t ld_rows, const int32_t* ids, int64_t n, int64_t D,
+                                 float* table_grad, int64_t ld_grad, int64_t N, int* bad_flag, void* stream);
+/* host-side count of the kernel launches tfgnn_embedding_scatter_rows has enqueued in this process (tests) */
+int64_t tfgnn_embedding_launch_count(void);
 
 #ifdef __cplusplus
 }

@@ -438,6 +438,12 @@ _SIGNATURES += [
      [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     ("tfgnn_negatives_launch_counts", c_int, [POINTER(c_int64), c_int]),
 ]
+# node embeddings: the dense table gradient of a row lookup with distinct ids (include/tfgnn.h, csrc/embedding.hip)
+_SIGNATURES += [
+    ("tfgnn_embedding_scatter_rows", c_int,
+     [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    ("tfgnn_embedding_launch_count", c_int64, []),
+]
 TRIPLE_SORT_TILE = 8192  # csrc/negatives.hip TS_TILE: keys per workgroup of the table sort
 TRIPLE_SORT_DIGIT_BITS = 9  # csrc/negatives.hip TS_DIGIT_BITS
 BLOCKDIAG_MAX_BLOCK = 64  # csrc/blockdiag.hip MAX_BLOCK: D / num_blocks and H / num_blocks at most

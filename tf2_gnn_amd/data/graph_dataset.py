@@ -8,7 +8,13 @@ host, ``FoldStore`` on the device) - and a batch is a range of positions of an e
     node count over ``max_nodes_per_batch`` starts a new batch, graph_dataset.py:167-171) on the host counts, and uploads
     the order and the prefix sums of the node and edge counts along it in ONE copy ([L + 2, P + 1] int32);
   * ``assemble_batch`` is one library call (tfgnn_batch_assemble, csrc/batch.hip: one launch) per batch: no host-to-device
-    copy, no synchronisation.
+    copy, no synchronisation.  A fold of more than 48 edge types (``_lib.BATCH_MAX_EDGE_TYPES``, the call's limit) takes
+    ceil(L / 48) calls: the first with the node arrays, the columns and types [0, 48), every further one with the next 48
+    types alone - same stream, same flag, still no copy, synchronisation or extra allocation.
+
+A fold may be FEATURELESS (``PackedFold.features`` of width 0: knowledge-graph entities, whose representation a task model
+learns - ``node_embedding_dim``, tasks.py).  The C entries need a feature width >= 1, so the store keeps one placeholder
+column of zeros; a batch exposes ``node_features`` as a float32 [V, 0] view of what the call wrote.
 
 ``GraphDataset.get_batches(fold)`` stands where the reference has ``get_tensorflow_dataset``: a re-iterable whose every
 ``iter()`` is one epoch of ``(batch_features, batch_labels)`` in the form run_one_epoch / predict / evaluate_model consume.
@@ -202,17 +208,18 @@ class FoldStore:
     reads nothing back."""
 
     def __init__(self, fold: PackedFold, device=None):
-        if fold.features.shape[1] < 1:
-            raise ValueError("a fold store needs node features of width >= 1")
-        if fold.num_edge_types > _lib.BATCH_MAX_EDGE_TYPES or len(fold.columns) > _lib.BATCH_MAX_COLUMNS:
-            raise ValueError(f"at most {_lib.BATCH_MAX_EDGE_TYPES} edge types and {_lib.BATCH_MAX_COLUMNS} per-graph columns")
+        if len(fold.columns) > _lib.BATCH_MAX_COLUMNS:  # (edge types: any number, assemble_batch chunks them)
+            raise ValueError(f"at most {_lib.BATCH_MAX_COLUMNS} per-graph columns")
         if len(fold.node_columns) > _lib.BATCH_MAX_NODE_COLUMNS:
             raise ValueError(f"at most {_lib.BATCH_MAX_NODE_COLUMNS} node columns")
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.fold = fold
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
         self.node_ptr = up(fold.node_ptr.astype(np.int32))
-        self.features = up(fold.features)
+        self.featureless = fold.features.shape[1] == 0
+        # a featureless fold: one placeholder column of zeros, the C entry needs a width >= 1 (see the module docstring)
+        self.features = (torch.zeros((fold.features.shape[0], 1), dtype=torch.float32, device=self.device) if self.featureless
+                         else up(fold.features))
         self.edge_ptr = [up(p.astype(np.int32)) for p in fold.edge_ptr]
         self.edges = [up(e) for e in fold.edges]
         self.column_names = list(fold.columns)
@@ -238,13 +245,15 @@ class FoldStore:
 
     @property
     def feature_dim(self) -> int:
+        """The width of the stored feature rows: 1, the placeholder's, for a featureless fold."""
         return int(self.features.shape[1])
 
     def sample(self, i: int) -> GraphSample:
         """Graph i read back from the device arrays (a few small copies: for checks, not for the hot path)."""
         ptr = self.fold.node_ptr
         adj = [e[int(p[i]):int(p[i + 1])].cpu().numpy() for e, p in zip(self.edges, self.fold.edge_ptr)]
-        return GraphSample(adj, None, self.features[int(ptr[i]):int(ptr[i + 1])].cpu().numpy())
+        feats = self.features[int(ptr[i]):int(ptr[i + 1]), :self.fold.features.shape[1]]
+        return GraphSample(adj, None, feats.cpu().numpy())
 
 
 def plan_batches(node_counts_in_order: np.ndarray, max_nodes_per_batch: int) -> List[Tuple[int, int]]:
@@ -317,9 +326,11 @@ def _carve(sizes: Sequence[int], dtype, device) -> List[torch.Tensor]:
 def assemble_batch(plan: EpochPlan, p0: int, p1: int, out: Optional[Dict[str, Any]] = None,
                    bad_flag: Optional[torch.Tensor] = None) -> Tuple[Dict[str, Any], Dict[str, Any]]:
     """The batch of positions [p0, p1) of ``plan`` -> (batch_features, batch_labels), by one tfgnn_batch_assemble call on the
-    current stream.  ``out`` may bring the output tensors (node_features [V, F], node_to_graph_map [V], adjacency_list_<t>
-    [E_t, 2], one [G] per column name, one [V, W] per node column name), ``bad_flag`` a zeroed int32 [1]; what is missing is
-    allocated here (two allocations).  The node columns come back in ``batch_labels`` next to the per-graph columns."""
+    current stream - ceil(L / 48) calls for a fold of L > 48 edge types, the further ones carrying edge types only.  ``out``
+    may bring the output tensors (node_features [V, F], node_to_graph_map [V], adjacency_list_<t> [E_t, 2], one [G] per column
+    name, one [V, W] per node column name), ``bad_flag`` a zeroed int32 [1]; what is missing is allocated here (two
+    allocations).  The node columns come back in ``batch_labels`` next to the per-graph columns.  A featureless store: F = 1
+    for ``out`` (the placeholder column), and the batch's ``node_features`` is the [V, 0] view of it."""
     store = plan.store
     L, C, F = store.num_edge_types, len(store.columns), store.feature_dim
     NC, widths = len(store.node_columns), store.node_column_widths
@@ -355,27 +366,42 @@ def assemble_batch(plan: EpochPlan, p0: int, p1: int, out: Optional[Dict[str, An
             raise ValueError(f"the {name} output must be a contiguous float32 [{V}, {w}]")
     a = _lib.BatchAssembleArgs()
     a.struct_size = ctypes.sizeof(_lib.BatchAssembleArgs)
-    a.num_edge_types, a.num_columns = L, C
+    a.num_columns = C
     a.num_graphs, a.store_nodes, a.feature_dim = store.num_graphs, int(store.features.shape[0]), F
     a.node_ptr, a.features = store.node_ptr.data_ptr(), store.features.data_ptr()
-    a.edge_ptr = ctypes.addressof(store._edge_ptr_tab)
-    a.edges = ctypes.addressof(store._edges_tab)
     a.columns = ctypes.addressof(store._columns_tab)
     a.order_len = plan.order.shape[0]
     a.order, a.pos_node_ptr = plan.device_arrays[0].data_ptr(), plan.device_arrays[1].data_ptr()
-    a.pos_edge_ptr = ctypes.addressof(plan._pos_edge_ptr_tab)
     a.p0, a.p1, a.num_nodes = p0, p1, V
     num_edges = (ctypes.c_int64 * max(L, 1))(*E)
     adj_tab = (ctypes.c_void_p * max(L, 1))(*[t.data_ptr() for t in adj])
     col_tab = (ctypes.c_void_p * max(C, 1))(*[t.data_ptr() for t in cols])
-    a.num_edges, a.adjacency_lists, a.column_out = ctypes.addressof(num_edges), ctypes.addressof(adj_tab), ctypes.addressof(col_tab)
+    a.column_out = ctypes.addressof(col_tab)
+
+    def edge_types_from(t0: int) -> None:
+        """the call's edge types: [t0, t0 + 48) of the fold's, every table advanced by t0 entries of 8 bytes (pointers, int64)"""
+        a.num_edge_types = min(L - t0, _lib.BATCH_MAX_EDGE_TYPES)
+        a.edge_ptr = ctypes.addressof(store._edge_ptr_tab) + 8 * t0
+        a.edges = ctypes.addressof(store._edges_tab) + 8 * t0
+        a.pos_edge_ptr = ctypes.addressof(plan._pos_edge_ptr_tab) + 8 * t0
+        a.num_edges, a.adjacency_lists = ctypes.addressof(num_edges) + 8 * t0, ctypes.addressof(adj_tab) + 8 * t0
+
+    edge_types_from(0)
     a.node_features, a.node_to_graph_map, a.bad_flag = nf.data_ptr(), n2g.data_ptr(), bad_flag.data_ptr()
     if NC:  # without node columns the four fields stay zero
         node_col_tab = (ctypes.c_void_p * NC)(*[t.data_ptr() for t in node_cols])
         a.num_node_columns = NC
         a.node_column_widths = ctypes.addressof(store._node_column_widths_tab)
         a.node_columns, a.node_column_out = ctypes.addressof(store._node_columns_tab), ctypes.addressof(node_col_tab)
-    _lib.check(_lib.load().tfgnn_batch_assemble(ctypes.byref(a), ops._stream()))
+    lib, stream = _lib.load(), ops._stream()
+    _lib.check(lib.tfgnn_batch_assemble(ctypes.byref(a), stream))
+    if L > _lib.BATCH_MAX_EDGE_TYPES:  # the types beyond the call's limit: calls that launch edge tiles only
+        a.num_nodes = a.num_columns = a.num_node_columns = 0
+        for t0 in range(_lib.BATCH_MAX_EDGE_TYPES, L, _lib.BATCH_MAX_EDGE_TYPES):
+            edge_types_from(t0)
+            _lib.check(lib.tfgnn_batch_assemble(ctypes.byref(a), stream))
+    if store.featureless:
+        nf = nf[:, :0]  # float32 [V, 0]
     features: Dict[str, Any] = {"node_features": nf, "node_to_graph_map": n2g, "num_graphs_in_batch": G}
     for t in range(L):
         features[f"adjacency_list_{t}"] = adj[t]

@@ -2,7 +2,10 @@
 over the SAME node set (FB15k / WN18 style, the second experiment of the R-GCN paper).  The reference has no such dataset.
 
 A data directory holds numpy files only:
-  ``node_features.npy`` [V, F];
+  ``node_features.npy`` [V, F] - optional: without it the dataset is FEATURELESS (knowledge-graph entities have no features;
+  ``node_feature_shape`` is (0,), a batch's ``node_features`` a float32 [V, 0], and a task model needs the hyper-parameter
+  ``node_embedding_dim``, tasks.py), with V from the optional scalar ``num_nodes.npy``, else the largest node id in any edge
+  file plus one;
   ``edges.npy`` [E, 2] (one forward edge type) or ``edges_0.npy``, ``edges_1.npy``, ... (one file per forward edge type),
   (source, target) pairs: the message-passing graph, and at the same time the TRAIN positives;
   ``valid_edges_<t>.npy`` / ``test_edges_<t>.npy`` (``valid_edges.npy`` / ``test_edges.npy`` with a single type): the
@@ -13,7 +16,8 @@ self-loop types message passing adds.  TRAIN positives are edges of the message-
 edge is held out of the graph while its score is trained.
 
 Every fold is the whole graph and ONE batch (a ``max_nodes_per_batch`` below the node count raises ValueError); the graph
-part of a batch comes out of the single tfgnn_batch_assemble launch like every dataset's.  On top, a batch carries, in
+part of a batch comes out of tfgnn_batch_assemble like every dataset's: one launch up to 48 processed edge types, one per
+48 beyond (238 types: five).  On top, a batch carries, in
 ``batch_labels`` and - the same tensors - in ``batch_features``:
   ``triples`` int32 [N, 3]: the fold's P positives followed by ``num_negatives_per_positive`` negatives per positive;
   ``triple_labels`` float32 [N] (1 / 0), ``triple_weights`` float32 [N] (1);
@@ -209,11 +213,13 @@ class LinkPredictionDataset(GraphDataset):
             return [np.load(f) if f.exists() else np.zeros((0, 2), dtype=np.int64) for f in files]
 
         wanted = lambda fold: folds_to_load is None or fold in folds_to_load
+        features_file, num_nodes_file = data_dir / "node_features.npy", data_dir / "num_nodes.npy"
         self.load_data_from_arrays(
-            np.load(data_dir / "node_features.npy"), edges,
+            np.load(features_file) if features_file.exists() else None, edges,
             valid_edges=fold_edges("valid") if wanted(DataFold.VALIDATION) else None,
             test_edges=fold_edges("test") if wanted(DataFold.TEST) else None,
             load_train=wanted(DataFold.TRAIN), what=str(data_dir),
+            num_nodes=np.load(num_nodes_file) if num_nodes_file.exists() else None,
         )
 
     def load_data_from_list(self, datapoints: List[Dict[str, Any]], target_fold: DataFold = DataFold.TEST):
@@ -240,12 +246,34 @@ class LinkPredictionDataset(GraphDataset):
         return np.ascontiguousarray(np.concatenate(parts), dtype=np.int32)
 
     def load_data_from_arrays(self, node_features, edges, valid_edges=None, test_edges=None, load_train: bool = True,
-                              what: str = "arrays") -> None:
+                              what: str = "arrays", num_nodes=None) -> None:
         """The files of ``load_data`` as arrays.  ``edges`` / ``valid_edges`` / ``test_edges``: one [E, 2] array, or a sequence
-        of them, one per forward edge type; a fold whose edges are None is not loaded."""
-        feats = np.asarray(node_features, dtype=np.float32)
-        if feats.ndim != 2 or feats.shape[0] < 1:
-            raise ValueError(f"{what}: node features must be [V, F] with V >= 1, not {list(feats.shape)}")
+        of them, one per forward edge type; a fold whose edges are None is not loaded.  ``node_features`` None: a featureless
+        dataset of ``num_nodes`` nodes (``num_nodes.npy``, a scalar), or, without it, of the largest node id of any given edge
+        array plus one; with features ``num_nodes``, if given, has to agree with them."""
+        if num_nodes is not None:
+            n = np.asarray(num_nodes).reshape(-1)
+            if n.shape[0] != 1 or n.dtype.kind not in "iu" or int(n[0]) < 1:
+                raise ValueError(f"{what}: num_nodes must be one integer >= 1, not {num_nodes!r}")
+            num_nodes = int(n[0])
+        if node_features is None:
+            if num_nodes is None:
+                every = [edges, valid_edges, test_edges]
+                arrays = [np.asarray(e) for part in every if part is not None
+                          for e in ([part] if isinstance(part, np.ndarray) and part.ndim == 2 else part)]
+                largest = [int(e.max()) for e in arrays if e.ndim == 2 and e.shape[0] and e.dtype.kind in "iu"]
+                if not largest:
+                    raise ValueError(f"{what}: neither node features, nor num_nodes, nor an edge to take the node count from")
+                num_nodes = max(largest) + 1
+            if num_nodes >= 2 ** 31:
+                raise ValueError(f"{what}: {num_nodes} nodes do not fit int32 node ids")
+            feats = np.zeros((max(num_nodes, 1), 0), dtype=np.float32)
+        else:
+            feats = np.asarray(node_features, dtype=np.float32)
+            if feats.ndim != 2 or feats.shape[0] < 1:
+                raise ValueError(f"{what}: node features must be [V, F] with V >= 1, not {list(feats.shape)}")
+            if num_nodes is not None and num_nodes != feats.shape[0]:
+                raise ValueError(f"{what}: num_nodes = {num_nodes}, but there are features of {feats.shape[0]} nodes")
         V = feats.shape[0]
         if self.params["max_nodes_per_batch"] < V:
             raise ValueError(f"{what}: max_nodes_per_batch = {self.params['max_nodes_per_batch']} would cut the graph of {V} nodes; "

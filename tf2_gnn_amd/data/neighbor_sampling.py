@@ -72,8 +72,6 @@ class NeighborStore:
         if fold.num_graphs != 1:
             raise ValueError(f"neighbour sampling needs a fold of one graph, not {fold.num_graphs}: node_to_graph_map must be sorted, "
                              "and a sampled batch is one graph")
-        if fold.features.shape[1] < 1:
-            raise ValueError("a neighbour store needs node features of width >= 1")
         if fold.num_edge_types > _lib.BATCH_MAX_EDGE_TYPES or len(fold.node_columns) > _lib.BATCH_MAX_NODE_COLUMNS:
             raise ValueError(f"at most {_lib.BATCH_MAX_EDGE_TYPES} edge types and {_lib.BATCH_MAX_NODE_COLUMNS} node columns")
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -104,7 +102,11 @@ class NeighborStore:
             self.in_ptr.append(share.in_ptr[t] if on_device else torch.from_numpy(ptr).to(self.device))
             self.in_src.append(share.in_src[t] if on_device else torch.from_numpy(src).to(self.device))
         self.max_in_degree = [int(np.diff(p).max()) for p in self.in_ptr_host]
-        self.features = up(fold.features)
+        # a featureless fold (width 0): one placeholder column of zeros, tfgnn_gather_node_rows needs a width >= 1; a sampled
+        # batch exposes the [n, 0] view of what the gather wrote
+        self.featureless = fold.features.shape[1] == 0
+        self.features = (torch.zeros((self.num_nodes, 1), dtype=torch.float32, device=self.device) if self.featureless
+                         else up(fold.features))
         self.node_column_names = list(fold.node_columns)
         self.node_columns = [up(fold.node_columns[k]) for k in self.node_column_names]
         L = len(self.in_ptr)
@@ -150,6 +152,8 @@ def sampled_batch(store: NeighborStore, seeds: torch.Tensor, fanouts: Sequence[i
     nf, cols = ops.gather_node_rows(sample.nodes, sample.num_seeds, store.features, store.node_columns,
                                     seed_only=[name in seed_only_columns for name in store.node_column_names], bad_flag=bad_flag)
     n = int(sample.nodes.shape[0])
+    if store.featureless:
+        nf = nf[:, :0]  # float32 [n, 0]
     features: Dict[str, Any] = {
         "node_features": nf,
         "node_to_graph_map": torch.zeros(n, dtype=torch.int32, device=store.device),

@@ -2,7 +2,10 @@
 the SAME graph(s) (ogbn-arxiv style).  The reference has no such dataset.
 
 A data directory holds numpy files only:
-  ``node_features.npy`` [V, F]; ``node_labels.npy`` int [V], -1 where the class is unknown;
+  ``node_features.npy`` [V, F] - optional: without it the dataset is FEATURELESS (``node_feature_shape`` is (0,), a batch's
+  ``node_features`` a float32 [V, 0], and a task model needs the hyper-parameter ``node_embedding_dim``, tasks.py: one
+  learned row per node, looked up through a sampled batch's ``sampled_node_ids``); ``node_labels.npy`` int [V], -1 where the
+  class is unknown, which also gives V;
   ``edges.npy`` [E, 2] (one forward edge type) or ``edges_0.npy``, ``edges_1.npy``, ... (one file per forward edge type),
   (source, target) pairs over the node axis;
   optionally ``node_graph_id.npy`` [V]: the graph of every node, each graph's nodes contiguous along the node axis as in
@@ -31,7 +34,9 @@ file order and epoch 0 (with ``eval_neighbor_fanouts``, default: the training fa
 every ``iter()``.  K should be at least the number of message passing layers: then a seed's output is exact for the sampled
 graph (all of it at fanout -1).  A sampled batch is one graph of a single-graph dataset, so ``node_graph_id`` with several
 graphs raises ValueError, and so do repeated indices in a fold; graph-global exchange sees only the sampled subgraph; the
-counts of every batch are read back once, so a sampled batch cannot be captured in a CapturedStep."""
+counts of every batch are read back once, so a sampled batch cannot be captured in a CapturedStep.  The sampler takes its
+per-type tables as kernel arguments, so the sampled route keeps its limit of 48 processed edge types (NeighborStore raises
+ValueError above it); the full-batch route has none, batch assembly chunks the types 48 to a call."""
 from __future__ import annotations
 
 from pathlib import Path
@@ -99,6 +104,13 @@ class NodeClassificationDataset(GraphDataset):
         self._loaded("num_node_classes")
         return self._num_node_classes
 
+    @property
+    def num_nodes(self) -> int:
+        """The nodes of the whole graph (all graphs of ``node_graph_id`` together): the rows of a learned embedding table."""
+        self._loaded("num_nodes")
+        some_fold = next(iter(self._loaded_data.values()))
+        return int(some_fold.features.shape[0])
+
     # ---- loading ------------------------------------------------------------------------------------------------------------
     def load_data(self, path, folds_to_load: Optional[Set[DataFold]] = None) -> None:
         data_dir = Path(path)
@@ -110,9 +122,9 @@ class NodeClassificationDataset(GraphDataset):
                 edges.append(np.load(data_dir / f"edges_{len(edges)}.npy"))
             if not edges:
                 raise ValueError(f"{data_dir}: neither edges.npy nor edges_0.npy")
-        graph_id_file = data_dir / "node_graph_id.npy"
+        graph_id_file, features_file = data_dir / "node_graph_id.npy", data_dir / "node_features.npy"
         self.load_data_from_arrays(
-            np.load(data_dir / "node_features.npy"),
+            np.load(features_file) if features_file.exists() else None,
             np.load(data_dir / "node_labels.npy"),
             edges,
             **{f"{name}_idx": np.load(data_dir / f"{name}_idx.npy") for fold, name in _FOLD_NAMES
@@ -127,11 +139,12 @@ class NodeClassificationDataset(GraphDataset):
     def load_data_from_arrays(self, node_features, node_labels, edges, train_idx=None, valid_idx=None, test_idx=None,
                               node_graph_id=None, what: str = "arrays") -> None:
         """The files of ``load_data`` as arrays.  ``edges``: one [E, 2] array, or a sequence of them, one per forward edge
-        type; a fold whose indices are None is not loaded."""
+        type; a fold whose indices are None is not loaded.  ``node_features`` None: a featureless dataset, its node count the
+        length of ``node_labels``."""
         fold_indices = {fold: idx for (fold, _), idx in zip(_FOLD_NAMES, (train_idx, valid_idx, test_idx)) if idx is not None}
-        feats = np.asarray(node_features, dtype=np.float32)
         raw_labels = np.asarray(node_labels).reshape(-1)
         V = raw_labels.shape[0]
+        feats = np.zeros((V, 0), dtype=np.float32) if node_features is None else np.asarray(node_features, dtype=np.float32)
         if feats.ndim != 2 or feats.shape[0] != V:
             raise ValueError(f"{what}: features {list(feats.shape)} and {V} labels do not describe the same nodes")
         if raw_labels.dtype.kind not in "iu":

@@ -2861,3 +2861,36 @@ def gather_node_rows(nodes: torch.Tensor, num_seeds: int, features: torch.Tensor
     a.bad_flag = bad_flag.data_ptr() if bad_flag is not None else None
     _lib.check(_lib.load().tfgnn_gather_node_rows(ctypes.byref(a), _stream()))
     return nf, list(cols)
+
+
+# ---- node embeddings: include/tfgnn.h "Node embeddings", csrc/embedding.hip --------------------------------------------------------
+def embedding_launch_count() -> int:
+    """tfgnn_embedding_launch_count: kernel launches of ``embedding_scatter_rows`` so far (a host counter)."""
+    return int(_lib.load().tfgnn_embedding_launch_count())
+
+
+@_writes_out
+def embedding_scatter_rows(rows: torch.Tensor, ids: torch.Tensor, num_rows: int, out: Optional[torch.Tensor] = None,
+                           bad_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The gradient of ``table[ids]`` (``gather_node_rows``) with respect to a table of ``num_rows`` rows, dense: -> float32
+    [num_rows, D] with row ids[i] = rows[i] and zeros elsewhere (tfgnn_embedding_scatter_rows: a fill and a scatter on the
+    current stream; capturable).  The ids are DISTINCT by precondition.  ``rows`` [n, D] and ``out`` may be pitched (unit inner
+    stride); the columns of ``out`` beyond D are left alone.  ``bad_flag`` (zeroed int32 [1]) is set by an id outside the table."""
+    _require_dev(rows, torch.float32, "rows")
+    _require_dev(ids, torch.int32, "ids")
+    rows, ld_rows = _rowmajor(rows, "rows")
+    ids = ids.contiguous().view(-1)
+    n, D, N = int(rows.shape[0]), int(rows.shape[1]), int(num_rows)
+    if int(ids.shape[0]) != n:
+        raise ValueError(f"embedding_scatter_rows: {int(ids.shape[0])} ids for {n} rows")
+    if out is None:
+        out = torch.empty((max(N, 0), D), dtype=torch.float32, device=rows.device)
+    _require_dev(out, torch.float32, "out")
+    if out.dim() != 2 or tuple(out.shape) != (N, D) or (D and out.stride(1) != 1):
+        raise ValueError(f"embedding_scatter_rows: out must be a float32 [{N}, {D}] with unit inner stride")
+    ld_out = int(out.stride(0)) if N > 1 else max(int(out.stride(0)), D)
+    if bad_flag is not None:
+        _require_dev(bad_flag, torch.int32, "bad_flag")
+    _lib.check(_lib.load().tfgnn_embedding_scatter_rows(_ptr(rows) if n else None, ld_rows, _ptr(ids) if n else None, n, D,
+                                                        _ptr(out) if N else None, ld_out, N, _ptr(bad_flag), _stream()))
+    return out

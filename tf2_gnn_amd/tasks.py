@@ -37,6 +37,14 @@ from .layers.nodes_to_graph_representation import (
 from .utils import eval_metrics
 
 
+def _feature_width(dataset) -> Optional[int]:
+    """the dataset's node feature width, None where it does not say (no such property, or nothing loaded yet)"""
+    try:
+        return int(dataset.node_feature_shape[-1])
+    except (AttributeError, ValueError, TypeError, IndexError, StopIteration):
+        return None
+
+
 class GraphTaskModel:
     """tf2_gnn/models/graph_task_model.py:14-399 without the Keras plumbing."""
 
@@ -61,14 +69,48 @@ class GraphTaskModel:
         return params
 
     def __init__(self, params: Dict[str, Any], dataset: Any = None, name: Optional[str] = None, *,
-                 num_edge_types: Optional[int] = None):
-        """``dataset``: anything with ``num_edge_types`` (graph_task_model.py:41-43), or pass ``num_edge_types``."""
+                 num_edge_types: Optional[int] = None, num_nodes: Optional[int] = None):
+        """``dataset``: anything with ``num_edge_types`` (graph_task_model.py:41-43), or pass ``num_edge_types``.
+
+        Learned node embeddings - the hyper-parameter ``node_embedding_dim``: absent or None (it is in no defaults dictionary)
+        is off, an integer >= 1 turns it on, anything else raises ValueError.  With it on the model owns one more trainable
+        variable, ``<ClassName>/node_embeddings`` [num_nodes, node_embedding_dim] (glorot_uniform; ``num_nodes`` from
+        ``dataset.num_nodes`` or the keyword), and its rows REPLACE the node features: the batch's ``node_features`` - the
+        dataset's, if it has any - are not read.  The hooks the reference leaves for this, ``get_initial_node_feature_shape``
+        and ``compute_initial_node_features`` (graph_task_model.py:133-156), do it: a batch of ``num_nodes`` rows without
+        ``sampled_node_ids`` (a transductive full batch) takes the table as it is, a batch that names its nodes in
+        ``sampled_node_ids`` (neighbour sampling: distinct ids) looks its rows up with ops.gather_node_rows.  ``backward()``
+        asks the stack for its input gradient, which is the table's gradient - through ops.embedding_scatter_rows into a
+        dense [num_nodes, node_embedding_dim] buffer on the sampled route - and the update is the optimizer's dense step, what
+        Keras does with the IndexedSlices of a lookup: every row is updated, the moments of untouched rows decay.  A
+        full-batch step stays capturable.  A dataset without node features (``node_feature_shape == (0,)``) needs the key."""
         self._params = params
         if num_edge_types is None:
             if dataset is None or not hasattr(dataset, "num_edge_types"):
                 raise ValueError("GraphTaskModel needs a dataset with num_edge_types, or num_edge_types=...")
             num_edge_types = dataset.num_edge_types
         self._num_edge_types = int(num_edge_types)
+        dim = params.get("node_embedding_dim")
+        if dim is not None and (isinstance(dim, bool) or not isinstance(dim, (int, np.integer)) or dim < 1):
+            raise ValueError(f"node_embedding_dim must be an integer >= 1 (or None: no learned node embeddings), not {dim!r}")
+        self._node_embedding_dim = None if dim is None else int(dim)
+        self._num_nodes: Optional[int] = None
+        self._node_embeddings: Optional[Variable] = None
+        self._node_embeddings_grad: Optional[torch.Tensor] = None  # the sampled route's dense [num_nodes, dim] buffer
+        self._embedding_ids: Optional[torch.Tensor] = None  # sampled_node_ids of the last forward pass; None: the whole table
+        self.embedding_bad_index: Optional[torch.Tensor] = None  # device flag: a sampled id outside the table (read lazily)
+        if dim is not None:
+            if num_nodes is None:
+                if dataset is None or not hasattr(dataset, "num_nodes"):
+                    raise ValueError("node_embedding_dim needs the number of nodes: a dataset with num_nodes (dataset.num_nodes), "
+                                     "or num_nodes=...")
+                num_nodes = dataset.num_nodes
+            self._num_nodes = int(num_nodes)
+            if not 1 <= self._num_nodes < 2 ** 31:
+                raise ValueError(f"node_embedding_dim: num_nodes must be in [1, 2^31), not {num_nodes!r}")
+        elif dataset is not None and _feature_width(dataset) == 0:
+            raise ValueError(f"{type(dataset).__name__} has no node features (node_feature_shape == (0,)): set the hyper-parameter "
+                             "node_embedding_dim, the width of one learned embedding per node")
         self._use_intermediate_gnn_results = params.get("use_intermediate_gnn_results", False)
         self.name = name or self.__class__.__name__
         self._gnn: Optional[GNN] = None
@@ -91,17 +133,45 @@ class GraphTaskModel:
                 num_graphs=(),
             )
         )
+        if self._node_embedding_dim is not None:  # created last: the other variables draw what they draw without it
+            self._node_embeddings = Variable(f"{self.__class__.__name__}/node_embeddings",
+                                             glorot_uniform((self._num_nodes, self._node_embedding_dim), device=default_device()))
         self.built = True
 
     def get_initial_node_feature_shape(self, input_shapes):
-        return tuple(input_shapes["node_features"])
+        """graph_task_model.py:133-135; with learned node embeddings (None, node_embedding_dim)."""
+        if self._node_embedding_dim is not None:
+            return (None, self._node_embedding_dim)
+        shape = tuple(input_shapes["node_features"])
+        if int(shape[-1]) == 0:
+            raise ValueError("the batch has no node features (width 0): set the hyper-parameter node_embedding_dim")
+        return shape
 
     def compute_initial_node_features(self, inputs, training: bool):
-        return inputs["node_features"]
+        """graph_task_model.py:137-156; with learned node embeddings the rows of the table (see ``__init__``)."""
+        table = self._node_embeddings
+        if table is None:
+            return inputs["node_features"]
+        ids = inputs.get("sampled_node_ids") if hasattr(inputs, "get") else None
+        self._embedding_ids = ids
+        N, dim = table.value.shape
+        if ids is None:
+            rows = int(inputs["node_to_graph_map"].shape[0])
+            if rows != N:
+                raise ValueError(f"a batch of {rows} nodes without sampled_node_ids cannot index the {N} node embeddings: only a "
+                                 "batch of the whole node set stands for the table's rows in order")
+            # the table itself, no launch and no copy.  A view of its own per pass: forms derived from the stack's input are
+            # remembered per tensor object (ops.sp_rows_of), and the optimizer rewrites the table between two passes
+            return table.value.view(N, dim)
+        if self.embedding_bad_index is None:
+            self.embedding_bad_index = torch.zeros(1, dtype=torch.int32, device=table.value.device)
+        rows, _ = ops.gather_node_rows(ids, int(ids.shape[0]), table.value, bad_flag=self.embedding_bad_index)
+        return rows
 
     @property
     def trainable_variables(self) -> List[Variable]:
-        return list(self._gnn.trainable_variables) + self._task_variables()
+        embeddings = [self._node_embeddings] if self._node_embeddings is not None else []
+        return list(self._gnn.trainable_variables) + self._task_variables() + embeddings
 
     def _task_variables(self) -> List[Variable]:
         return []
@@ -152,7 +222,17 @@ class GraphTaskModel:
         if self._step is None or "dloss" not in self._step:
             raise RuntimeError("backward() needs a forward pass followed by compute_task_metrics()")
         grad_final, grad_all = self._task_backward()
-        self._gnn.backward(grad_final, grad_all_representations=grad_all)
+        table = self._node_embeddings
+        if table is None:
+            self._gnn.backward(grad_final, grad_all_representations=grad_all)
+        else:  # the stack's input gradient is the gradient of the looked-up rows
+            d_rows = self._gnn.backward(grad_final, need_input_grad=True, grad_all_representations=grad_all)
+            if self._embedding_ids is None:
+                table.grad = d_rows
+            else:
+                self._node_embeddings_grad = table.grad = ops.embedding_scatter_rows(
+                    d_rows, self._embedding_ids, table.value.shape[0], out=self._node_embeddings_grad,
+                    bad_flag=self.embedding_bad_index)
         return [(v, v.grad) for v in self.trainable_variables]
 
     def _task_backward(self):
@@ -255,8 +335,9 @@ class NodeMulticlassTask(GraphTaskModel):
     cross entropy summed over labels and averaged over nodes, micro-F1."""
 
     def __init__(self, params: Dict[str, Any], dataset: Any = None, name: Optional[str] = None, *,
-                 num_edge_types: Optional[int] = None, num_node_target_labels: Optional[int] = None):
-        super().__init__(params, dataset=dataset, name=name, num_edge_types=num_edge_types)
+                 num_edge_types: Optional[int] = None, num_node_target_labels: Optional[int] = None,
+                 num_nodes: Optional[int] = None):
+        super().__init__(params, dataset=dataset, name=name, num_edge_types=num_edge_types, num_nodes=num_nodes)
         if num_node_target_labels is None:
             if not hasattr(dataset, "num_node_target_labels"):
                 raise ValueError(
@@ -311,13 +392,14 @@ class NodeClassificationTask(NodeMulticlassTask):
     kernel, so a captured step follows in-place changes of either (capture.py)."""
 
     def __init__(self, params: Dict[str, Any], dataset: Any = None, name: Optional[str] = None, *,
-                 num_edge_types: Optional[int] = None, num_node_classes: Optional[int] = None):
+                 num_edge_types: Optional[int] = None, num_node_classes: Optional[int] = None,
+                 num_nodes: Optional[int] = None):
         if num_node_classes is None:
             if not hasattr(dataset, "num_node_classes"):
                 raise ValueError(f"Provided dataset of type {type(dataset)} does not provide num_node_classes information.")
             num_node_classes = dataset.num_node_classes
         super().__init__(params, dataset=dataset, name=name, num_edge_types=num_edge_types,
-                         num_node_target_labels=num_node_classes)
+                         num_node_target_labels=num_node_classes, num_nodes=num_nodes)
 
     @property
     def num_node_classes(self) -> int:
@@ -372,8 +454,8 @@ class LinkPredictionTask(GraphTaskModel):
     device as part of the step, and of every replay of a captured one.  Inference never redraws."""
 
     def __init__(self, params: Dict[str, Any], dataset: Any = None, name: Optional[str] = None, *,
-                 num_edge_types: Optional[int] = None, num_relations: Optional[int] = None):
-        super().__init__(params, dataset=dataset, name=name, num_edge_types=num_edge_types)
+                 num_edge_types: Optional[int] = None, num_relations: Optional[int] = None, num_nodes: Optional[int] = None):
+        super().__init__(params, dataset=dataset, name=name, num_edge_types=num_edge_types, num_nodes=num_nodes)
         if num_relations is None:
             if not hasattr(dataset, "num_relations"):
                 raise ValueError(f"Provided dataset of type {type(dataset)} does not provide num_relations information.")

@@ -10,8 +10,9 @@ num_negatives_per_positive K = 1 and K = 4:
   (c) one epoch as the user runs it, RGCN_BlockDiag C = 64 at D = H = 320 with 2 layers, Adam, a CapturedStep of
       _run_step(training=True): the host route is `replay(); next(iter(train))`, the device route is `replay()` alone.  Wall
       clock over bursts of 5 epochs that end in a synchronise, the two routes alternating burst by burst in one process.
-      (The dataset's batch assembly takes at most 48 edge types and this graph has 238: the graph part of the batch is built
-      by hand, once, and `next(iter(train))` is triple_batch(TRAIN) - what an iter() does on top of the graph part.)
+      (The graph part of the batch is built by hand, once, and `next(iter(train))` is triple_batch(TRAIN) - what an iter()
+      does on top of the graph part.  When this probe was written batch assembly took at most 48 edge types and this graph
+      has 238; get_batches takes it now - tools/embedding_probe.py goes that way - and the probe stays as measured.)
 Per line: median, 10th and 90th percentile in milliseconds and the spread (p90 - p10) / median.  The bytes next to (b) are
 COMPUTED from the kernels' accesses, not measured.  No GPU: the script fails, it measures nothing on a CPU."""
 import argparse
@@ -88,7 +89,7 @@ def dataset(K, route, feats, edges):
 
 
 class _TripleEpochs:
-    """Stands in for ds.get_batches(TRAIN): batch assembly takes at most 48 edge types and this graph has 238, so the graph
+    """Stands in for ds.get_batches(TRAIN) (see the module docstring): the graph
     part of the batch is built once by hand, and every iter() does what the dataset's does on top of it - triple_batch(TRAIN):
     the draw, the tables and, on the host route, the copies."""
 
