@@ -1486,8 +1486,64 @@ int tfgnn_optimizer_apply(const tfgnn_opt_tensor* tensors, int n, const tfgnn_op
 /* state[0] -> *out (device or host-mapped memory) / state[0] = value, state[1] = 0: one-thread kernels, capturable */
 int tfgnn_optimizer_iterations_get(const int64_t* state, int64_t* out, void* stream);
 int tfgnn_optimizer_iterations_set(int64_t* state, int64_t value, void* stream);
-/* host-side count of the kernel launches tfgnn_optimizer_apply has enqueued in this process (tests) */
+/* host-side count of the kernel launches tfgnn_optimizer_apply and tfgnn_optimizer_apply_rows have enqueued in this process
+ * (tests) */
 int64_t tfgnn_optimizer_launch_count(void);
+
+/* The row-sparse ("lazy") step: the same update for variables whose gradient is a ROW GRADIENT - the pair (grad_rows [n, cols],
+ * ids [n]) against a table of N rows, standing for the dense gradient that is grad_rows[i] at row ids[i] and zero elsewhere
+ * (the gradient of tfgnn_gather_node_rows; the ids are DISTINCT by precondition, as for tfgnn_embedding_scatter_rows).
+ *
+ *   listed rows      value[ids[i], :] and the slots at those rows get exactly the arithmetic of the dense step: the same
+ *                    clipping, the learning rate from the device counter, Adam's alpha at t = iterations + 1.
+ *   all other rows   neither their value nor their slots are read or written.
+ *
+ * So plain SGD (momentum 0) equals the dense step on the dense gradient; SGD with momentum, RMSprop and Adam are the LAZY
+ * variant of the optimizer (LazyAdam / SparseAdam): the moments of rows without a gradient do not decay, and those rows do not
+ * move.  An id outside [0, N) skips its row and sets *bad_flag (nullable, zeroed by the caller).  With a repeated id the result
+ * of its row is unspecified; nothing else is affected.
+ *
+ * One call updates `n` dense tensors and `n_rows` row tensors (at most TFGNN_OPT_MAX_ROW_TENSORS) together:
+ *   counter   state[0] advances exactly once, after every workgroup of the call has read it: the ticket is taken in the LAST
+ *             launch of the call - the row update, or the last dense update when every row tensor has n == 0 (such a call
+ *             still updates its dense tensors and still advances the counter; no empty grid is launched - a call with nothing
+ *             at all to update advances the counter with one workgroup).
+ *   norms     in the norm modes a row tensor takes part in the squared-sum pass as the plain [n, cols] tensor grad_rows is,
+ *             after every dense tensor of the call, in the same 8192-element partition: its per-tensor norm and the global
+ *             norm are those of the dense gradient it stands for, and the bits of a tfgnn_optimizer_apply call that lists
+ *             grad_rows as the gradient of a contiguous, aligned [n, cols] variable in that position.  A row skipped for a
+ *             bad id still counts (the flag already says that the step is wrong).
+ *   launches  the dense tensors as in tfgnn_optimizer_apply, then ONE launch for all row tensors; in the norm modes the row
+ *             tensors' partial sums ride in the squared-sum launch of the last chunk of dense tensors.  32 dense tensors or
+ *             fewer and row tensors: 2 launches, 3 with a norm mode.
+ *   kernel    min(256, 8192 / cols) rows (one when a row is longer) to a workgroup; one thread per row checks the id and
+ *             leaves it in LDS, then consecutive lanes walk consecutive floats of a row: per element w, g, slot0, slot1 are
+ *             read and w, slot0, slot1 written.  float4 when cols % 4 == 0, both pitches are multiples of 4 and every base
+ *             is 16-byte aligned; otherwise scalar accesses, four consecutive elements of the [n, cols] gradient's flat index
+ *             space to a thread and its last n * cols % 4 elements one to a thread - the partition in which
+ *             tfgnn_optimizer_apply computes that tensor, so that the two agree bit for bit at every shape.  Table and slot
+ *             offsets are 64-bit: N * cols may pass 2^31 (tfgnn_optimizer_apply refuses such a tensor).  Plain stores, no
+ *             float atomics.
+ * No synchronisation, allocation or copy: capturable.  Rejected on the host before any HIP call: what tfgnn_optimizer_apply
+ * rejects for the config and the dense tensors; for a row tensor negative sizes, cols < 1, N or cols >= 2^31, n > N,
+ * n * cols >= 2^31 (grad_rows is an ordinary tensor of the squared-sum pass), a pitch below cols or (ld_grad) >= 2^32, and for
+ * n > 0 a NULL value, grad_rows, ids or slot the optimizer kind needs. */
+#define TFGNN_OPT_MAX_ROW_TENSORS 8
+typedef struct tfgnn_opt_row_tensor {
+  float* value;           /* the table [N, cols], row pitch ld_value >= cols */
+  int64_t ld_value;
+  const float* grad_rows; /* [n, cols], row pitch ld_grad >= cols */
+  int64_t ld_grad;
+  const int32_t* ids;     /* [n], distinct */
+  int64_t n, N, cols;     /* 0 <= n <= N < 2^31, 1 <= cols < 2^31; N * cols may exceed 2^31 */
+  float* slot0;           /* contiguous [N * cols], as in tfgnn_opt_tensor; unused may be NULL */
+  float* slot1;
+  int* bad_flag;          /* may be NULL */
+} tfgnn_opt_row_tensor;
+size_t tfgnn_optimizer_rows_workspace_bytes(const tfgnn_opt_tensor* tensors, int n, const tfgnn_opt_row_tensor* row_tensors,
+                                            int n_rows, int clip);
+int tfgnn_optimizer_apply_rows(const tfgnn_opt_tensor* tensors, int n, const tfgnn_opt_row_tensor* row_tensors, int n_rows,
+                               const tfgnn_opt_config* config, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Batch assembly from a device-resident fold (csrc/batch.hip): GraphDataset.graph_batch_iterator_from_graph_iterator

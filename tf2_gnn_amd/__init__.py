@@ -24,7 +24,7 @@ from .layers import (  # noqa: F401
 )
 
 from .capture import CapturedStep  # noqa: F401,E402
-from .optim import Optimizer, PolynomialWarmupAndDecaySchedule, make_optimizer  # noqa: F401,E402
+from .optim import Optimizer, PolynomialWarmupAndDecaySchedule, RowGradient, make_optimizer  # noqa: F401,E402
 from .autograd import TorchGNN, TorchGraphTaskModel, TorchMessagePassing, TorchNodesToGraphRepresentation  # noqa: F401,E402
 
 __version__ = "0.2.0"

@@ -364,7 +364,11 @@ _SIGNATURES += [
     ("tfgnn_optimizer_iterations_get", c_int, [c_void_p, c_void_p, c_void_p]),
     ("tfgnn_optimizer_iterations_set", c_int, [c_void_p, c_int64, c_void_p]),
     ("tfgnn_optimizer_launch_count", c_int64, []),
+    # the row-sparse step: dense tensors, row tensors (OptRowTensor array), config
+    ("tfgnn_optimizer_rows_workspace_bytes", c_size_t, [c_void_p, c_int, c_void_p, c_int, c_int]),
+    ("tfgnn_optimizer_apply_rows", c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
 ]
+OPT_MAX_ROW_TENSORS = 8  # include/tfgnn.h TFGNN_OPT_MAX_ROW_TENSORS
 
 # batch assembly from a device-resident fold (include/tfgnn.h, csrc/batch.hip): the argument struct travels by pointer
 _SIGNATURES += [
@@ -615,6 +619,15 @@ class OptConfig(ctypes.Structure):
         ("learning_rate", c_float), ("initial_learning_rate", c_float), ("final_learning_rate", c_float), ("power", c_float),
         ("warmup_steps", c_int64), ("decay_steps", c_int64), ("state", c_void_p), ("workspace", c_void_p),
         ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
+class OptRowTensor(ctypes.Structure):
+    """tfgnn_opt_row_tensor (include/tfgnn.h), field for field: a table and the row gradient (grad_rows, ids) against it."""
+
+    _fields_ = [
+        ("value", c_void_p), ("ld_value", c_int64), ("grad_rows", c_void_p), ("ld_grad", c_int64), ("ids", c_void_p),
+        ("n", c_int64), ("N", c_int64), ("cols", c_int64), ("slot0", c_void_p), ("slot1", c_void_p), ("bad_flag", c_void_p),
     ]
 
 

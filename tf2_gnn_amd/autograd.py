@@ -28,6 +28,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import ops
+from .optim import RowGradient
 from .layers.gnn import GNN, GNNInput
 from .layers.message_passing.message_passing import MessagePassing, MessagePassingInput, Variable
 from .layers.nodes_to_graph_representation import NodesToGraphRepresentation, NodesToGraphRepresentationInput
@@ -132,6 +133,8 @@ class _AutogradModule(torch.nn.Module):
         out = []
         for v in self._vars:
             g = v.grad
+            if isinstance(g, RowGradient):  # torch optimizers take dense gradients
+                g = g.to_dense()
             out.append(None if g is None else g.reshape(v.value.shape))
         return out
 

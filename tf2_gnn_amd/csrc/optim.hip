@@ -12,6 +12,8 @@ constexpr int OPT_CHUNK = 32;          // tensors per launch (the table travels 
 constexpr int OPT_THREADS = 256;
 constexpr int OPT_UPD_ELEMS = 2048;    // elements per workgroup of the update: two float4 per thread, loaded together
 constexpr int OPT_SUM_ELEMS = 8192;    // elements per workgroup of the squared-sum pass: 8 float4 per thread, loaded together
+constexpr int OPT_ROW_CHUNK = TFGNN_OPT_MAX_ROW_TENSORS;  // row tensors of a call: one update launch for all of them
+constexpr int OPT_ROW_TILE_ELEMS = 8192;  // floats of a row tensor's tile (whole rows; one row when a row is longer)
 
 enum { OPT_K_SGD = 0, OPT_K_SGD_MOM = 1, OPT_K_RMS = 2, OPT_K_RMS_MOM = 3, OPT_K_ADAM = 4 };
 
@@ -46,8 +48,39 @@ struct OptTable {
   OptEntry e[OPT_CHUNK];
 };
 
+// the squared-sum launch that also takes the row tensors of a call (as the [n, cols] tensors their gradients are)
+struct OptSumRowsTable {
+  OptParams p;
+  OptEntry e[OPT_CHUNK + OPT_ROW_CHUNK];
+};
+
+struct OptRowEntry {  // one row tensor of the row-update launch
+  float* w;           // the table [N, cols], pitch ldw
+  const float* g;     // [n, cols], pitch ldg
+  const int32_t* ids;
+  float* s0;          // [N * cols]
+  float* s1;
+  int* bad;
+  int64_t ldw, ldg;
+  uint32_t n, N, cols;
+  uint32_t rows_per_tile;
+  uint32_t blk0;      // first workgroup of this tensor in the launch
+  uint32_t part0;     // its partial sums in the workspace
+  uint32_t nparts;
+  uint32_t vec;       // 16-byte accesses: cols % 4 == 0, both pitches multiples of 4, every base aligned
+  uint32_t quad_elems;  // !vec: the elements of the [n, cols] gradient the dense step would compute four at a time
+};
+
+struct OptRowTable {
+  OptParams p;  // p.n: row tensors of the launch (0: nothing to update, the launch only advances the counter)
+  OptRowEntry r[OPT_ROW_CHUNK];
+};
+
 typedef const __attribute__((address_space(4))) OptTable* opt_table_cptr;
+typedef const __attribute__((address_space(4))) OptParams* opt_params_cptr;
 typedef const __attribute__((address_space(4))) OptEntry* opt_entry_cptr;
+typedef const __attribute__((address_space(4))) OptRowTable* opt_row_table_cptr;
+typedef const __attribute__((address_space(4))) OptRowEntry* opt_row_entry_cptr;
 
 // The table is the kernel's only explicit argument, at offset 0 of the argument segment: fields are read from there with
 // scalar loads (indexing the by-value parameter with a run-time entry index would copy it to scratch first - aux_jobs.hip).
@@ -71,15 +104,13 @@ __device__ __forceinline__ double opt_block_sum(double v, double* red) {
 }
 
 // ---- launch 1 of the norm modes: per-workgroup partial sums of g^2 -> partials[part_base + blockIdx.x] ----
-__global__ void __launch_bounds__(OPT_THREADS) opt_sumsq_kernel(OptTable table) {
-  (void)table;
-  __shared__ double red[OPT_THREADS / 64];
-  const opt_table_cptr T = opt_table();
-  const uint32_t b = T->p.part_base + blockIdx.x;
+// (both tables begin with the parameters followed by the entries: the body takes the two addresses)
+__device__ __forceinline__ void opt_sumsq_body(opt_params_cptr P, opt_entry_cptr entries, double* red) {
+  const uint32_t b = P->part_base + blockIdx.x;
   int k = 0;
-  const int n_t = T->p.n;
-  while (k + 1 < n_t && b >= T->e[k + 1].part0) ++k;
-  const opt_entry_cptr E = &T->e[k];
+  const int n_t = P->n;
+  while (k + 1 < n_t && b >= entries[k + 1].part0) ++k;
+  const opt_entry_cptr E = &entries[k];
   const float* __restrict__ g = E->g;
   const uint32_t n = E->n, cols = E->cols, ldg = E->ldg;
   const uint32_t lb = b - E->part0;
@@ -114,7 +145,21 @@ __global__ void __launch_bounds__(OPT_THREADS) opt_sumsq_kernel(OptTable table) 
     }
   }
   const double s = opt_block_sum(acc, red);
-  if (threadIdx.x == 0) T->p.partials[b] = s;
+  if (threadIdx.x == 0) P->partials[b] = s;
+}
+
+__global__ void __launch_bounds__(OPT_THREADS) opt_sumsq_kernel(OptTable table) {
+  (void)table;
+  __shared__ double red[OPT_THREADS / 64];
+  const opt_table_cptr T = opt_table();
+  opt_sumsq_body(&T->p, T->e, red);
+}
+
+__global__ void __launch_bounds__(OPT_THREADS) opt_sumsq_rows_kernel(OptSumRowsTable table) {
+  (void)table;
+  __shared__ double red[OPT_THREADS / 64];
+  const auto T = (const __attribute__((address_space(4))) OptSumRowsTable*)__builtin_amdgcn_kernarg_segment_ptr();
+  opt_sumsq_body(&T->p, T->e, red);
 }
 
 struct OptCoef {
@@ -166,13 +211,13 @@ constexpr bool opt_has_s1(int kind) { return kind == OPT_K_RMS_MOM || kind == OP
 
 // the learning rate at step = (float)iterations (polynomial_warmup_and_decay_schedule.py:90-111, fp32 like the float32 step Keras
 // passes in)
-__device__ __forceinline__ float opt_learning_rate(opt_table_cptr T, float step) {
-  const float lr = T->p.lr;
-  if (!T->p.schedule) return lr;
-  const float warmup = T->p.warmup, decay = T->p.decay, power = T->p.power;
-  if (step <= warmup) return (lr - T->p.lr_initial) * powf(step / warmup, power) + T->p.lr_initial;
+__device__ __forceinline__ float opt_learning_rate(opt_params_cptr P, float step) {
+  const float lr = P->lr;
+  if (!P->schedule) return lr;
+  const float warmup = P->warmup, decay = P->decay, power = P->power;
+  if (step <= warmup) return (lr - P->lr_initial) * powf(step / warmup, power) + P->lr_initial;
   const float s = fminf(step - warmup, decay);
-  return (lr - T->p.lr_final) * powf(1.f - s / decay, power) + T->p.lr_final;
+  return (lr - P->lr_final) * powf(1.f - s / decay, power) + P->lr_final;
 }
 
 // sum of partials[lo, hi) in a fixed order: every workgroup of a tensor (or of the call) computes the same bits
@@ -180,6 +225,55 @@ __device__ __forceinline__ double opt_sum_partials(const double* __restrict__ p,
   double acc = 0.0;
   for (uint32_t i = lo + threadIdx.x; i < hi; i += OPT_THREADS) acc += p[i];
   return opt_block_sum(acc, red);
+}
+
+// the coefficients of a workgroup's tensor at the counter value `it`: the learning rate of the schedule (Adam: alpha at
+// t = it + 1) and the clip factors from the partial sums [part0, part0 + nparts) of the tensor / of the whole call
+template <int KIND>
+__device__ __forceinline__ OptCoef opt_coefficients(opt_params_cptr P, unsigned long long it, uint32_t part0, uint32_t nparts,
+                                                    double* red) {
+  OptCoef c;
+  c.lr = opt_learning_rate(P, (float)it);
+  c.mu = P->momentum;
+  c.rho = P->rho;
+  c.one_minus_rho = 1.f - P->rho;
+  c.eps = P->epsilon;
+  c.one_minus_b1 = 1.f - P->beta_1;
+  c.one_minus_b2 = 1.f - P->beta_2;
+  if (KIND == OPT_K_ADAM) {
+    const float t = (float)(it + 1);
+    const float b1p = powf(P->beta_1, t), b2p = powf(P->beta_2, t);
+    c.lr = c.lr * (sqrtf(1.f - b2p) / (1.f - b1p));
+  }
+  c.clip = P->clip;
+  c.c = P->clip_value;
+  c.den = 1.f;
+  c.scale = 1.f;
+  if (c.clip == TFGNN_CLIP_NORM) {
+    const float norm = (float)sqrt(opt_sum_partials(P->partials, part0, part0 + nparts, red));
+    c.den = fmaxf(norm, c.c);
+  } else if (c.clip == TFGNN_CLIP_GLOBAL_NORM) {
+    const float norm = (float)sqrt(opt_sum_partials(P->partials, 0, P->total_parts, red));
+    // clip_by_global_norm: clip_norm * minimum(1 / use_norm, 1 / clip_norm), NaN when the norm is not finite
+    c.scale = isfinite(norm) ? c.c * fminf(1.f / norm, 1.f / c.c) : __builtin_nanf("");
+  }
+  return c;
+}
+
+// the ticket of a call's last update launch: the workgroup that arrives last has seen every other one read the counter and
+// advances it; it resets the ticket for the next call.  Relaxed: what orders a workgroup's read of the counter before its add is
+// that thread 0 has consumed the value (LDS store + barrier in the caller); the update's own stores need no ordering (the next
+// reader is another launch), and a release here would write the L2 back once per workgroup (buffer_wbl2; measured: it doubled
+// the call's time).
+__device__ __forceinline__ void opt_advance(opt_params_cptr P, unsigned long long it) {
+  if (P->advance && threadIdx.x == 0) {
+    unsigned long long* st = P->state;
+    const unsigned long long t = __hip_atomic_fetch_add(st + 1, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t == (unsigned long long)P->blocks - 1) {
+      __hip_atomic_store(st + 1, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(st, it + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
 }
 
 // ---- the update: one launch per chunk ----
@@ -200,31 +294,7 @@ __global__ void __launch_bounds__(OPT_THREADS) opt_update_kernel(OptTable table)
   if (threadIdx.x == 0) it_shared = __hip_atomic_load(T->p.state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __syncthreads();
   const unsigned long long it = it_shared;
-  OptCoef c;
-  c.lr = opt_learning_rate(T, (float)it);
-  c.mu = T->p.momentum;
-  c.rho = T->p.rho;
-  c.one_minus_rho = 1.f - T->p.rho;
-  c.eps = T->p.epsilon;
-  c.one_minus_b1 = 1.f - T->p.beta_1;
-  c.one_minus_b2 = 1.f - T->p.beta_2;
-  if (KIND == OPT_K_ADAM) {
-    const float t = (float)(it + 1);
-    const float b1p = powf(T->p.beta_1, t), b2p = powf(T->p.beta_2, t);
-    c.lr = c.lr * (sqrtf(1.f - b2p) / (1.f - b1p));
-  }
-  c.clip = T->p.clip;
-  c.c = T->p.clip_value;
-  c.den = 1.f;
-  c.scale = 1.f;
-  if (c.clip == TFGNN_CLIP_NORM) {
-    const float norm = (float)sqrt(opt_sum_partials(T->p.partials, E->part0, E->part0 + E->nparts, red));
-    c.den = fmaxf(norm, c.c);
-  } else if (c.clip == TFGNN_CLIP_GLOBAL_NORM) {
-    const float norm = (float)sqrt(opt_sum_partials(T->p.partials, 0, T->p.total_parts, red));
-    // clip_by_global_norm: clip_norm * minimum(1 / use_norm, 1 / clip_norm), NaN when the norm is not finite
-    c.scale = isfinite(norm) ? c.c * fminf(1.f / norm, 1.f / c.c) : __builtin_nanf("");
-  }
+  const OptCoef c = opt_coefficients<KIND>(&T->p, it, E->part0, E->nparts, red);
 
   float* __restrict__ w = E->w;
   const float* __restrict__ g = E->g;
@@ -286,20 +356,140 @@ __global__ void __launch_bounds__(OPT_THREADS) opt_update_kernel(OptTable table)
     }
   }
 
-  if (T->p.advance) {
-    // the ticket: the workgroup that arrives last has seen every other one read the counter and advances it; it resets the
-    // ticket for the next call.  Relaxed: what orders a workgroup's read of the counter before its add is that thread 0 has
-    // consumed the value (LDS store + barrier above); the update's own stores need no ordering (the next reader is another
-    // launch), and a release here would write the L2 back once per workgroup (buffer_wbl2; measured: it doubled the call's time).
-    if (threadIdx.x == 0) {
-      unsigned long long* st = T->p.state;
-      const unsigned long long t = __hip_atomic_fetch_add(st + 1, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (t == (unsigned long long)T->p.blocks - 1) {
-        __hip_atomic_store(st + 1, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(st, it + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  opt_advance(&T->p, it);
+}
+
+// ---- the row update: one launch for every row tensor of a call (include/tfgnn.h "The row-sparse step") ----
+// A workgroup takes rows_per_tile rows of grad_rows.  One thread per row reads the row's id, checks it against N and leaves it
+// in LDS (-1: skipped, *bad set); then the whole workgroup walks the tile's floats, consecutive lanes on consecutive float4 of
+// a row (without float4 accesses: on consecutive quads of the gradient's flat index space, see there): w, g and the slots are
+// loaded, then opt_elem runs, then w and the slots are stored.  The ids are distinct and every element has one owner, so no
+// two threads of the launch touch the same element: plain stores.  Table and slot offsets are 64-bit (N * cols may pass 2^31);
+// every access is to a row < N (value, slots) or < n (grad_rows, ids) and a column < cols.
+template <int KIND>
+__global__ void __launch_bounds__(OPT_THREADS) opt_update_rows_kernel(OptRowTable table) {
+  (void)table;
+  __shared__ double red[OPT_THREADS / 64];
+  __shared__ int32_t dst_rows[OPT_THREADS + 3];
+  __shared__ unsigned long long it_shared;
+  const opt_row_table_cptr T = (opt_row_table_cptr)__builtin_amdgcn_kernarg_segment_ptr();
+  const uint32_t b = blockIdx.x;
+  const int n_t = T->p.n;
+  int k = 0;
+  while (k + 1 < n_t && b >= T->r[k + 1].blk0) ++k;
+  const opt_row_entry_cptr E = &T->r[k];
+
+  // the counter is read by the thread that later takes the ticket, as in opt_update_kernel
+  if (threadIdx.x == 0) it_shared = __hip_atomic_load(T->p.state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const uint32_t rows_per_tile = n_t > 0 ? E->rows_per_tile : 0u;
+  const uint32_t r0 = (b - (n_t > 0 ? E->blk0 : 0u)) * rows_per_tile;  // < n < 2^31
+  const uint32_t rows = n_t > 0 ? min(rows_per_tile, E->n - r0) : 0u;
+  // the tile's ids and, for a quad that starts in the tile and ends in the next rows, up to three more (rows_per_tile <= OPT_THREADS)
+  const uint32_t ids_in_lds = rows > 0 ? min(rows + 3u, E->n - r0) : 0u;
+  for (uint32_t i = threadIdx.x; i < ids_in_lds; i += OPT_THREADS) {
+    int32_t id = E->ids[r0 + i];
+    if ((uint32_t)id >= E->N) {
+      id = -1;
+      if (E->bad) *E->bad = 1;
+    }
+    dst_rows[i] = id;
+  }
+  __syncthreads();
+  const unsigned long long it = it_shared;
+  if (rows > 0) {  // uniform over the workgroup
+    const OptCoef c = opt_coefficients<KIND>(&T->p, it, E->part0, E->nparts, red);
+    float* __restrict__ w = E->w;
+    float* __restrict__ s0 = E->s0;
+    float* __restrict__ s1 = E->s1;
+    const int64_t ldw = E->ldw, ldg = E->ldg, cols = E->cols;
+    const float* __restrict__ g = E->g + (int64_t)r0 * ldg;  // local rows from here on
+    if (E->vec) {
+      const uint32_t F4 = E->cols >> 2;
+      const uint32_t cnt = rows * F4;  // <= the tile, or one row of cols < 2^31 floats
+      for (uint32_t e = threadIdx.x; e < cnt; e += OPT_THREADS) {
+        const uint32_t row = e / F4, c4 = (e - row * F4) * 4u;
+        const int32_t d = dst_rows[row];
+        if (d < 0) continue;
+        float* wp = w + ((int64_t)d * ldw + c4);
+        const int64_t so = (int64_t)d * cols + c4;
+        float4 wv = *reinterpret_cast<const float4*>(wp);  // every load first
+        const float4 gv = *reinterpret_cast<const float4*>(g + ((int64_t)row * ldg + c4));
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), v = a;
+        if (opt_has_s0(KIND)) a = *reinterpret_cast<const float4*>(s0 + so);
+        if (opt_has_s1(KIND)) v = *reinterpret_cast<const float4*>(s1 + so);
+        opt_elem<KIND>(wv.x, gv.x, a.x, v.x, c);
+        opt_elem<KIND>(wv.y, gv.y, a.y, v.y, c);
+        opt_elem<KIND>(wv.z, gv.z, a.z, v.z, c);
+        opt_elem<KIND>(wv.w, gv.w, a.w, v.w, c);
+        *reinterpret_cast<float4*>(wp) = wv;
+        if (opt_has_s0(KIND)) *reinterpret_cast<float4*>(s0 + so) = a;
+        if (opt_has_s1(KIND)) *reinterpret_cast<float4*>(s1 + so) = v;
+      }
+    } else {
+      // Without float4 accesses.  opt_update_kernel computes the elements of an aligned contiguous tensor four at a time and
+      // the last numel % 4 (and every element of a tensor it cannot read as float4) one at a time, and the compiler contracts
+      // the two forms of opt_elem differently.  The element arithmetic here is that of the dense step at the element's place in
+      // the [n, cols] gradient: quads of four consecutive elements of its flat index space (they may cross rows), then the
+      // rest one at a time.  A workgroup owns the quads that START in its tile and the single elements of its tile.
+      const uint32_t F = E->cols;
+      const uint32_t e_lo = r0 * F, e_hi = e_lo + rows * F;  // the tile's flat range: n * cols < 2^31
+      const uint32_t quad_end = min(e_hi, E->quad_elems);     // elements below quad_elems (a multiple of 4) go in quads
+      for (uint32_t e0 = ((e_lo + 3u) & ~3u) + 4u * threadIdx.x; e0 < quad_end; e0 += 4u * OPT_THREADS) {
+        uint32_t row = e0 / F - r0, col = e0 - (row + r0) * F;  // row: local, below rows + 3 (ids_in_lds)
+        float* wp[4];
+        int64_t so[4];
+        float4 wv, gv, a = make_float4(0.f, 0.f, 0.f, 0.f), v = a;
+        float* const wq[4] = {&wv.x, &wv.y, &wv.z, &wv.w};
+        float* const gq[4] = {&gv.x, &gv.y, &gv.z, &gv.w};
+        float* const aq[4] = {&a.x, &a.y, &a.z, &a.w};
+        float* const vq[4] = {&v.x, &v.y, &v.z, &v.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {  // every load first
+          const int32_t d = dst_rows[row];
+          wp[j] = d >= 0 ? w + ((int64_t)d * ldw + col) : nullptr;
+          so[j] = (int64_t)d * cols + col;
+          *wq[j] = *gq[j] = 0.f;
+          if (d >= 0) {
+            *wq[j] = *wp[j];
+            *gq[j] = g[(int64_t)row * ldg + col];
+            if (opt_has_s0(KIND)) *aq[j] = s0[so[j]];
+            if (opt_has_s1(KIND)) *vq[j] = s1[so[j]];
+          }
+          if (++col == F) {
+            col = 0;
+            ++row;
+          }
+        }
+        opt_elem<KIND>(wv.x, gv.x, a.x, v.x, c);
+        opt_elem<KIND>(wv.y, gv.y, a.y, v.y, c);
+        opt_elem<KIND>(wv.z, gv.z, a.z, v.z, c);
+        opt_elem<KIND>(wv.w, gv.w, a.w, v.w, c);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (wp[j]) {
+            *wp[j] = *wq[j];
+            if (opt_has_s0(KIND)) s0[so[j]] = *aq[j];
+            if (opt_has_s1(KIND)) s1[so[j]] = *vq[j];
+          }
+        }
+      }
+      for (uint32_t e = max(e_lo, E->quad_elems) + threadIdx.x; e < e_hi; e += OPT_THREADS) {
+        const uint32_t row = e / F - r0, col = e - (row + r0) * F;
+        const int32_t d = dst_rows[row];
+        if (d < 0) continue;
+        float* wp = w + ((int64_t)d * ldw + col);
+        const int64_t so = (int64_t)d * cols + col;
+        float wv = *wp;
+        const float gv = g[(int64_t)row * ldg + col];
+        float a = opt_has_s0(KIND) ? s0[so] : 0.f, v = opt_has_s1(KIND) ? s1[so] : 0.f;
+        opt_elem<KIND>(wv, gv, a, v, c);
+        *wp = wv;
+        if (opt_has_s0(KIND)) s0[so] = a;
+        if (opt_has_s1(KIND)) s1[so] = v;
       }
     }
   }
+  opt_advance(&T->p, it);
 }
 
 __global__ void opt_iterations_get_kernel(const long long* state, long long* out) { *out = state[0]; }
@@ -362,17 +552,78 @@ static size_t opt_workspace_bytes(const OptPlan& plan, int clip) {
   return (size_t)plan.total_parts * sizeof(double);
 }
 
-}  // namespace tfgnn
+// the row tensors of a call: per tensor its entry of the row-update launch and - as the [n, cols] tensor grad_rows is - its
+// entry of the squared-sum pass, after the dense tensors of `plan` (tensors with n == 0 dropped)
+struct OptRowPlan {
+  std::vector<OptRowEntry> r;
+  std::vector<OptEntry> sum;
+  uint32_t blocks = 0;
+};
 
-extern "C" size_t tfgnn_optimizer_workspace_bytes(const tfgnn_opt_tensor* tensors, int n, int clip) {
-  using namespace tfgnn;
-  OptPlan plan;
-  if (opt_plan(tensors, n, TFGNN_OPT_SGD, 0.f, plan) != TFGNN_OK) return 0;
-  return opt_workspace_bytes(plan, clip);
+static int opt_plan_rows(const tfgnn_opt_row_tensor* t, int n_rows, int kind, float momentum, OptPlan& plan, OptRowPlan& rows) {
+  constexpr int64_t kLimit = (int64_t)1 << 31;
+  TFGNN_REQUIRE(n_rows >= 0 && (n_rows == 0 || t != nullptr), "tfgnn_optimizer: bad row tensor list (n_rows = %d)", n_rows);
+  TFGNN_REQUIRE(n_rows <= OPT_ROW_CHUNK, "tfgnn_optimizer: %d row tensors (at most %d to a call)", n_rows, OPT_ROW_CHUNK);
+  const bool need0 = kind != TFGNN_OPT_SGD || momentum > 0.f;
+  const bool need1 = kind == TFGNN_OPT_ADAM || (kind == TFGNN_OPT_RMSPROP && momentum > 0.f);
+  uint64_t blocks = 0;
+  for (int i = 0; i < n_rows; ++i) {
+    const tfgnn_opt_row_tensor& d = t[i];
+    TFGNN_REQUIRE(d.n >= 0 && d.N >= 0, "tfgnn_optimizer: row tensor %d has a negative size", i);
+    TFGNN_REQUIRE(d.cols >= 1 && d.cols < kLimit, "tfgnn_optimizer: row tensor %d: cols must be in [1, 2^31)", i);
+    TFGNN_REQUIRE(d.N < kLimit, "tfgnn_optimizer: row tensor %d: 2^31 or more table rows (int32 ids)", i);
+    TFGNN_REQUIRE(d.n <= d.N, "tfgnn_optimizer: row tensor %d: more rows than the table has (the ids are distinct)", i);
+    TFGNN_REQUIRE(d.ld_value >= d.cols && d.ld_grad >= d.cols,
+                  "tfgnn_optimizer: row tensor %d: row pitches %lld / %lld below the width %lld", i, (long long)d.ld_value,
+                  (long long)d.ld_grad, (long long)d.cols);
+    TFGNN_REQUIRE(d.ld_grad < (1ll << 32), "tfgnn_optimizer: row tensor %d: gradient row pitch too large", i);
+    const int64_t numel = d.n * d.cols;  // < 2^62
+    TFGNN_REQUIRE(numel < kLimit, "tfgnn_optimizer: row tensor %d: its gradient has %lld elements (at most 2^31 - 1)", i,
+                  (long long)numel);
+    if (d.n == 0) continue;
+    TFGNN_REQUIRE(d.value && d.grad_rows && d.ids, "tfgnn_optimizer: row tensor %d: NULL value, gradient rows or ids", i);
+    TFGNN_REQUIRE((!need0 || d.slot0) && (!need1 || d.slot1), "tfgnn_optimizer: row tensor %d: NULL slot the optimizer needs", i);
+    OptRowEntry e{};
+    e.w = d.value;
+    e.g = d.grad_rows;
+    e.ids = d.ids;
+    e.s0 = need0 ? d.slot0 : nullptr;
+    e.s1 = need1 ? d.slot1 : nullptr;
+    e.bad = d.bad_flag;
+    e.ldw = d.ld_value;
+    e.ldg = d.ld_grad;
+    e.n = (uint32_t)d.n;
+    e.N = (uint32_t)d.N;
+    e.cols = (uint32_t)d.cols;
+    e.rows_per_tile = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(OPT_THREADS, OPT_ROW_TILE_ELEMS / d.cols));
+    e.vec = d.cols % 4 == 0 && d.ld_value % 4 == 0 && d.ld_grad % 4 == 0 && opt_aligned(e.w) && opt_aligned(e.g) &&
+            (!e.s0 || opt_aligned(e.s0)) && (!e.s1 || opt_aligned(e.s1));
+    e.blk0 = (uint32_t)blocks;
+    blocks += (uint64_t)ceil_div(d.n, e.rows_per_tile);
+    // the squared-sum entry: what opt_plan makes of the gradient of a contiguous, aligned [n, cols] variable
+    OptEntry q{};
+    q.g = d.grad_rows;
+    q.n = (uint32_t)numel;
+    const bool contiguous = d.n == 1 || d.ld_grad == d.cols;
+    q.cols = contiguous ? q.n : (uint32_t)d.cols;
+    q.ldw = q.cols;
+    q.ldg = contiguous ? q.n : (uint32_t)d.ld_grad;
+    q.vec = opt_aligned(q.g) && (contiguous || (q.cols % 4 == 0 && q.ldg % 4 == 0));
+    q.nparts = (uint32_t)ceil_div(numel, OPT_SUM_ELEMS);
+    q.part0 = (uint32_t)plan.total_parts;
+    plan.total_parts += q.nparts;
+    e.part0 = q.part0;
+    e.nparts = q.nparts;
+    e.quad_elems = q.vec ? (q.n & ~3u) : 0u;
+    rows.r.push_back(e);
+    rows.sum.push_back(q);
+  }
+  TFGNN_REQUIRE(plan.total_parts < (1ull << 31) && blocks < (1ull << 31), "tfgnn_optimizer: too many elements");
+  rows.blocks = (uint32_t)blocks;
+  return TFGNN_OK;
 }
 
-extern "C" int tfgnn_optimizer_apply(const tfgnn_opt_tensor* tensors, int n, const tfgnn_opt_config* cfg, void* stream) {
-  using namespace tfgnn;
+static int opt_check_config(const tfgnn_opt_config* cfg) {
   TFGNN_REQUIRE(cfg != nullptr && cfg->struct_size == sizeof(tfgnn_opt_config),
                 "tfgnn_optimizer_apply: config missing or of another size (struct_size %zu, expected %zu)",
                 cfg ? cfg->struct_size : (size_t)0, sizeof(tfgnn_opt_config));
@@ -384,22 +635,23 @@ extern "C" int tfgnn_optimizer_apply(const tfgnn_opt_tensor* tensors, int n, con
   TFGNN_REQUIRE(c.momentum >= 0.f && c.momentum <= 1.f, "tfgnn_optimizer_apply: momentum %g outside [0, 1]", (double)c.momentum);
   TFGNN_REQUIRE(c.schedule == 0 || c.schedule == 1, "tfgnn_optimizer_apply: unknown schedule %d", c.schedule);
   TFGNN_REQUIRE(c.state != nullptr && opt_aligned(c.state), "tfgnn_optimizer_apply: NULL or unaligned state");
-  OptPlan plan;
-  const int st = opt_plan(tensors, n, c.kind, c.momentum, plan);
-  if (st != TFGNN_OK) return st;
-  TFGNN_REQUIRE(!plan.e.empty(), "tfgnn_optimizer_apply: no elements to update");
-  const size_t ws = opt_workspace_bytes(plan, c.clip);
+  return TFGNN_OK;
+}
+
+static int opt_check_workspace(const tfgnn_opt_config& c, size_t ws) {
   TFGNN_REQUIRE(ws == 0 || (c.workspace && opt_aligned(c.workspace) && c.workspace_bytes >= ws),
                 "tfgnn_optimizer_apply: the norm modes need a 16-byte aligned workspace of %zu bytes (got %zu)", ws,
                 c.workspace ? c.workspace_bytes : (size_t)0);
+  return TFGNN_OK;
+}
 
-  int kk;
-  if (c.kind == TFGNN_OPT_SGD) kk = c.momentum > 0.f ? OPT_K_SGD_MOM : OPT_K_SGD;
-  else if (c.kind == TFGNN_OPT_RMSPROP) kk = c.momentum > 0.f ? OPT_K_RMS_MOM : OPT_K_RMS;
-  else kk = OPT_K_ADAM;
+static int opt_kernel_kind(const tfgnn_opt_config& c) {
+  if (c.kind == TFGNN_OPT_SGD) return c.momentum > 0.f ? OPT_K_SGD_MOM : OPT_K_SGD;
+  if (c.kind == TFGNN_OPT_RMSPROP) return c.momentum > 0.f ? OPT_K_RMS_MOM : OPT_K_RMS;
+  return OPT_K_ADAM;
+}
 
-  OptTable tab{};
-  OptParams& p = tab.p;
+static void opt_fill_params(const tfgnn_opt_config& c, const OptPlan& plan, OptParams& p) {
   p.kind = c.kind;
   p.clip = c.clip;
   p.clip_value = c.clip_value;
@@ -418,11 +670,17 @@ extern "C" int tfgnn_optimizer_apply(const tfgnn_opt_tensor* tensors, int n, con
   p.state = (unsigned long long*)c.state;
   p.partials = (double*)c.workspace;
   p.total_parts = (uint32_t)plan.total_parts;
+}
 
-  const size_t ne = plan.e.size();
-  const hipStream_t s = (hipStream_t)stream;
-  for (int phase = ws ? 0 : 1; phase < 2; ++phase) {
-    for (size_t first = 0; first < ne; first += OPT_CHUNK) {
+// the launches of the dense tensors: with `sums` the squared-sum pass first (the row tensors' entries `row_sums` ride in the
+// launch of the last chunk, or have one of their own when there is no dense tensor), then the update, one launch per chunk;
+// the last update launch takes the ticket when `advance`
+static int opt_launch_dense(const OptPlan& plan, const std::vector<OptEntry>* row_sums, OptTable& tab, int kk, bool sums,
+                            bool advance, hipStream_t s) {
+  OptParams& p = tab.p;
+  const size_t ne = plan.e.size(), nr = row_sums ? row_sums->size() : 0;
+  for (int phase = sums ? 0 : 1; phase < 2; ++phase) {
+    for (size_t first = 0; first < ne || (phase == 0 && first == 0 && nr); first += OPT_CHUNK) {
       const size_t last = std::min(ne, first + OPT_CHUNK);
       p.n = (int)(last - first);
       uint32_t blocks = 0;
@@ -431,12 +689,25 @@ extern "C" int tfgnn_optimizer_apply(const tfgnn_opt_tensor* tensors, int n, con
         tab.e[i - first].blk0 = blocks;
         blocks += phase == 0 ? plan.e[i].nparts : plan.upd_blocks[i];
       }
-      p.part_base = plan.e[first].part0;
-      p.blocks = blocks;
-      p.advance = phase == 1 && last == ne;
-      if (phase == 0) {
+      p.part_base = first < ne ? plan.e[first].part0 : 0;
+      p.advance = phase == 1 && last == ne && advance;
+      if (phase == 0 && last == ne && nr) {
+        OptSumRowsTable big{};
+        for (size_t i = 0; i < last - first; ++i) big.e[i] = tab.e[i];
+        for (size_t i = 0; i < nr; ++i) {
+          big.e[last - first + i] = (*row_sums)[i];
+          blocks += (*row_sums)[i].nparts;
+        }
+        if (first == ne) p.part_base = (*row_sums)[0].part0;
+        p.n += (int)nr;
+        p.blocks = blocks;
+        big.p = p;
+        hipLaunchKernelGGL(opt_sumsq_rows_kernel, dim3(blocks), dim3(OPT_THREADS), 0, s, big);
+      } else if (phase == 0) {
+        p.blocks = blocks;
         hipLaunchKernelGGL(opt_sumsq_kernel, dim3(blocks), dim3(OPT_THREADS), 0, s, tab);
       } else {
+        p.blocks = blocks;
         switch (kk) {
           case OPT_K_SGD: hipLaunchKernelGGL(opt_update_kernel<OPT_K_SGD>, dim3(blocks), dim3(OPT_THREADS), 0, s, tab); break;
           case OPT_K_SGD_MOM: hipLaunchKernelGGL(opt_update_kernel<OPT_K_SGD_MOM>, dim3(blocks), dim3(OPT_THREADS), 0, s, tab); break;
@@ -449,6 +720,86 @@ extern "C" int tfgnn_optimizer_apply(const tfgnn_opt_tensor* tensors, int n, con
       g_opt_launches.fetch_add(1, std::memory_order_relaxed);
     }
   }
+  return TFGNN_OK;
+}
+
+}  // namespace tfgnn
+
+extern "C" size_t tfgnn_optimizer_workspace_bytes(const tfgnn_opt_tensor* tensors, int n, int clip) {
+  using namespace tfgnn;
+  OptPlan plan;
+  if (opt_plan(tensors, n, TFGNN_OPT_SGD, 0.f, plan) != TFGNN_OK) return 0;
+  return opt_workspace_bytes(plan, clip);
+}
+
+extern "C" int tfgnn_optimizer_apply(const tfgnn_opt_tensor* tensors, int n, const tfgnn_opt_config* cfg, void* stream) {
+  using namespace tfgnn;
+  int st = opt_check_config(cfg);
+  if (st != TFGNN_OK) return st;
+  const tfgnn_opt_config& c = *cfg;
+  OptPlan plan;
+  st = opt_plan(tensors, n, c.kind, c.momentum, plan);
+  if (st != TFGNN_OK) return st;
+  TFGNN_REQUIRE(!plan.e.empty(), "tfgnn_optimizer_apply: no elements to update");
+  const size_t ws = opt_workspace_bytes(plan, c.clip);
+  st = opt_check_workspace(c, ws);
+  if (st != TFGNN_OK) return st;
+  OptTable tab{};
+  opt_fill_params(c, plan, tab.p);
+  return opt_launch_dense(plan, nullptr, tab, opt_kernel_kind(c), ws != 0, true, (hipStream_t)stream);
+}
+
+extern "C" size_t tfgnn_optimizer_rows_workspace_bytes(const tfgnn_opt_tensor* tensors, int n, const tfgnn_opt_row_tensor* row_tensors,
+                                                       int n_rows, int clip) {
+  using namespace tfgnn;
+  OptPlan plan;
+  OptRowPlan rows;
+  if (opt_plan(tensors, n, TFGNN_OPT_SGD, 0.f, plan) != TFGNN_OK) return 0;
+  if (opt_plan_rows(row_tensors, n_rows, TFGNN_OPT_SGD, 0.f, plan, rows) != TFGNN_OK) return 0;
+  return opt_workspace_bytes(plan, clip);
+}
+
+extern "C" int tfgnn_optimizer_apply_rows(const tfgnn_opt_tensor* tensors, int n, const tfgnn_opt_row_tensor* row_tensors, int n_rows,
+                                          const tfgnn_opt_config* cfg, void* stream) {
+  using namespace tfgnn;
+  int st = opt_check_config(cfg);
+  if (st != TFGNN_OK) return st;
+  const tfgnn_opt_config& c = *cfg;
+  OptPlan plan;
+  OptRowPlan rows;
+  st = opt_plan(tensors, n, c.kind, c.momentum, plan);
+  if (st != TFGNN_OK) return st;
+  st = opt_plan_rows(row_tensors, n_rows, c.kind, c.momentum, plan, rows);
+  if (st != TFGNN_OK) return st;
+  const size_t ws = opt_workspace_bytes(plan, c.clip);
+  st = opt_check_workspace(c, ws);
+  if (st != TFGNN_OK) return st;
+  const int kk = opt_kernel_kind(c);
+  const hipStream_t s = (hipStream_t)stream;
+  // the row launch is the call's last and takes the ticket; without a row to update the last dense launch keeps it, and a call
+  // with nothing at all to update advances the counter with one workgroup of the row launch
+  const bool row_launch = rows.blocks > 0 || plan.e.empty();
+  OptTable tab{};
+  opt_fill_params(c, plan, tab.p);
+  st = opt_launch_dense(plan, &rows.sum, tab, kk, ws != 0, !row_launch, s);
+  if (st != TFGNN_OK || !row_launch) return st;
+  OptRowTable rt{};
+  rt.p = tab.p;
+  rt.p.n = (int)rows.r.size();
+  rt.p.part_base = 0;
+  rt.p.blocks = std::max(rows.blocks, 1u);
+  rt.p.advance = 1;
+  for (size_t i = 0; i < rows.r.size(); ++i) rt.r[i] = rows.r[i];
+  const dim3 grid(rt.p.blocks), block(OPT_THREADS);
+  switch (kk) {
+    case OPT_K_SGD: hipLaunchKernelGGL(opt_update_rows_kernel<OPT_K_SGD>, grid, block, 0, s, rt); break;
+    case OPT_K_SGD_MOM: hipLaunchKernelGGL(opt_update_rows_kernel<OPT_K_SGD_MOM>, grid, block, 0, s, rt); break;
+    case OPT_K_RMS: hipLaunchKernelGGL(opt_update_rows_kernel<OPT_K_RMS>, grid, block, 0, s, rt); break;
+    case OPT_K_RMS_MOM: hipLaunchKernelGGL(opt_update_rows_kernel<OPT_K_RMS_MOM>, grid, block, 0, s, rt); break;
+    default: hipLaunchKernelGGL(opt_update_rows_kernel<OPT_K_ADAM>, grid, block, 0, s, rt); break;
+  }
+  TFGNN_LAUNCH_CHECK();
+  g_opt_launches.fetch_add(1, std::memory_order_relaxed);
   return TFGNN_OK;
 }
 

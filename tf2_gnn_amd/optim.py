@@ -8,6 +8,10 @@ updates every variable: clipping, the slot updates and the weight write are one 
 norm modes).  The learning rate is computed on the device from the step counter ``iterations``, which the call advances on
 the device: a step captured with ``CapturedStep`` (forward + metrics + backward + ``apply_gradients``) is one complete training
 iteration per replay and follows the schedule.
+
+A gradient may also be a ``RowGradient`` - the rows of a lookup and their ids, the counterpart of ``tf.IndexedSlices`` - and then
+the call is ``tfgnn_optimizer_apply_rows``: the listed rows of the variable and of its slots get the dense step's arithmetic,
+every other row is neither read nor written (the LAZY variant of the optimizer: see ``RowGradient``).
 """
 from __future__ import annotations
 
@@ -79,6 +83,53 @@ def _rows(t: torch.Tensor) -> Optional[Tuple[int, int, int]]:
     return t.numel() // max(cols, 1), cols, t.stride(-2)
 
 
+class RowGradient:
+    """The gradient of a row lookup ``table[ids]`` (``ops.gather_node_rows``) against a table of ``num_rows`` rows, kept as the
+    pair it is: ``rows`` float32 [n, D] (unit inner stride, any row pitch >= D) and ``ids`` int32 [n], DISTINCT by precondition
+    (the neighbour sampler guarantees it).  It stands for the dense [num_rows, D] gradient that is ``rows[i]`` at row
+    ``ids[i]`` and zero elsewhere - ``tf.IndexedSlices`` without repeated indices.
+
+    ``Optimizer.apply_gradients`` updates the listed rows only (tfgnn_optimizer_apply_rows): their values and slots get exactly
+    the dense step's arithmetic, all other rows and their slots are not touched.  For plain SGD (momentum 0) that IS the dense
+    step.  For SGD with momentum, RMSprop and Adam it is the lazy variant (LazyAdam / SparseAdam): the moments of rows without
+    a gradient do not decay and those rows do not move, where the dense step would keep moving them along their old moments.
+    An id outside [0, num_rows) skips its row and sets ``bad_flag`` (a zeroed int32 [1] on the device, optional)."""
+
+    def __init__(self, rows: torch.Tensor, ids: torch.Tensor, num_rows: int, bad_flag: Optional[torch.Tensor] = None):
+        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float32 or rows.dim() != 2:
+            raise ValueError("RowGradient: rows must be a float32 [n, D] tensor")
+        if rows.shape[1] < 1 or (rows.shape[1] > 1 and rows.stride(1) != 1) or (rows.shape[0] > 1 and rows.stride(0) < rows.shape[1]):
+            raise ValueError(f"RowGradient: rows must have D >= 1 columns at unit stride and a row pitch >= D (shape "
+                             f"{tuple(rows.shape)}, strides {tuple(rows.stride())})")
+        if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or ids.dim() != 1 or (ids.shape[0] > 1 and ids.stride(0) != 1):
+            raise ValueError("RowGradient: ids must be a contiguous int32 [n] tensor")
+        if ids.shape[0] != rows.shape[0]:
+            raise ValueError(f"RowGradient: {int(ids.shape[0])} ids for {int(rows.shape[0])} rows")
+        if ids.device != rows.device:
+            raise ValueError(f"RowGradient: rows on {rows.device}, ids on {ids.device}")
+        if isinstance(num_rows, bool) or not isinstance(num_rows, (int, np.integer)) or not 0 <= num_rows < 2 ** 31:
+            raise ValueError(f"RowGradient: num_rows must be an integer in [0, 2^31), not {num_rows!r}")
+        if rows.shape[0] > num_rows:
+            raise ValueError(f"RowGradient: {int(rows.shape[0])} rows for a table of {int(num_rows)} (the ids are distinct)")
+        if bad_flag is not None and (not isinstance(bad_flag, torch.Tensor) or bad_flag.dtype != torch.int32 or bad_flag.numel() != 1
+                                     or bad_flag.device != rows.device):
+            raise ValueError("RowGradient: bad_flag must be an int32 tensor of one element on the device of rows")
+        self.rows, self.ids, self.num_rows, self.bad_flag = rows, ids, int(num_rows), bad_flag
+
+    @property
+    def shape(self) -> Tuple[int, int]:
+        """the shape of the dense gradient it stands for"""
+        return (self.num_rows, int(self.rows.shape[1]))
+
+    @property
+    def device(self):
+        return self.rows.device
+
+    def to_dense(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """the dense [num_rows, D] gradient (ops.embedding_scatter_rows: a fill and a scatter)"""
+        return ops.embedding_scatter_rows(self.rows, self.ids, self.num_rows, out=out, bad_flag=self.bad_flag)
+
+
 class Optimizer:
     """A Keras optimizer (SGD, RMSprop, Adam) over this package's ``Variable``s.  ``learning_rate``: a float or a
     ``PolynomialWarmupAndDecaySchedule``.  Slots are allocated at the first update of a variable and start at zero."""
@@ -142,8 +193,10 @@ class Optimizer:
     def apply_gradients(self, pairs: Iterable[Tuple[Any, Optional[torch.Tensor]]], clip: Optional[Tuple[str, float]] = None) -> None:
         """Update every variable of ``pairs`` - ``(variable, grad)`` as ``GraphTaskModel.backward()`` returns them, or Keras'
         ``(grad, variable)`` - in one library call on the current stream.  Pairs whose gradient is None are dropped (no slot
-        update, not part of the global norm).  ``clip``: None, ``("value", c)``, ``("norm", c)`` or ``("global_norm", c)``,
-        applied to the gradients first (graph_task_model.py:296-322).  Does not synchronise: it can be captured."""
+        update, not part of the global norm).  A gradient may be a ``RowGradient``: its variable's listed rows are updated and
+        no others, in the same call (tfgnn_optimizer_apply_rows; without one the call is tfgnn_optimizer_apply).  ``clip``:
+        None, ``("value", c)``, ``("norm", c)`` or ``("global_norm", c)``, applied to the gradients first
+        (graph_task_model.py:296-322).  Does not synchronise: it can be captured."""
         from .layers.message_passing.message_passing import Variable
 
         mode = _CLIP_MODES.get(clip[0] if clip is not None else None)
@@ -158,9 +211,21 @@ class Optimizer:
             raise ValueError("No gradients provided for any variable.")
         dev = live[0][0].value.device
         state = self._ensure_state(dev)
-        rows = np.empty((len(live), 8), dtype=np.int64)
+        dense = [(var, grad) for var, grad in live if not isinstance(grad, RowGradient)]
+        sparse = [(var, grad) for var, grad in live if isinstance(grad, RowGradient)]
+        rows = np.empty((len(dense), 8), dtype=np.int64)
         bases = {}
-        for i, (var, grad) in enumerate(live):
+
+        def slots_of(var, w):
+            hit = self._slots.get(id(var))
+            if hit is None or hit[0] is not var:
+                hit = (var, [torch.zeros(w.numel(), dtype=torch.float32, device=dev) for _ in range(self._nslots)])
+                self._slots[id(var)] = hit
+            base = w._base if w._base is not None else w
+            bases.setdefault(base.data_ptr(), w)
+            return hit[1] + [None, None]
+
+        for i, (var, grad) in enumerate(dense):
             w = var.value
             if tuple(grad.shape) != tuple(w.shape):
                 raise ValueError(f"gradient of {var.name} has shape {tuple(grad.shape)}, the variable {tuple(w.shape)}")
@@ -169,25 +234,46 @@ class Optimizer:
             lw, lg = _rows(w), _rows(grad)
             if lw is None or lg is None or lw[:2] != lg[:2]:
                 raise ValueError(f"{var.name}: value and gradient must be row-major views with unit inner stride")
-            hit = self._slots.get(id(var))
-            if hit is None or hit[0] is not var:
-                hit = (var, [torch.zeros(w.numel(), dtype=torch.float32, device=dev) for _ in range(self._nslots)])
-                self._slots[id(var)] = hit
-            s = hit[1] + [None, None]
+            s = slots_of(var, w)
             rows[i] = (w.data_ptr(), lw[2], grad.data_ptr(), lg[2], lw[0], lw[1],
                        s[0].data_ptr() if s[0] is not None else 0, s[1].data_ptr() if s[1] is not None else 0)
-            base = w._base if w._base is not None else w
-            bases.setdefault(base.data_ptr(), w)
         lib = _lib.load()
         cfg = self._cfg
         cfg.clip, cfg.clip_value = mode, float(clip[1]) if clip is not None else 0.0
         cfg.state = state.data_ptr()
-        ws_bytes = lib.tfgnn_optimizer_workspace_bytes(rows.ctypes.data, len(live), mode)
+        if sparse:
+            if len(sparse) > _lib.OPT_MAX_ROW_TENSORS:
+                raise ValueError(f"{len(sparse)} row gradients in one call (at most {_lib.OPT_MAX_ROW_TENSORS})")
+            row_tensors = (_lib.OptRowTensor * len(sparse))()
+            for r, (var, grad) in zip(row_tensors, sparse):
+                w = var.value
+                if w.dim() != 2 or tuple(grad.shape) != tuple(w.shape) or (w.shape[1] > 1 and w.stride(1) != 1) or (
+                        w.shape[0] > 1 and w.stride(0) < w.shape[1]):
+                    raise ValueError(f"row gradient of {var.name} stands for shape {tuple(grad.shape)}, the variable is "
+                                     f"{tuple(w.shape)} (a 2-D row-major table with unit inner stride)")
+                ops._require_dev(w, torch.float32, var.name)
+                ops._require_dev(grad.rows, torch.float32, f"row gradient of {var.name}")
+                ops._require_dev(grad.ids, torch.int32, f"ids of the row gradient of {var.name}")
+                s = slots_of(var, w)
+                n, cols = int(grad.rows.shape[0]), int(w.shape[1])
+                r.value, r.ld_value = w.data_ptr(), max(int(w.stride(0)), cols) if w.shape[0] > 1 else cols
+                r.grad_rows, r.ld_grad = (grad.rows.data_ptr() if n else None), (int(grad.rows.stride(0)) if n > 1 else cols)
+                r.ids, r.n, r.N, r.cols = (grad.ids.data_ptr() if n else None), n, int(w.shape[0]), cols
+                r.slot0 = s[0].data_ptr() if s[0] is not None else None
+                r.slot1 = s[1].data_ptr() if s[1] is not None else None
+                r.bad_flag = grad.bad_flag.data_ptr() if grad.bad_flag is not None else None
+            ws_bytes = lib.tfgnn_optimizer_rows_workspace_bytes(rows.ctypes.data, len(dense), row_tensors, len(sparse), mode)
+        else:
+            ws_bytes = lib.tfgnn_optimizer_workspace_bytes(rows.ctypes.data, len(dense), mode)
         if ws_bytes and (self._workspace is None or self._workspace.numel() < ws_bytes):
             self._workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         cfg.workspace = self._workspace.data_ptr() if ws_bytes else None
         cfg.workspace_bytes = self._workspace.numel() if ws_bytes else 0
-        _lib.check(lib.tfgnn_optimizer_apply(rows.ctypes.data, len(live), ctypes.byref(cfg), ops._stream()))
+        if sparse:
+            _lib.check(lib.tfgnn_optimizer_apply_rows(rows.ctypes.data, len(dense), row_tensors, len(sparse), ctypes.byref(cfg),
+                                                      ops._stream()))
+        else:
+            _lib.check(lib.tfgnn_optimizer_apply(rows.ctypes.data, len(dense), ctypes.byref(cfg), ops._stream()))
         for w in bases.values():  # the weights changed behind torch's version counter: drop their derived forms, once per buffer
             ops.notify_weights_changed(w)
 

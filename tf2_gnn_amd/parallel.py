@@ -16,6 +16,8 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from .optim import RowGradient
+
 
 def init_distributed(backend: Optional[str] = None, device: Optional[torch.device] = None):
     """Initialise torch.distributed from the torchrun environment (RANK / WORLD_SIZE / MASTER_*).
@@ -171,8 +173,13 @@ def allreduce_gradients(variables, dist, average: bool = True, bucket_bytes: int
     collectives).  Returns the number of all-reduce calls issued."""
     if dist is None:
         return 0
-    world = dist.get_world_size()
     variables = list(variables)
+    for v in variables:  # before any collective: every rank refuses alike
+        if isinstance(v.grad, RowGradient):
+            raise ValueError(f"the gradient of {getattr(v, 'name', 'a variable')} is a RowGradient: ranks sample different ids, and a "
+                             'row gradient cannot be summed over ranks - train with node_embedding_update="dense" (multi-rank '
+                             "training with row gradients is not implemented)")
+    world = dist.get_world_size()
     for v in variables:
         if v.grad is None:
             v.grad = torch.zeros_like(v.value)

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .optim import Optimizer, make_optimizer
+from .optim import Optimizer, RowGradient, make_optimizer
 from .layers.gnn import GNN, GNNInput
 from .layers.message_passing.message_passing import Variable, default_device, glorot_uniform
 from .layers.nodes_to_graph_representation import (
@@ -83,7 +83,16 @@ class GraphTaskModel:
         asks the stack for its input gradient, which is the table's gradient - through ops.embedding_scatter_rows into a
         dense [num_nodes, node_embedding_dim] buffer on the sampled route - and the update is the optimizer's dense step, what
         Keras does with the IndexedSlices of a lookup: every row is updated, the moments of untouched rows decay.  A
-        full-batch step stays capturable.  A dataset without node features (``node_feature_shape == (0,)``) needs the key."""
+        full-batch step stays capturable.  A dataset without node features (``node_feature_shape == (0,)``) needs the key.
+
+        ``node_embedding_update`` (absent: ``"dense"``; in no defaults dictionary; needs ``node_embedding_dim``) chooses the
+        sampled route's update.  ``"dense"`` is the above: its cost is that of the whole table, every step.  ``"rows"`` keeps
+        the gradient as the pair it is: ``backward()`` returns ``optim.RowGradient(d_rows, sampled_node_ids, num_nodes)`` for
+        the table, no dense buffer is allocated and no embedding kernel runs, and the optimizer updates the batch's rows and
+        their slots only (tfgnn_optimizer_apply_rows).  Plain SGD gives the dense result; with momentum, RMSprop or Adam it
+        is the LAZY optimizer (LazyAdam): the moments of rows outside the batch do not decay and those rows do not move.  A
+        full batch has a gradient for every row and takes the dense route under either value.  Anything else raises
+        ValueError."""
         self._params = params
         if num_edge_types is None:
             if dataset is None or not hasattr(dataset, "num_edge_types"):
@@ -94,6 +103,12 @@ class GraphTaskModel:
         if dim is not None and (isinstance(dim, bool) or not isinstance(dim, (int, np.integer)) or dim < 1):
             raise ValueError(f"node_embedding_dim must be an integer >= 1 (or None: no learned node embeddings), not {dim!r}")
         self._node_embedding_dim = None if dim is None else int(dim)
+        update = params.get("node_embedding_update")
+        if update is not None and (not isinstance(update, str) or update not in ("dense", "rows")):
+            raise ValueError(f'node_embedding_update must be "dense" or "rows", not {update!r}')
+        if update is not None and dim is None:
+            raise ValueError("node_embedding_update is set without node_embedding_dim: there is no embedding table to update")
+        self._node_embedding_rows = update == "rows"
         self._num_nodes: Optional[int] = None
         self._node_embeddings: Optional[Variable] = None
         self._node_embeddings_grad: Optional[torch.Tensor] = None  # the sampled route's dense [num_nodes, dim] buffer
@@ -229,6 +244,8 @@ class GraphTaskModel:
             d_rows = self._gnn.backward(grad_final, need_input_grad=True, grad_all_representations=grad_all)
             if self._embedding_ids is None:
                 table.grad = d_rows
+            elif self._node_embedding_rows:  # the pair itself: the optimizer updates these rows and no others
+                table.grad = RowGradient(d_rows, self._embedding_ids, table.value.shape[0], bad_flag=self.embedding_bad_index)
             else:
                 self._node_embeddings_grad = table.grad = ops.embedding_scatter_rows(
                     d_rows, self._embedding_ids, table.value.shape[0], out=self._node_embeddings_grad,
