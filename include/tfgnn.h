@@ -1763,6 +1763,77 @@ int tfgnn_gather_node_rows(const tfgnn_gather_node_rows_args* args, void* stream
 int tfgnn_sample_launch_counts(int64_t* out_counts, int n);
 
 /* ------------------------------------------------------------------------------------------
+ * Triple batches (csrc/triple_batch.hip): one mini-batch of link-prediction triples, built on the device.  A chunk of a
+ * fold's positives plus fresh negatives becomes (a) the triples in global ids, (b) the DISTINCT endpoints in increasing
+ * id - the seed list tfgnn_neighbor_sample demands - and (c) the triples in the batch's local ids.  The sampler puts its
+ * seeds in rows 0 .. S - 1 of the sampled batch in the given order, so the rank of an endpoint in `seeds` IS its row in
+ * the sampled batch: local_triples index the model's output directly.
+ *
+ * Inputs: V = num_nodes; positives int32 [P, 3], rows (u, t, v) in global ids (the fold's positives, uploaded once);
+ * positive_ids int32 [B], the rows of this batch, in order (repeats allowed); K = negatives_per_positive >= 0; seed.
+ * Outputs (device int32), N = B (1 + K):
+ *   triples [N, 3]        rows 0 .. B - 1: triples[i] = positives[positive_ids[i]].  Rows B .. N - 1: exactly what
+ *                         tfgnn_triples_draw_negatives(seed, use_epoch = 0) writes for these B positives: negative j copies
+ *                         positive j / K of the batch and uses word(2 j), word(2 j + 1), the slot rule and the multiply-high
+ *                         draw that skips the old node ("Negative sampling and triple tables on the device" above).  A
+ *                         negative reads its positive from the store, not from this buffer.
+ *   seeds [seed_capacity] seeds[0 : S] = the distinct endpoints (u and v of all N rows) in increasing global id.
+ *   local_triples [N, 3]  (rank(u), t, rank(v)), rank = the position in `seeds`; the relation is copied.
+ *   meta [2]              {status, S}, for ONE device-to-host copy (the sampler needs S on the host).
+ * All of it is fixed, integers only: tests/triple_batch_reference.py restates every output bit for bit.
+ * Status bits:
+ *   TFGNN_TRIPLE_BATCH_SEED_OVERFLOW    more than seed_capacity distinct endpoints: S stops at the capacity, seeds holds the
+ *                                       seed_capacity smallest, an endpoint beyond them gets local id -1, and nothing is
+ *                                       written at or beyond a capacity.  min(2 N, V) always suffices.
+ *   TFGNN_TRIPLE_BATCH_BAD_POSITIVE_ID  a positive_ids entry outside [0, P): its row - and the rows of its negatives - are
+ *                                       (-1, -1, -1) in triples and in local_triples and contribute no seed.
+ *   TFGNN_TRIPLE_BATCH_BAD_ENDPOINT     an endpoint outside [0, V): triples keeps the value, it contributes no seed and its
+ *                                       local id is -1.
+ * Every access of the store and of the table goes through an index checked against its size.
+ *
+ * Workspace: tfgnn_triple_batch_workspace_bytes(V) bytes, 16-byte aligned (0 for V outside [1, 2^31)).  Its first V int32
+ * words are an id table under the sampler's convention: ALL -1 ON ENTRY - filled once by the caller - and LEFT ALL -1 ON
+ * EXIT, in every case, overflow included; the rest needs no initialisation.  A sampler workspace of at least this size
+ * serves (the sampler's table is its first V words, too).
+ *
+ * Exactly 6 launches on `stream`, whatever the sizes: (1) gather + draw + mark - the rows are written and
+ * table[endpoint] = a marker where it was -1, plain stores of one value, idempotent; (2) marked ids per chunk of 1024 ids;
+ * (3) ONE workgroup: scan of the chunk counts with a carry across rounds of 256 chunks, S, the overflow bit; (4) assign: a
+ * marked id takes its rank, seeds[rank] = id, table[id] = rank; (5) translate; (6) restore.  Grids are sized from B, K, V
+ * and the capacity; S exists on the device only.  No allocation, no copy, no host synchronisation, no float arithmetic; the
+ * only atomic is an OR into the status word.
+ * Refused on the host before any launch: NULL args or another struct_size; B < 1; K < 0; N > 2^30; P outside [1, 2^31);
+ * V outside [1, 2^31); V < 2 with K > 0; seed_capacity < 1; NULL pointers; a short or misaligned workspace.
+ *
+ * tfgnn_triple_batch_launch_counts: out[0] = kernel launches enqueued by tfgnn_triple_batch_build in this process (6 per
+ * call; a host counter); further slots are zero.
+ * ------------------------------------------------------------------------------------------ */
+#define TFGNN_TRIPLE_BATCH_SEED_OVERFLOW 1
+#define TFGNN_TRIPLE_BATCH_BAD_POSITIVE_ID 2
+#define TFGNN_TRIPLE_BATCH_BAD_ENDPOINT 4
+typedef struct tfgnn_triple_batch_args {
+  size_t struct_size;
+  int64_t num_nodes;              /* V */
+  int64_t num_positives;          /* P */
+  const int32_t* positives;       /* device [P, 3] */
+  int64_t batch_size;             /* B */
+  const int32_t* positive_ids;    /* device [B] */
+  int64_t negatives_per_positive; /* K */
+  uint64_t seed;
+  int64_t seed_capacity;
+  /* outputs */
+  int32_t* triples;       /* device [N, 3] */
+  int32_t* local_triples; /* device [N, 3] */
+  int32_t* seeds;         /* device [seed_capacity] */
+  int32_t* meta;          /* device [2] */
+  void* workspace;
+  size_t workspace_bytes;
+} tfgnn_triple_batch_args;
+size_t tfgnn_triple_batch_workspace_bytes(int64_t num_nodes);
+int tfgnn_triple_batch_build(const tfgnn_triple_batch_args* args, void* stream);
+int tfgnn_triple_batch_launch_counts(int64_t* out_counts, int n);
+
+/* ------------------------------------------------------------------------------------------
  * R-GCN basis decomposition (csrc/basis.hip; Schlichtkrull et al. 2018, eq. 3: W_l = sum_b a[l,b] V_b with B shared bases),
  * aggregate first.  With s_e / m_v the scales of tfgnn_graph_scales (d_edge_weight_by_dst / d_node_scale), L the handle's
  * number of edge types and coeff = a [L, B] contiguous:

@@ -448,6 +448,15 @@ _SIGNATURES += [
      [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     ("tfgnn_embedding_launch_count", c_int64, []),
 ]
+# one mini-batch of link-prediction triples: gather, negatives, seeds, local ids (include/tfgnn.h "Triple batches",
+# csrc/triple_batch.hip)
+_SIGNATURES += [
+    ("tfgnn_triple_batch_workspace_bytes", c_size_t, [c_int64]),
+    ("tfgnn_triple_batch_build", c_int, [c_void_p, c_void_p]),
+    ("tfgnn_triple_batch_launch_counts", c_int, [POINTER(c_int64), c_int]),
+]
+TRIPLE_BATCH_SEED_OVERFLOW, TRIPLE_BATCH_BAD_POSITIVE_ID, TRIPLE_BATCH_BAD_ENDPOINT = 1, 2, 4  # TFGNN_TRIPLE_BATCH_*
+TRIPLE_BATCH_LAUNCHES = 6  # per tfgnn_triple_batch_build call
 TRIPLE_SORT_TILE = 8192  # csrc/negatives.hip TS_TILE: keys per workgroup of the table sort
 TRIPLE_SORT_DIGIT_BITS = 9  # csrc/negatives.hip TS_DIGIT_BITS
 BLOCKDIAG_MAX_BLOCK = 64  # csrc/blockdiag.hip MAX_BLOCK: D / num_blocks and H / num_blocks at most
@@ -606,6 +615,17 @@ class GatherNodeRowsArgs(ctypes.Structure):
         ("feature_dim", c_int64), ("features", c_void_p), ("node_features", c_void_p), ("num_node_columns", c_int),
         ("node_column_widths", c_void_p), ("node_columns", c_void_p), ("node_column_out", c_void_p), ("seed_only", c_void_p),
         ("bad_flag", c_void_p),
+    ]
+
+
+class TripleBatchArgs(ctypes.Structure):
+    """tfgnn_triple_batch_args (include/tfgnn.h), field for field"""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t), ("num_nodes", c_int64), ("num_positives", c_int64), ("positives", c_void_p),
+        ("batch_size", c_int64), ("positive_ids", c_void_p), ("negatives_per_positive", c_int64), ("seed", ctypes.c_uint64),
+        ("seed_capacity", c_int64), ("triples", c_void_p), ("local_triples", c_void_p), ("seeds", c_void_p), ("meta", c_void_p),
+        ("workspace", c_void_p), ("workspace_bytes", ctypes.c_size_t),
     ]
 
 

@@ -22,11 +22,12 @@
 #include <atomic>
 
 #include "common.hpp"
+#include "scan.hpp"
 
 namespace tfgnn {
 
-constexpr int kSampleThreads = 256;
-constexpr int kSampleChunk = 1024;  // rows (or ids) whose counts one workgroup scans: 4 per thread
+constexpr int kSampleThreads = kScanThreads;
+constexpr int kSampleChunk = kScanChunk;  // rows (or ids) whose counts one workgroup scans: 4 per thread (csrc/scan.hpp)
 constexpr int kSampleMaxBlocks = 2048;
 constexpr int32_t kMarked = -2;
 constexpr int kGatherTileElems = 8192;  // as kFeatTileElems of csrc/batch.hip
@@ -73,29 +74,6 @@ struct SampleParams {
 
 __device__ __forceinline__ int32_t* meta_edges(const SampleParams& P) { return P.meta + TFGNN_SAMPLE_META_EDGES; }
 __device__ __forceinline__ int32_t* meta_hop_ptr(const SampleParams& P) { return P.meta + TFGNN_SAMPLE_META_EDGES + P.L; }
-
-// exclusive scan of one value per thread over the workgroup (4 waves of 64); *total: the workgroup's sum
-__device__ __forceinline__ int32_t block_exclusive_scan(int32_t x, int32_t* total, int32_t* wave_sums) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int32_t incl = x;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int32_t y = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += y;
-  }
-  if (lane == 63) wave_sums[w] = incl;
-  __syncthreads();
-  int32_t base = 0, tot = 0;
-#pragma unroll
-  for (int k = 0; k < kSampleThreads / 64; ++k) {
-    const int32_t s = wave_sums[k];
-    if (k < w) base += s;
-    tot += s;
-  }
-  __syncthreads();  // wave_sums may be written again
-  *total = tot;
-  return base + incl - x;
-}
 
 // in-degree of type t of node v, 0 for anything the store's sizes do not admit
 __device__ __forceinline__ int32_t in_degree(const SampleParams& P, int t, int32_t v, int32_t* first) {
@@ -198,15 +176,7 @@ __global__ void __launch_bounds__(kSampleThreads) sample_count_scan_kernel(const
   const int32_t Fr = hop_ptr[hop] - hop_ptr[hop - 1];
   const int64_t R = (int64_t)P.L * Fr;
   const int64_t chunks = (R + kSampleChunk - 1) / kSampleChunk;
-  int32_t carry = 0;
-  for (int64_t c0 = 0; c0 < chunks; c0 += kSampleThreads) {
-    const int64_t ck = c0 + threadIdx.x;
-    const int32_t x = ck < chunks ? P.chunk_off[ck] : 0;
-    int32_t total;
-    const int32_t ex = block_exclusive_scan(x, &total, wave_sums);
-    if (ck < chunks) P.chunk_off[ck] = carry + ex;
-    carry += total;
-  }
+  const int32_t carry = scan_chunk_totals(P.chunk_off, chunks, wave_sums);
   if (threadIdx.x == 0) {
     P.chunk_off[chunks] = carry;
     P.state[kStateTotal] = carry;
@@ -282,32 +252,13 @@ __global__ void __launch_bounds__(kSampleThreads) sample_slots_kernel(const Samp
 
 __global__ void __launch_bounds__(kSampleThreads) sample_mark_count_kernel(const SampleParams P) {
   __shared__ int32_t wave_sums[kSampleThreads / 64];
-  const int64_t chunks = ((int64_t)P.V + kSampleChunk - 1) / kSampleChunk;
-  for (int64_t ck = blockIdx.x; ck < chunks; ck += gridDim.x) {
-    int32_t n = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int64_t v = ck * kSampleChunk + q * kSampleThreads + threadIdx.x;
-      if (v < P.V && P.table[v] == kMarked) ++n;
-    }
-    int32_t total;
-    block_exclusive_scan(n, &total, wave_sums);
-    if (threadIdx.x == 0) P.vchunk_off[ck] = total;
-  }
+  count_marked_chunks(P.table, P.V, kMarked, P.vchunk_off, wave_sums);
 }
 
 __global__ void __launch_bounds__(kSampleThreads) sample_mark_scan_kernel(const SampleParams P, int hop) {
   __shared__ int32_t wave_sums[kSampleThreads / 64];
   const int64_t chunks = ((int64_t)P.V + kSampleChunk - 1) / kSampleChunk;
-  int32_t carry = 0;
-  for (int64_t c0 = 0; c0 < chunks; c0 += kSampleThreads) {
-    const int64_t ck = c0 + threadIdx.x;
-    const int32_t x = ck < chunks ? P.vchunk_off[ck] : 0;
-    int32_t total;
-    const int32_t ex = block_exclusive_scan(x, &total, wave_sums);
-    if (ck < chunks) P.vchunk_off[ck] = carry + ex;
-    carry += total;
-  }
+  const int32_t carry = scan_chunk_totals(P.vchunk_off, chunks, wave_sums);
   if (threadIdx.x == 0) {
     const int32_t before = P.meta[TFGNN_SAMPLE_META_NODES];
     const int64_t want = (int64_t)before + carry;
@@ -322,34 +273,8 @@ __global__ void __launch_bounds__(kSampleThreads) sample_mark_scan_kernel(const 
 
 __global__ void __launch_bounds__(kSampleThreads) sample_mark_assign_kernel(const SampleParams P) {
   __shared__ int32_t wave_sums[kSampleThreads / 64];
-  const int64_t chunks = ((int64_t)P.V + kSampleChunk - 1) / kSampleChunk;
-  const int32_t before = P.state[kStateNodesBefore];
-  for (int64_t ck = blockIdx.x; ck < chunks; ck += gridDim.x) {
-    // thread x owns ids 4 x .. 4 x + 3 of the chunk, so that ranks grow with the id
-    const int64_t v0 = ck * kSampleChunk + threadIdx.x * 4;
-    bool m[4];
-    int32_t n = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      m[q] = v0 + q < P.V && P.table[v0 + q] == kMarked;
-      n += m[q];
-    }
-    int32_t total;
-    int32_t rank = block_exclusive_scan(n, &total, wave_sums);
-    if (total == 0) continue;
-    const int64_t base = (int64_t)before + P.vchunk_off[ck];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      if (!m[q]) continue;
-      const int64_t id = base + rank++;
-      if (id < P.node_cap) {
-        P.table[v0 + q] = (int32_t)id;
-        P.nodes[id] = (int32_t)(v0 + q);
-      } else {
-        P.table[v0 + q] = -1;  // no room: it is in no output, so the restore pass would not find it
-      }
-    }
-  }
+  // a marked id takes local id (nodes so far) + (its rank among the marked); no room: back to -1
+  assign_marked_chunks(P.table, P.V, kMarked, P.vchunk_off, P.state[kStateNodesBefore], P.node_cap, P.nodes, wave_sums);
 }
 
 __global__ void __launch_bounds__(kSampleThreads) sample_translate_kernel(const SampleParams P) {

@@ -44,7 +44,31 @@ synchronisation.  Such a sampled batch IS capturable: a CapturedStep of ``_run_s
 on new negatives at every ``replay()`` - the draw follows the dropout epoch word the captured step advances - with no
 ``next(iter(train))`` in between.  The draw's 64-bit seed is (``negative_sampling_seed`` << 32) | (draws & 0xFFFFFFFF),
 ``draws`` counting the sampler's ``redraw()`` calls on the host: eager steps differ through the counter, replays of one
-captured step through the epoch word."""
+captured step through the epoch word.
+
+Mini-batches.  Three hyper-parameters, read with ``.get`` and in no defaults dictionary: ``neighbor_fanouts`` (absent or None:
+everything above, untouched; a list of 1 .. SAMPLE_MAX_HOPS fanouts, one per hop, -1 for every in-edge: the route below; it
+needs ``negative_sampling`` = "device" - ValueError otherwise), ``triples_per_batch`` (absent: 1024; >= 1) and
+``sampling_seed`` (absent: 0).  Only TRAIN is mini-batched: filtered ranking needs every entity's representation and
+inference keeps no activations, so VALIDATION and TEST stay the single full-graph batch.  Every ``iter()`` of the TRAIN
+batches draws a fresh np.random.permutation of the P positives (numpy's global generator, as every dataset's epoch order),
+uploads it in one copy, takes the next epoch number and walks the chunks of ``plan_seed_chunks(P, triples_per_batch)``, the
+partial last one included.  A batch is three steps on the device:
+  ``ops.triple_batch`` (include/tfgnn.h "Triple batches", six launches): the chunk's positives, ``num_negatives_per_positive``
+  negatives each - the draw of the "device" route with seed (``negative_sampling_seed`` << 32) | (batches built so far &
+  0xFFFFFFFF) and the dropout epoch ignored -, their distinct endpoints in increasing id and the triples in local ids;
+  ``sampled_batch`` around those endpoints with ``batch_key(sampling_seed, epoch, batch index)``: the seeds are rows 0 .. S - 1;
+  ``ops.build_triple_tables_device`` on the local triples, for the batch's n nodes.
+``batch_features`` holds the sampled batch's keys (node_features, adjacency_list_<t>, node_to_graph_map, num_graphs_in_batch,
+num_seed_nodes, sampled_node_ids, hop_ptr, _bad_local_index) and ``triples`` - in LOCAL ids: rows of the batch -,
+``triple_labels`` (B ones, B K zeros), ``triple_weights`` (ones) and ``triple_tables``; ``batch_labels`` the same four tensors
+and ``global_triples`` int32 [N, 3].  No ``triple_sampler``, ``positive_triples`` or ``rank_filters``: ``evaluate_model`` on
+these batches raises ValueError.  The triple buffers, the id table and the table build's workspace are allocated once for a
+full chunk and reused: a batch's triple tensors are overwritten by the next batch.  Two small device-to-host copies per batch
+(S, then the sampler's counts): a mini-batch, like every sampled batch, cannot be captured.  TRAIN positives stay in the
+message-passing graph - no edge is held out, as on the full-batch route; removing a batch's positives from its subgraph is
+out of scope.  The sampler's limit of 48 processed edge types stands (the NeighborStore error, raised when the data is
+loaded): FB15k-237 with its 238 types stays on the full-batch route."""
 from __future__ import annotations
 
 from pathlib import Path
@@ -55,6 +79,8 @@ import torch
 
 from .. import ops
 from .graph_dataset import DataFold, GraphDataset, PackedFold, assemble_batch
+from .neighbor_sampling import (NeighborStore, batch_key, check_fanouts, check_store_limits, plan_seed_chunks,
+                                sampled_batch)
 from .utils import compute_number_of_edge_types, get_tied_edge_types
 
 _EVAL_NEGATIVES_SEED = {DataFold.VALIDATION: 0x5EED0001, DataFold.TEST: 0x5EED0002}
@@ -132,6 +158,23 @@ class _LinkBatches:
         yield features, labels
 
 
+class _LinkMiniBatches:
+    """What ``LinkPredictionDataset.get_batches(TRAIN)`` returns with ``neighbor_fanouts`` set: every ``iter()`` is one epoch
+    of mini-batches over a fresh permutation of the positives, which goes to the device in one copy.  The triple buffers are
+    the dataset's and are overwritten by the next batch."""
+
+    def __init__(self, dataset: "LinkPredictionDataset", device=None):
+        self._dataset, self._device = dataset, device
+
+    def __iter__(self) -> Iterator[Tuple[Dict[str, Any], Dict[str, Any]]]:
+        ds = self._dataset
+        store = ds.neighbor_store(self._device)
+        order, chunks, epoch = ds.plan_minibatch_epoch()
+        ids = torch.from_numpy(order.astype(np.int32)).to(store.device)
+        for b, (s, e) in enumerate(chunks):
+            yield ds.minibatch(store, ids[s:e], epoch, b)
+
+
 class LinkPredictionDataset(GraphDataset):
     @classmethod
     def get_default_hyperparameters(cls) -> Dict[str, Any]:
@@ -159,6 +202,21 @@ class LinkPredictionDataset(GraphDataset):
         if not isinstance(seed, (int, np.integer)) or isinstance(seed, bool) or not 0 <= seed < 2 ** 32:
             raise ValueError(f"negative_sampling_seed must be an integer in [0, 2^32), not {seed!r}")
         self._negative_sampling_seed = int(seed)
+        # the mini-batch route (module docstring): keys read with .get, in no defaults dictionary
+        fanouts = params.get("neighbor_fanouts")
+        self._fanouts: Optional[List[int]] = None if fanouts is None else check_fanouts(fanouts)
+        if self._fanouts is not None and self._negative_sampling != "device":
+            raise ValueError("neighbor_fanouts needs negative_sampling = 'device': the mini-batch route draws its negatives on the "
+                             f"device only, not {self._negative_sampling!r}")
+        per_batch = params.get("triples_per_batch", 1024)
+        if not isinstance(per_batch, (int, np.integer)) or isinstance(per_batch, bool) or per_batch < 1:
+            raise ValueError(f"triples_per_batch must be an integer >= 1, not {per_batch!r}")
+        self._triples_per_batch = int(per_batch)
+        self._sampling_epoch = 0
+        self._batches_built = 0
+        self.seed_of_last_batch: Optional[int] = None
+        self._neighbor_stores: Dict[str, NeighborStore] = {}
+        self._minibatch_buffers: Dict[str, Dict[str, Any]] = {}
         self._num_fwd_edge_types: Optional[int] = None
         self._num_nodes = 0
         self._positives: Dict[DataFold, np.ndarray] = {}
@@ -306,8 +364,11 @@ class LinkPredictionDataset(GraphDataset):
             tied_fwd_bkwd_edge_types=get_tied_edge_types(self.params["tie_fwd_bkwd_edges"], T),
             feature_dim=int(feats.shape[1]),
         )
+        if self.minibatched:  # the sampler's limit, known at load time: FB15k-237's 238 types stay on the full-batch route
+            check_store_limits(base)
         self._num_fwd_edge_types, self._num_nodes = T, V
         self._positives, self._triple_buffers = positives, {}
+        self._neighbor_stores, self._minibatch_buffers = {}, {}
         known = np.concatenate(list(positives.values())) if positives else np.zeros((0, 3), dtype=np.int32)
         self._filters = {fold: {"dst": _filter_csr(p, known, 2, V, T), "src": _filter_csr(p, known, 0, V, T)}
                          for fold, p in positives.items()}
@@ -398,5 +459,78 @@ class LinkPredictionDataset(GraphDataset):
             ops.build_triple_tables_device(triples, V, T, out=tables, workspace=workspace)
         return buffers
 
-    def get_batches(self, data_fold: DataFold, device=None) -> _LinkBatches:
+    # ---- mini-batches (TRAIN, with ``neighbor_fanouts``) --------------------------------------------------------------------
+    @property
+    def minibatched(self) -> bool:
+        return self._fanouts is not None
+
+    def neighbor_store(self, device=None) -> NeighborStore:
+        """The TRAIN fold - the message-passing graph - in the sampler's form on the device; built at the first request."""
+        self._loaded("neighbor_store")
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if str(dev) not in self._neighbor_stores:
+            self._neighbor_stores[str(dev)] = NeighborStore(self._loaded_data[DataFold.TRAIN], dev)
+        return self._neighbor_stores[str(dev)]
+
+    def plan_minibatch_epoch(self) -> Tuple[np.ndarray, List[Tuple[int, int]], int]:
+        """(order of the TRAIN positives, chunk ranges, epoch number) of a new epoch: a fresh permutation from numpy's global
+        generator - where every dataset draws its epoch order - and the next epoch number."""
+        P = self._positives[DataFold.TRAIN].shape[0]
+        epoch = self._sampling_epoch
+        self._sampling_epoch += 1
+        return np.random.permutation(P), plan_seed_chunks(P, self._triples_per_batch), epoch
+
+    def _minibatch_state(self, dev: torch.device) -> Dict[str, Any]:
+        """What the mini-batches of one device share, allocated once at the capacity of a full chunk: the uploaded positives,
+        the output buffers of ops.triple_batch, its id-table workspace and the table build's workspace."""
+        state = self._minibatch_buffers.get(str(dev))
+        if state is None:
+            V, T, K = self._num_nodes, self._num_fwd_edge_types, int(self.params["num_negatives_per_positive"])
+            pos = self._positives[DataFold.TRAIN]
+            N = min(self._triples_per_batch, pos.shape[0]) * (1 + K)
+            new = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+            state = self._minibatch_buffers[str(dev)] = {
+                "positives": torch.from_numpy(pos).to(dev),
+                "triples": new(N, 3), "local_triples": new(N, 3), "seeds": new(min(2 * N, V)),
+                "id_workspace": ops.triple_batch_workspace(V, dev),
+                "table_workspace": ops.triple_tables_workspace(N, V, T, device=dev),
+                "labels": {},  # B -> (triple_labels, triple_weights): a full chunk's and the partial last one's
+            }
+        return state
+
+    def minibatch(self, store: NeighborStore, positive_ids: torch.Tensor, epoch: int, batch_index: int):
+        """One TRAIN mini-batch of the positives ``positive_ids`` (device int32 [B], B <= triples_per_batch) as
+        ``(batch_features, batch_labels)``: ops.triple_batch, the sampler around its seeds, the triple tables in local ids.
+        ``seed_of_last_batch`` is the 64-bit seed the negatives were drawn with (tests/triple_batch_reference.py restates
+        them)."""
+        state = self._minibatch_state(store.device)
+        V, T, K = self._num_nodes, self._num_fwd_edge_types, int(self.params["num_negatives_per_positive"])
+        B = int(positive_ids.shape[0])
+        N = B * (1 + K)
+        seed = (self._negative_sampling_seed << 32) | (self._batches_built & 0xFFFFFFFF)
+        self._batches_built += 1
+        self.seed_of_last_batch = seed
+        out = (state["triples"][:N], state["local_triples"][:N], state["seeds"][:min(2 * N, V)])
+        triples, local, seeds, S, status = ops.triple_batch(state["positives"], positive_ids, K, V, seed, state["id_workspace"],
+                                                            out=out)
+        if status:
+            raise ValueError(f"building the triple batch failed with status {status} (include/tfgnn.h TFGNN_TRIPLE_BATCH_*)")
+        features, labels = sampled_batch(store, seeds, self._fanouts,
+                                         batch_key(self.params.get("sampling_seed", 0), epoch, batch_index), seed_only_columns=())
+        n = int(features["sampled_node_ids"].shape[0])
+        tables = ops.build_triple_tables_device(local, n, T, workspace=state["table_workspace"])
+        if B not in state["labels"]:
+            y = torch.zeros(N, dtype=torch.float32, device=store.device)
+            y[:B] = 1.0
+            state["labels"][B] = (y, torch.ones(N, dtype=torch.float32, device=store.device))
+        y, w = state["labels"][B]
+        triple_part = {"triples": local, "triple_labels": y, "triple_weights": w, "triple_tables": tables}
+        features.update(triple_part)
+        labels.update(triple_part)
+        labels["global_triples"] = triples
+        return features, labels
+
+    def get_batches(self, data_fold: DataFold, device=None):
+        if self.minibatched and data_fold == DataFold.TRAIN:
+            return _LinkMiniBatches(self, device)
         return _LinkBatches(self, data_fold, device)

@@ -58,6 +58,13 @@ def check_fanouts(fanouts) -> List[int]:
     return fanouts
 
 
+def check_store_limits(fold: PackedFold) -> None:
+    """ValueError for a fold the sampler cannot take: its per-type tables are kernel arguments (a dataset that knows its
+    route when it loads calls this then, NeighborStore always)."""
+    if fold.num_edge_types > _lib.BATCH_MAX_EDGE_TYPES or len(fold.node_columns) > _lib.BATCH_MAX_NODE_COLUMNS:
+        raise ValueError(f"at most {_lib.BATCH_MAX_EDGE_TYPES} edge types and {_lib.BATCH_MAX_NODE_COLUMNS} node columns")
+
+
 def _array_key(a: np.ndarray):
     """names the memory an array shows: two folds of one dataset hold views of the same host arrays"""
     return (a.__array_interface__["data"][0], a.shape, a.strides, a.dtype.str)
@@ -72,8 +79,7 @@ class NeighborStore:
         if fold.num_graphs != 1:
             raise ValueError(f"neighbour sampling needs a fold of one graph, not {fold.num_graphs}: node_to_graph_map must be sorted, "
                              "and a sampled batch is one graph")
-        if fold.num_edge_types > _lib.BATCH_MAX_EDGE_TYPES or len(fold.node_columns) > _lib.BATCH_MAX_NODE_COLUMNS:
-            raise ValueError(f"at most {_lib.BATCH_MAX_EDGE_TYPES} edge types and {_lib.BATCH_MAX_NODE_COLUMNS} node columns")
+        check_store_limits(fold)
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.fold = fold
         self.num_nodes = int(fold.features.shape[0])

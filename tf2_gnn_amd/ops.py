@@ -2863,6 +2863,74 @@ def gather_node_rows(nodes: torch.Tensor, num_seeds: int, features: torch.Tensor
     return nf, list(cols)
 
 
+# ---- triple batches (include/tfgnn.h "Triple batches", csrc/triple_batch.hip) ----------------------------------------------------
+def triple_batch_launch_counts() -> int:
+    """tfgnn_triple_batch_launch_counts: kernel launches of ``triple_batch`` so far (6 per call; a host counter)."""
+    buf = (ctypes.c_int64 * 1)()
+    _lib.check(_lib.load().tfgnn_triple_batch_launch_counts(buf, 1))
+    return int(buf[0])
+
+
+def triple_batch_workspace(V: int, device=None) -> torch.Tensor:
+    """An int32 workspace of tfgnn_triple_batch_workspace_bytes(V) for ``triple_batch``, its id table (the first V words)
+    filled with -1 as every call expects and leaves it."""
+    nbytes = int(_lib.load().tfgnn_triple_batch_workspace_bytes(int(V)))
+    if nbytes == 0:
+        raise ValueError(f"no triple-batch workspace for V = {V} (include/tfgnn.h: V in [1, 2^31))")
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    ws = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+    ws[:int(V)].fill_(-1)
+    return ws
+
+
+def triple_batch(positives: torch.Tensor, positive_ids: torch.Tensor, K: int, V: int, seed: int, workspace: torch.Tensor,
+                 out=None):
+    """One mini-batch of link-prediction triples by one tfgnn_triple_batch_build call (6 launches on the current stream):
+    ``positives`` int32 [P, 3] (device, global ids), ``positive_ids`` int32 [B] (device) -> ``(triples, local_triples,
+    seeds[:S], S, status)``: triples int32 [B (1 + K), 3] = the B positives followed by K negatives each, drawn as
+    ``draw_negative_triples(seed, use_epoch=False)`` draws them; seeds = their distinct endpoints in increasing id - what
+    ``neighbor_sample`` takes as seeds; local_triples = the triples with every endpoint replaced by its position in seeds,
+    which is its row in the sampled batch.  ``status``: the TFGNN_TRIPLE_BATCH_* bits (include/tfgnn.h).
+    ``workspace``: int32, ``triple_batch_workspace(V)`` or a NeighborStore workspace of at least that size - its first V
+    words are -1 on entry and on exit.  ``out`` = (triples [N, 3], local_triples [N, 3], seeds [capacity]) brings the
+    outputs; otherwise they are allocated, seeds at min(2 N, V), which cannot overflow.
+    After the call ONE 8-byte device-to-host copy reads (status, S): the sampler needs S on the host.  That copy
+    synchronises: with the sampler's own copy of its counts a mini-batch costs two small copies, and - like every sampled
+    batch - it cannot be captured in a CapturedStep."""
+    _require_dev(positives, torch.int32, "positives")
+    _require_dev(positive_ids, torch.int32, "positive_ids")
+    _require_dev(workspace, torch.int32, "workspace")
+    P = _device_triples(positives, "positives")
+    if positive_ids.dim() != 1 or not positive_ids.is_contiguous():
+        raise ValueError("positive_ids must be a contiguous int32 [B]")
+    B, K, V = int(positive_ids.shape[0]), int(K), int(V)
+    N = B * (1 + max(K, 0))
+    dev = positives.device
+    if out is None:
+        out = (torch.empty((N, 3), dtype=torch.int32, device=dev), torch.empty((N, 3), dtype=torch.int32, device=dev),
+               torch.empty(max(1, min(2 * N, V)), dtype=torch.int32, device=dev))
+    triples, local, seeds = out
+    for t, what in ((triples, "triples"), (local, "local_triples")):
+        if _device_triples(t, what) != N:
+            raise ValueError(f"{what} must hold B (1 + K) = {N} rows, not {t.shape[0]}")
+    _require_dev(seeds, torch.int32, "seeds")
+    if seeds.dim() != 1 or not seeds.is_contiguous():
+        raise ValueError("seeds must be a contiguous int32 [capacity]")
+    meta = torch.empty(2, dtype=torch.int32, device=dev)
+    a = _lib.TripleBatchArgs()
+    a.struct_size = ctypes.sizeof(_lib.TripleBatchArgs)
+    a.num_nodes, a.num_positives, a.positives = V, P, positives.data_ptr()
+    a.batch_size, a.positive_ids, a.negatives_per_positive = B, positive_ids.data_ptr(), K
+    a.seed, a.seed_capacity = int(seed) & (2 ** 64 - 1), int(seeds.shape[0])
+    a.triples, a.local_triples, a.seeds, a.meta = triples.data_ptr(), local.data_ptr(), seeds.data_ptr(), meta.data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * 4
+    _lib.check(_lib.load().tfgnn_triple_batch_build(ctypes.byref(a), _stream()))
+    for t in (triples, local, seeds):
+        torch.autograd.graph.increment_version(t)  # written through raw pointers, which torch does not see
+    status, S = (int(x) for x in meta.cpu().numpy())  # the one copy
+    return triples, local, seeds[:S], S, status
+
+
 # ---- node embeddings: include/tfgnn.h "Node embeddings", csrc/embedding.hip --------------------------------------------------------
 def embedding_launch_count() -> int:
     """tfgnn_embedding_launch_count: kernel launches of ``embedding_scatter_rows`` so far (a host counter)."""

@@ -468,7 +468,13 @@ class LinkPredictionTask(GraphTaskModel):
     weights and tables are read from device memory by the kernels, so a captured step follows in-place changes (new
     negatives) of all of them.  A training step on a batch that carries ``triple_sampler`` (LinkPredictionDataset with
     ``negative_sampling = "device"``) first calls its ``redraw()``: the negatives and the node tables are rewritten on the
-    device as part of the step, and of every replay of a captured one.  Inference never redraws."""
+    device as part of the step, and of every replay of a captured one.  Inference never redraws.
+
+    Mini-batches (LinkPredictionDataset with ``neighbor_fanouts``): a TRAIN batch is a sampled subgraph whose ``triples`` are
+    in the batch's LOCAL ids - rows of the node representations - so nothing here changes: the loss is the mean over the
+    batch's counted triples, a learned embedding table is read through ``sampled_node_ids`` and, with
+    ``node_embedding_update="rows"``, gets a RowGradient.  Such a batch carries no ``triple_sampler`` and cannot be ranked:
+    ``evaluate_model`` on it raises ValueError (use VALIDATION or TEST, which stay full-graph batches)."""
 
     def __init__(self, params: Dict[str, Any], dataset: Any = None, name: Optional[str] = None, *,
                  num_edge_types: Optional[int] = None, num_relations: Optional[int] = None, num_nodes: Optional[int] = None):
@@ -554,6 +560,10 @@ class LinkPredictionTask(GraphTaskModel):
     def rank_counts(self, batch_features, batch_labels) -> Tuple[torch.Tensor, torch.Tensor]:
         """(greater, equal) of tfgnn_distmult_rank for the batch's ``positive_triples``, filtered by ``rank_filters``: the
         queries with the target corrupted, then the same queries with the source corrupted (int32 [2 P] each, on the device)."""
+        if "rank_filters" not in batch_labels or "positive_triples" not in batch_labels:
+            raise ValueError("this batch carries no positive_triples / rank_filters: filtered ranking needs every entity's "
+                             "representation, which a neighbour-sampled TRAIN mini-batch does not hold; use the VALIDATION or "
+                             "TEST batches")
         h = self._final(self.compute_final_node_representations(batch_features, training=False))
         greater, equal = [], []
         for side in ("dst", "src"):
