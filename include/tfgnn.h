@@ -1834,6 +1834,86 @@ int tfgnn_triple_batch_build(const tfgnn_triple_batch_args* args, void* stream);
 int tfgnn_triple_batch_launch_counts(int64_t* out_counts, int n);
 
 /* ------------------------------------------------------------------------------------------
+ * Excluding a batch's positives (csrc/sample_exclude.hip): the edges whose score a link-prediction mini-batch trains are
+ * taken out of the subgraph the sampler drew for it.  Both endpoints of a positive (u, r, v) are seeds, so the sampler
+ * draws row (v, type of r) at hop 1 and - at fanout -1 always - hands the encoder the very edge u -> v, and v -> u on the
+ * inverse type.  tfgnn_sample_exclude_edges runs on the outputs of tfgnn_neighbor_sample, on the same stream, BEFORE the
+ * sampler's meta words are copied to the host: draw first, then drop.
+ *
+ * Inputs: L = num_edge_types lists adjacency_lists[t] int32 [edge_capacity[t], 2] in LOCAL ids (after the sampler's
+ * translate pass) with their live counts in meta[TFGNN_SAMPLE_META_EDGES + t]; S = num_seeds; positives int32 [B, 3], rows
+ * (u, r, v) in local ids - rows 0 .. B - 1 of tfgnn_triple_batch_build's local_triples; and two HOST tables over the
+ * T = num_relations relations, read during the call: fwd_type[r], the processed edge type that carries the forward edges
+ * of relation r, and inv_type[r], the type that carries their inverses (the same type for a tied relation, the backward
+ * type otherwise); -1 = none.
+ * For every positive (u, r, v) the call removes from list fwd_type[r] every edge (u, v) and from list inv_type[r] every
+ * edge (v, u) - multi-edges all go, a repeated positive removes nothing more, u == v on a tied type removes the loops
+ * (u, u) of that list.  Types that no table entry names (the self loops) are never touched.
+ * PRECONDITION the sampler guarantees: every list is sorted by target (hops append rows in frontier order and frontier
+ * local ids increase).  Both endpoints are seeds and a row is drawn once, when its node is a frontier node, so every
+ * such edge sits in a hop-1 row and its endpoints are in `nodes` regardless: nodes, hop_ptr and the node count do not
+ * change, and dropping after the whole sample equals dropping per hop.  At a finite fanout a row may keep fewer than f
+ * edges: nothing is drawn in place of a dropped edge.
+ *
+ * Outputs:
+ *   adjacency_lists[t][0 : new count)   the kept edges in their old order.  Nothing is written at or beyond the OLD
+ *                                       count; the slots between the new and the old count are unspecified.
+ *   meta[TFGNN_SAMPLE_META_EDGES + t]   the new count, in place: the sampler's one device-to-host copy carries it.
+ *   meta[TFGNN_SAMPLE_META_STATUS]      OR-ed with the status word below (the bits do not collide with TFGNN_SAMPLE_*).
+ *   record int32 [TFGNN_SAMPLE_EXCLUDE_RECORD_WORDS(L)]:  record[t] = removed[t] = old count - new count, record[L] =
+ *                                       the status word: 0 or an OR of
+ *       TFGNN_SAMPLE_EXCLUDE_BAD_RELATION   a positive whose relation is outside [0, T)
+ *       TFGNN_SAMPLE_EXCLUDE_BAD_ENDPOINT   a positive with an endpoint outside [0, S)
+ *                                       Such a row is skipped.  A row (-1, -1, -1) - what tfgnn_triple_batch_build writes
+ *                                       for a bad positive id - is skipped and sets no bit.
+ * An edge whose source is -1 (the sampler's mark of a bad store entry) is kept.  A live count above its capacity is read
+ * as the capacity.  All of it is fixed, integers only: tests/sample_exclude_reference.py restates it.
+ *
+ * Workspace: tfgnn_sample_exclude_workspace_bytes(L, edge_capacity) bytes, 16-byte aligned (0 for arguments outside the
+ * limits below); no initialisation.  It holds a packed copy of the lists (sum_t ceil(cap_t / 1024) * 1024 edges).
+ *
+ * Exactly TFGNN_SAMPLE_EXCLUDE_LAUNCHES = 4 launches on `stream`, whatever the sizes: (1) mark - one wave per
+ * (positive, direction): a binary search for the target's row, then the wave strides over the row and overwrites the
+ * source of every matching edge with a marker, plain stores of one value, idempotent; a hub row with hundreds of
+ * positives pointing at it is hundreds of strided walks, not one thread's loop; (2) pack - per chunk of 1024 slots, the
+ * types flattened into one grid: the unmarked edges, in order, into the workspace, and their number; (3) ONE workgroup:
+ * scan of the chunk counts with a carry across rounds of 256 chunks, the new counts, removed[], the status; (4) move
+ * - the packed chunks back into the lists at their scanned offsets.  Grids are sized from B and the capacities; the live
+ * counts exist on the device only.  No allocation, no copy, no host synchronisation, no float arithmetic; the only
+ * atomic is an OR into the status word.  The per-type pointers and both tables travel as kernel arguments.
+ * Refused on the host before any HIP call: NULL args or another struct_size; negative sizes or capacities; B < 1 or
+ * > 2^30; S >= 2^31; a capacity >= 2^31 or 2^31 or more slots in all; a table entry outside [-1, L); NULL pointers;
+ * edge lists that are not 8-byte aligned; a short or misaligned workspace.  More than TFGNN_BATCH_MAX_EDGE_TYPES types
+ * or relations: TFGNN_ERR_UNSUPPORTED.
+ *
+ * tfgnn_sample_exclude_launch_counts: out[0] = kernel launches enqueued by tfgnn_sample_exclude_edges in this process
+ * (4 per call; a host counter); further slots are zero.
+ * ------------------------------------------------------------------------------------------ */
+#define TFGNN_SAMPLE_EXCLUDE_LAUNCHES 4
+#define TFGNN_SAMPLE_EXCLUDE_BAD_RELATION 32
+#define TFGNN_SAMPLE_EXCLUDE_BAD_ENDPOINT 64
+#define TFGNN_SAMPLE_EXCLUDE_RECORD_WORDS(L) ((L) + 1)
+typedef struct tfgnn_sample_exclude_args {
+  size_t struct_size;
+  int num_edge_types;              /* L */
+  int num_relations;               /* T */
+  int64_t num_seeds;               /* S */
+  int64_t num_positives;           /* B */
+  const int32_t* positives;        /* device [B, 3], local ids */
+  const int32_t* fwd_type;         /* host [T] */
+  const int32_t* inv_type;         /* host [T] */
+  const int64_t* edge_capacity;    /* host [L] */
+  int32_t* const* adjacency_lists; /* host [L] of device [edge_capacity[t], 2] */
+  int32_t* meta;                   /* device: the sampler's meta words */
+  int32_t* record;                 /* device [TFGNN_SAMPLE_EXCLUDE_RECORD_WORDS(L)] */
+  void* workspace;
+  size_t workspace_bytes;
+} tfgnn_sample_exclude_args;
+size_t tfgnn_sample_exclude_workspace_bytes(int num_edge_types, const int64_t* edge_capacity);
+int tfgnn_sample_exclude_edges(const tfgnn_sample_exclude_args* args, void* stream);
+int tfgnn_sample_exclude_launch_counts(int64_t* out_counts, int n);
+
+/* ------------------------------------------------------------------------------------------
  * R-GCN basis decomposition (csrc/basis.hip; Schlichtkrull et al. 2018, eq. 3: W_l = sum_b a[l,b] V_b with B shared bases),
  * aggregate first.  With s_e / m_v the scales of tfgnn_graph_scales (d_edge_weight_by_dst / d_node_scale), L the handle's
  * number of edge types and coeff = a [L, B] contiguous:

@@ -457,6 +457,14 @@ _SIGNATURES += [
 ]
 TRIPLE_BATCH_SEED_OVERFLOW, TRIPLE_BATCH_BAD_POSITIVE_ID, TRIPLE_BATCH_BAD_ENDPOINT = 1, 2, 4  # TFGNN_TRIPLE_BATCH_*
 TRIPLE_BATCH_LAUNCHES = 6  # per tfgnn_triple_batch_build call
+# a batch's positives out of its sampled subgraph (include/tfgnn.h "Excluding a batch's positives", csrc/sample_exclude.hip)
+_SIGNATURES += [
+    ("tfgnn_sample_exclude_workspace_bytes", c_size_t, [c_int, c_void_p]),
+    ("tfgnn_sample_exclude_edges", c_int, [c_void_p, c_void_p]),
+    ("tfgnn_sample_exclude_launch_counts", c_int, [POINTER(c_int64), c_int]),
+]
+SAMPLE_EXCLUDE_LAUNCHES = 4  # TFGNN_SAMPLE_EXCLUDE_LAUNCHES, per tfgnn_sample_exclude_edges call
+SAMPLE_EXCLUDE_BAD_RELATION, SAMPLE_EXCLUDE_BAD_ENDPOINT = 32, 64  # TFGNN_SAMPLE_EXCLUDE_*
 TRIPLE_SORT_TILE = 8192  # csrc/negatives.hip TS_TILE: keys per workgroup of the table sort
 TRIPLE_SORT_DIGIT_BITS = 9  # csrc/negatives.hip TS_DIGIT_BITS
 BLOCKDIAG_MAX_BLOCK = 64  # csrc/blockdiag.hip MAX_BLOCK: D / num_blocks and H / num_blocks at most
@@ -625,6 +633,18 @@ class TripleBatchArgs(ctypes.Structure):
         ("struct_size", ctypes.c_size_t), ("num_nodes", c_int64), ("num_positives", c_int64), ("positives", c_void_p),
         ("batch_size", c_int64), ("positive_ids", c_void_p), ("negatives_per_positive", c_int64), ("seed", ctypes.c_uint64),
         ("seed_capacity", c_int64), ("triples", c_void_p), ("local_triples", c_void_p), ("seeds", c_void_p), ("meta", c_void_p),
+        ("workspace", c_void_p), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
+class SampleExcludeArgs(ctypes.Structure):
+    """tfgnn_sample_exclude_args (include/tfgnn.h), field for field.  The two type tables, the capacities and the pointer
+    table are host arrays that the caller keeps alive for the duration of the call."""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t), ("num_edge_types", c_int), ("num_relations", c_int), ("num_seeds", c_int64),
+        ("num_positives", c_int64), ("positives", c_void_p), ("fwd_type", c_void_p), ("inv_type", c_void_p),
+        ("edge_capacity", c_void_p), ("adjacency_lists", c_void_p), ("meta", c_void_p), ("record", c_void_p),
         ("workspace", c_void_p), ("workspace_bytes", ctypes.c_size_t),
     ]
 

@@ -66,8 +66,18 @@ and ``global_triples`` int32 [N, 3].  No ``triple_sampler``, ``positive_triples`
 these batches raises ValueError.  The triple buffers, the id table and the table build's workspace are allocated once for a
 full chunk and reused: a batch's triple tensors are overwritten by the next batch.  Two small device-to-host copies per batch
 (S, then the sampler's counts): a mini-batch, like every sampled batch, cannot be captured.  TRAIN positives stay in the
-message-passing graph - no edge is held out, as on the full-batch route; removing a batch's positives from its subgraph is
-out of scope.  The sampler's limit of 48 processed edge types stands (the NeighborStore error, raised when the data is
+message-passing graph, as on the full-batch route, unless ``exclude_batch_positives`` (read with ``.get``, in no defaults
+dictionary; absent or False: everything above, launch for launch; True without ``neighbor_fanouts``: ValueError at
+construction) is True.  Then every TRAIN mini-batch's subgraph loses, for every positive (u, t, v) of the batch - rows [0, B)
+of its triples; a negative is never excluded, even when it coincides with a true edge - the edges u -> v of the processed
+type that carries forward relation t and the edges v -> u of its inverse type: the same list for a tied relation, the
+backward type otherwise (``exclusion_type_tables``).  Self loops are never touched.  Both endpoints of a positive are seeds,
+so without this the sampler hands the encoder, at hop 1, the very edge whose score is trained.  Draw first, then drop:
+the sampler draws as always, ops.sample_exclude_edges (include/tfgnn.h "Excluding a batch's positives", four launches) then
+takes the edges out before the counts are read back, so ``sampled_node_ids`` and ``hop_ptr`` do not change, a batch still
+costs two small copies, and at a finite fanout a row may keep FEWER than f edges - nothing is drawn in their place.
+``batch_features["excluded_edge_counts"]`` (device int32 [L]) counts the edges removed per list.  VALIDATION and TEST are
+full-graph batches and unaffected.  The sampler's limit of 48 processed edge types stands (the NeighborStore error, raised when the data is
 loaded): FB15k-237 with its 238 types stays on the full-batch route."""
 from __future__ import annotations
 
@@ -212,6 +222,10 @@ class LinkPredictionDataset(GraphDataset):
         if not isinstance(per_batch, (int, np.integer)) or isinstance(per_batch, bool) or per_batch < 1:
             raise ValueError(f"triples_per_batch must be an integer >= 1, not {per_batch!r}")
         self._triples_per_batch = int(per_batch)
+        self._exclude_batch_positives = bool(params.get("exclude_batch_positives", False))
+        if self._exclude_batch_positives and self._fanouts is None:
+            raise ValueError("exclude_batch_positives needs neighbor_fanouts: only a mini-batch's sampled subgraph can lose its "
+                             "positives; a full-batch fold is the whole graph")
         self._sampling_epoch = 0
         self._batches_built = 0
         self.seed_of_last_batch: Optional[int] = None
@@ -472,6 +486,20 @@ class LinkPredictionDataset(GraphDataset):
             self._neighbor_stores[str(dev)] = NeighborStore(self._loaded_data[DataFold.TRAIN], dev)
         return self._neighbor_stores[str(dev)]
 
+    def exclusion_type_tables(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(fwd_type, inv_type), int32 [num_relations] each: the processed edge type that carries the forward edges of a
+        relation and the one that carries their inverses, as PackedFold.from_raw_graphs lays the types out - the self loops
+        first where there are any, then the forward types (a tied one holds its own inverses), then one backward type per
+        untied forward type, in forward-type order."""
+        self._loaded("exclusion_type_tables")
+        T = self._num_fwd_edge_types
+        tied = get_tied_edge_types(self.params["tie_fwd_bkwd_edges"], T)
+        first = int(bool(self.params["add_self_loop_edges"]))
+        untied = [t for t in range(T) if t not in tied]
+        fwd = np.arange(first, first + T, dtype=np.int32)
+        inv = np.array([first + t if t in tied else first + T + untied.index(t) for t in range(T)], dtype=np.int32)
+        return fwd, inv
+
     def plan_minibatch_epoch(self) -> Tuple[np.ndarray, List[Tuple[int, int]], int]:
         """(order of the TRAIN positives, chunk ranges, epoch number) of a new epoch: a fresh permutation from numpy's global
         generator - where every dataset draws its epoch order - and the next epoch number."""
@@ -515,8 +543,14 @@ class LinkPredictionDataset(GraphDataset):
                                                             out=out)
         if status:
             raise ValueError(f"building the triple batch failed with status {status} (include/tfgnn.h TFGNN_TRIPLE_BATCH_*)")
+        exclude = None
+        if self._exclude_batch_positives:  # rows [0, B) of the local triples are the positives; negatives are never excluded
+            if "exclusion_tables" not in state:
+                state["exclusion_tables"] = tuple(t.tolist() for t in self.exclusion_type_tables())
+            exclude = (local[:B],) + state["exclusion_tables"]
         features, labels = sampled_batch(store, seeds, self._fanouts,
-                                         batch_key(self.params.get("sampling_seed", 0), epoch, batch_index), seed_only_columns=())
+                                         batch_key(self.params.get("sampling_seed", 0), epoch, batch_index), seed_only_columns=(),
+                                         exclude=exclude)
         n = int(features["sampled_node_ids"].shape[0])
         tables = ops.build_triple_tables_device(local, n, T, workspace=state["table_workspace"])
         if B not in state["labels"]:

@@ -121,6 +121,7 @@ class NeighborStore:
         self._store_edges_tab = (ctypes.c_int64 * max(L, 1))(*self.store_edges)
         self._workspace: Optional[torch.Tensor] = None
         self._workspace_capacity = -1
+        self._exclude_workspace: Optional[torch.Tensor] = None
 
     @property
     def num_edge_types(self) -> int:
@@ -138,22 +139,33 @@ class NeighborStore:
             self._workspace, self._workspace_capacity = ws, node_capacity
         return self._workspace
 
+    def exclude_workspace(self, words: int) -> torch.Tensor:
+        """An int32 workspace of at least ``words`` words for ops.sample_exclude_edges (no initialisation): allocated when
+        a larger one than before is asked for."""
+        if self._exclude_workspace is None or self._exclude_workspace.numel() < words:
+            self._exclude_workspace = torch.empty(words, dtype=torch.int32, device=self.device)
+        return self._exclude_workspace
+
     def local_id_table(self) -> Optional[torch.Tensor]:
         """The first V words of the workspace (None before the first sample): all -1 between calls."""
         return None if self._workspace is None else self._workspace[:self.num_nodes]
 
 
 def sampled_batch(store: NeighborStore, seeds: torch.Tensor, fanouts: Sequence[int], key: int,
-                  seed_only_columns: Sequence[str] = ("node_label_weights",)) -> Tuple[Dict[str, Any], Dict[str, Any]]:
+                  seed_only_columns: Sequence[str] = ("node_label_weights",), exclude=None) -> Tuple[Dict[str, Any], Dict[str, Any]]:
     """The sampled K-hop subgraph of the int32 device tensor ``seeds`` as ``(batch_features, batch_labels)``: node_features
     [n, F], adjacency_list_<t> (local ids), node_to_graph_map = 0 and num_graphs_in_batch = 1, num_seed_nodes,
     sampled_node_ids (device, global ids; the seeds are rows 0 .. num_seed_nodes - 1) and hop_ptr (host); the store's node
     columns as labels [n, W], those named in ``seed_only_columns`` zero below the seed rows.  Not capturable: the counts are
-    read back once between the two library calls."""
-    sample = ops.neighbor_sample(store, seeds, fanouts, key)
+    read back once between the two library calls.
+    ``exclude`` = (positives int32 [B, 3] in local ids, fwd_type, inv_type) goes to ``ops.neighbor_sample``: those edges are
+    taken out of the lists before the counts are read back - no further copy - and ``excluded_edge_counts`` (device int32
+    [L]) says how many went from every list."""
+    sample = ops.neighbor_sample(store, seeds, fanouts, key, exclude=exclude)
     if sample.status:
         raise ValueError(f"neighbour sampling failed with status {sample.status} (include/tfgnn.h TFGNN_SAMPLE_*: 4 a repeated "
-                         "seed, 8 a seed outside the graph, 16 an in-CSR that disagrees with its sizes)")
+                         "seed, 8 a seed outside the graph, 16 an in-CSR that disagrees with its sizes; 32 / 64 an excluded "
+                         "positive with a relation / an endpoint outside the batch)")
     bad_flag = torch.zeros(1, dtype=torch.int32, device=store.device)
     nf, cols = ops.gather_node_rows(sample.nodes, sample.num_seeds, store.features, store.node_columns,
                                     seed_only=[name in seed_only_columns for name in store.node_column_names], bad_flag=bad_flag)
@@ -171,4 +183,6 @@ def sampled_batch(store: NeighborStore, seeds: torch.Tensor, fanouts: Sequence[i
     }
     for t, a in enumerate(sample.adjacency_lists):
         features[f"adjacency_list_{t}"] = a
+    if sample.removed is not None:
+        features["excluded_edge_counts"] = sample.removed
     return features, dict(zip(store.node_column_names, cols))

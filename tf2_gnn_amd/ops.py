@@ -2742,10 +2742,11 @@ class NeighborSample:
     int32 [K + 2]), ``adjacency_lists`` (device int32 [E_t, 2], local ids), ``status`` (int, the TFGNN_SAMPLE_* bits).  The
     device tensors are prefix views of buffers allocated at the capacity."""
 
-    __slots__ = ("nodes", "hop_ptr", "adjacency_lists", "status", "num_seeds")
+    __slots__ = ("nodes", "hop_ptr", "adjacency_lists", "status", "num_seeds", "removed")
 
-    def __init__(self, nodes, hop_ptr, adjacency_lists, status, num_seeds):
+    def __init__(self, nodes, hop_ptr, adjacency_lists, status, num_seeds, removed=None):
         self.nodes, self.hop_ptr, self.adjacency_lists, self.status, self.num_seeds = nodes, hop_ptr, adjacency_lists, status, num_seeds
+        self.removed = removed  # with ``exclude``: device int32 [L], the edges taken out of every list; else None
 
 
 def sample_capacities(num_seeds: int, fanouts: Sequence[int], num_nodes: int, store_edges: Sequence[int],
@@ -2775,13 +2776,83 @@ def sample_launch_counts():
     return int(buf[0]), int(buf[1])
 
 
-def neighbor_sample(store, seeds: torch.Tensor, fanouts: Sequence[int], seed: int, out=None) -> NeighborSample:
+def sample_exclude_launch_counts() -> int:
+    """tfgnn_sample_exclude_launch_counts: kernel launches of ``sample_exclude_edges`` so far (4 per call; a host counter)."""
+    buf = (ctypes.c_int64 * 1)()
+    _lib.check(_lib.load().tfgnn_sample_exclude_launch_counts(buf, 1))
+    return int(buf[0])
+
+
+def sample_exclude_workspace_words(edge_capacity: Sequence[int]) -> int:
+    """int32 words of tfgnn_sample_exclude_workspace_bytes for lists of these capacities"""
+    L = len(edge_capacity)
+    caps = (ctypes.c_int64 * max(L, 1))(*[int(e) for e in edge_capacity])
+    nbytes = int(_lib.load().tfgnn_sample_exclude_workspace_bytes(L, ctypes.addressof(caps)))
+    if nbytes == 0:
+        raise ValueError("no exclusion workspace for these capacities (include/tfgnn.h: limits of tfgnn_sample_exclude_edges)")
+    return nbytes // 4
+
+
+def sample_exclude_edges(adjacency_lists: Sequence[torch.Tensor], meta: torch.Tensor, num_seeds: int, positives: torch.Tensor,
+                         fwd_type: Sequence[int], inv_type: Sequence[int], workspace: Optional[torch.Tensor] = None,
+                         record: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Take a batch's positives out of a sampled subgraph by one tfgnn_sample_exclude_edges call (4 launches on the current
+    stream; include/tfgnn.h "Excluding a batch's positives").  ``adjacency_lists``: the sampler's lists at their CAPACITY
+    (int32 [cap_t, 2], local ids, sorted by target), ``meta`` its meta words on the device - the live counts are read and
+    updated there -, ``positives`` int32 [B, 3] rows (u, r, v) in local ids, ``fwd_type`` / ``inv_type``: per relation the
+    processed edge type of its forward edges and of their inverses (-1: none).  Every edge (u, v) of list fwd_type[r] and
+    every edge (v, u) of list inv_type[r] goes; the kept edges keep their order.  -> ``record`` int32 [L + 1] on the device:
+    the edges removed per list, then the status word (``_lib.SAMPLE_EXCLUDE_*``; also OR-ed into meta's status).  Nothing
+    is read back here."""
+    _require_dev(meta, torch.int32, "meta")
+    L, T = len(adjacency_lists), len(fwd_type)
+    if len(inv_type) != T:
+        raise ValueError("fwd_type and inv_type name the same relations")
+    for t in adjacency_lists:
+        _require_dev(t, torch.int32, "an adjacency list")
+        if t.dim() != 2 or t.shape[1] != 2 or not t.is_contiguous():
+            raise ValueError(f"an adjacency list must be a contiguous int32 [capacity, 2], got {tuple(t.shape)}")
+    if not meta.is_contiguous() or meta.numel() < _lib.SAMPLE_META_EDGES + L:
+        raise ValueError("meta must be the sampler's contiguous meta words")
+    B = _device_triples(positives, "positives")
+    dev = meta.device
+    edge_cap = [int(t.shape[0]) for t in adjacency_lists]
+    if workspace is None:
+        workspace = torch.empty(sample_exclude_workspace_words(edge_cap), dtype=torch.int32, device=dev)
+    _require_dev(workspace, torch.int32, "workspace")
+    if record is None:
+        record = torch.empty(L + 1, dtype=torch.int32, device=dev)
+    _require_dev(record, torch.int32, "record")
+    if not record.is_contiguous() or record.numel() < L + 1:
+        raise ValueError(f"record must be a contiguous int32 [{L + 1}]")
+    a = _lib.SampleExcludeArgs()
+    a.struct_size = ctypes.sizeof(_lib.SampleExcludeArgs)
+    a.num_edge_types, a.num_relations, a.num_seeds, a.num_positives = L, T, int(num_seeds), B
+    fwd = (ctypes.c_int32 * max(T, 1))(*[int(x) for x in fwd_type])
+    inv = (ctypes.c_int32 * max(T, 1))(*[int(x) for x in inv_type])
+    caps = (ctypes.c_int64 * max(L, 1))(*edge_cap)
+    adj_tab = (ctypes.c_void_p * max(L, 1))(*[t.data_ptr() for t in adjacency_lists])
+    a.positives, a.fwd_type, a.inv_type = positives.data_ptr(), ctypes.addressof(fwd), ctypes.addressof(inv)
+    a.edge_capacity, a.adjacency_lists = ctypes.addressof(caps), ctypes.addressof(adj_tab)
+    a.meta, a.record = meta.data_ptr(), record.data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * 4
+    _lib.check(_lib.load().tfgnn_sample_exclude_edges(ctypes.byref(a), _stream()))
+    for t in list(adjacency_lists) + [meta, record]:
+        torch.autograd.graph.increment_version(t)  # written through raw pointers, which torch does not see
+    return record
+
+
+def neighbor_sample(store, seeds: torch.Tensor, fanouts: Sequence[int], seed: int, out=None, exclude=None) -> NeighborSample:
     """One K-hop neighbour sample (K = len(fanouts); a fanout < 0 takes every in-edge) of the int32 device tensor ``seeds``
     on ``store`` (data.NeighborStore: the in-CSR per edge type, kept on the device): 3 + 6 K launches on the current stream,
     then ONE small device-to-host copy of the counts - the sizes are data-dependent and the graph build needs them on the
     host.  That copy synchronises, so a sampled batch cannot be captured in a CapturedStep.  Buffers are allocated at
     ``sample_capacities`` - they cannot overflow - unless ``out`` = (nodes [cap], [adjacency_list [cap_t, 2]]) brings smaller
-    ones; what does not fit then sets an overflow bit in ``status``.  The draw is a pure function of (seed, node, type)."""
+    ones; what does not fit then sets an overflow bit in ``status``.  The draw is a pure function of (seed, node, type).
+    ``exclude`` = (positives int32 [B, 3] in local ids, fwd_type, inv_type): ``sample_exclude_edges`` is enqueued between
+    the sampler and the copy - draw first, then drop; a row may keep fewer edges than its fanout - and ``removed`` of the
+    result is the device int32 [L] of edges taken out of every list; ``nodes`` and ``hop_ptr`` are what they are without
+    it.  None: the call above and nothing else."""
     _require_dev(seeds, torch.int32, "seeds")
     seeds = seeds.contiguous().view(-1)
     S, L, K, V = int(seeds.shape[0]), store.num_edge_types, len(fanouts), store.num_nodes
@@ -2816,11 +2887,17 @@ def neighbor_sample(store, seeds: torch.Tensor, fanouts: Sequence[int], seed: in
     a.adjacency_lists, a.meta = ctypes.addressof(adj_tab), meta.data_ptr()
     a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * 4
     _lib.check(_lib.load().tfgnn_neighbor_sample(ctypes.byref(a), _stream()))
+    removed = None
+    if exclude is not None:
+        positives, fwd_type, inv_type = exclude
+        removed = sample_exclude_edges(adj, meta, S, positives, fwd_type, inv_type,
+                                       workspace=store.exclude_workspace(sample_exclude_workspace_words(edge_cap)))[:L]
     host = meta.cpu().numpy()  # the one copy
     n = int(host[_lib.SAMPLE_META_NODES])
     counts = host[_lib.SAMPLE_META_EDGES:_lib.SAMPLE_META_EDGES + L]
     hop_ptr = host[_lib.SAMPLE_META_EDGES + L:].copy()
-    return NeighborSample(nodes[:n], hop_ptr, [t[:int(c)] for t, c in zip(adj, counts)], int(host[_lib.SAMPLE_META_STATUS]), S)
+    return NeighborSample(nodes[:n], hop_ptr, [t[:int(c)] for t, c in zip(adj, counts)], int(host[_lib.SAMPLE_META_STATUS]), S,
+                          removed)
 
 
 def gather_node_rows(nodes: torch.Tensor, num_seeds: int, features: torch.Tensor, columns: Sequence[torch.Tensor] = (),
