@@ -14,7 +14,8 @@
 // CSR row and a window of LPR*VPL float4 chunks of the feature dimension.  Lane j of the group
 // owns chunks j, j+LPR, ... so that each load instruction of a group reads LPR*16 contiguous bytes
 // of one source row (>= one 128 B line for LPR >= 8).  Edges are walked UNROLL at a time to keep
-// UNROLL*VPL 16-byte loads in flight per lane.  Accumulation order inside a row is the CSR order
+// UNROLL*VPL 16-byte loads in flight per lane; their column indices and weights are read LPR edges
+// at a time, one edge per lane, and handed round inside the group (EdgeBlocks).  Accumulation order inside a row is the CSR order
 // (cols ascending) -> bit-reproducible, no atomics.
 //
 // Skew (R-MAT hubs): with a plan (graph views), rows longer than LONG_ROW_THRESHOLD are skipped by
@@ -208,11 +209,128 @@ __device__ __forceinline__ float sp_row_scale(const GatherArgs& a, unsigned mx, 
   return sc;
 }
 
+// ---- the edge walk's index blocks (round 12) --------------------------------------------------------------------------------
+// A lane group reads what it needs to know about its edges - column index, scalar weight, (MODE_HEADS_DOT) output position -
+// LPR consecutive edges at a time: lane j of the group loads edge p0 + j of the block, one coalesced load per array.  An
+// edge's values reach all lanes of the group by a cross-lane read (__shfl inside the group: ds_bpermute, no memory access).
+// Before, every lane of the group loaded the same col[e] at the top of every round and waited for it with no source row in
+// flight: two latencies in series per round; now the walk waits for indices once per LPR edges (a typed short row of <= 48
+// edges: at most three times).  Keeping the block after the current one in flight as well was measured and dropped: the two
+// registers it holds across the loop took the SP16 kernel at width 320 from 90 to 107 registers, 5 waves per SIMD to 4, and
+// the launch from 84 to 86 us (NOTEBOOK section 46).
+// All lanes of a group walk the same edges, so the cross-lane reads are convergent inside the group; other groups of the
+// wave may be anywhere, their lanes are not read.
+template <int MODE>
+struct EdgeBlock {
+  int32_t idx;  // lanes past the end of the walk: 0 (never used for a load)
+  float w;
+  int32_t pos;
+};
+template <int MODE>
+__device__ __forceinline__ EdgeBlock<MODE> load_edge_block(const GatherArgs& a, int32_t p, int32_t end) {
+  EdgeBlock<MODE> b;
+  b.idx = 0;
+  b.w = 1.f;
+  b.pos = p;
+  if (p < end) {
+    b.idx = a.col[p];
+    if (!mode_heads(MODE) && a.ew) b.w = a.ew[p];
+    if (MODE == MODE_HEADS_DOT && a.dot_pos) b.pos = a.dot_pos[p];
+  }
+  return b;
+}
+// the block being walked (first edge `base`)
+template <int LPR, int MODE>
+struct EdgeBlocks {
+  EdgeBlock<MODE> cur;
+  int32_t base, end;
+  int gl;
+  __device__ __forceinline__ void start(const GatherArgs& a, int32_t beg, int32_t end_) {
+    gl = threadIdx.x % LPR;
+    base = beg;
+    end = end_;
+    cur = load_edge_block<MODE>(a, beg + gl, end);
+  }
+  // make the block that holds edge e (>= base, at most one block on) the current one
+  __device__ __forceinline__ void seek(const GatherArgs& a, int32_t e) {
+    if (e - base >= LPR) {
+      base += LPR;
+      cur = load_edge_block<MODE>(a, base + gl, end);
+    }
+  }
+  __device__ __forceinline__ int32_t idx(int32_t e) const { return __shfl(cur.idx, e - base, LPR); }
+  __device__ __forceinline__ float w(int32_t e) const { return __shfl(cur.w, e - base, LPR); }
+  __device__ __forceinline__ int32_t pos(int32_t e) const { return __shfl(cur.pos, e - base, LPR); }
+};
+
+// Which walks read their indices in blocks: the ones with rounds of two edges (rows of 256 floats and more, where a round
+// is short and a row has many of them), except MODE_GENERAL.  The variants with rounds of four and eight edges keep one index
+// load per edge and round: their wait is spread over a longer round, the (node, type) buckets of a molecule batch hold fewer
+// edges than one round, and with the blocks qm9-ggnn (width 128) ran 0.26 % slower in three pairs of three.  MODE_GENERAL:
+// the block registers cost its narrow variants a wave per SIMD (80 -> 86, 77 -> 84 registers; tools/kernel_resources.py).
+__host__ __device__ constexpr bool index_blocks(int mode, int unroll) { return mode != MODE_GENERAL && unroll <= 2; }
+
+// plain sums: the source rows of the round of edges [e, e + UNROLL) (part of one index block: UNROLL divides LPR and rounds
+// start at multiples of UNROLL from the first edge).  Edges past `end` are not loaded (the walk of the other modes re-reads
+// the last edge of an odd row).
+template <int LPR, int VPL, int VEC, int UNROLL>
+__device__ __forceinline__ void issue_round(const GatherArgs& a, EdgeBlocks<LPR, MODE_SUM>& blocks, int32_t e, int32_t end, int f0,
+                                            const bool (&live)[VPL], typename VecT<VEC>::type (&v)[UNROLL][VPL], float (&w)[UNROLL]) {
+  static_assert(LPR % UNROLL == 0, "a round must not straddle two index blocks");
+  if (e >= end) return;
+  blocks.seek(a, e);
+#pragma unroll
+  for (int u = 0; u < UNROLL; ++u) {
+    const int32_t idx = blocks.idx(e + u);
+    w[u] = a.ew ? blocks.w(e + u) : 1.f;
+    if (e + u < end) {
+      const float* src = a.in + (int64_t)idx * a.ld_in + f0;
+#pragma unroll
+      for (int i = 0; i < VPL; ++i)
+        if (live[i]) v[u][i] = vload<VEC>(src + i * LPR * VEC);
+    }
+  }
+}
+template <int LPR, int VPL, int VEC, int UNROLL>
+__device__ __forceinline__ void add_round(int32_t e, int32_t end, const bool (&live)[VPL], const typename VecT<VEC>::type (&v)[UNROLL][VPL],
+                                          const float (&w)[UNROLL], float (&acc)[VPL][VEC]) {
+#pragma unroll
+  for (int u = 0; u < UNROLL; ++u) {
+    if (e + u < end) {
+#pragma unroll
+      for (int i = 0; i < VPL; ++i) {
+        if (live[i]) {
+          float x[VEC];
+          vunpack<VEC>(v[u][i], x);
+#pragma unroll
+          for (int c = 0; c < VEC; ++c) {
+            float m = w[u] * x[c];
+            acc[i][c] += m;
+          }
+        }
+      }
+    }
+  }
+}
+
 // accumulate edges [beg, end) into acc (lane-private chunks)
 template <int LPR, int VPL, int VEC, int UNROLL, int MODE>
 __device__ __forceinline__ void accumulate_edges(const GatherArgs& a, int32_t beg, int32_t end, int f0,
                                                  const bool (&live)[VPL], float (&acc)[VPL][VEC], int64_t row) {
   using V = typename VecT<VEC>::type;
+  EdgeBlocks<LPR, MODE> blocks;
+  if constexpr (index_blocks(MODE, UNROLL)) blocks.start(a, beg, end);
+  if constexpr (MODE == MODE_SUM && index_blocks(MODE, UNROLL)) {
+    // (loading the rows of round n + 1 before the adds of round n - whole rounds at 3 waves per SIMD, half rounds at 5 - was
+    // slower than this loop at width 320: NOTEBOOK section 46)
+    V v[UNROLL][VPL];
+    float w[UNROLL];
+    for (int32_t e = beg; e < end; e += UNROLL) {
+      issue_round<LPR, VPL, VEC, UNROLL>(a, blocks, e, end, f0, live, v, w);
+      add_round<LPR, VPL, VEC, UNROLL>(e, end, live, v, w, acc);
+    }
+    return;
+  }
   const bool is_max = MODE == MODE_GENERAL && a.is_max;
   int hidx[VPL];
   if (mode_heads(MODE)) {
@@ -252,15 +370,23 @@ __device__ __forceinline__ void accumulate_edges(const GatherArgs& a, int32_t be
     int32_t dpos[UNROLL];
     float w[UNROLL];
     bool ok[UNROLL];
+    if constexpr (index_blocks(MODE, UNROLL)) blocks.seek(a, e);
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
       int32_t ee = e + u;
       ok[u] = ee < end;
-      ee = ok[u] ? ee : end - 1;
+      ee = ok[u] ? ee : end - 1;  // (in the block of e: e <= end - 1 < e + u)
       eid[u] = ee;
-      idx[u] = a.col[ee];
-      if constexpr (MODE == MODE_HEADS_DOT) dpos[u] = a.dot_pos ? a.dot_pos[ee] : ee;
-      w[u] = (!mode_heads(MODE) && a.ew) ? a.ew[ee] : 1.f;
+      if constexpr (index_blocks(MODE, UNROLL)) {
+        static_assert(LPR % UNROLL == 0, "a round must not straddle two index blocks");
+        idx[u] = blocks.idx(ee);
+        if constexpr (MODE == MODE_HEADS_DOT) dpos[u] = blocks.pos(ee);
+        w[u] = (!mode_heads(MODE) && a.ew) ? blocks.w(ee) : 1.f;
+      } else {
+        idx[u] = a.col[ee];
+        if constexpr (MODE == MODE_HEADS_DOT) dpos[u] = a.dot_pos ? a.dot_pos[ee] : ee;
+        w[u] = (!mode_heads(MODE) && a.ew) ? a.ew[ee] : 1.f;
+      }
     }
     V v[UNROLL][VPL];
     float wh[UNROLL][VPL];
