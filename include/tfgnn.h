@@ -1194,6 +1194,78 @@ int tfgnn_distmult_rank(const float* d_H, int64_t ld_H, const float* d_R, const 
 int tfgnn_link_launch_counts(int64_t* out_counts, int n);
 
 /* ------------------------------------------------------------------------------------------
+ * Link prediction with a ComplEx decoder (LinkPredictionTask link_decoder="complex", csrc/link.hip; Trouillon et al. 2016; the
+ * reference has no counterpart, PARITY UNPINNED).  DistMult is symmetric in its two entities; ComplEx is not.  D is even,
+ * m = D / 2, and a row x of H or R is the complex vector x_re = x[0 .. m), x_im = x[m .. D): HALVES, not interleaved, so a
+ * wave's loads of either part are coalesced.  For a triple (u, t, v) with a = H[u], r = R[t], b = H[v]:
+ *   s = Re sum_k a[k] r[k] conj(b[k])
+ *     = sum_k r_re[k] (a_re[k] b_re[k] + a_im[k] b_im[k]) + r_im[k] (a_re[k] b_im[k] - a_im[k] b_re[k])
+ * The three calls have the parameter lists of their tfgnn_distmult_* namesakes (the rank workspace size also takes D) and
+ * everything said there to be common holds here: d_H [V, D] with row stride ld_H >= D, d_R [T, D] contiguous, int32 [N, 3]
+ * triples, the same triple tables, indices and tables NOT checked by the kernels, no allocation, no host synchronisation,
+ * capturable on the one stream given, no floating-point atomic - every floating-point sum has an order that is a function
+ * of the arguments and tables only, not of timing and not of which optional outputs are requested.  2 <= D <= 1024, D even
+ * (an odd D is refused: "must be even"), 1 <= V, T < 2^31, 1 <= N <= 2^30.  Bad arguments are refused before any launch, by
+ * the rules and with the messages of the DistMult calls.
+ *   score     s_e in fp32 by ONE device routine shared by the kernels of tfgnn_complex_ce_metrics: lane l of a wave adds the
+ *             complex columns k = l, l + 64, l + 128, ... in ascending order, per column
+ *               x = fma(a_im, b_im, a_re * b_re);  y = fma(-a_im, b_re, a_re * b_im);  p = fma(r_re, x, p);  p = fma(r_im, y, p)
+ *             and the 64 lane sums are added by the xor butterfly (distances 32, 16, 8, 4, 2, 1).  Against exact arithmetic
+ *             |s_e - s| <= (2 D + 3) 2^-24 P_e, P_e = sum_k |r_re| (|a_re b_re| + |a_im b_im|) + |r_im| (|a_re b_im| + |a_im b_re|).
+ *
+ * tfgnn_complex_ce_metrics: tfgnn_distmult_ce_metrics with that score.  Counted triples, W, the loss element, the counts, the
+ * s > 0 prediction, d_gscore, the NaN rule, the three launches and the bit-identity of d_metrics / d_counts whatever optional
+ * outputs are requested are those of the DistMult call - it is the same code.  d_workspace:
+ * tfgnn_complex_ce_workspace_bytes() bytes, 8-byte aligned.
+ *
+ * tfgnn_complex_backward: from g = d_gscore [N], over the same tables in the same SUM ORDER as tfgnn_distmult_backward (rows
+ * of at most 256 list positions in list order, longer rows in chunks of 256 - one wave per chunk - and the chunk sums in
+ * ascending chunk order), four launches (two per requested gradient), the same accumulate rule, exact 0 rows for a node or a
+ * relation without entries, columns >= D of d_dH untouched.  The term of a list position, with role 0: the node is the
+ * source a of the triple, role 1: it is the target b,
+ *   dH_re += g (r_re b_re + r_im b_im)   dH_im += g (r_re b_im - r_im b_re)      (role 0)
+ *   dH_re += g (r_re a_re - r_im a_im)   dH_im += g (r_re a_im + r_im a_re)      (role 1)
+ *   dR_re += g (a_re b_re + a_im b_im)   dR_im += g (a_re b_im - a_im b_re)
+ * is added as two fused multiply-adds per part.  With (x, y) = (R[t_e], H[other end]) for dH and (H[u_e], H[v_e]) for dR,
+ * gr = g_e * x_re, gi = g_e * x_im, and sg = -gi for a role-1 entry of dH, gi otherwise:
+ *   acc_re = fma(gr, y_re, acc_re);  acc_re = fma(sg, y_im, acc_re);  acc_im = fma(gr, y_im, acc_im);  acc_im = fma(-sg, y_re, acc_im)
+ * A wave holds 256 complex columns at a time, re and im of a column in the same lane, so the four row reads of a term serve
+ * both parts.  d_workspace: tfgnn_complex_backward_workspace_bytes(N, D) bytes, 4-byte aligned.
+ *
+ * tfgnn_complex_rank: the outputs, the filter semantics and the NaN rule of tfgnn_distmult_rank; the counts are exact integers
+ * (integer atomics).  The score of a candidate is linear in its row, so the pre-pass (one wave per query) writes one QUERY
+ * VECTOR q [D] per query into the workspace,
+ *   side 0, candidates (u, t, c):  q_re = fma(r_re, a_re, -(r_im * a_im))   q_im = fma(r_re, a_im, r_im * a_re)
+ *   side 1, candidates (c, t, v):  q_re = fma(r_re, b_re, r_im * b_im)      q_im = fma(r_re, b_im, -(r_im * b_re))
+ * and EVERY score of the call - the true triple's (the true entity's row as the candidate), the filter ids', the candidates' -
+ * is the dot product <q, H[c]> by one routine: lane l adds d = l, l + 64, ... in ascending order as p = fma(q[d], H[c, d], p),
+ * then the butterfly.  A candidate whose row equals the true entity's bit for bit therefore counts as equal.  These scores are
+ * NOT the bits of tfgnn_complex_ce_metrics (another operation order); they lie within the same (2 D + 3) 2^-24 P_e of exact
+ * arithmetic.  Launches: the pre-pass (query vectors, true scores, MINUS the counts over the filter ids) and the main pass - a
+ * workgroup per (candidate slice, tile of 16 queries), each wave scoring its LDS-resident candidate row against the 16 query
+ * vectors.  d_workspace: tfgnn_complex_rank_workspace_bytes(Q, D) = Q (D + 1) floats, 4-byte aligned.
+ *
+ * The *_workspace_bytes(..) calls return 0 for sizes the calls refuse (D odd or outside [2, 1024], N or Q outside [1, 2^30]).
+ * tfgnn_complex_launch_counts: kernel launches so far of {tfgnn_complex_ce_metrics, tfgnn_complex_backward,
+ * tfgnn_complex_rank} (host counters; entries beyond the third are 0).  tfgnn_link_launch_counts counts the DistMult calls
+ * only. */
+size_t tfgnn_complex_ce_workspace_bytes(void);
+int tfgnn_complex_ce_metrics(const float* d_H, int64_t ld_H, const float* d_R, const int32_t* d_triples, const float* d_labels,
+                             int64_t ld_labels, const float* d_weights, int64_t ld_weights, int64_t V, int64_t T, int64_t N,
+                             int64_t D, float* d_metrics, int64_t* d_counts, float* d_scores, float* d_gscore,
+                             void* d_workspace, size_t workspace_bytes, void* stream);
+size_t tfgnn_complex_backward_workspace_bytes(int64_t N, int64_t D);
+int tfgnn_complex_backward(const float* d_H, int64_t ld_H, const float* d_R, const int32_t* d_triples, const float* d_gscore,
+                           const int32_t* d_node_offsets, const int32_t* d_node_entries, const int32_t* d_rel_offsets,
+                           const int32_t* d_rel_order, int64_t V, int64_t T, int64_t N, int64_t D, float* d_dH, int64_t ld_dH,
+                           int accumulate, float* d_dR, void* d_workspace, size_t workspace_bytes, void* stream);
+size_t tfgnn_complex_rank_workspace_bytes(int64_t Q, int64_t D);
+int tfgnn_complex_rank(const float* d_H, int64_t ld_H, const float* d_R, const int32_t* d_queries, int64_t Q, int side,
+                       const int32_t* d_filter_offsets, const int32_t* d_filter_ids, int64_t V, int64_t T, int64_t D,
+                       int32_t* d_greater, int32_t* d_equal, void* d_workspace, size_t workspace_bytes, void* stream);
+int tfgnn_complex_launch_counts(int64_t* out_counts, int n);
+
+/* ------------------------------------------------------------------------------------------
  * Negative sampling and triple tables on the device (csrc/negatives.hip): what LinkPredictionDataset does per epoch on the
  * host - draw the negatives, rebuild the triple tables - as calls on the caller's stream, so that a captured training step
  * carries its own fresh negatives.  Integers only: no call does float arithmetic.  No call allocates or synchronises with

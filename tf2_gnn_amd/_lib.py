@@ -404,6 +404,31 @@ _SIGNATURES += [
     ),
     ("tfgnn_link_launch_counts", c_int, [POINTER(c_int64), c_int]),
 ]
+# ... and with a ComplEx decoder: the same argument lists; the rank workspace size also takes D
+_SIGNATURES += [
+    ("tfgnn_complex_ce_workspace_bytes", c_size_t, []),
+    (
+        "tfgnn_complex_ce_metrics",
+        c_int,
+        [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    ("tfgnn_complex_backward_workspace_bytes", c_size_t, [c_int64, c_int64]),
+    (
+        "tfgnn_complex_backward",
+        c_int,
+        [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
+         c_void_p, c_int64, c_int, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    ("tfgnn_complex_rank_workspace_bytes", c_size_t, [c_int64, c_int64]),
+    (
+        "tfgnn_complex_rank",
+        c_int,
+        [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+         c_void_p, c_size_t, c_void_p],
+    ),
+    ("tfgnn_complex_launch_counts", c_int, [POINTER(c_int64), c_int]),
+]
 LINK_CHUNK = 256  # csrc/link.hip LINK_CHUNK: list positions per chunk of the backward passes
 
 # neighbour sampling and the row gather of a sampled batch (include/tfgnn.h "Neighbour sampling", csrc/sample.hip)

@@ -1631,7 +1631,7 @@ def softmax_ce_metrics(logits: torch.Tensor, labels: torch.Tensor, weights: Opti
     return metrics, counts, grad, pred
 
 
-# ---- link prediction with a DistMult decoder: include/tfgnn.h tfgnn_distmult_*, csrc/link.hip ------------------------------
+# ---- link prediction decoders: include/tfgnn.h tfgnn_distmult_* / tfgnn_complex_*, csrc/link.hip ---------------------------
 def check_triples(triples, V: int, T: int, what: str = "triples") -> np.ndarray:
     """Host triples [N, 3] (source, relation, target) as a contiguous int32 array, every index in range - the check the
     kernels leave to the host (include/tfgnn.h).  Raises ValueError otherwise."""
@@ -1672,9 +1672,15 @@ def build_triple_tables(triples, V: int, T: int) -> Dict[str, np.ndarray]:
 TRIPLE_TABLE_NAMES = ("node_offsets", "node_entries", "rel_offsets", "rel_order")
 
 
-def _link_common(H: torch.Tensor, R: torch.Tensor, triples, what: str):
+LINK_DECODERS = ("distmult", "complex")
+
+
+def _link_common(H: torch.Tensor, R: torch.Tensor, triples, what: str, decoder: str = "distmult"):
     """-> (H, ld_H, R, triples on the device, V, T, N, D).  Host triples (numpy) are validated and uploaded; a device tensor is
-    taken as validated by whoever uploaded it (build_triple_tables / check_triples): reading it back would synchronise."""
+    taken as validated by whoever uploaded it (build_triple_tables / check_triples): reading it back would synchronise.
+    ``decoder`` "complex": a row is [re ; im], so an odd width is a ValueError."""
+    if decoder == "complex" and isinstance(H, torch.Tensor) and H.dim() == 2 and H.shape[1] % 2:
+        raise ValueError(f"the ComplEx decoder reads a row as [re ; im] halves: the width must be even, not {H.shape[1]}")
     _require_dev(H, torch.float32, "H")
     _require_dev(R, torch.float32, "R")
     H, ldh = _rowmajor(H, "H")
@@ -1692,15 +1698,9 @@ def _link_common(H: torch.Tensor, R: torch.Tensor, triples, what: str):
     return H, ldh, R, triples, V, T, triples.shape[0], D
 
 
-def distmult_ce_metrics(H: torch.Tensor, R: torch.Tensor, triples, labels: torch.Tensor, weights: Optional[torch.Tensor] = None,
-                        need_grad: bool = True, want_scores: bool = True, want_counts: bool = True):
-    """DistMult scores of ``triples`` [N, 3] from node representations H [V, D] and relation embeddings R [T, D], their
-    weighted sigmoid cross-entropy against ``labels`` (0 / 1), confusion counts and d loss / d score (include/tfgnn.h
-    tfgnn_distmult_ce_metrics: a triple is counted iff its weight is > 0 and its label exactly 0 or 1) ->
-    (metrics [2] = (loss, accuracy), counts int64 [4] = (tp, fp, tn, fn) or None, scores [N] or None, gscore [N] or None),
-    all on the device.  ``labels`` / ``weights``: [N], [N, 1] or a strided column view, passed by stride."""
+def _link_ce_metrics(decoder, H, R, triples, labels, weights, need_grad, want_scores, want_counts):
     lib = _lib.load()
-    H, ldh, R, triples, V, T, N, D = _link_common(H, R, triples, "triples")
+    H, ldh, R, triples, V, T, N, D = _link_common(H, R, triples, "triples", decoder)
     _require_dev(labels, torch.float32, "labels")
     labels, ldy = _node_column(labels, N, "labels")
     ldw = 0
@@ -1712,22 +1712,34 @@ def distmult_ce_metrics(H: torch.Tensor, R: torch.Tensor, triples, labels: torch
     counts = torch.empty(4, dtype=torch.int64, device=dev) if want_counts else None
     scores = torch.empty(N, dtype=torch.float32, device=dev) if want_scores else None
     gscore = torch.empty(N, dtype=torch.float32, device=dev) if need_grad else None
-    ws = _workspace(dev, lib.tfgnn_distmult_ce_workspace_bytes())
-    _lib.check(lib.tfgnn_distmult_ce_metrics(_ptr(H), ldh, _ptr(R), _ptr(triples), _ptr(labels), ldy, _ptr(weights), ldw, V, T, N, D,
-                                             _ptr(metrics), _ptr(counts), _ptr(scores), _ptr(gscore), _ptr(ws), ws.numel(),
-                                             _stream()))
+    ws = _workspace(dev, getattr(lib, f"tfgnn_{decoder}_ce_workspace_bytes")())
+    _lib.check(getattr(lib, f"tfgnn_{decoder}_ce_metrics")(_ptr(H), ldh, _ptr(R), _ptr(triples), _ptr(labels), ldy, _ptr(weights), ldw,
+                                                           V, T, N, D, _ptr(metrics), _ptr(counts), _ptr(scores), _ptr(gscore),
+                                                           _ptr(ws), ws.numel(), _stream()))
     return metrics, counts, scores, gscore
 
 
-@_writes_out
-def distmult_backward(H: torch.Tensor, R: torch.Tensor, triples, gscore: torch.Tensor, tables: Dict[str, torch.Tensor],
-                      want_dH: bool = True, want_dR: bool = True, accumulate: bool = False, out: Optional[torch.Tensor] = None):
-    """d loss / d H [V, D] and d loss / d R [T, D] from ``gscore`` [N] (include/tfgnn.h tfgnn_distmult_backward; the sum order is
-    stated there) -> (dH or None, dR or None).  ``tables``: the four int32 device tensors of ``build_triple_tables``.  ``out``:
-    where dH goes instead of a new tensor - a float32 [V, D] with unit inner stride, e.g. D columns of a wider array whose
-    other columns stay as they are; with ``accumulate`` the sums are added to what it holds."""
+def distmult_ce_metrics(H: torch.Tensor, R: torch.Tensor, triples, labels: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                        need_grad: bool = True, want_scores: bool = True, want_counts: bool = True):
+    """DistMult scores of ``triples`` [N, 3] from node representations H [V, D] and relation embeddings R [T, D], their
+    weighted sigmoid cross-entropy against ``labels`` (0 / 1), confusion counts and d loss / d score (include/tfgnn.h
+    tfgnn_distmult_ce_metrics: a triple is counted iff its weight is > 0 and its label exactly 0 or 1) ->
+    (metrics [2] = (loss, accuracy), counts int64 [4] = (tp, fp, tn, fn) or None, scores [N] or None, gscore [N] or None),
+    all on the device.  ``labels`` / ``weights``: [N], [N, 1] or a strided column view, passed by stride."""
+    return _link_ce_metrics("distmult", H, R, triples, labels, weights, need_grad, want_scores, want_counts)
+
+
+def complex_ce_metrics(H: torch.Tensor, R: torch.Tensor, triples, labels: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                       need_grad: bool = True, want_scores: bool = True, want_counts: bool = True):
+    """``distmult_ce_metrics`` with the ComplEx score s = Re sum_k H[u, k] R[t, k] conj(H[v, k]), a row of H or R being the
+    complex vector [re ; im] (include/tfgnn.h tfgnn_complex_ce_metrics): the same arguments, outputs and counting rule.  An
+    odd width is a ValueError."""
+    return _link_ce_metrics("complex", H, R, triples, labels, weights, need_grad, want_scores, want_counts)
+
+
+def _link_backward(decoder, H, R, triples, gscore, tables, want_dH, want_dR, accumulate, out):
     lib = _lib.load()
-    H, ldh, R, triples, V, T, N, D = _link_common(H, R, triples, "triples")
+    H, ldh, R, triples, V, T, N, D = _link_common(H, R, triples, "triples", decoder)
     _require_dev(gscore, torch.float32, "gscore")
     if gscore.dim() != 1 or gscore.shape[0] != N:
         raise ValueError(f"gscore {tuple(gscore.shape)} must be [{N}]")
@@ -1752,11 +1764,30 @@ def distmult_backward(H: torch.Tensor, R: torch.Tensor, triples, gscore: torch.T
             raise ValueError("accumulate needs the tensor to add to: out=")
         dH = torch.empty((V, D), dtype=torch.float32, device=dev)
     dR = torch.empty((T, D), dtype=torch.float32, device=dev) if want_dR else None
-    ws = _workspace(dev, lib.tfgnn_distmult_backward_workspace_bytes(N, D))
-    _lib.check(lib.tfgnn_distmult_backward(_ptr(H), ldh, _ptr(R), _ptr(triples), _ptr(gscore), _ptr(tabs["node_offsets"]),
-                                           _ptr(tabs["node_entries"]), _ptr(tabs["rel_offsets"]), _ptr(tabs["rel_order"]), V, T, N, D,
-                                           _ptr(dH), ldd, int(bool(accumulate)), _ptr(dR), _ptr(ws), ws.numel(), _stream()))
+    ws = _workspace(dev, getattr(lib, f"tfgnn_{decoder}_backward_workspace_bytes")(N, D))
+    _lib.check(getattr(lib, f"tfgnn_{decoder}_backward")(_ptr(H), ldh, _ptr(R), _ptr(triples), _ptr(gscore), _ptr(tabs["node_offsets"]),
+                                                         _ptr(tabs["node_entries"]), _ptr(tabs["rel_offsets"]), _ptr(tabs["rel_order"]),
+                                                         V, T, N, D, _ptr(dH), ldd, int(bool(accumulate)), _ptr(dR), _ptr(ws),
+                                                         ws.numel(), _stream()))
     return dH, dR
+
+
+@_writes_out
+def distmult_backward(H: torch.Tensor, R: torch.Tensor, triples, gscore: torch.Tensor, tables: Dict[str, torch.Tensor],
+                      want_dH: bool = True, want_dR: bool = True, accumulate: bool = False, out: Optional[torch.Tensor] = None):
+    """d loss / d H [V, D] and d loss / d R [T, D] from ``gscore`` [N] (include/tfgnn.h tfgnn_distmult_backward; the sum order is
+    stated there) -> (dH or None, dR or None).  ``tables``: the four int32 device tensors of ``build_triple_tables``.  ``out``:
+    where dH goes instead of a new tensor - a float32 [V, D] with unit inner stride, e.g. D columns of a wider array whose
+    other columns stay as they are; with ``accumulate`` the sums are added to what it holds."""
+    return _link_backward("distmult", H, R, triples, gscore, tables, want_dH, want_dR, accumulate, out)
+
+
+@_writes_out
+def complex_backward(H: torch.Tensor, R: torch.Tensor, triples, gscore: torch.Tensor, tables: Dict[str, torch.Tensor],
+                     want_dH: bool = True, want_dR: bool = True, accumulate: bool = False, out: Optional[torch.Tensor] = None):
+    """``distmult_backward`` for the ComplEx score (include/tfgnn.h tfgnn_complex_backward: the same tables, the same sum
+    order, the term of an entry depending on whether the node is the triple's source or target)."""
+    return _link_backward("complex", H, R, triples, gscore, tables, want_dH, want_dR, accumulate, out)
 
 
 def check_rank_filter(filter_offsets, filter_ids, Q: int, V: int):
@@ -1776,15 +1807,11 @@ def check_rank_filter(filter_offsets, filter_ids, Q: int, V: int):
     return np.ascontiguousarray(off, dtype=np.int32), np.ascontiguousarray(ids, dtype=np.int32)
 
 
-def distmult_rank(H: torch.Tensor, R: torch.Tensor, queries, corrupt: str = "dst", filter_offsets=None, filter_ids=None):
-    """For every query triple, how many candidate entities in the corrupted slot (``corrupt``: "dst" or "src") score above /
-    exactly as the true triple, the true entity and the filter's ids left out (include/tfgnn.h tfgnn_distmult_rank) ->
-    (greater int32 [Q], equal int32 [Q]) on the device.  Host arrays (numpy) are validated and uploaded; device tensors are
-    taken as validated."""
+def _link_rank(decoder, H, R, queries, corrupt, filter_offsets, filter_ids):
     lib = _lib.load()
     if corrupt not in ("dst", "src"):
         raise ValueError(f"corrupt must be 'dst' or 'src', not {corrupt!r}")
-    H, ldh, R, queries, V, T, Q, D = _link_common(H, R, queries, "queries")
+    H, ldh, R, queries, V, T, Q, D = _link_common(H, R, queries, "queries", decoder)
     if (filter_offsets is None) != (filter_ids is None):
         raise ValueError("a filter needs both filter_offsets and filter_ids")
     if filter_offsets is not None:
@@ -1801,10 +1828,28 @@ def distmult_rank(H: torch.Tensor, R: torch.Tensor, queries, corrupt: str = "dst
             filter_ids = torch.zeros(1, dtype=torch.int32, device=H.device)
     greater = torch.empty(Q, dtype=torch.int32, device=H.device)
     equal = torch.empty(Q, dtype=torch.int32, device=H.device)
-    ws = _workspace(H.device, lib.tfgnn_distmult_rank_workspace_bytes(Q))
-    _lib.check(lib.tfgnn_distmult_rank(_ptr(H), ldh, _ptr(R), _ptr(queries), Q, 0 if corrupt == "dst" else 1, _ptr(filter_offsets),
-                                       _ptr(filter_ids), V, T, D, _ptr(greater), _ptr(equal), _ptr(ws), ws.numel(), _stream()))
+    if decoder == "complex":
+        ws = _workspace(H.device, lib.tfgnn_complex_rank_workspace_bytes(Q, D))
+    else:
+        ws = _workspace(H.device, lib.tfgnn_distmult_rank_workspace_bytes(Q))
+    _lib.check(getattr(lib, f"tfgnn_{decoder}_rank")(_ptr(H), ldh, _ptr(R), _ptr(queries), Q, 0 if corrupt == "dst" else 1,
+                                                     _ptr(filter_offsets), _ptr(filter_ids), V, T, D, _ptr(greater), _ptr(equal),
+                                                     _ptr(ws), ws.numel(), _stream()))
     return greater, equal
+
+
+def distmult_rank(H: torch.Tensor, R: torch.Tensor, queries, corrupt: str = "dst", filter_offsets=None, filter_ids=None):
+    """For every query triple, how many candidate entities in the corrupted slot (``corrupt``: "dst" or "src") score above /
+    exactly as the true triple, the true entity and the filter's ids left out (include/tfgnn.h tfgnn_distmult_rank) ->
+    (greater int32 [Q], equal int32 [Q]) on the device.  Host arrays (numpy) are validated and uploaded; device tensors are
+    taken as validated."""
+    return _link_rank("distmult", H, R, queries, corrupt, filter_offsets, filter_ids)
+
+
+def complex_rank(H: torch.Tensor, R: torch.Tensor, queries, corrupt: str = "dst", filter_offsets=None, filter_ids=None):
+    """``distmult_rank`` with the ComplEx score (include/tfgnn.h tfgnn_complex_rank: one query vector per query, every score
+    of the call the dot product of that vector with a node's row)."""
+    return _link_rank("complex", H, R, queries, corrupt, filter_offsets, filter_ids)
 
 
 def link_launch_counts() -> dict:
@@ -1812,6 +1857,13 @@ def link_launch_counts() -> dict:
     buf = (ctypes.c_int64 * 3)()
     _lib.check(_lib.load().tfgnn_link_launch_counts(buf, 3))
     return {"distmult_fwd": int(buf[0]), "distmult_bwd": int(buf[1]), "distmult_rank": int(buf[2])}
+
+
+def complex_launch_counts() -> dict:
+    """tfgnn_complex_launch_counts: kernel launches of the three ComplEx calls so far (host counters)."""
+    buf = (ctypes.c_int64 * 3)()
+    _lib.check(_lib.load().tfgnn_complex_launch_counts(buf, 3))
+    return {"complex_fwd": int(buf[0]), "complex_bwd": int(buf[1]), "complex_rank": int(buf[2])}
 
 
 def _device_triples(triples: torch.Tensor, what: str) -> int:

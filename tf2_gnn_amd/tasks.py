@@ -460,6 +460,12 @@ class LinkPredictionTask(GraphTaskModel):
     tfgnn_distmult_ce_metrics: a triple is counted iff its ``triple_weights`` entry (1 when absent) is > 0 and its label is
     0 or 1.
 
+    ``params["link_decoder"]`` chooses the decoder: ``"distmult"`` (the default; the key is in no defaults dictionary) or
+    ``"complex"``.  DistMult is symmetric - s(u, t, v) == s(v, t, u) whatever the parameters - so it cannot tell a directed
+    relation from its reverse.  ComplEx (Trouillon et al. 2016) reads a row of h and of ``relation_embeddings`` as the complex
+    vector [re ; im] (two halves, ``gnn_hidden_dim`` even) and scores s = Re sum_k h_u[k] R[t, k] conj(h_v[k]) with the
+    tfgnn_complex_* kernels: the same variable, batches, loss, counts and filtered ranking, an asymmetric score.
+
     The triples travel in BOTH dictionaries of a batch (LinkPredictionDataset puts the same tensors into each): the forward
     pass needs them for its output, ``compute_task_metrics`` takes the labels from ``batch_labels`` like every task.  When
     ``batch_features`` also carries ``triple_labels`` - the dataset's batches do - the forward pass runs the fused kernel once
@@ -486,10 +492,23 @@ class LinkPredictionTask(GraphTaskModel):
         self._num_relations = int(num_relations)
         if self._num_relations < 1:
             raise ValueError("LinkPredictionTask needs at least one relation")
+        self._decoder = params.get("link_decoder", "distmult")
+        if self._decoder not in ops.LINK_DECODERS:
+            raise ValueError(f"link_decoder must be 'distmult' or 'complex', not {self._decoder!r}")
+        if self._decoder == "complex" and int(self._params["gnn_hidden_dim"]) % 2:
+            raise ValueError(f"link_decoder='complex' reads a row as [re ; im] halves: gnn_hidden_dim must be even, not "
+                             f"{self._params['gnn_hidden_dim']}")
+        self._ce_metrics, self._backward_op, self._rank_op = (
+            (ops.complex_ce_metrics, ops.complex_backward, ops.complex_rank) if self._decoder == "complex"
+            else (ops.distmult_ce_metrics, ops.distmult_backward, ops.distmult_rank))
 
     @property
     def num_relations(self) -> int:
         return self._num_relations
+
+    @property
+    def link_decoder(self) -> str:
+        return self._decoder
 
     def build(self, input_shapes):
         H = int(self._params["gnn_hidden_dim"])
@@ -505,8 +524,8 @@ class LinkPredictionTask(GraphTaskModel):
         return final_node_representations[0] if isinstance(final_node_representations, tuple) else final_node_representations
 
     def _fused(self, h, triples, labels, weights, need_grad=True):
-        metrics, counts, scores, gscore = ops.distmult_ce_metrics(h, self._relation_embeddings.value, triples, labels, weights,
-                                                                  need_grad=need_grad)
+        metrics, counts, scores, gscore = self._ce_metrics(h, self._relation_embeddings.value, triples, labels, weights,
+                                                           need_grad=need_grad)
         return {"scores": scores, "metrics": metrics, "counts": counts, "gscore": gscore, "triples": triples, "labels": labels,
                 "weights": weights}
 
@@ -551,15 +570,16 @@ class LinkPredictionTask(GraphTaskModel):
         s = self._step
         if s.get("tables") is None:
             raise RuntimeError("backward() needs batch_labels['triple_tables'] (ops.build_triple_tables, on the device)")
-        d_h, d_r = ops.distmult_backward(s["h"], self._relation_embeddings.value, s["triples"], s["dloss"], s["tables"])
+        d_h, d_r = self._backward_op(s["h"], self._relation_embeddings.value, s["triples"], s["dloss"], s["tables"])
         self._relation_embeddings.grad = d_r
         if self._use_intermediate_gnn_results:
             return d_h, [None] * (int(self._params["gnn_num_layers"]) + 1)
         return d_h, None
 
     def rank_counts(self, batch_features, batch_labels) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(greater, equal) of tfgnn_distmult_rank for the batch's ``positive_triples``, filtered by ``rank_filters``: the
-        queries with the target corrupted, then the same queries with the source corrupted (int32 [2 P] each, on the device)."""
+        """(greater, equal) of tfgnn_distmult_rank (tfgnn_complex_rank with that decoder) for the batch's ``positive_triples``,
+        filtered by ``rank_filters``: the queries with the target corrupted, then the same queries with the source corrupted
+        (int32 [2 P] each, on the device)."""
         if "rank_filters" not in batch_labels or "positive_triples" not in batch_labels:
             raise ValueError("this batch carries no positive_triples / rank_filters: filtered ranking needs every entity's "
                              "representation, which a neighbour-sampled TRAIN mini-batch does not hold; use the VALIDATION or "
@@ -568,7 +588,7 @@ class LinkPredictionTask(GraphTaskModel):
         greater, equal = [], []
         for side in ("dst", "src"):
             offsets, ids = batch_labels["rank_filters"][side]
-            g, e = ops.distmult_rank(h, self._relation_embeddings.value, batch_labels["positive_triples"], side, offsets, ids)
+            g, e = self._rank_op(h, self._relation_embeddings.value, batch_labels["positive_triples"], side, offsets, ids)
             greater.append(g)
             equal.append(e)
         return torch.cat(greater), torch.cat(equal)
