@@ -400,6 +400,7 @@ struct PlanJob {
   int64_t R;
   int thr, chunk;
   int32_t* counters;  // {items, multi-item rows, partial slots, short rows}
+  int32_t* num_empty;  // short rows without an edge (bin 0 of the histogram, for the host: CsrPlan::num_empty)
   int32_t *item_row, *item_chunk, *item_slot, *item_multi, *multi_row, *multi_base, *multi_n;
   uint32_t* arrive;
   int32_t *bin_count, *bin_cursor, *short_rows;
@@ -441,7 +442,7 @@ __device__ __forceinline__ void plan_rows_body(const int32_t* __restrict__ rowpt
 // ---- short rows ordered by length (CsrPlan::short_rows) ------------------------------------------
 __device__ __forceinline__ void
 short_hist_body(const int32_t* __restrict__ rowptr, int64_t R, int thr, int32_t* __restrict__ bin_count,
-                int32_t* __restrict__ num_short, int* h, int& n_short) {
+                int32_t* __restrict__ num_short, int32_t* __restrict__ num_empty, int* h, int& n_short) {
   for (int i = threadIdx.x; i <= thr; i += 256) h[i] = 0;
   if (threadIdx.x == 0) n_short = 0;
   __syncthreads();
@@ -458,6 +459,7 @@ short_hist_body(const int32_t* __restrict__ rowptr, int64_t R, int thr, int32_t*
   for (int i = threadIdx.x; i <= thr; i += 256)
     if (h[i]) atomicAdd(&bin_count[i], h[i]);
   if (threadIdx.x == 0 && n_short) atomicAdd(num_short, n_short);
+  if (threadIdx.x == 0 && h[0]) atomicAdd(num_empty, h[0]);
 }
 
 // blockIdx.y = view of the pair + 2 * job: job 0 = length histogram of the short rows, job 1 = items of the long rows
@@ -467,7 +469,7 @@ __global__ void __launch_bounds__(256) plan_hist_kernel(PlanJobs jobs) {
   const PlanJob& j = jobs.j[blockIdx.y & 1];
   if (j.R <= 0) return;
   if ((blockIdx.y >> 1) == 0) {
-    short_hist_body(j.rowptr, j.R, j.thr, j.bin_count, j.counters + 3, h, n_short);
+    short_hist_body(j.rowptr, j.R, j.thr, j.bin_count, j.counters + 3, j.num_empty, h, n_short);
   } else if (j.want_items) {
     plan_rows_body(j.rowptr, j.R, j.thr, j.chunk, j.counters, j.item_row, j.item_chunk, j.item_slot, j.item_multi, j.multi_row,
                    j.multi_base, j.multi_n, j.arrive);
@@ -842,6 +844,7 @@ int build_plans(tfgnn_graph* g, int node_views, int32_t* counters, int32_t* bins
     j.thr = pl.long_threshold;
     j.chunk = pl.item_chunk_edges;
     j.counters = counters + 16 + 4 * v;
+    j.num_empty = counters + 32 + v;
     j.item_row = pl.item_row; j.item_chunk = pl.item_chunk; j.item_slot = pl.item_slot; j.item_multi = pl.item_multi;
     j.multi_row = pl.multi_row; j.multi_base = pl.multi_base; j.multi_n = pl.multi_n; j.arrive = pl.arrive;
     j.bin_count = bins + (size_t)v * 2 * SHORT_BINS;
@@ -1276,6 +1279,7 @@ static void graph_read_counters(tfgnn_graph* g, unsigned parts) {
     g->views[v].plan.num_multi = h_counters[16 + 4 * v + 1];
     g->views[v].plan.num_partials = h_counters[16 + 4 * v + 2];
     g->views[v].plan.num_short = h_counters[16 + 4 * v + 3];
+    g->views[v].plan.num_empty = h_counters[32 + v];
   }
   if (parts & TFGNN_GRAPH_PART_COMPACT)
     for (int side = 0; side < 2; ++side) {

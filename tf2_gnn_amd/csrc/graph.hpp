@@ -37,6 +37,7 @@ struct CsrPlan {
   // length, so a wave is not held up by its longest row (65 % -> ~100 % lane use on an R-MAT batch)
   int32_t* short_rows = nullptr;  // [num_short]
   int32_t num_short = 0;
+  int32_t num_empty = 0;  // of them without an edge: the last num_empty entries of short_rows
 };
 constexpr int SHORT_BINS = 257;  // long_threshold <= 256
 

@@ -31,6 +31,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "common.hpp"
 #include "graph.hpp"
@@ -191,6 +192,10 @@ struct GatherArgs {
   float* inv_out;          // [rows] 2^-e of every output row (not written when fixed_inv is given)
   const float* fixed_inv;  // nullable: one caller-chosen 2^-e for the whole tensor
   bool multi_pairs;  // host only: the short rows go two to a lane group, one edge of each per round (gather_rows_block_multi)
+  // > 0: short_rows[0, rider_ne) are the non-empty short rows and the only ones with a lane group of their own; the group
+  // of slot i also zero-fills the empty rows short_rows[i + rider_ne], [i + 2 * rider_ne], .. (< num_short) while its first
+  // source rows are in flight (empty_riders).  0: every short row has its own group
+  int64_t rider_ne;
 };
 
 // scale of one output row from the maximum (sp_absmax_bits) over its LANES lanes (lanes of one group are contiguous)
@@ -270,14 +275,29 @@ struct EdgeBlocks {
 // the block registers cost its narrow variants a wave per SIMD (80 -> 86, 77 -> 84 registers; tools/kernel_resources.py).
 __host__ __device__ constexpr bool index_blocks(int mode, int unroll) { return mode != MODE_GENERAL && unroll <= 2; }
 
+// Which row walks zero-fill empty short rows on the side (GatherArgs::rider_ne): the plain sums with two-edge rounds.  An
+// empty (node, type) bucket still needs its zero row, but not a lane group that walks short_rows -> rowptr -> out_row_map
+// for it at the end of the launch, when no source row is being read any more: the group of a non-empty row sends those
+// stores between issuing its first round of source-row loads and waiting for them.  MODE_GENERAL keeps one group per row
+// (an empty max-row holds kFloatLowest, and its registers are tight), the per-head and edge-product walks and the rows that
+// go two to a group (gather_rows_block_multi) likewise.
+__host__ __device__ constexpr bool empty_riders(int mode, int unroll) { return mode == MODE_SUM && index_blocks(mode, unroll); }
+struct NoRiders {
+  __device__ __forceinline__ void operator()() const {}
+};
+
 // plain sums: the source rows of the round of edges [e, e + UNROLL) (part of one index block: UNROLL divides LPR and rounds
 // start at multiples of UNROLL from the first edge).  Edges past `end` are not loaded (the walk of the other modes re-reads
-// the last edge of an odd row).
-template <int LPR, int VPL, int VEC, int UNROLL>
+// the last edge of an odd row).  `riders` is called once, behind the loads of the round's first edge.
+template <int LPR, int VPL, int VEC, int UNROLL, class Riders = NoRiders>
 __device__ __forceinline__ void issue_round(const GatherArgs& a, EdgeBlocks<LPR, MODE_SUM>& blocks, int32_t e, int32_t end, int f0,
-                                            const bool (&live)[VPL], typename VecT<VEC>::type (&v)[UNROLL][VPL], float (&w)[UNROLL]) {
+                                            const bool (&live)[VPL], typename VecT<VEC>::type (&v)[UNROLL][VPL], float (&w)[UNROLL],
+                                            const Riders& riders = Riders()) {
   static_assert(LPR % UNROLL == 0, "a round must not straddle two index blocks");
-  if (e >= end) return;
+  if (e >= end) {
+    riders();
+    return;
+  }
   blocks.seek(a, e);
 #pragma unroll
   for (int u = 0; u < UNROLL; ++u) {
@@ -289,6 +309,7 @@ __device__ __forceinline__ void issue_round(const GatherArgs& a, EdgeBlocks<LPR,
       for (int i = 0; i < VPL; ++i)
         if (live[i]) v[u][i] = vload<VEC>(src + i * LPR * VEC);
     }
+    if (u == 0) riders();
   }
 }
 template <int LPR, int VPL, int VEC, int UNROLL>
@@ -313,10 +334,15 @@ __device__ __forceinline__ void add_round(int32_t e, int32_t end, const bool (&l
   }
 }
 
-// accumulate edges [beg, end) into acc (lane-private chunks)
-template <int LPR, int VPL, int VEC, int UNROLL, int MODE>
+// accumulate edges [beg, end) into acc (lane-private chunks).  `riders` (row walks with empty_riders only): the zero-fill of
+// the empty rows that ride with the lane group.  It runs once, in the first round, when the source row of the first edge has
+// been asked for and nothing waits for it yet: the stores leave while that row is on its way.  They stand before the loads of
+// the round's second edge, whose registers are still free there - behind the whole round the SP16 kernel at width 320 needs
+// 108 registers instead of 90 and loses a wave per SIMD (NOTEBOOK section 48).
+template <int LPR, int VPL, int VEC, int UNROLL, int MODE, class Riders = NoRiders>
 __device__ __forceinline__ void accumulate_edges(const GatherArgs& a, int32_t beg, int32_t end, int f0,
-                                                 const bool (&live)[VPL], float (&acc)[VPL][VEC], int64_t row) {
+                                                 const bool (&live)[VPL], float (&acc)[VPL][VEC], int64_t row,
+                                                 const Riders& riders = Riders()) {
   using V = typename VecT<VEC>::type;
   EdgeBlocks<LPR, MODE> blocks;
   if constexpr (index_blocks(MODE, UNROLL)) blocks.start(a, beg, end);
@@ -325,7 +351,13 @@ __device__ __forceinline__ void accumulate_edges(const GatherArgs& a, int32_t be
     // slower than this loop at width 320: NOTEBOOK section 46)
     V v[UNROLL][VPL];
     float w[UNROLL];
-    for (int32_t e = beg; e < end; e += UNROLL) {
+    int32_t e = beg;
+    if constexpr (!std::is_same<Riders, NoRiders>::value) {  // the first round, with the riders in it
+      issue_round<LPR, VPL, VEC, UNROLL>(a, blocks, e, end, f0, live, v, w, riders);
+      add_round<LPR, VPL, VEC, UNROLL>(e, end, live, v, w, acc);
+      e += UNROLL;
+    }
+    for (; e < end; e += UNROLL) {
       issue_round<LPR, VPL, VEC, UNROLL>(a, blocks, e, end, f0, live, v, w);
       add_round<LPR, VPL, VEC, UNROLL>(e, end, live, v, w, acc);
     }
@@ -466,35 +498,11 @@ __device__ __forceinline__ void accumulate_edges(const GatherArgs& a, int32_t be
   }
 }
 
-template <int LPR, int VPL, int VEC, int UNROLL, int MODE, bool SP = false>
-__device__ __forceinline__ void gather_rows_block(const GatherArgs& a, unsigned row_block, unsigned window) {
-  constexpr int GROUPS_PER_BLOCK = 256 / LPR;
-  constexpr int WINDOW = LPR * VPL * VEC;  // floats covered per pass
-  const int tid = threadIdx.x;
-  const int group = tid / LPR;
-  const int gl = tid % LPR;
-  const int64_t slot = (int64_t)row_block * GROUPS_PER_BLOCK + group;
-  if (slot >= (a.short_rows ? a.num_short : a.num_rows)) return;
-  const int64_t row = a.short_rows ? a.short_rows[slot] : slot;
-  const int f0 = window * WINDOW + gl * VEC;  // first float of this lane's chunk 0
-  const int32_t beg = a.rowptr[row];
-  const int32_t end = a.rowptr[row + 1];
-  if (a.long_threshold > 0 && end - beg > a.long_threshold) return;  // handled by the item kernels
-  const int64_t orow = a.out_row_map ? a.out_row_map[row] : row;
-  if (orow < 0) return;  // compact output: empty buckets have no row
-  const bool is_max = MODE == MODE_GENERAL && a.is_max;
-
-  float acc[VPL][VEC];
-  bool live[VPL];
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    live[i] = (f0 + i * LPR * VEC) < a.width;
-#pragma unroll
-    for (int c = 0; c < VEC; ++c) acc[i][c] = is_max ? kFloatLowest : 0.f;
-  }
-  accumulate_edges<LPR, VPL, VEC, UNROLL, MODE>(a, beg, end, f0, live, acc, row);
-
-  const float rs = a.row_scale ? a.row_scale[row] : 1.f;
+// the reduced row of a lane group (acc: the lane's chunks) -> output row orow: times the row's scale, then the SP16 bytes
+// and scale, or the activation and the fp32 row
+template <int LPR, int VPL, int VEC, int MODE, bool SP>
+__device__ __forceinline__ void store_group_row(const GatherArgs& a, float (&acc)[VPL][VEC], const bool (&live)[VPL], float rs,
+                                                int64_t orow, int f0, int gl, bool is_max, bool nonempty) {
   if constexpr (SP) {  // VEC == 4, one window: the lane group holds the whole row
     unsigned mx = 0u;
 #pragma unroll
@@ -521,12 +529,92 @@ __device__ __forceinline__ void gather_rows_block(const GatherArgs& a, unsigned 
         float y = acc[i][c];
         // an empty max-segment keeps the lowest float (tf.math.unsorted_segment_max); scaling it
         // would overflow to -inf, so the scale only touches real results
-        if (!is_max || end > beg) y *= rs;
+        if (!is_max || nonempty) y *= rs;
         o[c] = act_apply(a.post_act, y);
       }
       vstore<VEC>(dst + i * LPR * VEC, o);
     }
   }
+}
+
+// The empty short rows that ride with the lane group of non-empty slot `slot` (empty_riders): slots slot + rider_ne,
+// slot + 2 * rider_ne, .. of the list.  start() reads the first one's output row and scale next to the group's own opening
+// loads; store_all() writes, for each of them, what a group of its own stores for a row without an edge (zero sums times the
+// row's scale through the same epilogue, nothing where the row has no output row) and reads the next one's.
+template <int LPR, int VPL, int VEC, int MODE, bool SP>
+struct EmptyRiders {
+  int64_t slot;
+  int32_t orow;
+  float rs;
+  bool any;
+  __device__ __forceinline__ void load(const GatherArgs& a) {
+    any = slot < a.num_short;
+    if (any) {
+      const int32_t r = a.short_rows[slot];
+      orow = a.out_row_map ? a.out_row_map[r] : r;
+      rs = a.row_scale ? a.row_scale[r] : 1.f;
+    }
+  }
+  __device__ __forceinline__ void start(const GatherArgs& a, int64_t own_slot) {
+    slot = own_slot + a.rider_ne;
+    orow = -1;
+    rs = 1.f;
+    any = false;
+    if (a.rider_ne > 0) load(a);
+  }
+  __device__ __forceinline__ void store_all(const GatherArgs& a, const bool (&live)[VPL], int f0, int gl) {
+    while (any) {
+      if (orow >= 0) {
+        float zero[VPL][VEC];
+#pragma unroll
+        for (int i = 0; i < VPL; ++i)
+#pragma unroll
+          for (int c = 0; c < VEC; ++c) zero[i][c] = 0.f;
+        store_group_row<LPR, VPL, VEC, MODE, SP>(a, zero, live, rs, orow, f0, gl, false, false);
+      }
+      slot += a.rider_ne;
+      load(a);
+    }
+  }
+};
+
+template <int LPR, int VPL, int VEC, int UNROLL, int MODE, bool SP = false>
+__device__ __forceinline__ void gather_rows_block(const GatherArgs& a, unsigned row_block, unsigned window) {
+  constexpr int GROUPS_PER_BLOCK = 256 / LPR;
+  constexpr int WINDOW = LPR * VPL * VEC;  // floats covered per pass
+  constexpr bool RIDERS = empty_riders(MODE, UNROLL);
+  const int tid = threadIdx.x;
+  const int group = tid / LPR;
+  const int gl = tid % LPR;
+  const int64_t slot = (int64_t)row_block * GROUPS_PER_BLOCK + group;
+  if (slot >= ((RIDERS && a.rider_ne > 0) ? a.rider_ne : a.short_rows ? a.num_short : a.num_rows)) return;
+  const int64_t row = a.short_rows ? a.short_rows[slot] : slot;
+  EmptyRiders<LPR, VPL, VEC, MODE, SP> riders;
+  if constexpr (RIDERS) riders.start(a, slot);
+  const int f0 = window * WINDOW + gl * VEC;  // first float of this lane's chunk 0
+  const int32_t beg = a.rowptr[row];
+  const int32_t end = a.rowptr[row + 1];
+  // (with riders, rider_ne > 0, neither happens: the slots below rider_ne hold short rows of a view with a row for every bucket)
+  if (a.long_threshold > 0 && end - beg > a.long_threshold) return;  // handled by the item kernels
+  const int64_t orow = a.out_row_map ? a.out_row_map[row] : row;
+  if (orow < 0) return;  // compact output: empty buckets have no row
+  const bool is_max = MODE == MODE_GENERAL && a.is_max;
+
+  float acc[VPL][VEC];
+  bool live[VPL];
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) {
+    live[i] = (f0 + i * LPR * VEC) < a.width;
+#pragma unroll
+    for (int c = 0; c < VEC; ++c) acc[i][c] = is_max ? kFloatLowest : 0.f;
+  }
+  if constexpr (RIDERS)
+    accumulate_edges<LPR, VPL, VEC, UNROLL, MODE>(a, beg, end, f0, live, acc, row, [&]() { riders.store_all(a, live, f0, gl); });
+  else
+    accumulate_edges<LPR, VPL, VEC, UNROLL, MODE>(a, beg, end, f0, live, acc, row);
+
+  const float rs = a.row_scale ? a.row_scale[row] : 1.f;
+  store_group_row<LPR, VPL, VEC, MODE, SP>(a, acc, live, rs, orow, f0, gl, is_max, end > beg);
 }
 
 // Short rows (round 6): a lane group takes R rows AT ONCE and walks them side by side, U edges of each per round.  A bucket of
@@ -896,7 +984,9 @@ static int launch_mode(GatherArgs a, int num_items, hipStream_t s) {
   constexpr int GROUPS_PER_BLOCK = 256 / LPR;
   constexpr int WINDOW = LPR * VPL * VEC;
   const unsigned windows = (unsigned)ceil_div(a.width, WINDOW);
-  const unsigned units = (unsigned)(num_items + ceil_div(a.short_rows ? a.num_short : a.num_rows, GROUPS_PER_BLOCK));
+  if constexpr (!empty_riders(MODE, UNROLL)) a.rider_ne = 0;
+  // (with riders the empty short rows have no lane group: row workgroups for the non-empty ones only)
+  const unsigned units = (unsigned)(num_items + ceil_div(a.rider_ne > 0 ? a.rider_ne : a.short_rows ? a.num_short : a.num_rows, GROUPS_PER_BLOCK));
   dim3 block(256);
   bool multi_done = false;
   if constexpr (MODE == MODE_SUM && VEC == 4 && LPR * VPL <= 128) {
@@ -1084,6 +1174,9 @@ static int graph_gather_impl(const tfgnn_graph* g, int view, const int32_t* d_co
   // compact output: the empty buckets have no row, and they close the length-ordered list - no lane groups for them
   // (configs[4]: 452 517 of 6.8 M by-source buckets are non-empty; walking all of them was 0.85 M workgroups with nothing to do)
   if (compact_nz >= 0) a.num_short = std::max<int64_t>(0, (int64_t)p.num_short - (gv.num_rows - compact_nz));
+  // every other output has a zero row for an empty bucket: written by the lane groups of the non-empty short rows, which the
+  // list holds first (the walks with empty_riders; launch_mode sets it back for the others)
+  else if (a.short_rows && p.num_empty > 0 && p.num_short > p.num_empty) a.rider_ne = (int64_t)p.num_short - p.num_empty;
   {
     // short rows side by side (gather_rows_block_multi) when the rows the row workgroups walk hold <= 1.5 edges on average -
     // the (node, type) buckets of a molecule batch (0.6): tools/gather_short_probe.py, 128k molecules, H = 128: typed by-target
