@@ -4,18 +4,12 @@
 // and the two reverse passes of the gather (tfgnn_basis_gather_backward).  The contracts and the order of every sum are
 // stated in include/tfgnn.h ("R-GCN basis decomposition"); DESIGN.md has the byte model.
 //
-// All three walks share one skeleton over a NODE view of the graph handle (all edge types of a node in one row, the edges of
-// a row sorted by type) and that view's long-row plan (graph.hpp CsrPlan):
-//   * a row of at most long_threshold edges is walked by one lane group (LPR lanes over the feature columns, VEC floats each);
-//   * a longer row is cut into items of item_chunk_edges edges, one workgroup per item: the 256 / LPR lane groups take
-//     consecutive runs of the item's edges, their sums meet in LDS and are added in group order;
-//   * a row made of several items leaves one partial row per item in the workspace, and a second, small launch adds them
-//     in item order.  Nobody counts arrivals or waits for another workgroup.
+// All three walks run on the skeleton of node_walk.hpp over a NODE view of the graph handle and that view's long-row plan (short
+// rows: one lane group each, LPR lanes over the feature columns, VEC floats each; long rows: items of item_chunk_edges edges,
+// one workgroup each; rows of several items: partial rows in the workspace and a second, small launch).  The coefficient walk
+// uses the ranges alone: it writes per run, not per row.
 // blockIdx.y walks the feature windows (LPR * VEC columns) and, in the forward and coefficient walks, the tiles of bases.
-#include <atomic>
-
-#include "common.hpp"
-#include "graph.hpp"
+#include "node_walk.hpp"
 
 namespace tfgnn {
 namespace {
@@ -27,45 +21,16 @@ constexpr int MAX_D = 1 << 20;
 
 std::atomic<int64_t> g_basis_launches[3];  // forward, dX, dcoeff
 
-struct BasisArgs {
-  const int32_t* nodeptr;  // [V+1] the node view's row pointers
-  const int32_t* coll;     // [E]   other end * L + type
-  int64_t V;
-  int L, B, D;
+struct BasisArgs : NodeWalkArgs {
+  int B, D;
   const float* coeff;  // [L, B]
-  const float* ew;     // [E] in the view's edge order, or NULL (= 1)
-  const float* ns;     // [V] m_v, or NULL (= 1)
   const float* in;     // forward, dcoeff: X [V, D]; dX: dZ [V, B*D]
   int64_t ld_in;
   const float* dz;  // dcoeff: dZ
   int64_t ld_dz;
   float* out;  // forward: Z; dX: dX; dcoeff: P [E, B] (dot products at the first edge of every run)
   int64_t ld_out;
-  float* partial;  // [num_partials, row width]
-  int long_threshold, item_chunk_edges, num_items;
-  const int32_t *item_row, *item_chunk, *item_slot;
 };
-
-template <int VEC>
-struct Vec {
-  float v[VEC];
-};
-template <int VEC>
-__device__ __forceinline__ Vec<VEC> load_vec(const float* p, bool live) {
-  Vec<VEC> r;
-  if constexpr (VEC == 4) {
-    const float4 t = live ? *reinterpret_cast<const float4*>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
-    r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
-  } else {
-    r.v[0] = live ? *p : 0.f;
-  }
-  return r;
-}
-template <int VEC>
-__device__ __forceinline__ void store_vec(float* p, const float (&v)[VEC], float scale) {
-  if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0] * scale, v[1] * scale, v[2] * scale, v[3] * scale);
-  else *p = v[0] * scale;
-}
 
 // ---- forward: edges [beg, end) of target row -> acc[j][:] = sum over the type runs (ascending) of a[l, b0+j] * run sum, the
 // run sum taken over the run's edges in order: run = fma(s_e, x, run) ----
@@ -161,64 +126,27 @@ __global__ void __launch_bounds__(256) basis_rows_kernel(BasisArgs a) {
 #pragma unroll
     for (int c = 0; c < VEC; ++c) acc[j][c] = 0.f;
 
-  if ((int)blockIdx.x >= a.num_items) {  // short rows, in node order: one lane group per row, no LDS
-    const int64_t row = ((int64_t)blockIdx.x - a.num_items) * GROUPS + group;
-    if (row >= a.V) return;
-    const int32_t beg = a.nodeptr[row], end = a.nodeptr[row + 1];
-    if (end - beg > a.long_threshold || !live) return;  // long rows: the item workgroups
-    if constexpr (FWD) forward_walk<VEC>(a, beg, end, d, live, b0, acc);
-    else dx_walk<VEC>(a, beg, end, d, live, acc[0]);
-    const float m = (FWD && a.ns) ? a.ns[row] : 1.f;
-    float* orow = a.out + row * a.ld_out;
+  const GroupRange r = group_range<GROUPS>(a, blockIdx.x, group);
+  const float* ns = FWD ? a.ns : nullptr;
+  if (r.whole_row) {  // a short row: one lane group, no LDS
+    if (r.row < 0 || !live) return;
+    if constexpr (FWD) forward_walk<VEC>(a, r.beg, r.end, d, live, b0, acc);
+    else dx_walk<VEC>(a, r.beg, r.end, d, live, acc[0]);
+    const float m = ns ? ns[r.row] : 1.f;
+    float* orow = a.out + r.row * a.ld_out;
 #pragma unroll
     for (int j = 0; j < NACC; ++j)
       if (!FWD || b0 + j < a.B) store_vec<VEC>(orow + (int64_t)(b0 + j) * a.D + d, acc[j], m);
     return;
   }
-
-  const int item = blockIdx.x;
-  const int64_t row = a.item_row[item];
-  const int32_t rbeg = a.nodeptr[row], rend = a.nodeptr[row + 1];
-  const int32_t ibeg = min(rend, rbeg + a.item_chunk[item] * a.item_chunk_edges);
-  const int32_t iend = min(rend, ibeg + a.item_chunk_edges);
-  const int per = (iend - ibeg + GROUPS - 1) / GROUPS;  // consecutive edges per lane group
-  const int32_t beg = min(iend, ibeg + group * per), end = min(iend, beg + per);
   if (live) {
-    if constexpr (FWD) forward_walk<VEC>(a, beg, end, d, live, b0, acc);
-    else dx_walk<VEC>(a, beg, end, d, live, acc[0]);
+    if constexpr (FWD) forward_walk<VEC>(a, r.beg, r.end, d, live, b0, acc);
+    else dx_walk<VEC>(a, r.beg, r.end, d, live, acc[0]);
   }
-#pragma unroll
-  for (int j = 0; j < NACC; ++j)
-#pragma unroll
-    for (int c = 0; c < VEC; ++c) red[group][j * PW + gl * VEC + c] = acc[j][c];
-  __syncthreads();
-  const int32_t slot = a.item_slot[item];
-  const float m = (FWD && a.ns && slot < 0) ? a.ns[row] : 1.f;
-  float* orow = slot < 0 ? a.out + row * a.ld_out : a.partial + (int64_t)slot * width;
-  for (int f = tid; f < NACC * PW; f += 256) {
+  item_epilogue<VEC, LPR, NACC>(a, r, red, acc, ns, a.out, a.ld_out, width, NACC * PW, [&](int f) {
     const int j = f / PW, dd = win * PW + f % PW;
-    if (dd >= a.D || (FWD && b0 + j >= a.B)) continue;
-    float s = red[0][f];
-#pragma unroll
-    for (int g = 1; g < GROUPS; ++g) s += red[g][f];
-    orow[(int64_t)(b0 + j) * a.D + dd] = s * m;
-  }
-}
-
-// rows made of several items: out[row, :] = m_row * (partial rows of the row added in item order)
-__global__ void __launch_bounds__(256)
-basis_combine_kernel(const int32_t* __restrict__ multi_row, const int32_t* __restrict__ multi_base, const int32_t* __restrict__ multi_n,
-                     const float* __restrict__ partial, int width, const float* __restrict__ ns, float* __restrict__ out,
-                     int64_t ld_out) {
-  const int m = blockIdx.x;
-  const int64_t row = multi_row[m];
-  const int32_t base = multi_base[m], n = multi_n[m];
-  const float scale = ns ? ns[row] : 1.f;
-  for (int f = blockIdx.y * 256 + threadIdx.x; f < width; f += gridDim.y * 256) {
-    float s = partial[(int64_t)base * width + f];
-    for (int k = 1; k < n; ++k) s += partial[(int64_t)(base + k) * width + f];
-    out[row * ld_out + f] = s * scale;
-  }
+    return Column<int64_t>{dd < a.D && (!FWD || b0 + j < a.B), (int64_t)(b0 + j) * a.D + dd};
+  });
 }
 
 // ---- dcoeff, walk: for every run of one edge type inside the edges a lane group walks, P[first edge of the run, b] =
@@ -229,28 +157,13 @@ __global__ void __launch_bounds__(256) basis_dcoeff_walk_kernel(BasisArgs a) {
   constexpr int PW = LPR * VEC;
   const int tid = threadIdx.x, group = tid / LPR, gl = tid % LPR;
   const int b0 = blockIdx.y * DC_BT;
-  int64_t row;
-  int32_t beg, end;
-  if ((int)blockIdx.x >= a.num_items) {
-    row = ((int64_t)blockIdx.x - a.num_items) * GROUPS + group;
-    if (row >= a.V) return;
-    beg = a.nodeptr[row];
-    end = a.nodeptr[row + 1];
-    if (end - beg > a.long_threshold) return;
-  } else {
-    const int item = blockIdx.x;
-    row = a.item_row[item];
-    const int32_t rbeg = a.nodeptr[row], rend = a.nodeptr[row + 1];
-    const int32_t ibeg = min(rend, rbeg + a.item_chunk[item] * a.item_chunk_edges);
-    const int32_t iend = min(rend, ibeg + a.item_chunk_edges);
-    const int per = (iend - ibeg + GROUPS - 1) / GROUPS;
-    beg = min(iend, ibeg + group * per);
-    end = min(iend, beg + per);
-  }
-  const float m = a.ns ? a.ns[row] : 1.f;
-  const float* zrow = a.dz + row * a.ld_dz;
+  const GroupRange r = group_range<GROUPS>(a, blockIdx.x, group);
+  if (r.row < 0) return;
+  const int32_t end = r.end;
+  const float m = a.ns ? a.ns[r.row] : 1.f;
+  const float* zrow = a.dz + r.row * a.ld_dz;
   // every lane of the group runs the same loops (the shuffles below stay inside the group)
-  int32_t e = beg;
+  int32_t e = r.beg;
   while (e < end) {
     const int l = a.coll[e] % a.L;
     int32_t e1 = e + 1;
@@ -323,7 +236,6 @@ basis_dcoeff_reduce2_kernel(const float* __restrict__ part2, int chunks, int LB,
   dcoeff[i] = s;
 }
 
-inline size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
 inline int64_t red_chunks(int64_t V) { return std::max<int64_t>(1, ceil_div(V, RED_NODES)); }
 
 struct Shape {
@@ -338,28 +250,22 @@ inline Shape pick_shape(int D, bool aligned) {
   s.lpr = chunks <= 16 ? 16 : (chunks <= 32 && s.vec ? 32 : 64);
   return s;
 }
-inline bool rows_aligned(const void* p, int64_t ld) { return (uintptr_t)p % 16 == 0 && ld % 4 == 0; }
 
+// the rows walk and, when some row has several items, the launch that adds their partial rows; `slot`: launch counter
 template <bool FWD>
-void launch_rows(const Shape& sh, const BasisArgs& a, dim3 grid, hipStream_t s) {
-  if (sh.vec) {
-    if (sh.lpr == 16) hipLaunchKernelGGL((basis_rows_kernel<4, 16, FWD>), grid, dim3(256), 0, s, a);
-    else if (sh.lpr == 32) hipLaunchKernelGGL((basis_rows_kernel<4, 32, FWD>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((basis_rows_kernel<4, 64, FWD>), grid, dim3(256), 0, s, a);
-  } else {
-    if (sh.lpr == 16) hipLaunchKernelGGL((basis_rows_kernel<1, 16, FWD>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((basis_rows_kernel<1, 64, FWD>), grid, dim3(256), 0, s, a);
-  }
+int launch_rows(const Shape& sh, const BasisArgs& a, const GraphView& gv, int64_t gy, int slot, hipStream_t s) {
+  const dim3 grid((unsigned)(a.num_items + ceil_div(a.V, 256 / sh.lpr)), (unsigned)gy);
+  auto walk = [&] {
+    dispatch_shape(sh.vec, sh.lpr, [&](auto vec, auto lpr) {
+      hipLaunchKernelGGL((basis_rows_kernel<decltype(vec)::value, decltype(lpr)::value, FWD>), grid, dim3(256), 0, s, a);
+    });
+  };
+  return launch_walk(walk, gv, a.partial, FWD ? a.ns : nullptr, FWD ? a.B * a.D : a.D, a.out, a.ld_out, g_basis_launches[slot], s);
 }
 void launch_dcoeff_walk(const Shape& sh, const BasisArgs& a, dim3 grid, hipStream_t s) {
-  if (sh.vec) {
-    if (sh.lpr == 16) hipLaunchKernelGGL((basis_dcoeff_walk_kernel<4, 16>), grid, dim3(256), 0, s, a);
-    else if (sh.lpr == 32) hipLaunchKernelGGL((basis_dcoeff_walk_kernel<4, 32>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((basis_dcoeff_walk_kernel<4, 64>), grid, dim3(256), 0, s, a);
-  } else {
-    if (sh.lpr == 16) hipLaunchKernelGGL((basis_dcoeff_walk_kernel<1, 16>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((basis_dcoeff_walk_kernel<1, 64>), grid, dim3(256), 0, s, a);
-  }
+  dispatch_shape(sh.vec, sh.lpr, [&](auto vec, auto lpr) {
+    hipLaunchKernelGGL((basis_dcoeff_walk_kernel<decltype(vec)::value, decltype(lpr)::value>), grid, dim3(256), 0, s, a);
+  });
 }
 
 // the checks both entries share, before anything touches the device; `who` names the entry in the message
@@ -373,16 +279,7 @@ int check_limits(const char* who, const tfgnn_graph* g, int B, int D) {
     set_error("%s: D = %d is above the limit D <= %d", who, D, MAX_D);
     return TFGNN_ERR_UNSUPPORTED;
   }
-  TFGNN_REQUIRE(g != nullptr, "%s: graph is NULL", who);
-  TFGNN_REQUIRE(g->L >= 1 && g->L <= 256, "%s: %d edge types, the graph handle's limit is 1 <= L <= 256", who, g->L);
-  return graph_require_parts(g, TFGNN_GRAPH_PART_PLAN_NODE, who);
-}
-
-void fill_plan(BasisArgs& a, const GraphView& gv) {
-  const CsrPlan& p = gv.plan;
-  a.nodeptr = gv.rowptr; a.coll = gv.col;
-  a.long_threshold = p.long_threshold; a.item_chunk_edges = p.item_chunk_edges; a.num_items = p.num_items;
-  a.item_row = p.item_row; a.item_chunk = p.item_chunk; a.item_slot = p.item_slot;
+  return check_graph(who, g);
 }
 
 }  // namespace
@@ -429,19 +326,7 @@ extern "C" int tfgnn_basis_gather_forward(const tfgnn_basis_forward_args* p, voi
   const int pw = sh.lpr * (sh.vec ? 4 : 1);
   const int64_t gy = ceil_div(D, pw) * ceil_div(B, FWD_BT);
   TFGNN_REQUIRE(gy <= 65535, "tfgnn_basis_gather_forward: D = %d with B = %d needs more than 65535 feature windows", D, B);
-  const int64_t gx = a.num_items + ceil_div(g->V, 256 / sh.lpr);
-  hipStream_t s = (hipStream_t)stream;
-  launch_rows<true>(sh, a, dim3((unsigned)gx, (unsigned)gy), s);
-  TFGNN_LAUNCH_CHECK();
-  g_basis_launches[0].fetch_add(1, std::memory_order_relaxed);
-  if (gv.plan.num_multi > 0) {
-    hipLaunchKernelGGL(basis_combine_kernel, dim3((unsigned)gv.plan.num_multi, (unsigned)std::min<int64_t>(ceil_div(width, 256), 64)),
-                       dim3(256), 0, s, gv.plan.multi_row, gv.plan.multi_base, gv.plan.multi_n, a.partial, (int)width, a.ns, a.out,
-                       a.ld_out);
-    TFGNN_LAUNCH_CHECK();
-    g_basis_launches[0].fetch_add(1, std::memory_order_relaxed);
-  }
-  return TFGNN_OK;
+  return launch_rows<true>(sh, a, gv, gy, 0, (hipStream_t)stream);
 }
 
 extern "C" int tfgnn_basis_gather_backward(const tfgnn_basis_backward_args* p, void* stream) {
@@ -477,15 +362,8 @@ extern "C" int tfgnn_basis_gather_backward(const tfgnn_basis_backward_args* p, v
     a.in = p->dZ; a.ld_in = p->lddZ; a.out = p->dX; a.ld_out = p->lddX; a.partial = (float*)ws;
     const Shape sh = pick_shape(D, rows_aligned(p->dZ, p->lddZ) && rows_aligned(p->dX, p->lddX));
     const int pw = sh.lpr * (sh.vec ? 4 : 1);
-    launch_rows<false>(sh, a, dim3((unsigned)(a.num_items + ceil_div(V, 256 / sh.lpr)), (unsigned)ceil_div(D, pw)), s);
-    TFGNN_LAUNCH_CHECK();
-    g_basis_launches[1].fetch_add(1, std::memory_order_relaxed);
-    if (gs.plan.num_multi > 0) {
-      hipLaunchKernelGGL(basis_combine_kernel, dim3((unsigned)gs.plan.num_multi, (unsigned)std::min<int64_t>(ceil_div(D, 256), 64)), dim3(256), 0,
-                         s, gs.plan.multi_row, gs.plan.multi_base, gs.plan.multi_n, a.partial, D, (const float*)nullptr, a.out, a.ld_out);
-      TFGNN_LAUNCH_CHECK();
-      g_basis_launches[1].fetch_add(1, std::memory_order_relaxed);
-    }
+    const int rc_dx = launch_rows<false>(sh, a, gs, ceil_div(D, pw), 1, s);
+    if (rc_dx) return rc_dx;
   }
   if (p->dcoeff) {
     if (V == 0 || E == 0) {  // no edge, no term: zeros

@@ -7,17 +7,14 @@
 // The contracts and the order of every sum are stated in include/tfgnn.h ("R-GCN block-diagonal decomposition"); DESIGN.md §5g
 // has the byte model.
 //
-// The two walks share the skeleton of basis.hip over a NODE view of the graph handle and that view's long-row plan (short rows:
-// one lane group each; long rows: items of item_chunk_edges edges, one workgroup each; rows of several items: partial rows in the
-// workspace and a second, small launch).  blockIdx.y walks windows of whole blocks: window w holds blocks [w*cw, (w+1)*cw), its
+// The two walks follow the skeleton of node_walk.hpp (the range and the item epilogue written out here, see there) over a NODE view of the graph handle and that view's long-row plan (short
+// rows: one lane group each; long rows: items of item_chunk_edges edges, one workgroup each; rows of several items: partial rows in
+// the workspace and a second, small launch).  blockIdx.y walks windows of whole blocks: window w holds blocks [w*cw, (w+1)*cw), its
 // lane group owns their input columns (the run sum) AND their output columns (the accumulator); the run sum changes hands
 // through a slab of LDS that belongs to the lane group.  A lane group never spans two waves, so the hand-over needs no
 // workgroup barrier.  dQb does not walk rows: the caller's edge lists are type-major already, so stage 1 takes chunks of 256
 // consecutive list positions of one type and stage 2 adds the chunk partials of a type in chunk order.
-#include <atomic>
-
-#include "common.hpp"
-#include "graph.hpp"
+#include "node_walk.hpp"
 
 namespace tfgnn {
 namespace {
@@ -29,7 +26,7 @@ constexpr int DQ_COLS = 64;    // output columns per stage-1 workgroup: one per 
 
 std::atomic<int64_t> g_blockdiag_launches[3];  // forward, dX, dQb
 
-struct WalkArgs {
+struct WalkArgs {  // the fields of NodeWalkArgs (node_walk.hpp) in this kernel's own order, then its own
   const int32_t* nodeptr;  // [V+1] the node view's row pointers
   const int32_t* coll;     // [E]   other end * L + type
   int64_t V;
@@ -48,22 +45,6 @@ struct WalkArgs {
   int long_threshold, item_chunk_edges, num_items;
   const int32_t *item_row, *item_chunk, *item_slot;
 };
-
-template <int VEC>
-struct Vec {
-  float v[VEC];
-};
-template <int VEC>
-__device__ __forceinline__ Vec<VEC> load_vec(const float* p, bool live) {
-  Vec<VEC> r;
-  if constexpr (VEC == 4) {
-    const float4 t = live ? *reinterpret_cast<const float4*>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
-    r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
-  } else {
-    r.v[0] = live ? *p : 0.f;
-  }
-  return r;
-}
 
 // the lanes of a group run in one wave: what they wrote to the group's slab is visible to them after this
 __device__ __forceinline__ void group_sync() {
@@ -191,22 +172,6 @@ __global__ void __launch_bounds__(256) blockdiag_rows_kernel(WalkArgs a) {
   }
 }
 
-// rows made of several items: out[row, :] = m_row * (partial rows of the row added in item order)
-__global__ void __launch_bounds__(256)
-blockdiag_combine_kernel(const int32_t* __restrict__ multi_row, const int32_t* __restrict__ multi_base, const int32_t* __restrict__ multi_n,
-                         const float* __restrict__ partial, int width, const float* __restrict__ ns, float* __restrict__ out,
-                         int64_t ld_out) {
-  const int m = blockIdx.x;
-  const int64_t row = multi_row[m];
-  const int32_t base = multi_base[m], n = multi_n[m];
-  const float scale = ns ? ns[row] : 1.f;
-  for (int f = blockIdx.y * 256 + threadIdx.x; f < width; f += gridDim.y * 256) {
-    float s = partial[(int64_t)base * width + f];
-    for (int k = 1; k < n; ++k) s += partial[(int64_t)(base + k) * width + f];
-    out[row * ld_out + f] = s * scale;
-  }
-}
-
 struct DqArgs {
   const int32_t* list_to_dst;  // [E] position in concat(adjacency_lists) -> position in the by-target order
   const int32_t* chunk_first;  // [num_chunks] first list position
@@ -274,8 +239,6 @@ blockdiag_dq_stage2_kernel(const int32_t* __restrict__ type_chunk_ptr, const flo
   dq[(int64_t)l * n + f] = s;
 }
 
-inline size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
-
 struct Shape {
   bool vec;
   int lpr, cw;
@@ -299,19 +262,17 @@ inline Shape pick_shape(int C, int di, int ho, bool aligned) {
   }
   return s;
 }
-inline bool rows_aligned(const void* p, int64_t ld) { return (uintptr_t)p % 16 == 0 && ld % 4 == 0; }
 
+// the walk launch and, when some row has several items, the launch that adds their partial rows; `slot`: launch counter
 template <bool TR>
-void launch_rows(const Shape& sh, const WalkArgs& a, dim3 grid, hipStream_t s) {
-  if (sh.vec) {
-    if (sh.lpr == 16) hipLaunchKernelGGL((blockdiag_rows_kernel<4, 16, TR>), grid, dim3(256), 0, s, a);
-    else if (sh.lpr == 32) hipLaunchKernelGGL((blockdiag_rows_kernel<4, 32, TR>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((blockdiag_rows_kernel<4, 64, TR>), grid, dim3(256), 0, s, a);
-  } else {
-    if (sh.lpr == 16) hipLaunchKernelGGL((blockdiag_rows_kernel<1, 16, TR>), grid, dim3(256), 0, s, a);
-    else if (sh.lpr == 32) hipLaunchKernelGGL((blockdiag_rows_kernel<1, 32, TR>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((blockdiag_rows_kernel<1, 64, TR>), grid, dim3(256), 0, s, a);
-  }
+int launch_rows(const Shape& sh, const WalkArgs& a, const GraphView& gv, int slot, hipStream_t s) {
+  const dim3 grid((unsigned)(a.num_items + ceil_div(a.V, (int64_t)(256 / sh.lpr))), (unsigned)ceil_div(a.C, sh.cw));
+  auto walk = [&] {
+    dispatch_shape(sh.vec, sh.lpr, [&](auto vec, auto lpr) {
+      hipLaunchKernelGGL((blockdiag_rows_kernel<decltype(vec)::value, decltype(lpr)::value, TR>), grid, dim3(256), 0, s, a);
+    });
+  };
+  return launch_walk(walk, gv, a.partial, a.ns, a.width_out, a.out, a.ld_out, g_blockdiag_launches[slot], s);
 }
 
 // the limits on the three widths alone (no handle): TFGNN_OK or the error code, the message set
@@ -334,34 +295,7 @@ int check_widths(const char* who, int C, int D, int H) {
 int check_limits(const char* who, const tfgnn_graph* g, int C, int D, int H) {
   const int rc = check_widths(who, C, D, H);
   if (rc) return rc;
-  TFGNN_REQUIRE(g != nullptr, "%s: graph is NULL", who);
-  TFGNN_REQUIRE(g->L >= 1 && g->L <= 256, "%s: %d edge types, the graph handle's limit is 1 <= L <= 256", who, g->L);
-  return graph_require_parts(g, TFGNN_GRAPH_PART_PLAN_NODE, who);
-}
-
-void fill_plan(WalkArgs& a, const GraphView& gv) {
-  const CsrPlan& p = gv.plan;
-  a.nodeptr = gv.rowptr; a.coll = gv.col;
-  a.long_threshold = p.long_threshold; a.item_chunk_edges = p.item_chunk_edges; a.num_items = p.num_items;
-  a.item_row = p.item_row; a.item_chunk = p.item_chunk; a.item_slot = p.item_slot;
-}
-
-// the walk launch and, when some row has several items, the launch that adds their partial rows; `slot`: launch counter
-int launch_walk(bool tr, const Shape& sh, WalkArgs& a, const GraphView& gv, int slot, hipStream_t s) {
-  const int64_t gx = a.num_items + ceil_div(a.V, (int64_t)(256 / sh.lpr));
-  const dim3 grid((unsigned)gx, (unsigned)ceil_div(a.C, sh.cw));
-  if (tr) launch_rows<true>(sh, a, grid, s);
-  else launch_rows<false>(sh, a, grid, s);
-  TFGNN_LAUNCH_CHECK();
-  g_blockdiag_launches[slot].fetch_add(1, std::memory_order_relaxed);
-  if (gv.plan.num_multi > 0) {
-    hipLaunchKernelGGL(blockdiag_combine_kernel, dim3((unsigned)gv.plan.num_multi, (unsigned)std::min<int64_t>(ceil_div(a.width_out, 256), 64)),
-                       dim3(256), 0, s, gv.plan.multi_row, gv.plan.multi_base, gv.plan.multi_n, a.partial, a.width_out, a.ns, a.out,
-                       a.ld_out);
-    TFGNN_LAUNCH_CHECK();
-    g_blockdiag_launches[slot].fetch_add(1, std::memory_order_relaxed);
-  }
-  return TFGNN_OK;
+  return check_graph(who, g);
 }
 
 }  // namespace
@@ -407,7 +341,7 @@ extern "C" int tfgnn_blockdiag_forward(const tfgnn_blockdiag_forward_args* p, vo
   a.in = p->X; a.ld_in = p->ldX; a.out = p->pre; a.ld_out = p->ldpre; a.partial = (float*)p->workspace; a.width_out = H;
   const Shape sh = pick_shape(C, di, ho, rows_aligned(p->X, p->ldX) && rows_aligned(p->pre, p->ldpre) && (uintptr_t)p->Qb % 16 == 0);
   a.cw = sh.cw;
-  return launch_walk(false, sh, a, gv, 0, (hipStream_t)stream);
+  return launch_rows<false>(sh, a, gv, 0, (hipStream_t)stream);
 }
 
 extern "C" int tfgnn_blockdiag_backward(const tfgnn_blockdiag_backward_args* p, void* stream) {
@@ -444,7 +378,7 @@ extern "C" int tfgnn_blockdiag_backward(const tfgnn_blockdiag_backward_args* p, 
     a.in = p->dPre; a.ld_in = p->lddPre; a.out = p->dX; a.ld_out = p->lddX; a.partial = (float*)ws; a.width_out = D;
     const Shape sh = pick_shape(C, di, ho, rows_aligned(p->dPre, p->lddPre) && rows_aligned(p->dX, p->lddX));
     a.cw = sh.cw;
-    const int lrc = launch_walk(true, sh, a, gs, 1, s);
+    const int lrc = launch_rows<true>(sh, a, gs, 1, s);
     if (lrc) return lrc;
   }
   if (p->dQb) {

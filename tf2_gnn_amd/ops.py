@@ -1054,27 +1054,22 @@ def pool_launch_counts() -> dict:
     return {"pool_fwd": int(buf[0]), "pool_bwd": int(buf[1])}
 
 
-def _basis_common(who: str, graph: "Graph", coeff: torch.Tensor, edge_weights, node_scale):
-    """The checks the two basis-gather wrappers share -> (L, B, contiguous coeff)."""
-    _require_dev(coeff, torch.float32, "coeff")
-    L = graph.num_edge_types
-    if coeff.dim() != 2 or coeff.shape[0] != L:
-        raise ValueError(f"{who}: coeff must be [{L}, num_bases] (one row per edge type), got {tuple(coeff.shape)}")
-    B = int(coeff.shape[1])
-    if not 1 <= B <= _lib.BASIS_MAX_BASES:
-        raise ValueError(f"{who}: num_bases = {B} is outside the limit 1 <= num_bases <= {_lib.BASIS_MAX_BASES}")
+def _node_walk_vectors(who: str, graph: "Graph", anchor: torch.Tensor, anchor_name: str, edge_weights, node_scale):
+    """The per-edge weights ([(name, tensor or None)]) and the node scale of a node-view walk: float32 device vectors of E / V
+    floats on the device of ``anchor`` (the weight tensor, named ``anchor_name`` in the message)."""
     for name, t, n in [(k, t, graph.num_edges) for k, t in edge_weights] + [("node_scale", node_scale, graph.num_nodes)]:
         if t is None:
             continue
         _require_dev(t, torch.float32, name)
         if t.dim() != 1 or t.numel() != n or not t.is_contiguous():
             raise ValueError(f"{who}: {name} must be a contiguous vector of {n} floats, got {tuple(t.shape)}")
-        if t.device != coeff.device:
-            raise ValueError(f"{who}: {name} lives on {t.device}, coeff on {coeff.device}")
-    return L, B, coeff.contiguous()
+        if t.device != anchor.device:
+            raise ValueError(f"{who}: {name} lives on {t.device}, {anchor_name} on {anchor.device}")
 
 
-def _basis_matrix(who: str, t: torch.Tensor, rows: int, cols: int, what: str, device, writable: bool = False):
+def _node_walk_matrix(who: str, t: torch.Tensor, rows: int, cols: int, what: str, device, writable: bool = False):
+    """A [rows, cols] float32 operand of a node-view walk -> (tensor with unit inner stride, row stride).  The device message
+    names the basis layer's anchor whoever calls."""
     _require_dev(t, torch.float32, what)
     if t.dim() != 2 or tuple(t.shape) != (rows, cols):
         raise ValueError(f"{who}: {what} must be [{rows}, {cols}], got {tuple(t.shape)}")
@@ -1086,12 +1081,30 @@ def _basis_matrix(who: str, t: torch.Tensor, rows: int, cols: int, what: str, de
     return t2, ld
 
 
-def _basis_workspace(graph: "Graph", B: int, D: int, device):
+def _node_plan_partials(graph: "Graph"):
+    """-> (by target, by source): the partial rows the node views' plans keep for rows made of several items"""
     lib = _lib.load()
     graph.ensure(G_PART_PLAN_NODE)
-    pd = lib.tfgnn_graph_gather_workspace_bytes(graph._h, VIEW_BY_DST_NODE, 1) // 4  # the plans' multi-item partial rows
-    ps = lib.tfgnn_graph_gather_workspace_bytes(graph._h, VIEW_BY_SRC_NODE, 1) // 4
-    nbytes = lib.tfgnn_basis_workspace_bytes(graph.num_nodes, graph.num_edges, graph.num_edge_types, B, D, pd, ps)
+    return (lib.tfgnn_graph_gather_workspace_bytes(graph._h, VIEW_BY_DST_NODE, 1) // 4,
+            lib.tfgnn_graph_gather_workspace_bytes(graph._h, VIEW_BY_SRC_NODE, 1) // 4)
+
+
+def _basis_common(who: str, graph: "Graph", coeff: torch.Tensor, edge_weights, node_scale):
+    """The checks the two basis-gather wrappers share -> (L, B, contiguous coeff)."""
+    _require_dev(coeff, torch.float32, "coeff")
+    L = graph.num_edge_types
+    if coeff.dim() != 2 or coeff.shape[0] != L:
+        raise ValueError(f"{who}: coeff must be [{L}, num_bases] (one row per edge type), got {tuple(coeff.shape)}")
+    B = int(coeff.shape[1])
+    if not 1 <= B <= _lib.BASIS_MAX_BASES:
+        raise ValueError(f"{who}: num_bases = {B} is outside the limit 1 <= num_bases <= {_lib.BASIS_MAX_BASES}")
+    _node_walk_vectors(who, graph, coeff, "coeff", edge_weights, node_scale)
+    return L, B, coeff.contiguous()
+
+
+def _basis_workspace(graph: "Graph", B: int, D: int, device):
+    nbytes = _lib.load().tfgnn_basis_workspace_bytes(graph.num_nodes, graph.num_edges, graph.num_edge_types, B, D,
+                                                     *_node_plan_partials(graph))
     return _aligned_workspace(device, nbytes) if nbytes else (None, 0, None)
 
 
@@ -1107,10 +1120,10 @@ def basis_gather_forward(graph: "Graph", coeff: torch.Tensor, X: torch.Tensor, *
     if X.dim() != 2 or X.shape[0] != V or X.shape[1] < 1:
         raise ValueError(f"{who}: X must be [{V}, D] with D >= 1, got {tuple(X.shape)}")
     D = int(X.shape[1])
-    X, ldX = _basis_matrix(who, X, V, D, "X", coeff.device)
+    X, ldX = _node_walk_matrix(who, X, V, D, "X", coeff.device)
     if out is None:
         out = torch.empty((V, B * D), dtype=torch.float32, device=X.device)
-    out, ldZ = _basis_matrix(who, out, V, B * D, "out", coeff.device, writable=True)
+    out, ldZ = _node_walk_matrix(who, out, V, B * D, "out", coeff.device, writable=True)
     ws_ptr, ws_len, ws = _basis_workspace(graph, B, D, X.device)
     a = _lib.BasisForwardArgs()
     a.struct_size = ctypes.sizeof(a)
@@ -1140,7 +1153,7 @@ def basis_gather_backward(graph: "Graph", coeff: torch.Tensor, dZ: torch.Tensor,
     if dZ.dim() != 2 or dZ.shape[0] != V or dZ.shape[1] < B or dZ.shape[1] % B:
         raise ValueError(f"{who}: dZ must be [{V}, num_bases * D] with num_bases = {B}, got {tuple(dZ.shape)}")
     D = int(dZ.shape[1]) // B
-    dZ, lddZ = _basis_matrix(who, dZ, V, B * D, "dZ", coeff.device)
+    dZ, lddZ = _node_walk_matrix(who, dZ, V, B * D, "dZ", coeff.device)
     a = _lib.BasisBackwardArgs()
     a.struct_size = ctypes.sizeof(a)
     a.graph, a.B, a.D = graph._h, B, D
@@ -1149,13 +1162,13 @@ def basis_gather_backward(graph: "Graph", coeff: torch.Tensor, dZ: torch.Tensor,
     if want_dcoeff:
         if X is None:
             raise ValueError(f"{who}: dcoeff needs X")
-        X, ldX = _basis_matrix(who, X, V, D, "X", coeff.device)
+        X, ldX = _node_walk_matrix(who, X, V, D, "X", coeff.device)
         a.X, a.ldX = X.data_ptr(), ldX
         dcoeff = torch.empty((L, B), dtype=torch.float32, device=coeff.device)
         a.dcoeff = dcoeff.data_ptr()
     if want_dx:
         dX = out_dx if out_dx is not None else torch.empty((V, D), dtype=torch.float32, device=coeff.device)
-        dX, lddX = _basis_matrix(who, dX, V, D, "out_dx", coeff.device, writable=True)
+        dX, lddX = _node_walk_matrix(who, dX, V, D, "out_dx", coeff.device, writable=True)
         a.dX, a.lddX = dX.data_ptr(), lddX
     a.edge_weight_by_dst = None if edge_weight_by_dst is None else edge_weight_by_dst.data_ptr()
     a.edge_weight_by_src = None if edge_weight_by_src is None else edge_weight_by_src.data_ptr()
@@ -1228,23 +1241,13 @@ def _blockdiag_common(who: str, graph: "Graph", Qb: torch.Tensor, num_blocks: in
     if di > _lib.BLOCKDIAG_MAX_BLOCK or H // C > _lib.BLOCKDIAG_MAX_BLOCK:
         raise ValueError(f"{who}: blocks of {di} x {H // C} are above the limit D / num_blocks <= {_lib.BLOCKDIAG_MAX_BLOCK} and "
                          f"H / num_blocks <= {_lib.BLOCKDIAG_MAX_BLOCK}")
-    for name, t, n in [(k, t, graph.num_edges) for k, t in edge_weights] + [("node_scale", node_scale, graph.num_nodes)]:
-        if t is None:
-            continue
-        _require_dev(t, torch.float32, name)
-        if t.dim() != 1 or t.numel() != n or not t.is_contiguous():
-            raise ValueError(f"{who}: {name} must be a contiguous vector of {n} floats, got {tuple(t.shape)}")
-        if t.device != Qb.device:
-            raise ValueError(f"{who}: {name} lives on {t.device}, Qb on {Qb.device}")
+    _node_walk_vectors(who, graph, Qb, "Qb", edge_weights, node_scale)
     return L, C, di, H, Qb.contiguous()
 
 
 def _blockdiag_workspace(graph: "Graph", C: int, D: int, H: int, num_chunks: int, device):
-    lib = _lib.load()
-    graph.ensure(G_PART_PLAN_NODE)
-    pd = lib.tfgnn_graph_gather_workspace_bytes(graph._h, VIEW_BY_DST_NODE, 1) // 4  # the plans' multi-item partial rows
-    ps = lib.tfgnn_graph_gather_workspace_bytes(graph._h, VIEW_BY_SRC_NODE, 1) // 4
-    nbytes = lib.tfgnn_blockdiag_workspace_bytes(C, D, H, pd, ps, num_chunks)
+    pd, ps = _node_plan_partials(graph)
+    nbytes = _lib.load().tfgnn_blockdiag_workspace_bytes(C, D, H, pd, ps, num_chunks)
     return _aligned_workspace(device, nbytes) if nbytes else (None, 0, None)
 
 
@@ -1259,10 +1262,10 @@ def blockdiag_forward(graph: "Graph", Qb: torch.Tensor, X: torch.Tensor, num_blo
     who = "blockdiag_forward"
     L, C, di, H, Qb = _blockdiag_common(who, graph, Qb, num_blocks, [("edge_weight", edge_weight)], node_scale)
     V, D = graph.num_nodes, C * di
-    X, ldX = _basis_matrix(who, X, V, D, "X", Qb.device)
+    X, ldX = _node_walk_matrix(who, X, V, D, "X", Qb.device)
     if out is None:
         out = torch.empty((V, H), dtype=torch.float32, device=X.device)
-    out, ldpre = _basis_matrix(who, out, V, H, "out", Qb.device, writable=True)
+    out, ldpre = _node_walk_matrix(who, out, V, H, "out", Qb.device, writable=True)
     ws_ptr, ws_len, ws = _blockdiag_workspace(graph, C, D, H, 0, X.device)
     a = _lib.BlockdiagForwardArgs()
     a.struct_size = ctypes.sizeof(a)
@@ -1289,7 +1292,7 @@ def blockdiag_backward(graph: "Graph", Qb: torch.Tensor, dPre: torch.Tensor, X: 
     L, C, di, H, Qb = _blockdiag_common(who, graph, Qb, num_blocks, [("edge_weight_by_dst", edge_weight_by_dst),
                                                                     ("edge_weight_by_src", edge_weight_by_src)], node_scale)
     V, D = graph.num_nodes, C * di
-    dPre, lddPre = _basis_matrix(who, dPre, V, H, "dPre", Qb.device)
+    dPre, lddPre = _node_walk_matrix(who, dPre, V, H, "dPre", Qb.device)
     a = _lib.BlockdiagBackwardArgs()
     a.struct_size = ctypes.sizeof(a)
     a.graph, a.C, a.D, a.H = graph._h, C, D, H
@@ -1299,7 +1302,7 @@ def blockdiag_backward(graph: "Graph", Qb: torch.Tensor, dPre: torch.Tensor, X: 
     if want_dq:
         if X is None:
             raise ValueError(f"{who}: dQb needs X")
-        X, ldX = _basis_matrix(who, X, V, D, "X", Qb.device)
+        X, ldX = _node_walk_matrix(who, X, V, D, "X", Qb.device)
         a.X, a.ldX = X.data_ptr(), ldX
         dQb = torch.empty((L, di, H), dtype=torch.float32, device=Qb.device)
         a.dQb = dQb.data_ptr()
@@ -1309,7 +1312,7 @@ def blockdiag_backward(graph: "Graph", Qb: torch.Tensor, dPre: torch.Tensor, X: 
         a.num_chunks = num_chunks
     if want_dx:
         dX = out_dx if out_dx is not None else torch.empty((V, D), dtype=torch.float32, device=Qb.device)
-        dX, lddX = _basis_matrix(who, dX, V, D, "out_dx", Qb.device, writable=True)
+        dX, lddX = _node_walk_matrix(who, dX, V, D, "out_dx", Qb.device, writable=True)
         a.dX, a.lddX = dX.data_ptr(), lddX
     a.edge_weight_by_dst = None if edge_weight_by_dst is None else edge_weight_by_dst.data_ptr()
     a.edge_weight_by_src = None if edge_weight_by_src is None else edge_weight_by_src.data_ptr()
