@@ -1022,6 +1022,26 @@ int tfgnn_graph_gather_reduce_sp(const tfgnn_graph* graph, int view, const int32
                                  const float* d_edge_weight, const float* d_row_scale, const float* d_in, int64_t ld_in,
                                  int width, void* d_out_sp, int64_t ld_out_sp_bytes, float* d_inv_scale,
                                  const float* d_fixed_inv_scale, void* d_workspace, size_t workspace_bytes, void* stream);
+/* tfgnn_graph_gather_reduce_sp into an operand that ALREADY HOLDS the rows of the view's empty buckets.  Which buckets are
+ * empty depends on the graph and the view, not on d_in: an operand that stays with the graph needs its zero rows and their
+ * marker scales written once, not once per layer (RGCN H = 320 on 30 000 nodes: 45 % of the buckets, 69 MB per launch).
+ * keep_empty_rows == 0: exactly tfgnn_graph_gather_reduce_sp.  keep_empty_rows != 0: the launch covers the non-empty buckets
+ * only - an empty bucket's row of d_out_sp and its entry of d_inv_scale are neither read nor written; every other row comes out
+ * bit for bit as above (same kernel, same order of the edges).
+ * CONTRACT of keep_empty_rows != 0 - the caller promises, and the library cannot check without another pass over the operand:
+ *   - d_out_sp / d_inv_scale were last written, in full, by a gather of the SAME graph handle, view, width and
+ *     ld_out_sp_bytes that wrote every row (keep_empty_rows == 0, or a launch that fell back as described below);
+ *   - that gather had the same d_row_scale VALUES (or NULL both times): an empty row holds 0 * row_scale, which is NaN where
+ *     the scale is infinite or NaN, so a changed scale array needs a filling launch;
+ *   - nothing else has written to either array since (gathers with keep_empty_rows != 0 in between are fine).
+ * The request is honoured for the full-row views (0 - 3 and TFGNN_VIEW_BY_DST_TYPED_PATTERN) with per-row scales
+ * (d_inv_scale); with d_fixed_inv_scale, on a compact view (which has no empty rows), on a handle whose view has no empty
+ * bucket or no length-ordered row list, the launch is the filling one of tfgnn_graph_gather_reduce_sp. */
+int tfgnn_graph_gather_reduce_sp_keep_empty(const tfgnn_graph* graph, int view, const int32_t* d_col_override,
+                                            const float* d_edge_weight, const float* d_row_scale, const float* d_in,
+                                            int64_t ld_in, int width, void* d_out_sp, int64_t ld_out_sp_bytes,
+                                            float* d_inv_scale, const float* d_fixed_inv_scale, void* d_workspace,
+                                            size_t workspace_bytes, int keep_empty_rows, void* stream);
 
 /* [batch, rows, cols] -> [batch, cols, rows] (LDS-tiled).  Used to hand the GEMMs K-contiguous weights
  * (W^T of gnn_edge_mlp.py:100 / rgcn.py:52-56 kernels) and to bring dW^T = G^T X back to the [L, D, H] layout. */
@@ -1368,6 +1388,10 @@ typedef struct tfgnn_mp_forward_args {
   float* out_inv_scale;
   void* workspace;          /* tfgnn_graph_gather_workspace_bytes(graph, view, D) bytes */
   size_t workspace_bytes;
+  int agg_filled;           /* != 0: agg_sp / agg_inv_scale already hold the empty buckets' rows of this graph and view (same D,
+                             * same row_scale values, written by an earlier call and untouched since): the gather leaves them
+                             * alone - keep_empty_rows of tfgnn_graph_gather_reduce_sp_keep_empty, with its contract.  0: every
+                             * row is written.  A caller that keeps the pair with the graph sets it from the second layer on */
 } tfgnn_mp_forward_args;
 
 typedef struct tfgnn_mp_backward_args {
@@ -1418,6 +1442,8 @@ typedef struct tfgnn_mp_backward_args {
    * input-gradient product runs.  tn_workspace may overlap neither workspace nor the K-split workspace of the NT product
    * (tfgnn_sp_gemm_nt_set_splitk_workspace); a call where it does is refused.  Over more nodes the order is gather - input-
    * gradient product - tfgnn_sp_gemm_tn, its reduce pass in its own launch.  Same results either way, bit for bit. */
+  int g_filled;             /* != 0: g_sp / g_inv_scale already hold the empty buckets' rows of this graph's by-source view
+                             * (same H; see agg_filled of tfgnn_mp_forward_args).  0: every row is written */
 } tfgnn_mp_backward_args;
 
 /* = tfgnn_graph_gather_reduce_sp_deferred + tfgnn_sp_split_cols_job + tfgnn_aux_launch + tfgnn_sp_gemm_nt_rows */

@@ -239,6 +239,12 @@ _SIGNATURES = [
         [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p,
          c_void_p, c_size_t, c_void_p],
     ),
+    (
+        "tfgnn_graph_gather_reduce_sp_keep_empty",
+        c_int,
+        [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p,
+         c_void_p, c_size_t, c_int, c_void_p],
+    ),
     ("tfgnn_sp_gemm_tn_workspace_bytes", c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int]),
     ("tfgnn_sp_gemm_tn_grouped_workspace_bytes", c_size_t, [c_int64, c_int64, c_int64, c_int, c_int]),
     (
@@ -529,7 +535,7 @@ class MpForwardArgs(ctypes.Structure):
         ("ld_wt_sp_bytes", c_int64), ("wt_inv_scale", c_void_p), ("agg_sp", c_void_p), ("agg_inv_scale", c_void_p), ("bias", c_void_p),
         ("act", c_int), ("dropout_rate", ctypes.c_float), ("dropout_seed", ctypes.c_uint64), ("tile_kmask", c_void_p),
         ("row_map", c_void_p), ("out", c_void_p), ("ld_out", c_int64), ("out_sp", c_void_p), ("ld_out_sp_bytes", c_int64),
-        ("out_inv_scale", c_void_p), ("workspace", c_void_p), ("workspace_bytes", ctypes.c_size_t),
+        ("out_inv_scale", c_void_p), ("workspace", c_void_p), ("workspace_bytes", ctypes.c_size_t), ("agg_filled", c_int),
     ]
 
 
@@ -545,7 +551,7 @@ class MpBackwardArgs(ctypes.Structure):
         ("dx_sp", c_void_p), ("ld_dx_sp_bytes", c_int64), ("dx_inv_scale", c_void_p), ("tile_kmask", c_void_p), ("a_rows", c_void_p),
         ("row_map", c_void_p), ("dw", c_void_p), ("x_sp", c_void_p), ("ld_x_sp_bytes", c_int64), ("x_inv_scale", c_void_p),
         ("tn_workspace", c_void_p), ("tn_workspace_bytes", ctypes.c_size_t), ("workspace", c_void_p),
-        ("workspace_bytes", ctypes.c_size_t),
+        ("workspace_bytes", ctypes.c_size_t), ("g_filled", c_int),
     ]
 
 

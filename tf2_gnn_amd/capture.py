@@ -85,11 +85,15 @@ class CapturedStep:
                                "ops.set_gemm_mode('bf16x3'), or arm ops.set_guard_repair(True) before building it")
         # every derived form of the weights is rebuilt INSIDE the capture: replays follow in-place weight updates
         ops.clear_weight_operand_cache()
+        # the graph-owned gather operands (ops.Graph.gather_operand) count as unfilled: the first gather of each direction
+        # inside the captured sequence writes the empty buckets' rows, the later ones keep them, and a replay repeats that
+        ops.gather_operands_touched()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, stream=side):
             if self._advance:
                 ops.dropout_epoch_advance()
             out = self._fn()
+        ops.gather_operands_touched()
         self._graph, self._out, self._stream = graph, out, side
         # the derived-weight forms made during the capture live in the graph's memory pool and are rewritten by replays the
         # library's cache cannot see: eager calls after this must rebuild their own
@@ -100,6 +104,7 @@ class CapturedStep:
         if self._graph is None:
             self.capture()
         self._graph.replay()
+        ops.gather_operands_touched()  # (a replay rewrites them: an eager call behind it fills its operand again)
         self.replays += 1
         return self._out
 

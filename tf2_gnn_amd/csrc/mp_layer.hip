@@ -44,8 +44,9 @@ extern "C" int tfgnn_mp_forward(const tfgnn_mp_forward_args* a, void* stream) {
   TFGNN_REQUIRE(V > 0 && L > 0 && D > 0 && H > 0, "tfgnn_mp_forward: empty layer");
   // 1. the aggregate, one SP16 row of L blocks per node (one scale per (node, type) bucket); buckets cut into several items
   //    are combined inside the gather's launch
-  rc = tfgnn_graph_gather_reduce_sp(a->graph, a->view, nullptr, nullptr, a->row_scale, a->x, a->ldx, (int)D, a->agg_sp, D * 4,
-                                    a->agg_inv_scale, nullptr, a->workspace, a->workspace_bytes, stream);
+  //    (agg_filled: the empty buckets' rows are in agg_sp / agg_inv_scale already and are left alone)
+  rc = tfgnn_graph_gather_reduce_sp_keep_empty(a->graph, a->view, nullptr, nullptr, a->row_scale, a->x, a->ldx, (int)D, a->agg_sp, D * 4,
+                                               a->agg_inv_scale, nullptr, a->workspace, a->workspace_bytes, a->agg_filled, stream);
   if (rc) return rc;
   // 2. W^T as the [H, L * D] operand, when the caller's copy is stale: a small-pass launch of its own.  A layer stack
   //    splits all its weights at the start of the pass instead (they do not change before the optimizer update) and hands
@@ -85,8 +86,10 @@ extern "C" int tfgnn_mp_backward(const tfgnn_mp_backward_args* a, void* stream) 
   const int64_t D = a->in_dim, H = a->hidden_dim, K = (int64_t)L * H;
   TFGNN_REQUIRE(V > 0 && L > 0 && D > 0 && H > 0, "tfgnn_mp_backward: empty layer");
   // 1. G = [G_0 | .. | G_{L-1}]: d_pre summed over the out-edges of every (source, type) bucket
-  rc = tfgnn_graph_gather_reduce_sp(a->graph, TFGNN_VIEW_BY_SRC_TYPED, nullptr, a->edge_weight, nullptr, a->d_pre, a->ld_d_pre, (int)H,
-                                    a->g_sp, H * 4, a->g_inv_scale, nullptr, a->workspace, a->workspace_bytes, stream);
+  //    (g_filled: as agg_filled of the forward call)
+  rc = tfgnn_graph_gather_reduce_sp_keep_empty(a->graph, TFGNN_VIEW_BY_SRC_TYPED, nullptr, a->edge_weight, nullptr, a->d_pre, a->ld_d_pre,
+                                               (int)H, a->g_sp, H * 4, a->g_inv_scale, nullptr, a->workspace, a->workspace_bytes,
+                                               a->g_filled, stream);
   if (rc) return rc;
   // 2. the kernels as rows [W_0[d, :] | W_1[d, :] | ..] of the [D, L * H] operand, when the caller's copy is stale (see above)
   if (a->w) {

@@ -1117,7 +1117,7 @@ static int graph_gather_impl(const tfgnn_graph* g, int view, const int32_t* d_co
                              void* d_workspace, size_t workspace_bytes, void* stream, void* d_out_sp, int64_t ld_out_sp,
                              float* d_inv_scale, const float* d_fixed_inv, tfgnn_aux_job* combine_job = nullptr,
                              const float* d_dot_rows = nullptr, int64_t ld_dot = 0, const int32_t* d_dot_pos = nullptr,
-                             float* d_dot_out = nullptr) {
+                             float* d_dot_out = nullptr, bool keep_empty = false) {
   using namespace tfgnn;
   TFGNN_REQUIRE(g != nullptr, "graph is NULL");
   TFGNN_REQUIRE(view >= 0 && view <= 6, "unknown graph view %d", view);
@@ -1177,6 +1177,10 @@ static int graph_gather_impl(const tfgnn_graph* g, int view, const int32_t* d_co
   // every other output has a zero row for an empty bucket: written by the lane groups of the non-empty short rows, which the
   // list holds first (the walks with empty_riders; launch_mode sets it back for the others)
   else if (a.short_rows && p.num_empty > 0 && p.num_short > p.num_empty) a.rider_ne = (int64_t)p.num_short - p.num_empty;
+  // ... unless the caller vouches that the operand already holds them (tfgnn_graph_gather_reduce_sp_keep_empty): the empty rows
+  // close the list, so the launch ends in front of them - no lane group, no rider, no store for any of them.  Per-row scales
+  // only: an empty row's scale is the marker, whatever the tensor-wide one would be
+  const bool keep = keep_empty && compact_nz < 0 && d_out_sp && d_inv_scale && !d_fixed_inv && a.short_rows && p.num_empty > 0;
   {
     // short rows side by side (gather_rows_block_multi) when the rows the row workgroups walk hold <= 1.5 edges on average -
     // the (node, type) buckets of a molecule batch (0.6): tools/gather_short_probe.py, 128k molecules, H = 128: typed by-target
@@ -1189,6 +1193,11 @@ static int graph_gather_impl(const tfgnn_graph* g, int view, const int32_t* d_co
     const int64_t nslots = a.short_rows ? a.num_short : a.num_rows;
     if (multi_knob == 21) a.multi_pairs = true;
     else if (multi_knob == 0) a.multi_pairs = nslots > 0 && !a.is_max && ew_heads == 1 && (double)g->E <= kMultiAvgLen * (double)nslots;
+  }
+  if (keep) {  // (cut after the choice above: the keeping launch runs the kernel of the filling one)
+    a.num_short = (int64_t)p.num_short - p.num_empty;
+    a.rider_ne = 0;
+    if (a.num_short == 0 && p.num_items == 0) return TFGNN_OK;  // no edge at all: every row is an empty one
   }
   count_launch(d_out_sp ? TFGNN_KFAM_GATHER_SP : TFGNN_KFAM_GATHER);
   return gather_dispatch(a, p.num_items, (hipStream_t)stream);
@@ -1243,6 +1252,23 @@ extern "C" int tfgnn_graph_gather_reduce_sp(const tfgnn_graph* g, int view, cons
   return graph_gather_impl(g, view, d_col_override, d_edge_weight, 1, d_row_scale, d_in, ld_in, width, nullptr, 0,
                            TFGNN_REDUCE_SUM, TFGNN_ACT_NONE, TFGNN_ACT_NONE, d_workspace, workspace_bytes, stream, d_out_sp,
                            ld_out_sp_bytes, d_inv_scale, d_fixed_inv_scale);
+}
+
+/* tfgnn_graph_gather_reduce_sp into an operand that already holds the rows and marker scales of the view's empty buckets
+ * (keep_empty_rows != 0; the contract is stated in include/tfgnn.h): they are neither read nor written. */
+extern "C" int tfgnn_graph_gather_reduce_sp_keep_empty(const tfgnn_graph* g, int view, const int32_t* d_col_override,
+                                                       const float* d_edge_weight, const float* d_row_scale, const float* d_in,
+                                                       int64_t ld_in, int width, void* d_out_sp, int64_t ld_out_sp_bytes,
+                                                       float* d_inv_scale, const float* d_fixed_inv_scale, void* d_workspace,
+                                                       size_t workspace_bytes, int keep_empty_rows, void* stream) {
+  using namespace tfgnn;
+  TFGNN_REQUIRE(d_out_sp && (d_inv_scale || d_fixed_inv_scale), "tfgnn_graph_gather_reduce_sp_keep_empty: NULL output");
+  TFGNN_REQUIRE(ld_out_sp_bytes >= (int64_t)width * 4 && ld_out_sp_bytes % 64 == 0 && (uintptr_t)d_out_sp % 64 == 0,
+                "tfgnn_graph_gather_reduce_sp_keep_empty: bad SP16 leading dimension / alignment");
+  return graph_gather_impl(g, view, d_col_override, d_edge_weight, 1, d_row_scale, d_in, ld_in, width, nullptr, 0,
+                           TFGNN_REDUCE_SUM, TFGNN_ACT_NONE, TFGNN_ACT_NONE, d_workspace, workspace_bytes, stream, d_out_sp,
+                           ld_out_sp_bytes, d_inv_scale, d_fixed_inv_scale, nullptr, nullptr, 0, nullptr, nullptr,
+                           keep_empty_rows != 0);
 }
 
 /* tfgnn_graph_gather_reduce_sp in the form that used to hand the combine pass of the long buckets back as a job for

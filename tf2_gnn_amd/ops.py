@@ -217,6 +217,51 @@ def _array_parts(array_id: int) -> int:
     return G_PART_COMPACT if G_NZ_CPOS_BY_DST <= array_id <= G_NZ_COL_BY_SRC else 0
 
 
+_OPERAND_EPOCH = [0]
+
+
+def gather_operands_touched() -> None:
+    """Every graph-owned gather operand counts as unfilled from here on (its next gather writes every row).  ``CapturedStep``
+    calls it around a capture and at every replay: the first gather of each direction INSIDE the captured sequence then writes
+    the empty rows itself, and eager calls never rely on what a replay left behind."""
+    _OPERAND_EPOCH[0] += 1
+
+
+class _GatherOperand:
+    """A graph-owned SP16 gather operand (``Graph.gather_operand``).  ``filled``: None, or what the last gather that wrote
+    EVERY row of the pair ran with - (the row_scale tensor | None, its version, inside a capture?, the operand epoch); a
+    gather whose own description equals it may leave the empty buckets' rows alone (include/tfgnn.h,
+    tfgnn_graph_gather_reduce_sp_keep_empty)."""
+
+    __slots__ = ("data", "inv_scale", "filled")
+
+    def __init__(self, data: torch.Tensor, inv_scale: torch.Tensor):
+        self.data, self.inv_scale, self.filled = data, inv_scale, None
+
+    def _description(self, row_scale: Optional[torch.Tensor]):
+        return (row_scale, row_scale._version if row_scale is not None else 0, capturing(), _OPERAND_EPOCH[0])
+
+    def begin(self, row_scale: Optional[torch.Tensor]) -> bool:
+        """-> may the gather about to run keep the empty rows?  Marks the pair unfilled until ``done`` (a call that fails
+        leaves it so)."""
+        rec, self.filled = self.filled, None
+        if rec is None:
+            return False
+        t, version, in_capture, epoch = rec
+        if in_capture != capturing() or epoch != _OPERAND_EPOCH[0]:
+            return False
+        if t is None or row_scale is None:
+            return t is None and row_scale is None
+        # the same values: the same memory (the record keeps its tensor alive, so the address cannot have been handed out
+        # again) that nothing has written since - in-place writes, also the library's through raw pointers, raise the version
+        same = t is row_scale or (t.data_ptr() == row_scale.data_ptr() and t.shape == row_scale.shape
+                                  and t.stride() == row_scale.stride() and t.dtype == row_scale.dtype)
+        return same and t._version == version and row_scale._version == version
+
+    def done(self, row_scale: Optional[torch.Tensor]) -> None:
+        self.filled = self._description(row_scale)
+
+
 class Graph:
     """Edge-bucketed adjacency of one batch (``tfgnn_graph``); build once, reuse for every layer
     and for forward + backward.  ``adjacency_lists``: sequence of int32 device tensors [E_l, 2]
@@ -260,6 +305,7 @@ class Graph:
         self.edges_per_type = tuple(int(a.shape[0]) for a in adjs)  # host-side: known without touching the device
         self.device = adjs[0].device if adjs else torch.device("cuda")
         self._cache = {}
+        self._gather_operands = {}  # (view, width, stream) -> _GatherOperand: the aggregate operands of the layer-level calls
         if wait:
             self.wait()
 
@@ -316,9 +362,35 @@ class Graph:
             self._cache[key] = off
         return off
 
+    def gather_operand(self, view: int, width: int) -> "_GatherOperand":
+        """The graph's own SP16 gather operand for (``view``, ``width``, the current stream): data [rows, row bytes] + inverse
+        scales, allocated on first use and kept until ``close()`` / ``release_gather_operands()``.  The layer-level calls
+        (``mp_forward`` / ``mp_backward``) and ``graph_gather_sp_owned`` gather into it.  Which buckets of a view are empty depends
+        on the graph alone, so only the first gather into a pair has to write their zero rows and marker scales; the pair
+        records what it was filled with (``_GatherOperand.filled``) and later gathers leave those rows alone.  NOTHING but
+        these gathers may write to the pair: whoever does resets ``filled`` to None."""
+        key = (int(view), int(width), _stream())
+        pair = self._gather_operands.get(key)
+        if pair is None:
+            typed = view in (VIEW_BY_DST_TYPED, VIEW_BY_SRC_TYPED, VIEW_BY_DST_TYPED_PATTERN)
+            if view in (VIEW_BY_DST_TYPED_COMPACT, VIEW_BY_SRC_TYPED_COMPACT):
+                rows, per = int(self.nonempty_offsets(view == VIEW_BY_SRC_TYPED_COMPACT)[-1]), 1
+            else:
+                rows, per = self.num_nodes, (self.num_edge_types if typed else 1)
+            pair = _GatherOperand(torch.empty((rows, per * int(width) * 4), dtype=torch.uint8, device=self.device),
+                                  torch.empty((rows, per), dtype=torch.float32, device=self.device))
+            self._gather_operands[key] = pair
+        return pair
+
+    def release_gather_operands(self) -> None:
+        """Drop the graph-owned gather operands (work already enqueued may still read them: the allocator reuses the memory in
+        stream order); the next layer call allocates and fills its pair again."""
+        self._gather_operands = {}
+
     def close(self):
         """Return the handle's memory to the library; work already enqueued on the current stream may
         still read it (the memory is only reused after that work)."""
+        self._gather_operands = {}
         if getattr(self, "_h", None) is not None and self._h:
             self._cache = {}
             h, self._h = self._h, None
@@ -2440,6 +2512,37 @@ def graph_gather_sp(graph: "Graph", view: int, inp: torch.Tensor, *, col=None, e
     return SplitOperand(data, inv, num_rows // R, R * width, width)
 
 
+def graph_gather_sp_owned(graph: "Graph", view: int, inp: torch.Tensor, *, edge_weight=None, row_scale=None) -> SplitOperand:
+    """``graph_gather_sp`` into the operand the GRAPH owns for (view, width, stream) - ``Graph.gather_operand`` - as the
+    layer-level calls gather: the rows (v, l) of a typed view folded into [V, L * width], one scale block per edge type.  The
+    first gather into a pair writes every row; later ones with the same ``row_scale`` values leave the empty buckets' rows and
+    marker scales alone (tfgnn_graph_gather_reduce_sp_keep_empty).  The result is a view of the graph's buffers: the next
+    gather of the same (view, width) on this stream overwrites it - consume it first, and never write to it."""
+    lib = _lib.load()
+    _require_dev(inp, torch.float32, "inp")
+    if view == VIEW_BY_DST_TYPED_PATTERN and graph.num_edge_types > 8:
+        raise ValueError("graph_gather_sp_owned: the pattern order exists for at most 8 edge types")
+    inp, ld_in = _rowmajor(inp, "inp")
+    width = inp.shape[1]
+    graph.ensure(_VIEW_PARTS[view])
+    pair = graph.gather_operand(view, width)
+    per = pair.inv_scale.shape[1]
+    keep = pair.begin(row_scale)  # (unfilled from here until the call has succeeded)
+    for t, what in ((edge_weight, "edge_weight"), (row_scale, "row_scale")):
+        if t is not None:
+            _require_dev(t, torch.float32, what)
+    ws_bytes = lib.tfgnn_graph_gather_workspace_bytes(graph._h, view, width)
+    ws = _workspace(inp.device, ws_bytes) if ws_bytes else None
+    _lib.check(
+        lib.tfgnn_graph_gather_reduce_sp_keep_empty(
+            graph._h, view, None, _ptr(edge_weight), _ptr(row_scale), _ptr(inp), ld_in, width, _ptr(pair.data), width * 4,
+            _ptr(pair.inv_scale), None, _ptr(ws), ws.numel() if ws is not None else 0, int(keep), _stream(),
+        )
+    )
+    pair.done(row_scale)
+    return SplitOperand(pair.data, pair.inv_scale, pair.data.shape[0], per * width, width)
+
+
 # ---- layer-level entry points (include/tfgnn.h tfgnn_mp_forward / tfgnn_mp_backward, csrc/mp_layer.hip) --------------------------
 def mp_entry_enabled() -> bool:
     """The aggregate-first layers drive ONE C call per pass (default) instead of the op-level calls it is made of
@@ -2472,8 +2575,9 @@ def mp_forward(graph: "Graph", view: int, x: torch.Tensor, W: torch.Tensor, *, r
     dev = x.device
     graph.ensure(_VIEW_PARTS[view])
     wt, stale = _weight_operand_for_call(W, "cols", H, L * D)
-    agg = torch.empty((V, L * D * 4), dtype=torch.uint8, device=dev)
-    agg_inv = torch.empty((V, L), dtype=torch.float32, device=dev)
+    # the aggregate is scratch of the call, but it stays with the graph: the layers of a stack gather into the same pair, and
+    # only the first of them writes the rows of the empty buckets
+    pair = graph.gather_operand(view, D)
     out = torch.empty((V, H), dtype=torch.float32, device=dev) if want_fp32 else None
     op = _empty_split(V, H, dev) if want_split else None
     ws_bytes = lib.tfgnn_graph_gather_workspace_bytes(graph._h, view, D)
@@ -2490,7 +2594,8 @@ def mp_forward(graph: "Graph", view: int, x: torch.Tensor, W: torch.Tensor, *, r
     a.row_scale = row_scale.data_ptr() if row_scale is not None else None
     a.w = W.data_ptr() if stale else None
     a.wt_sp, a.ld_wt_sp_bytes, a.wt_inv_scale = wt.data.data_ptr(), wt.data.stride(0), wt.inv_scale.data_ptr()
-    a.agg_sp, a.agg_inv_scale = agg.data_ptr(), agg_inv.data_ptr()
+    a.agg_sp, a.agg_inv_scale = pair.data.data_ptr(), pair.inv_scale.data_ptr()
+    a.agg_filled = int(pair.begin(row_scale))
     a.bias = None
     a.act = act_id(act)
     a.dropout_rate, a.dropout_seed = float(rate), int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -2501,6 +2606,7 @@ def mp_forward(graph: "Graph", view: int, x: torch.Tensor, W: torch.Tensor, *, r
         a.out_sp, a.ld_out_sp_bytes, a.out_inv_scale = op.data.data_ptr(), op.data.stride(0), op.inv_scale.data_ptr()
     a.workspace, a.workspace_bytes = (ws.data_ptr(), ws.numel()) if ws is not None else (None, 0)
     _lib.check(lib.tfgnn_mp_forward(ctypes.byref(a), stream))
+    pair.done(row_scale)
     if stale:
         _cache_weight_operand(W, "cols", wt)
     if out is not None and op is not None:
@@ -2526,8 +2632,7 @@ def mp_backward(graph: "Graph", d_pre: torch.Tensor, W: torch.Tensor, x_sp: Opti
     dev = d_pre.device
     graph.ensure(_VIEW_PARTS[VIEW_BY_SRC_TYPED])
     wh, stale = _weight_operand_for_call(W, "rows", D, L * H)
-    g_sp = torch.empty((V, L * H * 4), dtype=torch.uint8, device=dev)
-    g_inv = torch.empty((V, L), dtype=torch.float32, device=dev)
+    pair = graph.gather_operand(VIEW_BY_SRC_TYPED, H)  # (as the aggregate of mp_forward)
     out, ldc = _product_out(out, V, D, accumulate, dev)
     if want_split and accumulate:
         raise ValueError("mp_backward: the split result needs no accumulation")
@@ -2555,7 +2660,8 @@ def mp_backward(graph: "Graph", d_pre: torch.Tensor, W: torch.Tensor, x_sp: Opti
     a.edge_weight = edge_weight.data_ptr() if edge_weight is not None else None
     a.w = W.data_ptr() if stale else None
     a.wh_sp, a.ld_wh_sp_bytes, a.wh_inv_scale = wh.data.data_ptr(), wh.data.stride(0), wh.inv_scale.data_ptr()
-    a.g_sp, a.g_inv_scale = g_sp.data_ptr(), g_inv.data_ptr()
+    a.g_sp, a.g_inv_scale = pair.data.data_ptr(), pair.inv_scale.data_ptr()
+    a.g_filled = int(pair.begin(None))  # (edge weights do not reach a row without an edge)
     a.dx, a.ld_dx, a.accumulate = out.data_ptr(), ldc, int(bool(accumulate))
     if out_mul is not None:
         a.mul, a.ld_mul = out_mul.data_ptr(), out_mul.stride(0)
@@ -2576,6 +2682,7 @@ def mp_backward(graph: "Graph", d_pre: torch.Tensor, W: torch.Tensor, x_sp: Opti
         a.tn_workspace, a.tn_workspace_bytes = tn_ptr, tn_len
     a.workspace, a.workspace_bytes = (ws.data_ptr(), ws.numel()) if ws is not None else (None, 0)
     _lib.check(lib.tfgnn_mp_backward(ctypes.byref(a), stream))
+    pair.done(None)
     if stale:
         _cache_weight_operand(W, "rows", wh)
     del tn_ws

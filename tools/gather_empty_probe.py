@@ -11,6 +11,9 @@ an output row:
   fwd-l2       fwd with its columns folded onto 2048 distinct source rows (every source row an L2 hit)
   fwd-compact  the by-target buckets through TFGNN_VIEW_BY_DST_TYPED_COMPACT: non-empty buckets only
   bwd-compact  the by-source buckets through TFGNN_VIEW_BY_SRC_TYPED_COMPACT
+  fwd-keep     fwd into the operand the graph owns (ops.graph_gather_sp_owned), every launch after the first: the rows of the
+               empty buckets are in the operand already and the launch ends in front of them
+  bwd-keep     bwd likewise (a tree without ops.graph_gather_sp_owned has neither of the two)
 
 fwd - fwd-compact and bwd - bwd-compact are what the empty buckets cost a launch: their lane groups plus their zero rows.
 That difference is the ceiling for anything that moves the zero-fill elsewhere inside the launch (the rows still have to be
@@ -28,6 +31,7 @@ HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 V, E, L, H = 30000, 900000, 4, 320
 ROUNDS, REPS, WARM = 9, 20, 5
 VARIANTS = ("fwd", "bwd", "fwd-l2", "fwd-compact", "bwd-compact")
+KEEP_VARIANTS = ("fwd-keep", "bwd-keep")
 CHILD_SECONDS = 240  # a process that takes longer than this is stuck: the probe stops, it starts nothing after it
 
 
@@ -55,13 +59,17 @@ def measure(root):
         "fwd-compact": lambda: ops.graph_gather_sp(g, ops.VIEW_BY_DST_TYPED_COMPACT, X),
         "bwd-compact": lambda: ops.graph_gather_sp(g, ops.VIEW_BY_SRC_TYPED_COMPACT, X),
     }
-    for v in VARIANTS:
+    if hasattr(ops, "graph_gather_sp_owned"):
+        run["fwd-keep"] = lambda: ops.graph_gather_sp_owned(g, ops.VIEW_BY_DST_TYPED_PATTERN, X)
+        run["bwd-keep"] = lambda: ops.graph_gather_sp_owned(g, ops.VIEW_BY_SRC_TYPED, X)
+    variants = tuple(v for v in VARIANTS + KEEP_VARIANTS if v in run)
+    for v in variants:
         for _ in range(WARM):
             run[v]()
     torch.cuda.synchronize()
-    times = {v: [] for v in VARIANTS}
+    times = {v: [] for v in variants}
     for _ in range(ROUNDS):
-        for v in VARIANTS:
+        for v in variants:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for _ in range(REPS):
@@ -74,14 +82,22 @@ def measure(root):
 
 def table(title, per_variant, unit):
     lines = [title]
-    for v in VARIANTS:
+    for v in VARIANTS + KEEP_VARIANTS:
         t = per_variant[v]
+        if not t:
+            continue
         lines.append(f"  {v:12s} {statistics.median(t):8.1f} us   spread {max(t) - min(t):5.1f}   ({unit})")
     for full, compact in (("fwd", "fwd-compact"), ("bwd", "bwd-compact")):
         a, b = per_variant[full], per_variant[compact]
         diff = statistics.median(a) - statistics.median(b)
         spread = max(max(a) - min(a), max(b) - min(b))
         lines.append(f"  {full} - {compact}: {diff:6.1f} us, the empty buckets of a launch; three times the larger spread: {3 * spread:5.1f} us")
+        k = per_variant[full + "-keep"]
+        if k:
+            gain = statistics.median(a) - statistics.median(k)
+            spread = max(max(a) - min(a), max(k) - min(k))
+            lines.append(f"  {full} - {full}-keep:    {gain:6.1f} us recovered by keeping the empty rows ({100 * gain / diff if diff else 0:.0f} % of the line above); "
+                         f"three times the larger spread: {3 * spread:5.1f} us")
     return lines
 
 
@@ -100,7 +116,7 @@ def main():
             f"us per launch, {ROUNDS} rounds of {REPS} launches, variants alternating")
     lines = [head]
     trees = [HERE] + [os.path.abspath(r) for r in args.root]
-    medians = {t: {v: [] for v in VARIANTS} for t in trees}
+    medians = {t: {v: [] for v in VARIANTS + KEEP_VARIANTS} for t in trees}
     facts = None
     for _ in range(args.processes):
         for t in trees:  # one process at a time has the device open
@@ -113,7 +129,7 @@ def main():
                 sys.exit(f"gather_empty_probe: the process for {t} failed ({res.returncode}):\n{res.stdout[-2000:]}\n{res.stderr[-2000:]}")
             got = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("PROBE ")][-1][6:])
             facts = got["facts"]
-            for v in VARIANTS:
+            for v in got["times"]:
                 medians[t][v].append(statistics.median(got["times"][v]))
     lines.append(f"{facts['rows']} buckets per typed view; non-empty: {facts['nonempty_by_dst']} by target, {facts['nonempty_by_src']} by source")
     lines.append("")
