@@ -533,7 +533,8 @@ int tfgnn_gru_gates_backward_sp_dropout(const float* d_dh_new, const float* d_ga
                                         int H, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* tf.maximum(x, lower) then tf.minimum(., upper) (nodes_to_graph_representation.py:194-197; pass -inf / +inf for an absent
- * bound) and its gradient: dx = dy where lower <= x <= upper, else 0 (TensorFlow's MaximumMinimumGrad). */
+ * bound) and its gradient: dx = dy where lower <= x <= upper, else 0 (TensorFlow's MaximumMinimumGrad).  A NaN in x stays a
+ * NaN in y, as in TensorFlow; +-inf clips to the bound (and stays where there is none). */
 int tfgnn_clip(const float* d_x, int64_t n, float lower, float upper, float* d_y, void* stream);
 int tfgnn_clip_backward(const float* d_dy, const float* d_x, int64_t n, float lower, float upper, float* d_dx, void* stream);
 /* out[n] = sum_m in[m, n] (bias gradients of Dense / GRUCell). */
@@ -1466,7 +1467,8 @@ int tfgnn_mp_backward(const tfgnn_mp_backward_args* args, void* stream);
  *   dw[v, h] = sum over the features f of head h of clip(T[v, f]) * dOut[g, f]                       (never written to memory)
  *   SOFTMAX  dS[v, h] = w * (dw - sum over the graph of w * dw);   SIGMOID  dS = dw (pass w = S);   dS NULL: not computed
  * lo / hi: -INFINITY / +INFINITY for an absent bound.  T, S, w, dT, dS have leading dimensions (floats); out and dOut are
- * contiguous [G, GD]; ptr [G + 1] comes from tfgnn_segment_offsets*.
+ * contiguous [G, GD]; ptr [G + 1] comes from tfgnn_segment_offsets*.  A NaN in T stays a NaN through the clip (it reaches
+ * out and dS; the mask of dT is false there), +-inf in T clips to a finite bound: what tf.maximum / tf.minimum do.
  *
  * The nodes are cut into tiles of TFGNN_POOL_CHUNK_NODES; a graph with more nodes than that is reduced chunk by chunk by
  * several workgroups, whose partial results (in `workspace`) a second launch combines in ascending chunk order - no float

@@ -481,6 +481,37 @@ def test_layernorm_large_row_mean(dev):
     assert float((mean.cpu().double() - mu.view(-1)).abs().max()) <= delta
 
 
+@pytest.mark.parametrize("bounds", [(-0.5, 0.75), (-0.5, None), (None, 0.75), (None, None)], ids=["both", "lower", "upper", "none"])
+def test_clip_at_nan_inf_and_the_bounds(dev, bounds):
+    """tfgnn_clip / tfgnn_clip_backward against torch.clamp on the CPU: a NaN stays a NaN (tf.maximum / tf.minimum propagate
+    it; fmaxf / fminf would return the bound), +-inf clips to a finite bound and stays without one, values exactly on a
+    bound pass the gradient.  Exact: a clip rounds nothing."""
+    from tf2_gnn_amd import ops
+
+    lo, hi = bounds
+    g = torch.Generator().manual_seed(2)
+    x = torch.round(4 * torch.randn(1000, generator=g)) / 8  # a grid of eighths: many values exactly on the bounds
+    x[::97] = float("nan")
+    x[1::97] = float("inf")
+    x[2::97] = float("-inf")
+    assert int((x == -0.5).sum()) > 20 and int((x == 0.75).sum()) > 20
+    dy = torch.randn(1000, generator=g)
+    want = x if lo is None and hi is None else torch.clamp(x, min=lo, max=hi)
+    y = ops.clip(x.to(dev), lo, hi).cpu()
+    assert torch.equal(torch.isnan(y), torch.isnan(x)) and int(torch.isnan(y).sum()) == 11
+    zero = torch.zeros_like(x)
+    assert torch.equal(torch.where(torch.isnan(y), zero, y), torch.where(torch.isnan(want), zero, want))  # +-inf included
+    keep = torch.ones_like(x, dtype=torch.bool)
+    if lo is not None:
+        keep &= x >= lo
+    if hi is not None:
+        keep &= x <= hi
+    if lo is None and hi is None:  # ops.clip_backward compares with -inf / +inf: all pass but a NaN
+        keep &= ~torch.isnan(x)
+    dx = ops.clip_backward(dy.to(dev), x.to(dev), lo, hi).cpu()
+    assert torch.equal(dx, torch.where(keep, dy, torch.zeros_like(dy)))
+
+
 @pytest.mark.parametrize("M", [1, 200, 256, 257, 4097, 7110, 150001])
 @pytest.mark.parametrize("N", [7, 121, 320])
 def test_colsum_bias_gradient_sums(dev, M, N):

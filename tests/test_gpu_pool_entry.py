@@ -2,15 +2,13 @@
 parity of WeightedSumGraphRepresentation on the new kernels against the fp64 oracle from 1-node graphs to one graph of
 200 000 nodes, the C ABI called directly with non-trivial leading dimensions against the op-level sequence it replaces,
 the launch counters, run-to-run and capture determinism, and the error paths."""
-import ctypes
-import math
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import tf2gnn_oracle as orc
 from tests.helpers import assert_close, record_parity, scaled_error
+from tests.pool_abi import _raw_backward, _raw_forward
 
 pytestmark = pytest.mark.gpu
 
@@ -217,57 +215,6 @@ def test_one_graph_of_200000_nodes_is_no_worse_than_the_op_level_route(dev, wf, 
         record_parity(f"{tag} {k}", max_scaled_error=e_new[k], max_scaled_error_op_level=e_old[k], bound=max(e_old[k], 1e-5))
     for k in e_new:
         assert e_new[k] <= e_old[k] or e_new[k] <= 1e-5, (k, e_new[k], e_old[k])
-
-
-def _raw_forward(kind, ptr, T, S, heads, lo, hi, w=None, ws_bytes=None, struct_size=None):
-    from tf2_gnn_amd import _lib, ops
-
-    lib = _lib.load()
-    V, GD = T.shape
-    G = ptr.numel() - 1
-    a = _lib.PoolForwardArgs()
-    a.struct_size = ctypes.sizeof(a) if struct_size is None else struct_size
-    a.kind = ops._POOL_KINDS[kind]
-    a.V, a.G, a.GD, a.heads = V, G, GD, heads
-    a.ptr, a.T, a.ldT = ptr.data_ptr(), T.data_ptr(), T.stride(0)
-    if S is not None:
-        a.S, a.ldS = S.data_ptr(), S.stride(0)
-    a.lo = -math.inf if lo is None else lo
-    a.hi = math.inf if hi is None else hi
-    out = torch.full((G, GD), float("nan"), dtype=torch.float32, device=T.device)
-    a.out = out.data_ptr()
-    if w is not None:
-        a.w, a.ldw = w.data_ptr(), w.stride(0)
-    need = lib.tfgnn_pool_workspace_bytes(V, G, GD, heads, a.kind)
-    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=T.device)
-    a.workspace, a.workspace_bytes = ws.data_ptr(), need if ws_bytes is None else ws_bytes
-    _lib.check(lib.tfgnn_pool_forward(ctypes.byref(a), ops._stream()))
-    return out
-
-
-def _raw_backward(kind, ptr, ids, g, T, w, heads, lo, hi, dT, dS):
-    from tf2_gnn_amd import _lib, ops
-
-    lib = _lib.load()
-    V, GD = T.shape
-    G = ptr.numel() - 1
-    a = _lib.PoolBackwardArgs()
-    a.struct_size = ctypes.sizeof(a)
-    a.kind = ops._POOL_KINDS[kind]
-    a.V, a.G, a.GD, a.heads = V, G, GD, heads
-    a.ptr, a.ids, a.dOut = ptr.data_ptr(), ids.data_ptr(), g.data_ptr()
-    a.T, a.ldT = T.data_ptr(), T.stride(0)
-    if w is not None:
-        a.w, a.ldw = w.data_ptr(), w.stride(0)
-    a.lo = -math.inf if lo is None else lo
-    a.hi = math.inf if hi is None else hi
-    a.dT, a.lddT = dT.data_ptr(), dT.stride(0)
-    if dS is not None:
-        a.dS, a.lddS = dS.data_ptr(), dS.stride(0)
-    need = lib.tfgnn_pool_workspace_bytes(V, G, GD, heads, a.kind)
-    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=T.device)
-    a.workspace, a.workspace_bytes = ws.data_ptr(), need
-    _lib.check(lib.tfgnn_pool_backward(ctypes.byref(a), ops._stream()))
 
 
 def _raw_inputs(dev, sizes, GD, heads, col0, seed=5):

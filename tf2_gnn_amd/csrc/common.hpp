@@ -144,6 +144,10 @@ __device__ __forceinline__ float4 dropout_mask4(const DropoutKey& k, uint64_t id
 constexpr float kSmallNumber = 1e-7f;  // tf2_gnn/utils/constants.py:2
 constexpr float kFloatLowest = -3.402823466e+38f;
 
+// tf.minimum(tf.maximum(x, lo), hi) (-inf / +inf: no bound).  Comparisons, not fmaxf / fminf, which return the bound for a
+// NaN: a NaN stays a NaN as it does in TensorFlow, +-inf clips to a finite bound.
+__device__ __forceinline__ float clip_value(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
+
 // ---- activations (tf2_gnn/utils/param_helpers.py:25-33, utils/activation.py:7-14) -------------
 // tanh in two pieces, selected without a branch (the epilogue of a product applies it to 160 elements per thread):
 //   |x| <  0.625: x + x u q(u), u = x^2, q = degree-4 minimax fit of (tanh(sqrt u) / sqrt u - 1) / u on [0, 0.625^2]

@@ -866,7 +866,7 @@ transpose_batched_kernel(const float* __restrict__ src, int64_t rows, int64_t co
 // MaximumMinimumGrad: x >= lo for the maximum, x <= hi for the minimum) - nodes_to_graph_representation.py:194-197
 __global__ void __launch_bounds__(256) clip_kernel(const float* __restrict__ x, int64_t n, float lo, float hi, float* __restrict__ y) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    y[i] = fminf(fmaxf(x[i], lo), hi);
+    y[i] = clip_value(x[i], lo, hi);
 }
 __global__ void __launch_bounds__(256) clip_backward_kernel(const float* __restrict__ dy, const float* __restrict__ x, int64_t n, float lo,
                                                             float hi, float* __restrict__ dx) {

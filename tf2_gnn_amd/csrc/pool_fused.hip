@@ -238,7 +238,7 @@ pool_forward_kernel(PoolShape p, const int32_t* __restrict__ ptr, const float* _
             float wt = 1.f;
             if (p.kind == TFGNN_POOL_SIGMOID) wt = S[(int64_t)v * ldS + hj[j]];
             else if (p.kind == TFGNN_POOL_SOFTMAX) wt = expf(S[(int64_t)v * ldS + hj[j]] - stat_m[hj[j]]) * stat_i[hj[j]];
-            acc[j] += wt * fminf(fmaxf(x.x[j], lo), hi);
+            acc[j] += wt * clip_value(x.x[j], lo, hi);
           }
         }
       }
@@ -375,7 +375,7 @@ pool_backward_kernel(PoolShape p, const int32_t* __restrict__ ptr, const float* 
             const float wt = weighted ? w[(int64_t)v * ldw + (c + j) / ph] : wconst;
             const float xv = x.x[j];
             r.x[j] = (xv >= lo && xv <= hi) ? wt * d.x[j] : 0.f;  // tfgnn_clip_backward's mask
-            if (need_dw) prod[nl * p.GD + c + j] = fminf(fmaxf(xv, lo), hi) * d.x[j];
+            if (need_dw) prod[nl * p.GD + c + j] = clip_value(xv, lo, hi) * d.x[j];
           }
           row_store<VEC>(dT + (int64_t)v * lddT + c, r);
         }
