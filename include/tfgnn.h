@@ -2226,6 +2226,84 @@ int tfgnn_embedding_scatter_rows(const float* rows, int64_t ld_rows, const int32
 /* host-side count of the kernel launches tfgnn_embedding_scatter_rows has enqueued in this process (tests) */
 int64_t tfgnn_embedding_launch_count(void);
 
+/* ------------------------------------------------------------------------------------------
+ * Vocabulary embeddings (csrc/vocab_embedding.hip): a row lookup whose ids REPEAT - categorical nodes: atom type, token,
+ * node kind - and its table gradient, a segment sum of d_rows over equal ids.
+ *
+ *   tfgnn_vocab_embedding_forward    out[i, 0:D]        = table[id_i, 0:D]  bit for bit      if id_i is valid
+ *                                                       = 0                                  otherwise (and *bad_flag = 1)
+ *   tfgnn_vocab_embedding_backward   table_grad[r, 0:D] = sum over the valid i with id_i == r of  d_rows[i, 0:D],  every r < N
+ *
+ * table fp32 [N, D], out and d_rows fp32 [n, D], table_grad fp32 [N, D], each with a row pitch in floats; columns >= D of a
+ * pitched row are not touched.  The ids are int32 [n] (ids_i32) or fp32 [n] (ids_f32), exactly one of the two non-NULL, read
+ * at element pitch ids_pitch - column 0 of a [n, W] feature matrix is ids_f32 = the matrix, ids_pitch = W.  A valid id is an
+ * integer in [0, N); a float id must be finite and equal to its floor (-0.0 is id 0), and float ids need N <= 2^24.  An
+ * invalid id sets *bad_flag (nullable; zeroed by the caller), gets a zero row and takes no part in the gradient.
+ *
+ * THE PLAN.  The forward call leaves in `workspace` what the backward call walks: the row indices 0 .. n-1 stably sorted by id
+ * (equal ids in increasing row index, the invalid rows last), the sorted keys, and the row pointers off[0 .. N] of the ids in
+ * that order.  The sort is an LSD radix sort with 9-bit digits, per-tile histograms and no global atomics, in
+ * ceil(bit_length(N) / 9) passes - one for N <= 511.  The layout is a function of (n, N) alone; the backward call takes the
+ * same workspace, n and N.  tfgnn_vocab_embedding_workspace_bytes(n, N): its size (16-byte aligned; 0 outside the limits).
+ *
+ * ORDER OF THE SUMS - fp32 adds, no float atomics, a function of the ids alone: two calls, or a call and its replay from a
+ * captured graph, give the same bits.  The sorted positions [off[r], off[r+1]) of id r are cut into chunks of 256: chunk k is
+ * [off[r] + 256 k, min(off[r] + 256 (k+1), off[r+1])), so a chunk never crosses an id and a hub id is many chunks.  One wave
+ * takes one (chunk, slab of 256 columns); a lane owns a float4 column group (four columns 64 apart when D % 4 != 0, a pitch
+ * % 4 != 0 or a base that is not 16-byte aligned forbids float4).  Inside a chunk: the first row as it is, then + the next
+ * row, in increasing sorted position, which is increasing row index.  An id of one chunk is stored straight to table_grad -
+ * an id with one row gets that row's bits -; an id of several chunks writes one partial row per chunk, and a second launch
+ * adds them: chunk 0, + chunk 1, + chunk 2 ...  An absent id gets zeros.  Every row < N and column < D of table_grad is
+ * written: the caller does not pre-fill.  At most 255 adds in a chunk and one per further chunk: to first order an element is
+ * within (256 + ceil(m / 256)) * 2^-24 * sum |d_rows| (over the m rows of the id) of the exact sum.
+ * The partial rows need D, which the plan does not know: the backward call takes `partials`, at least
+ * TFGNN_VOCAB_EMBEDDING_PARTIAL_ROWS(n) * D floats, 16-byte aligned, no initialisation (not read for n <= 256: may be NULL).
+ *
+ * Launches on `stream`: forward 2 + 2 * passes (lookup, histogram + scatter per pass, row pointers), none for n == 0;
+ * backward 1, + 1 when n > 256; for n == 0 the one launch writes an all-zero gradient, for N == 0 there is none.  Grids are
+ * sized from n, N and D; no size is read back.  No allocation, no copy, no memset, no host synchronisation: capturable.
+ * Every read through the order is checked against n, every write is below N rows.
+ * Rejected on the host before any HIP call: NULL args or another struct_size; negative sizes; n, N or D >= 2^31; D < 1;
+ * N == 0 with n > 0; a pitch below D; both or neither of ids_i32 / ids_f32; ids_pitch < 1; float ids with N > 2^24; NULL
+ * pointers where they are read; a short or misaligned workspace or partials.  D above 65535 * 256: TFGNN_ERR_UNSUPPORTED.
+ *
+ * tfgnn_vocab_embedding_launch_counts: out[0] = kernel launches of the forward entry so far, out[1] = of the backward entry
+ * (host counters); further slots are zero.
+ * ------------------------------------------------------------------------------------------ */
+#define TFGNN_VOCAB_EMBEDDING_PARTIAL_ROWS(n) (2 * (((int64_t)(n) + 255) / 256))
+typedef struct tfgnn_vocab_embedding_forward_args {
+  size_t struct_size;
+  int64_t n, N, D;
+  const float* table;      /* [N, D], row pitch ld_table */
+  int64_t ld_table;
+  const int32_t* ids_i32;  /* [n] at element pitch ids_pitch, or NULL */
+  const float* ids_f32;    /* [n] at element pitch ids_pitch, or NULL */
+  int64_t ids_pitch;
+  float* out;              /* [n, D], row pitch ld_out */
+  int64_t ld_out;
+  void* workspace;         /* the plan: tfgnn_vocab_embedding_workspace_bytes(n, N) */
+  size_t workspace_bytes;
+  int* bad_flag;           /* nullable */
+} tfgnn_vocab_embedding_forward_args;
+
+typedef struct tfgnn_vocab_embedding_backward_args {
+  size_t struct_size;
+  int64_t n, N, D;
+  const float* d_rows;     /* [n, D], row pitch ld_rows */
+  int64_t ld_rows;
+  const void* workspace;   /* the plan the forward call left for this (n, N) */
+  size_t workspace_bytes;
+  float* partials;         /* [TFGNN_VOCAB_EMBEDDING_PARTIAL_ROWS(n), D] */
+  size_t partials_bytes;
+  float* table_grad;       /* [N, D], row pitch ld_grad */
+  int64_t ld_grad;
+} tfgnn_vocab_embedding_backward_args;
+
+size_t tfgnn_vocab_embedding_workspace_bytes(int64_t n, int64_t N);
+int tfgnn_vocab_embedding_forward(const tfgnn_vocab_embedding_forward_args* args, void* stream);
+int tfgnn_vocab_embedding_backward(const tfgnn_vocab_embedding_backward_args* args, void* stream);
+int tfgnn_vocab_embedding_launch_counts(int64_t* out_counts, int n);
+
 #ifdef __cplusplus
 }
 #endif

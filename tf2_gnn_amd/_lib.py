@@ -479,6 +479,18 @@ _SIGNATURES += [
      [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     ("tfgnn_embedding_launch_count", c_int64, []),
 ]
+# vocabulary embeddings: a lookup with repeated ids and its segment-sum gradient (include/tfgnn.h, csrc/vocab_embedding.hip)
+_SIGNATURES += [
+    ("tfgnn_vocab_embedding_workspace_bytes", c_size_t, [c_int64, c_int64]),
+    ("tfgnn_vocab_embedding_forward", c_int, [c_void_p, c_void_p]),
+    ("tfgnn_vocab_embedding_backward", c_int, [c_void_p, c_void_p]),
+    ("tfgnn_vocab_embedding_launch_counts", c_int, [POINTER(c_int64), c_int]),
+]
+
+
+def vocab_embedding_partial_rows(n: int) -> int:
+    """TFGNN_VOCAB_EMBEDDING_PARTIAL_ROWS: rows of the reduce's partial buffer for n looked-up rows"""
+    return 2 * ((int(n) + 255) // 256)
 # one mini-batch of link-prediction triples: gather, negatives, seeds, local ids (include/tfgnn.h "Triple batches",
 # csrc/triple_batch.hip)
 _SIGNATURES += [
@@ -677,6 +689,26 @@ class SampleExcludeArgs(ctypes.Structure):
         ("num_positives", c_int64), ("positives", c_void_p), ("fwd_type", c_void_p), ("inv_type", c_void_p),
         ("edge_capacity", c_void_p), ("adjacency_lists", c_void_p), ("meta", c_void_p), ("record", c_void_p),
         ("workspace", c_void_p), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
+class VocabEmbeddingForwardArgs(ctypes.Structure):
+    """tfgnn_vocab_embedding_forward_args (include/tfgnn.h), field for field"""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t), ("n", c_int64), ("N", c_int64), ("D", c_int64), ("table", c_void_p),
+        ("ld_table", c_int64), ("ids_i32", c_void_p), ("ids_f32", c_void_p), ("ids_pitch", c_int64), ("out", c_void_p),
+        ("ld_out", c_int64), ("workspace", c_void_p), ("workspace_bytes", ctypes.c_size_t), ("bad_flag", c_void_p),
+    ]
+
+
+class VocabEmbeddingBackwardArgs(ctypes.Structure):
+    """tfgnn_vocab_embedding_backward_args (include/tfgnn.h), field for field"""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t), ("n", c_int64), ("N", c_int64), ("D", c_int64), ("d_rows", c_void_p),
+        ("ld_rows", c_int64), ("workspace", c_void_p), ("workspace_bytes", ctypes.c_size_t), ("partials", c_void_p),
+        ("partials_bytes", ctypes.c_size_t), ("table_grad", c_void_p), ("ld_grad", c_int64),
     ]
 
 

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Dict, Optional, Sequence
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -3200,4 +3200,108 @@ def embedding_scatter_rows(rows: torch.Tensor, ids: torch.Tensor, num_rows: int,
         _require_dev(bad_flag, torch.int32, "bad_flag")
     _lib.check(_lib.load().tfgnn_embedding_scatter_rows(_ptr(rows) if n else None, ld_rows, _ptr(ids) if n else None, n, D,
                                                         _ptr(out) if N else None, ld_out, N, _ptr(bad_flag), _stream()))
+    return out
+
+
+# ---- vocabulary embeddings: include/tfgnn.h "Vocabulary embeddings", csrc/vocab_embedding.hip ------------------------------------------
+def vocab_embedding_launch_counts() -> Tuple[int, int]:
+    """tfgnn_vocab_embedding_launch_counts: kernel launches of ``vocab_embedding_forward`` and of ``vocab_embedding_backward``
+    so far (host counters)."""
+    buf = (ctypes.c_int64 * 2)()
+    _lib.check(_lib.load().tfgnn_vocab_embedding_launch_counts(buf, 2))
+    return int(buf[0]), int(buf[1])
+
+
+class VocabEmbeddingPlan:
+    """What ``vocab_embedding_forward`` leaves for ``vocab_embedding_backward``: the device workspace with the rows sorted by id
+    and the ids' row pointers (``n`` rows, a vocabulary of ``N``), and the reduce's partial rows once a backward call has asked
+    for them.  It owns its buffers: handed back to the forward call it is reused whenever (n, N) repeats, so that a captured
+    step replays on the same memory."""
+
+    __slots__ = ("n", "N", "workspace", "_partials")
+
+    def __init__(self, n: int, N: int, device):
+        nbytes = int(_lib.load().tfgnn_vocab_embedding_workspace_bytes(n, N)) if n else 0
+        if n and nbytes == 0:
+            raise ValueError(f"no vocabulary-embedding plan for n = {n}, N = {N} (include/tfgnn.h: n in [0, 2^31), N in [1, 2^31))")
+        self.n, self.N = n, N
+        self.workspace = torch.empty(nbytes // 4, dtype=torch.int32, device=device)
+        self._partials = None
+
+    def partials(self, D: int) -> Optional[torch.Tensor]:
+        if self.n <= 256:
+            return None
+        if self._partials is None or self._partials.shape[1] != D:
+            self._partials = torch.empty((_lib.vocab_embedding_partial_rows(self.n), D), dtype=torch.float32,
+                                         device=self.workspace.device)
+        return self._partials
+
+
+def _pitched_out(out: Optional[torch.Tensor], rows: int, D: int, device, what: str):
+    if out is None:
+        out = torch.empty((rows, D), dtype=torch.float32, device=device)
+    _require_dev(out, torch.float32, "out")
+    if out.dim() != 2 or tuple(out.shape) != (rows, D) or out.stride(1) != 1:
+        raise ValueError(f"{what}: out must be a float32 [{rows}, {D}] with unit inner stride")
+    return out, (int(out.stride(0)) if rows > 1 else max(int(out.stride(0)), D))
+
+
+@_writes_out
+def vocab_embedding_forward(table: torch.Tensor, ids: torch.Tensor, *, plan: Optional[VocabEmbeddingPlan] = None,
+                            out: Optional[torch.Tensor] = None, bad_flag: Optional[torch.Tensor] = None):
+    """``table[ids]`` for ids that may repeat -> ``(rows [n, D], plan)`` (tfgnn_vocab_embedding_forward on the current stream;
+    capturable).  ``ids`` is 1-D, int32 or float32, with any element stride: column 0 of a float32 [n, W] feature matrix goes
+    in as the view ``features[:, 0]``.  An id outside [0, N) - or a float id that is no integer - gets a zero row, sets
+    ``bad_flag`` (zeroed int32 [1]) and takes no part in the gradient.  ``plan``: the plan of an earlier call, reused when its
+    (n, N) matches; the returned plan is what ``vocab_embedding_backward`` takes.  ``table`` and ``out`` may be pitched."""
+    _require_dev(table, torch.float32, "table")
+    table, ld_table = _rowmajor(table, "table")
+    if ids.dim() != 1 or ids.dtype not in (torch.int32, torch.float32):
+        raise ValueError(f"vocab_embedding_forward: ids must be a 1-D int32 or float32 tensor, not {ids.dtype} {tuple(ids.shape)}")
+    _require_dev(ids, ids.dtype, "ids")
+    n, N, D = int(ids.shape[0]), int(table.shape[0]), int(table.shape[1])
+    pitch = int(ids.stride(0)) if n > 1 else 1
+    if pitch < 1:
+        ids, pitch = ids.contiguous(), 1
+    if plan is None or plan.n != n or plan.N != N or plan.workspace.device != table.device:
+        plan = VocabEmbeddingPlan(n, N, table.device)
+    out, ld_out = _pitched_out(out, n, D, table.device, "vocab_embedding_forward")
+    if bad_flag is not None:
+        _require_dev(bad_flag, torch.int32, "bad_flag")
+    a = _lib.VocabEmbeddingForwardArgs()
+    a.struct_size = ctypes.sizeof(_lib.VocabEmbeddingForwardArgs)
+    a.n, a.N, a.D = n, N, D
+    a.table, a.ld_table = table.data_ptr() if N else None, ld_table
+    a.ids_i32 = ids.data_ptr() if n and ids.dtype == torch.int32 else None
+    a.ids_f32 = ids.data_ptr() if n and ids.dtype == torch.float32 else None
+    a.ids_pitch = pitch
+    a.out, a.ld_out = out.data_ptr() if n else None, ld_out
+    a.workspace, a.workspace_bytes = plan.workspace.data_ptr() if n else None, plan.workspace.numel() * 4
+    a.bad_flag = bad_flag.data_ptr() if bad_flag is not None else None
+    _lib.check(_lib.load().tfgnn_vocab_embedding_forward(ctypes.byref(a), _stream()))
+    return out, plan
+
+
+@_writes_out
+def vocab_embedding_backward(d_rows: torch.Tensor, plan: VocabEmbeddingPlan, num_rows: int, *,
+                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The gradient of ``vocab_embedding_forward`` with respect to its table of ``num_rows`` rows, dense: -> float32
+    [num_rows, D], row r = the sum of ``d_rows[i]`` over the valid i with ids[i] == r, zeros for an absent id
+    (tfgnn_vocab_embedding_backward: one or two launches on the current stream; no float atomics, the same bits every call;
+    capturable).  Every element of ``out`` is written.  ``d_rows`` [n, D] and ``out`` may be pitched."""
+    _require_dev(d_rows, torch.float32, "d_rows")
+    d_rows, ld_rows = _rowmajor(d_rows, "d_rows")
+    n, D, N = int(d_rows.shape[0]), int(d_rows.shape[1]), int(num_rows)
+    if plan.n != n or plan.N != N:
+        raise ValueError(f"vocab_embedding_backward: the plan is of {plan.n} rows and {plan.N} ids, not of {n} and {N}")
+    out, ld_out = _pitched_out(out, max(N, 0), D, d_rows.device, "vocab_embedding_backward")
+    partials = plan.partials(D)
+    a = _lib.VocabEmbeddingBackwardArgs()
+    a.struct_size = ctypes.sizeof(_lib.VocabEmbeddingBackwardArgs)
+    a.n, a.N, a.D = n, N, D
+    a.d_rows, a.ld_rows = d_rows.data_ptr() if n else None, ld_rows
+    a.workspace, a.workspace_bytes = plan.workspace.data_ptr() if n else None, plan.workspace.numel() * 4
+    a.partials, a.partials_bytes = (partials.data_ptr(), partials.numel() * 4) if partials is not None else (None, 0)
+    a.table_grad, a.ld_grad = out.data_ptr() if N else None, ld_out
+    _lib.check(_lib.load().tfgnn_vocab_embedding_backward(ctypes.byref(a), _stream()))
     return out

@@ -92,7 +92,16 @@ class GraphTaskModel:
         their slots only (tfgnn_optimizer_apply_rows).  Plain SGD gives the dense result; with momentum, RMSprop or Adam it
         is the LAZY optimizer (LazyAdam): the moments of rows outside the batch do not decay and those rows do not move.  A
         full batch has a gradient for every row and takes the dense route under either value.  Anything else raises
-        ValueError."""
+        ValueError.
+
+        ``node_vocabulary_size`` (absent or None: off; in no defaults dictionary; needs ``node_embedding_dim``) makes the
+        table a VOCABULARY of that many rows, for categorical nodes (atom type, token, node kind) whose ids repeat: the
+        variable keeps its name and initialiser, ``num_nodes`` is not needed, and a batch's ids are its
+        ``node_vocabulary_ids`` (int32 [V]) or, without that key, column 0 of ``node_features`` [V, 1] - a JSONL dataset whose
+        node features are ``[[id], ...]`` needs no change.  The lookup is ops.vocab_embedding_forward, the table's gradient the
+        deterministic segment sum of ops.vocab_embedding_backward (dense [node_vocabulary_size, node_embedding_dim]), the
+        update the optimizer's dense step; ``node_embedding_update="rows"`` with it raises ValueError.  An id outside the
+        vocabulary gets a zero row and sets ``embedding_bad_index``.  A static batch's step stays capturable."""
         self._params = params
         if num_edge_types is None:
             if dataset is None or not hasattr(dataset, "num_edge_types"):
@@ -109,12 +118,24 @@ class GraphTaskModel:
         if update is not None and dim is None:
             raise ValueError("node_embedding_update is set without node_embedding_dim: there is no embedding table to update")
         self._node_embedding_rows = update == "rows"
+        vocab = params.get("node_vocabulary_size")
+        if vocab is not None and (isinstance(vocab, bool) or not isinstance(vocab, (int, np.integer)) or not 1 <= vocab < 2 ** 31):
+            raise ValueError(f"node_vocabulary_size must be an integer in [1, 2^31) (or None: no vocabulary embeddings), not {vocab!r}")
+        if vocab is not None and dim is None:
+            raise ValueError("node_vocabulary_size is set without node_embedding_dim, the width of one learned embedding per id")
+        if vocab is not None and self._node_embedding_rows:
+            raise ValueError('node_embedding_update="rows" with node_vocabulary_size: a vocabulary table takes the dense update '
+                             "(a lazy row update over the batch's unique ids is not implemented)")
+        self._node_vocabulary_size = None if vocab is None else int(vocab)
+        self._vocabulary_plan = None  # ops.VocabEmbeddingPlan of the last forward pass, reused while the batch shape repeats
         self._num_nodes: Optional[int] = None
         self._node_embeddings: Optional[Variable] = None
         self._node_embeddings_grad: Optional[torch.Tensor] = None  # the sampled route's dense [num_nodes, dim] buffer
         self._embedding_ids: Optional[torch.Tensor] = None  # sampled_node_ids of the last forward pass; None: the whole table
         self.embedding_bad_index: Optional[torch.Tensor] = None  # device flag: a sampled id outside the table (read lazily)
-        if dim is not None:
+        if vocab is not None:
+            pass  # the table has one row per id: the number of nodes is not asked of anybody
+        elif dim is not None:
             if num_nodes is None:
                 if dataset is None or not hasattr(dataset, "num_nodes"):
                     raise ValueError("node_embedding_dim needs the number of nodes: a dataset with num_nodes (dataset.num_nodes), "
@@ -150,7 +171,8 @@ class GraphTaskModel:
         )
         if self._node_embedding_dim is not None:  # created last: the other variables draw what they draw without it
             self._node_embeddings = Variable(f"{self.__class__.__name__}/node_embeddings",
-                                             glorot_uniform((self._num_nodes, self._node_embedding_dim), device=default_device()))
+                                             glorot_uniform((self._node_vocabulary_size or self._num_nodes, self._node_embedding_dim),
+                                                            device=default_device()))
         self.built = True
 
     def get_initial_node_feature_shape(self, input_shapes):
@@ -167,6 +189,8 @@ class GraphTaskModel:
         table = self._node_embeddings
         if table is None:
             return inputs["node_features"]
+        if self._node_vocabulary_size is not None:
+            return self._vocabulary_rows(inputs, table)
         ids = inputs.get("sampled_node_ids") if hasattr(inputs, "get") else None
         self._embedding_ids = ids
         N, dim = table.value.shape
@@ -181,6 +205,23 @@ class GraphTaskModel:
         if self.embedding_bad_index is None:
             self.embedding_bad_index = torch.zeros(1, dtype=torch.int32, device=table.value.device)
         rows, _ = ops.gather_node_rows(ids, int(ids.shape[0]), table.value, bad_flag=self.embedding_bad_index)
+        return rows
+
+    def _vocabulary_rows(self, inputs, table):
+        """The rows of the vocabulary table for a batch's categorical nodes: the ids are ``node_vocabulary_ids`` (int32 [V])
+        when the batch has that key, otherwise column 0 of its ``node_features``, which must then be [V, 1] - what batch
+        assembly and the sampler's row gather hand through untouched.  ``sampled_node_ids`` is not consulted."""
+        ids = inputs.get("node_vocabulary_ids") if hasattr(inputs, "get") else None
+        if ids is None:
+            features = inputs["node_features"]
+            if features.dim() != 2 or int(features.shape[1]) != 1:
+                raise ValueError(f"node_vocabulary_size without node_vocabulary_ids in the batch reads the ids from node_features "
+                                 f"[V, 1], not from {tuple(features.shape)}")
+            ids = features[:, 0]
+        if self.embedding_bad_index is None:
+            self.embedding_bad_index = torch.zeros(1, dtype=torch.int32, device=table.value.device)
+        rows, self._vocabulary_plan = ops.vocab_embedding_forward(table.value, ids.reshape(-1) if ids.dim() != 1 else ids,
+                                                                  plan=self._vocabulary_plan, bad_flag=self.embedding_bad_index)
         return rows
 
     @property
@@ -242,7 +283,10 @@ class GraphTaskModel:
             self._gnn.backward(grad_final, grad_all_representations=grad_all)
         else:  # the stack's input gradient is the gradient of the looked-up rows
             d_rows = self._gnn.backward(grad_final, need_input_grad=True, grad_all_representations=grad_all)
-            if self._embedding_ids is None:
+            if self._node_vocabulary_size is not None:  # the segment sum of the rows' gradients over equal ids, dense
+                self._node_embeddings_grad = table.grad = ops.vocab_embedding_backward(
+                    d_rows, self._vocabulary_plan, table.value.shape[0], out=self._node_embeddings_grad)
+            elif self._embedding_ids is None:
                 table.grad = d_rows
             elif self._node_embedding_rows:  # the pair itself: the optimizer updates these rows and no others
                 table.grad = RowGradient(d_rows, self._embedding_ids, table.value.shape[0], bad_flag=self.embedding_bad_index)
